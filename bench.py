@@ -54,12 +54,6 @@ import sys
 import tempfile
 import time
 
-# The library runs up to six streams beside the caller's (two planner streams, the encode-plan stream, the object layer's two
-# copy streams).  The HIP runtime multiplexes a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4): with
-# more streams than queues, two of them share a queue and run one after the other -- seen as the encode-plan build (14 ms at
-# K'=56403) serialised into the solve stream.  Must be set before the runtime initialises (torch import).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
@@ -123,7 +117,32 @@ def parse():
     ap.add_argument("--force-device", type=int, default=-1,
                     help="plumbing tests only: every rank uses this GPU (several ranks on one device; use with gloo)")
     ap.add_argument("--digest-out", default="", help="plumbing tests: write the per-block SHA-256 of this rank's repair symbols here")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (a fixed sample of rank 0's decoded, repair "
+                         "and intermediate rows, and the symbols each decode used) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_ARRAY_BYTES = 16 << 20   # per sampled array, its row numbers included: the dump stays under 64 MB
+
+
+def dump_outputs(out_dir, rows, used):
+    """`rows`: {name: (2-D uint8 device tensor, device tensor of the row numbers to sample from, or None for all rows)}.  The
+    sample is a function of the shapes alone (fixed seed), so two builds run with the same arguments dump the same rows."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20261015)
+    for name, (t, cand) in rows.items():
+        total = t.shape[0] if cand is None else cand.numel()
+        n = min(total, max(1, DUMP_ARRAY_BYTES // (4 * t.shape[1] + 8)))
+        pick = torch.from_numpy(np.sort(rng.choice(total, n, replace=False)).astype(np.int64)).to(t.device)
+        ix = pick if cand is None else cand.index_select(0, pick)
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, ix).to(torch.float32).cpu().numpy())
+        np.save(os.path.join(out_dir, name + "_rows.npy"), ix.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "decode_symbols_used.npy"), used.astype(np.float64))
 
 
 def algorithmic_bytes(st, K, T, L, nsym_loaded, nsym_generated_rows):
@@ -595,6 +614,7 @@ def main():
 
     rep_rows_all, int_rows_all = rep.view(NB * nrep, T), inter.view(NB * L, T)
     step_no = 0
+    used_last = np.zeros(NB, np.int64)   # symbols each block's decode used in the latest step (what the decode call returns)
 
     def poison(ph):
         rep_rows_all.index_fill_(0, ph_rep[ph], 0xCD)
@@ -658,6 +678,7 @@ def main():
             if not st.all():
                 raise RuntimeError("decode failed for %d blocks" % int((st == 0).sum()))
             retries += int((used - nr_first[lo:hi]).sum())
+            used_last[lo:hi] = used
             if ahead:
                 # the decode plans of the NEXT steps (same reception pattern every step in this bench; a planner run per step
                 # all the same): enqueued now, they run beside this step's decode solve and the next steps' solves
@@ -699,6 +720,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     host_cpu_ms = (time.process_time() - cpu0) / args.steps * 1e3
+    if args.dump_outputs and rank == 0:   # (before the untimed steps below overwrite the buffers)
+        dump_outputs(args.dump_outputs, {"decoded": (work_rows, lost_rows_p[pat_of(step_no - 1)]), "repair": (rep_rows_all, None),
+                                         "intermediate": (int_rows_all, None)}, used_last)
     # solve-kernel launches of all streams on one time axis (HIP events recorded around each launch)
     intervals, ptimes = [], []
     for c_ in ctxs:

@@ -25,9 +25,9 @@
  *   - nanorq_repair_block decodes, in the same device batch, the other decodable blocks of the object and hands their rows
  *     out when their own call comes (same verdicts, same bytes); NANORQ_HIP_REPAIR_AHEAD=0 decodes one block per call;
  *   - NANORQ_HIP_DEVICES=0,1,... / NANORQ_HIP_DEVICE=n choose the GPUs (nanorq_batch.h);
- *   - the library runs six streams beside the caller's and the HIP runtime multiplexes a process's streams over 4 hardware
- *     queues by default: a host process should export GPU_MAX_HW_QUEUES=8 before its first HIP call.  The library leaves the
- *     process environment alone; NANORQ_HIP_SET_ENV=1 asks it to set the variable (if unset) when it is loaded.
+ *   - the library runs six streams beside the caller's and the HIP runtime multiplexes a process's streams over its hardware
+ *     queues (GPU_MAX_HW_QUEUES, the host process's setting): streams that share a queue run one after the other.  The
+ *     library leaves the process environment alone.
  */
 #ifndef NANORQ_H
 #define NANORQ_H

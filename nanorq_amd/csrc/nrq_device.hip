@@ -1969,19 +1969,6 @@ int nrq_params(uint32_t K, uint32_t out[10]) {
   return 0;
 }
 
-/* The runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues, 4 by default; a context runs up to six
- * streams beside the caller's, and two streams on one queue execute one after the other (seen as the encode-plan build
- * serialised into the solve stream).  The variable must be there before the runtime initialises, and it belongs to the HOST
- * process: the library does not touch the environment unless asked to -- NANORQ_HIP_SET_ENV=1 makes this load-time
- * constructor set GPU_MAX_HW_QUEUES=8 if it is unset (a constructor runs before the library's first HIP call and, for a
- * library linked at program start, before the process has other threads that could be reading the environment; a library
- * dlopen'ed late gets neither guarantee, which is why it is opt-in).  bench.py, the tools and the tests export the variable
- * themselves; include/nanorq.h and INTEGRATION.md tell a host process to. */
-__attribute__((constructor)) static void nrq_env_at_load(void) {
-  const char *e = getenv("NANORQ_HIP_SET_ENV");
-  if (e && *e == '1') setenv("GPU_MAX_HW_QUEUES", "8", 0);
-}
-
 int nrq_ctx_create(int device, void *stream, nrq_ctx **out) {
   if (!out) return -1;
   *out = nullptr;

@@ -34,7 +34,13 @@ def blocks_of(rank, world, total_blocks):
 def barrier(world):
     if world > 1:
         import torch.distributed as dist
-        dist.barrier()
+        if dist.get_backend() == "gloo":
+            # (dist.barrier() first asks the runtime for the machine's accelerator, which opens the GPU device: the ranks of a
+            # CPU job must leave it to the processes that use it.  A collective on a CPU tensor orders the ranks the same way.)
+            import torch
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
 
 
 def reduce_max(value, world, device=None):

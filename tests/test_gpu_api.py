@@ -113,14 +113,14 @@ def test_decode_retry_after_more_symbols():
 
 
 def test_reference_benchmark_harness_on_the_hip_path():
-    """oracle/_refprog/benchmark_hip = the reference's benchmark.c compiled (in the build container, sources read in
+    """oracle/_ref/benchmark_hip = the reference's benchmark.c compiled (in the build container, sources read in
     place) against this library: encode / precalc-encode / decode / decode-with-overhead runs, 6 % loss, ending in
     the harness's own assert(in[i] == out[i]) (reference benchmark.c:233-235)."""
     import os
     import subprocess
-    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_refprog", "benchmark_hip")
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "benchmark_hip")
     if not os.path.isfile(exe):
-        pytest.skip("oracle/_refprog/benchmark_hip not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/benchmark_hip not built (needs the reference tree at build time)")
     for argv in (["1024", "100", "0"], ["1280", "1000", "5.0"]):
         r = subprocess.run([exe] + argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert r.returncode == 0, (argv, r.stderr.decode()[-500:])
@@ -207,6 +207,38 @@ def test_two_ranks_through_the_real_library(tmp_path):
     outs = [p.communicate(timeout=600)[0].decode() for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
     assert json.loads([ln for ln in outs[0].splitlines() if ln.startswith("{")][-1])["n_gpus"] == 2
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_same_outputs_run_after_run(tmp_path):
+    """bench.py --dump-outputs: the last timed step's decoded / repair / intermediate rows (a fixed sample) and the symbols each
+    decode used, as float32 / float64 .npy files under 64 MB; two runs with the same arguments write the same arrays, and the
+    line reports the --steps it was given with its ms_per_step."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--K", "1024", "--T", "256", "--blocks", "4", "--steps", "3",
+           "--warmup", "1", "--cpu-sample", "0", "--alg-sample", "0", "--pmc", "off", "--no-e2e"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        line = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == sorted(["decode_symbols_used.npy"] + ["%s%s.npy" % (n, s) for n in ("decoded", "repair", "intermediate")
+                                                               for s in ("", "_rows")])
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(tmp_path / run / f) for f in files})
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and a[f].size > 0, f
+        assert np.array_equal(a[f], b[f]), f
+    assert a["decoded.npy"].shape == (len(a["decoded_rows.npy"]), 256) and a["repair.npy"].shape[1] == 256
+    assert (a["decode_symbols_used.npy"] >= 1).all()
 
 
 # ------------------------------------------------------------------ streaming path (page-locked memory) ----

@@ -60,9 +60,9 @@ def test_too_few_packets_is_reported(tmp_path):
 
 
 def _refprog(name):
-    p = os.path.join(ROOT, "oracle", "_refprog", name)
+    p = os.path.join(ROOT, "oracle", "_ref", name)
     if not os.path.isfile(p):
-        pytest.skip("oracle/_refprog/%s not built (needs the reference tree at build time)" % name)
+        pytest.skip("oracle/_ref/%s not built (needs the reference tree at build time)" % name)
     return p
 
 

@@ -2,8 +2,9 @@
 # Build-container helper: registers, spills and scratch of every kernel of nrq_device.hip (code object metadata of the gfx950
 # build) -> stdout.   bash tools/kernel_registers.sh > profiles/r4_kernel_registers.txt
 set -e
+R=$(cd "$(dirname "$0")/.." && pwd)
 D=$(mktemp -d)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -Wno-pass-failed -I/root/repo/include -I/root/repo/nanorq_amd/csrc --cuda-device-only -S /root/repo/nanorq_amd/csrc/nrq_device.hip -o $D/dev.s 2>/dev/null
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -Wno-pass-failed -I"$R/include" -I"$R/nanorq_amd/csrc" --cuda-device-only -S "$R/nanorq_amd/csrc/nrq_device.hip" -o $D/dev.s 2>/dev/null
 python3 - $D/dev.s <<'PY'
 import re, subprocess, sys
 txt = open(sys.argv[1]).read()

@@ -21,7 +21,7 @@ b.build_lib(out='$REPO/build_var/lib_stop$p.so', extra=['-DNRQ_STOP_AFTER=$p'])"
   wait
   ;;
 run)
-  export TMPDIR=/tmp GPU_MAX_HW_QUEUES=8
+  export TMPDIR=/tmp
   OUT=$REPO/gpurun_out/phase; rm -rf $OUT; mkdir -p $OUT
   CTRS="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_BUSY_CYCLES"
   cd /tmp

@@ -9,7 +9,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import nanorq_amd  # noqa: E402
 from util import loss_pattern  # noqa: E402
 

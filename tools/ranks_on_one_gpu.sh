@@ -9,7 +9,6 @@
 #   gpurun --timeout 2400 -- 'bash tools/ranks_on_one_gpu.sh > gpurun_out/r6_ranks_on_one_gpu.txt 2>&1'
 REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd $REPO
-export GPU_MAX_HW_QUEUES=8
 echo "# host: $(nproc) hardware threads, $(grep -m1 'model name' /proc/cpuinfo | cut -d: -f2 | xargs); NUMA nodes: $(ls -d /sys/devices/system/node/node* 2>/dev/null | wc -l)"
 python - <<'PY'
 from nanorq_amd import shard

@@ -1,5 +1,6 @@
-import sys, time
-sys.path[:0] = ["/root/repo", "/root/repo/tests"]
+import os, sys, time
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [_ROOT, os.path.join(_ROOT, "tests")]
 import numpy as np, nanorq_amd
 import gpu_support as G
 from util import loss_pattern, payload
