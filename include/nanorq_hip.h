@@ -228,6 +228,42 @@ int nrq_move_rows_dev(nrq_ctx *ctx, int stream, const uint64_t *d_pairs, uint32_
 /* the address at which a kernel reaches page-locked host memory (hipHostMalloc'ed or hipHostRegister'ed); 0 = it cannot */
 uint64_t nrq_host_device_address(const void *p);
 
+/* ---- device-resident receiver: packets that are already in device memory (a GPU-direct NIC, another kernel's output, a peer
+ * copy) are classified, placed into their rows and booked on the GPU; only the reception pattern comes down, to the planner ----
+ * A reception is nblk blocks of equal (K, K', T) with SBNs sbn0 .. sbn0+nblk-1 (an object with two block classes is two
+ * receptions fed from the same packets).  Block b's source row e lies at src + b*src_stride + e*T, its repair row q at
+ * rep + b*rep_stride + q*T; d_src / d_rep NULL: allocated from the context's pool (strides K*T and rep_cap*T).  max_esi 0 = 2*K'
+ * (the object layer's default); rep_cap: repair rows per block.  Kp 0 = the row RFC 6330 assigns to K.
+ * A reception belongs to its context and is destroyed before it. */
+typedef struct nrq_rx nrq_rx;
+#define NRQ_RX_TAG_INLINE 1u /* nrq_rx_add flag: each packet starts with the RFC 6330 section 3.2 FEC Payload ID (SBN 8 bits, ESI 24
+                              * bits, network byte order); its payload follows at +4 */
+#define NRQ_RX_FULL 3        /* result code beside NANORQ_SYM_*: a repair symbol that found the block's rep_cap rows used (not marked seen) */
+int nrq_rx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, uint32_t max_esi, uint32_t rep_cap,
+                  void *d_src, size_t src_stride, void *d_rep, size_t rep_stride, nrq_rx **out);
+void nrq_rx_destroy(nrq_rx *rx);
+/* Ingest n packets (enqueue only, on the context's stream): packet k at d_pkts + k*pkt_stride, its tag (nanorq_tag() form) at
+ * d_tags[k], or in the packet with NRQ_RX_TAG_INLINE (d_tags NULL; pkt_stride >= T + 4).  Each packet of the reception's blocks
+ * gets the code nanorq_decoder_add_symbol would give it, in packet order (ERR: ESI > max_esi; IGN: the block has no source gaps;
+ * DUP: the ESI was seen, in an earlier call or earlier in this one; else ADDED, or NRQ_RX_FULL) into d_results[k] (device,
+ * nullable); packets of other SBNs and their result entries are left untouched.  An added source symbol goes to row esi, an
+ * added repair symbol to the block's next repair row: the repair list is in arrival (packet) order. */
+int nrq_rx_add(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results);
+/* per block: missing source symbols and repair rows used (waits for the work enqueued before) */
+int nrq_rx_counts(nrq_rx *rx, uint32_t *h_nlost, uint32_t *h_nrep);
+/* the same plus the lists (each nullable): block b's missing source ESIs, ascending, at h_lost[b*K ..], its repair ESIs in
+ * arrival order at h_rep_esi[b*rep_cap ..] (waits) */
+int nrq_rx_lists(nrq_rx *rx, uint32_t *h_nlost, uint32_t *h_nrep, uint32_t *h_lost, uint32_t *h_rep_esi);
+/* Decode the reception's blocks in place (nrq_decode_blocks_v on the compact lists: the planner, its host fallback and the
+ * lazy use of spare symbols as in every decode).  h_status[b]: 1 = the block is complete (nothing was missing, or recovered:
+ * later packets for it are IGN, as after nanorq_repair_block), 0 = not decodable yet (too few repair symbols, too many for the
+ * rows beyond L, or rank deficient: ingest more and decode again).  h_used (nullable): repair symbols a recovered block used.
+ * h_status is final on return; the solve is enqueued on the context's stream. */
+int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used);
+void *nrq_rx_src(nrq_rx *rx);
+void *nrq_rx_rep(nrq_rx *rx);
+int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the rows keep their bytes */
+
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()
  * synchronises, returns the durations of the launches since the last read/enable in launch order. */

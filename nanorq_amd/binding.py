@@ -73,6 +73,19 @@ def lib():
     L.nrq_ktime_read_intervals.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, u32p]
     L.nrq_timer_start.argtypes = [vp]
     L.nrq_timer_stop_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.nrq_rx_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, sz, vp, sz,
+                                C.POINTER(vp)]
+    L.nrq_rx_destroy.argtypes = [vp]
+    L.nrq_rx_destroy.restype = None
+    L.nrq_rx_add.argtypes = [vp, vp, sz, vp, C.c_uint32, C.c_uint32, vp]
+    L.nrq_rx_counts.argtypes = [vp, u32p, u32p]
+    L.nrq_rx_lists.argtypes = [vp, u32p, u32p, u32p, u32p]
+    L.nrq_rx_decode.argtypes = [vp, ip, u32p]
+    L.nrq_rx_src.argtypes = [vp]
+    L.nrq_rx_src.restype = vp
+    L.nrq_rx_rep.argtypes = [vp]
+    L.nrq_rx_rep.restype = vp
+    L.nrq_rx_reset.argtypes = [vp]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -294,6 +307,109 @@ class Context:
         ms = C.c_float()
         self._chk(self._L.nrq_timer_stop_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+
+RX_TAG_INLINE = 1   # NRQ_RX_TAG_INLINE
+RX_FULL = 3         # NRQ_RX_FULL
+
+
+def _dptr(x):
+    """device address of a torch tensor (data_ptr()) or of a raw integer address; None -> 0"""
+    if x is None:
+        return 0
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+
+class Receiver:
+    """A device-resident reception (nrq_rx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
+    fed with packets that are already in device memory.  Buffers are torch HIP tensors or raw device addresses.  src None: the
+    source rows are a torch tensor of the reception's own (`source`, [nblk, K, T] uint8); rep None: the repair rows come from the
+    context's pool."""
+
+    def __init__(self, ctx, K, T, nblk, rep_cap, sbn0=0, max_esi=0, Kp=0, src=None, src_stride=0, rep=None, rep_stride=0):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.K, self.T, self.nblk, self.rep_cap, self.sbn0 = K, T, nblk, rep_cap, sbn0
+        self._source = None
+        if src is None:
+            import torch
+            self._source = torch.empty((nblk, K, T), dtype=torch.uint8, device="cuda:%d" % ctx.device)
+            src, src_stride = self._source, K * T
+        self._keep = (src, rep)  # the tensors stay alive as long as the reception
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_rx_create(ctx._h, K, Kp, T, nblk, sbn0, max_esi, rep_cap, C.c_void_p(_dptr(src)), src_stride,
+                                       C.c_void_p(_dptr(rep)), rep_stride, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._L.nrq_rx_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def src_ptr(self):
+        return self._L.nrq_rx_src(self._h) or 0
+
+    @property
+    def rep_ptr(self):
+        return self._L.nrq_rx_rep(self._h) or 0
+
+    @property
+    def source(self):
+        """[nblk, K, T] uint8 tensor of the source rows when the reception was created without `src` (None otherwise)."""
+        return self._source
+
+    def add(self, payload, tags=None, inline=False, results=None, n=None, stride=None):
+        """Ingest packets (enqueue only).  payload: [n, stride] uint8 tensor (or an address with n and stride); tags: [n] int32 /
+        uint32 tensor in nanorq_tag() form, or inline=True when each packet starts with the 4-byte FEC Payload ID; results:
+        optional [n] int32 device tensor for the NANORQ_SYM_* / RX_FULL codes."""
+        if hasattr(payload, "data_ptr"):
+            n = payload.shape[0] if n is None else n
+            stride = payload.stride(0) * payload.element_size() if stride is None else stride
+        if n is None or stride is None:
+            raise ValueError("a raw payload address needs n and stride")
+        if inline == (tags is not None):
+            raise ValueError("give either tags or inline=True")
+        self.ctx._chk(self._L.nrq_rx_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(tags)), n,
+                                         RX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+
+    def counts(self):
+        """(missing source symbols, repair rows used) per block, as numpy arrays (waits)."""
+        nl = np.zeros(self.nblk, np.uint32)
+        nr = np.zeros(self.nblk, np.uint32)
+        self.ctx._chk(self._L.nrq_rx_counts(self._h, _u32(nl), _u32(nr)))
+        return nl, nr
+
+    def lists(self):
+        """(lost, rep_esi): per block the ascending missing source ESIs and the repair ESIs in arrival order (waits)."""
+        nl = np.zeros(self.nblk, np.uint32)
+        nr = np.zeros(self.nblk, np.uint32)
+        lost = np.zeros((self.nblk, self.K), np.uint32)
+        resi = np.zeros((self.nblk, self.rep_cap), np.uint32)
+        self.ctx._chk(self._L.nrq_rx_lists(self._h, _u32(nl), _u32(nr), _u32(lost), _u32(resi)))
+        return [lost[b, :nl[b]].copy() for b in range(self.nblk)], [resi[b, :nr[b]].copy() for b in range(self.nblk)]
+
+    def decode(self):
+        """Decode in place; returns (status, used) numpy arrays (1 = block complete; 0 = ingest more and decode again)."""
+        st = np.zeros(self.nblk, np.int32)
+        used = np.zeros(self.nblk, np.uint32)
+        self.ctx._chk(self._L.nrq_rx_decode(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
+        return st, used
+
+    def reset(self):
+        self.ctx._chk(self._L.nrq_rx_reset(self._h))
 
 
 def plan_ops(plan, header=None):

@@ -17,6 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnanorq_hip.so")
 EMU = os.path.join(ROOT, "tests", "emu", "libsolve_emu.so")
 PEMU = os.path.join(ROOT, "tests", "emu", "libplanner_emu.so")
+IEMU = os.path.join(ROOT, "tests", "emu", "libingest_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -120,8 +121,18 @@ def build_planner_emu(force=False):
     return PEMU
 
 
+def build_ingest_emu(force=False):
+    """tests/emu/libingest_emu.so: CPU emulation of the device-resident receiver's ingest kernels (ingest_body.h)."""
+    src = os.path.join(ROOT, "tests", "emu", "ingest_emu.cpp")
+    deps = [src, os.path.join(CSRC, "ingest_body.h")]
+    if force or _newer(IEMU, deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", IEMU, src], check=True)
+    return IEMU
+
+
 if __name__ == "__main__":
     build_lib(force="-f" in sys.argv, verbose=True)
     build_emu(force="-f" in sys.argv)
     build_planner_emu(force="-f" in sys.argv)
+    build_ingest_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

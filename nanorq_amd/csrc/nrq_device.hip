@@ -12,6 +12,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -20,6 +21,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -30,6 +32,7 @@
 #include "rq_math.h"
 #include "solve_body.h"
 #include "planner_body.h"
+#include "ingest_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 
 #define NRQ_LDS_MAX 163840u /* 160 KiB per workgroup on gfx950 */
@@ -3177,6 +3180,455 @@ int nrq_timer_stop_ms(nrq_ctx *ctx, float *ms) {
   HIPCHK(ctx, hipEventRecord(ctx->t1, ctx->stream));
   HIPCHK(ctx, hipEventSynchronize(ctx->t1));
   HIPCHK(ctx, hipEventElapsedTime(ms, ctx->t0, ctx->t1));
+  return 0;
+}
+
+} /* extern "C" */
+
+/* ================================================ device-resident receiver (nrq_rx_*, ingest_body.h) ==== */
+__global__ __launch_bounds__(256) void nrq_ing_init_kernel(ing_rx r) {
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  if (b < r.nblk) { r.gaps[b] = r.K; r.nrep[b] = 0; }
+}
+
+__global__ __launch_bounds__(256) void nrq_ing_first_kernel(ing_rx r, ing_call c) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k < c.n) ing_first(&r, &c, k);
+}
+
+/* one workgroup per block: the max and the count of ing_done_part over the block's K source ESIs */
+__global__ __launch_bounds__(256) void nrq_ing_done_kernel(ing_rx r) {
+  __shared__ uint32_t smx[256], scnt[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x;
+  uint32_t mx = 0, cnt = 0;
+  if (r.gaps[b])
+    for (uint32_t e = t; e < r.K; e += 256u) ing_done_part(&r, b, e, &mx, &cnt);
+  smx[t] = mx;
+  scnt[t] = cnt;
+  __syncthreads();
+  for (uint32_t s = 128; s; s >>= 1) {
+    if (t < s) { smx[t] = max(smx[t], smx[t + s]); scnt[t] += scnt[t + s]; }
+    __syncthreads();
+  }
+  if (t == 0) ing_done_finish(&r, b, smx[0], scnt[0]);
+}
+
+/* one workgroup per tile of ING_TILE packets: repair candidates per block */
+__global__ __launch_bounds__(256) void nrq_ing_hist_kernel(ing_rx r, ing_call c) {
+  __shared__ uint32_t h[256];
+  const uint32_t t = threadIdx.x, k = blockIdx.x * ING_TILE + t;
+  h[t] = 0;
+  __syncthreads();
+  if (k < c.n) {
+    const uint32_t b = ing_cand(&r, &c, k);
+    if (b != ING_NONE) atomicAdd(&h[b], 1u);
+  }
+  __syncthreads();
+  if (t < r.nblk) c.base[(size_t)t * c.ntiles + blockIdx.x] = h[t];
+}
+
+/* one workgroup per block: exclusive scan of the block's tile counts, starting at the rows already used */
+__global__ __launch_bounds__(256) void nrq_ing_scan_kernel(ing_rx r, ing_call c) {
+  __shared__ uint32_t ps[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x, nt = c.ntiles;
+  const uint32_t per = (nt + 255u) / 256u, t0 = min(nt, t * per), t1 = min(nt, t0 + per);
+  uint32_t *base = c.base + (size_t)b * nt;
+  uint32_t s = 0;
+  for (uint32_t i = t0; i < t1; i++) s += base[i];
+  ps[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+    const uint32_t v = t >= d ? ps[t - d] : 0u;
+    __syncthreads();
+    ps[t] += v;
+    __syncthreads();
+  }
+  const uint32_t nrep0 = r.nrep[b], total = ps[255];
+  uint32_t run = nrep0 + ps[t] - s;
+  for (uint32_t i = t0; i < t1; i++) { const uint32_t v = base[i]; base[i] = run; run += v; }
+  __syncthreads(); /* (every thread has read nrep[b]) */
+  if (t == 0) r.nrep[b] = min(nrep0 + total, r.rep_cap);
+}
+
+/* one workgroup per tile: a candidate's rank among its block's candidates in the tile, in packet order (wave by wave: a ballot
+ * per distinct block present in the wave), then the result of every packet */
+__global__ __launch_bounds__(256) void nrq_ing_classify_kernel(ing_rx r, ing_call c) {
+  __shared__ uint32_t wc[4][256];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6, k = blockIdx.x * ING_TILE + t;
+  for (uint32_t i = t; i < 4u * 256u; i += 256u) wc[i >> 8][i & 255u] = 0;
+  __syncthreads();
+  const uint32_t b = k < c.n ? ing_cand(&r, &c, k) : ING_NONE;
+  const bool cand = b != ING_NONE;
+  uint64_t todo = __ballot(cand);
+  uint32_t rank = 0;
+  while (todo) { /* (wave-uniform) */
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t lb = __shfl(b, leader);
+    const bool mine = cand && b == lb;
+    const uint64_t m = __ballot(mine);
+    if (mine) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if ((int)lane == leader) wc[w][lb] = (uint32_t)__popcll(m);
+    todo &= ~m;
+  }
+  __syncthreads();
+  uint32_t row = ING_NONE;
+  if (cand) {
+    row = c.base[(size_t)b * c.ntiles + blockIdx.x] + rank;
+    for (uint32_t w2 = 0; w2 < w; w2++) row += wc[w2][b];
+  }
+  if (k < c.n) ing_classify(&r, &c, k, row);
+}
+
+/* one wave per packet: the payload to its row, 16-byte accesses when both ends and T allow (tag mode with a 16-byte stride),
+ * else 4-byte (an inline header leaves the payload at +4), else bytes; two accesses in flight per lane */
+__global__ __launch_bounds__(256) void nrq_ing_copy_kernel(ing_call c, uint32_t T) {
+  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (k >= c.n) return;
+  uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(c.dst[k]);
+  if (!d) return;
+  const uint8_t *__restrict__ s = c.pkts + (size_t)k * c.pkt_stride + ing_payload_off(&c);
+  const uintptr_t al = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) | T;
+  if ((al & 15u) == 0) {
+    for (uint32_t off = lane * 16u; off < T; off += 2u * 1024u) {
+      const uint4 v0 = *reinterpret_cast<const uint4 *>(s + off);
+      const bool two = off + 1024u < T;
+      uint4 v1;
+      if (two) v1 = *reinterpret_cast<const uint4 *>(s + off + 1024u);
+      *reinterpret_cast<uint4 *>(d + off) = v0;
+      if (two) *reinterpret_cast<uint4 *>(d + off + 1024u) = v1;
+    }
+  } else if ((al & 3u) == 0) {
+    for (uint32_t off = lane * 4u; off < T; off += 2u * 256u) {
+      const uint32_t v0 = *reinterpret_cast<const uint32_t *>(s + off);
+      const bool two = off + 256u < T;
+      uint32_t v1 = 0;
+      if (two) v1 = *reinterpret_cast<const uint32_t *>(s + off + 256u);
+      *reinterpret_cast<uint32_t *>(d + off) = v0;
+      if (two) *reinterpret_cast<uint32_t *>(d + off + 256u) = v1;
+    }
+  } else {
+    for (uint32_t off = lane; off < T; off += 64u) d[off] = s[off];
+  }
+}
+
+__global__ __launch_bounds__(256) void nrq_ing_fold_kernel(ing_rx r, ing_call c) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k < c.n) ing_fold(&r, &c, k);
+}
+
+struct ing_mask { uint32_t w[8]; }; /* a bit per block of the reception (nblk <= 256) */
+
+/* blocks a decode recovered: every source ESI counts as seen from now on (what nanorq_repair_block does to the bitmap) */
+__global__ __launch_bounds__(256) void nrq_ing_mark_kernel(ing_rx r, ing_mask m) {
+  const uint32_t b = blockIdx.x;
+  if (!((m.w[b >> 5] >> (b & 31u)) & 1u)) return;
+  uint32_t *seen = r.seen + (size_t)b * r.bm_words;
+  for (uint32_t w = threadIdx.x; w * 32u < r.K; w += 256u) {
+    const uint32_t nb = min(32u, r.K - w * 32u);
+    seen[w] |= nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+  }
+  if (threadIdx.x == 0) r.gaps[b] = 0;
+}
+
+/* one workgroup per block: the compact lists.  out = gaps[nblk], nrep[nblk], then block by block its repair ESIs (arrival
+ * order) and its missing source ESIs (ascending) */
+__global__ __launch_bounds__(256) void nrq_ing_lists_kernel(ing_rx r, uint32_t *out) {
+  __shared__ uint32_t ps[256];
+  __shared__ uint32_t s_off;
+  const uint32_t b = blockIdx.x, t = threadIdx.x;
+  if (t == 0) {
+    uint32_t off = 2u * r.nblk;
+    for (uint32_t i = 0; i < b; i++) off += r.gaps[i] + r.nrep[i];
+    s_off = off;
+    out[b] = r.gaps[b];
+    out[r.nblk + b] = r.nrep[b];
+  }
+  __syncthreads();
+  const uint32_t nrep = r.nrep[b];
+  uint32_t off = s_off;
+  for (uint32_t q = t; q < nrep; q += 256u) out[off + q] = r.rep_esi[(size_t)b * r.rep_cap + q];
+  off += nrep;
+  const uint32_t *seen = r.seen + (size_t)b * r.bm_words;
+  const uint32_t nw = (r.K + 31u) / 32u;
+  for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
+    const uint32_t w = w0 + t;
+    uint32_t miss = 0;
+    if (w < nw) {
+      const uint32_t nb = min(32u, r.K - w * 32u);
+      miss = ~seen[w] & (nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u));
+    }
+    const uint32_t cnt = (uint32_t)__popc(miss);
+    ps[t] = cnt;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) {
+      const uint32_t v = t >= d ? ps[t - d] : 0u;
+      __syncthreads();
+      ps[t] += v;
+      __syncthreads();
+    }
+    uint32_t o = off + ps[t] - cnt;
+    while (miss) {
+      const uint32_t i = (uint32_t)__ffs(miss) - 1u;
+      out[o++] = w * 32u + i;
+      miss &= miss - 1u;
+    }
+    off += ps[255];
+    __syncthreads();
+  }
+}
+
+struct nrq_rx {
+  nrq_ctx *ctx;
+  ing_rx r;
+  uint32_t Kp;
+  void *state;          /* first | seen | gaps | nrep | live | rep_esi */
+  void *own_src, *own_rep;
+  void *scratch;        /* per-call arrays */
+  size_t scratch_cap;
+  void *lists;          /* nrq_ing_lists_kernel output */
+};
+
+static size_t rx_al(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+static int rx_init_state(nrq_rx *rx) {
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  HIPCHK(ctx, hipMemsetAsync(r.first, 0xFF, (size_t)r.nblk * r.m1 * 4u, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(r.seen, 0, (size_t)r.nblk * r.bm_words * 4u, ctx->stream));
+  hipLaunchKernelGGL(nrq_ing_init_kernel, dim3(1), dim3(256), 0, ctx->stream, r);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, uint32_t max_esi, uint32_t rep_cap,
+                  void *d_src, size_t src_stride, void *d_rep, size_t rep_stride, nrq_rx **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_rx_create: out is NULL");
+  *out = nullptr;
+  uint32_t prm[10];
+  if (nrq_params(K, prm) != 0) return fail(ctx, -1, "nrq_rx_create: K=%u out of range", K);
+  if (Kp == 0) Kp = prm[0];
+  if (Kp < prm[0] || nrq_params(Kp, prm) != 0 || prm[0] != Kp) return fail(ctx, -1, "nrq_rx_create: K'=%u is not a table row for K=%u", Kp, K);
+  if (max_esi == 0) max_esi = 2u * Kp; /* the object layer's default (nanorq_api.c) */
+  if (T == 0 || nblk == 0 || nblk > 256u || sbn0 + nblk > 256u) return fail(ctx, -1, "nrq_rx_create: bad T / nblk / sbn0 (%u %u %u)", T, nblk, sbn0);
+  if (max_esi < Kp || max_esi >= (1u << 24)) return fail(ctx, -1, "nrq_rx_create: max_esi %u outside [K', 2^24)", max_esi);
+  if (rep_cap == 0) return fail(ctx, -1, "nrq_rx_create: rep_cap is 0");
+  if ((d_src && src_stride < (size_t)K * T) || (d_rep && rep_stride < (size_t)rep_cap * T))
+    return fail(ctx, -1, "nrq_rx_create: a row stride is shorter than its block");
+  nrq_rx *rx = new (std::nothrow) nrq_rx();
+  if (!rx) return fail(ctx, -1, "nrq_rx_create: out of host memory");
+  rx->ctx = ctx;
+  rx->Kp = Kp;
+  ing_rx &r = rx->r;
+  r.K = K; r.T = T; r.nblk = nblk; r.sbn0 = sbn0; r.max_esi = max_esi; r.rep_cap = rep_cap;
+  r.m1 = max_esi + 1u;
+  r.bm_words = max_esi / 32u + 1u;
+  int rc = 0;
+  if (!d_src) {
+    src_stride = (size_t)K * T;
+    if ((rc = nrq_dev_alloc(ctx, (size_t)nblk * src_stride, &rx->own_src))) goto bad;
+    d_src = rx->own_src;
+  }
+  if (!d_rep) {
+    rep_stride = (size_t)rep_cap * T;
+    if ((rc = nrq_dev_alloc(ctx, (size_t)nblk * rep_stride, &rx->own_rep))) goto bad;
+    d_rep = rx->own_rep;
+  }
+  r.src = (uint8_t *)d_src; r.src_stride = src_stride;
+  r.rep = (uint8_t *)d_rep; r.rep_stride = rep_stride;
+  {
+    const size_t o_seen = rx_al((size_t)nblk * r.m1 * 4u), o_gaps = o_seen + rx_al((size_t)nblk * r.bm_words * 4u),
+                 o_nrep = o_gaps + rx_al(nblk * 4u), o_live = o_nrep + rx_al(nblk * 4u), o_resi = o_live + rx_al(nblk * 4u),
+                 total = o_resi + rx_al((size_t)nblk * rep_cap * 4u);
+    if ((rc = nrq_dev_alloc(ctx, total, &rx->state))) goto bad;
+    uint8_t *s = (uint8_t *)rx->state;
+    r.first = (uint32_t *)s; r.seen = (uint32_t *)(s + o_seen); r.gaps = (uint32_t *)(s + o_gaps); r.nrep = (uint32_t *)(s + o_nrep);
+    r.live = (uint32_t *)(s + o_live); r.rep_esi = (uint32_t *)(s + o_resi);
+  }
+  if ((rc = nrq_dev_alloc(ctx, ((size_t)2 * nblk + (size_t)nblk * K + (size_t)nblk * rep_cap) * 4u, &rx->lists))) goto bad;
+  if ((rc = rx_init_state(rx))) goto bad;
+  *out = rx;
+  return 0;
+bad:
+  nrq_rx_destroy(rx);
+  return rc;
+}
+
+void nrq_rx_destroy(nrq_rx *rx) {
+  if (!rx) return;
+  nrq_ctx *ctx = rx->ctx;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {rx->own_src, rx->own_rep, rx->state, rx->scratch, rx->lists})
+    if (p) nrq_dev_free(ctx, p);
+  delete rx;
+}
+
+int nrq_rx_reset(nrq_rx *rx) {
+  if (!rx) return -1;
+  HIPCHK(rx->ctx, hipSetDevice(rx->ctx->device));
+  return rx_init_state(rx);
+}
+
+void *nrq_rx_src(nrq_rx *rx) { return rx ? rx->r.src : nullptr; }
+void *nrq_rx_rep(nrq_rx *rx) { return rx ? rx->r.rep : nullptr; }
+
+int nrq_rx_add(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  const bool inl = (flags & NRQ_RX_TAG_INLINE) != 0;
+  if (flags & ~(uint32_t)NRQ_RX_TAG_INLINE) return fail(ctx, -1, "nrq_rx_add: unknown flags 0x%x", flags);
+  if (n == 0) return 0;
+  if (!d_pkts || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_rx_add: bad packets (n=%u)", n);
+  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "nrq_rx_add: give either d_tags or NRQ_RX_TAG_INLINE");
+  if (pkt_stride < (size_t)r.T + (inl ? 4u : 0u)) return fail(ctx, -1, "nrq_rx_add: pkt_stride %zu shorter than a packet", pkt_stride);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ing_call c{};
+  c.pkts = (const uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.tags = d_tags;
+  c.n = n;
+  c.ntiles = (n + ING_TILE - 1u) / ING_TILE;
+  const size_t o_codes = rx_al((size_t)n * 4u), o_fidx = o_codes + rx_al((size_t)n * 4u), o_dst = o_fidx + rx_al((size_t)n * 4u),
+               o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)r.nblk * c.ntiles * 4u);
+  if (rx->scratch_cap < need) {
+    if (rx->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, rx->scratch);
+      rx->scratch = nullptr;
+      rx->scratch_cap = 0;
+    }
+    int rc = nrq_dev_alloc(ctx, need, &rx->scratch);
+    if (rc) return rc;
+    rx->scratch_cap = need;
+  }
+  uint8_t *s = (uint8_t *)rx->scratch;
+  c.tagv = (uint32_t *)s;
+  c.codes = d_results ? d_results : (int32_t *)(s + o_codes);
+  c.fidx = (uint32_t *)(s + o_fidx);
+  c.dst = (uint64_t *)(s + o_dst);
+  c.base = (uint32_t *)(s + o_base);
+  hipStream_t st = ctx->stream;
+  const uint32_t g = (n + 255u) / 256u;
+  hipLaunchKernelGGL(nrq_ing_first_kernel, dim3(g), dim3(256), 0, st, r, c);
+  hipLaunchKernelGGL(nrq_ing_done_kernel, dim3(r.nblk), dim3(256), 0, st, r);
+  hipLaunchKernelGGL(nrq_ing_hist_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c);
+  hipLaunchKernelGGL(nrq_ing_scan_kernel, dim3(r.nblk), dim3(256), 0, st, r, c);
+  hipLaunchKernelGGL(nrq_ing_classify_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c);
+  hipLaunchKernelGGL(nrq_ing_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c, r.T);
+  hipLaunchKernelGGL(nrq_ing_fold_kernel, dim3(g), dim3(256), 0, st, r, c);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int nrq_rx_counts(nrq_rx *rx, uint32_t *h_nlost, uint32_t *h_nrep) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t nb = rx->r.nblk;
+  if (h_nlost) HIPCHK(ctx, hipMemcpyAsync(h_nlost, rx->r.gaps, nb * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_nrep) HIPCHK(ctx, hipMemcpyAsync(h_nrep, rx->r.nrep, nb * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+/* the compact lists, downloaded (counts first, then exactly the list bytes) and spread to strided host arrays */
+static int rx_fetch_lists(nrq_rx *rx, std::vector<uint32_t> &cnt, std::vector<uint32_t> &lists) {
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  hipLaunchKernelGGL(nrq_ing_lists_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, (uint32_t *)rx->lists);
+  HIPCHK(ctx, hipGetLastError());
+  cnt.assign(2u * r.nblk, 0);
+  HIPCHK(ctx, hipMemcpyAsync(cnt.data(), rx->lists, cnt.size() * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  size_t total = 0;
+  for (uint32_t v : cnt) total += v;
+  lists.assign(total ? total : 1, 0);
+  if (total) {
+    HIPCHK(ctx, hipMemcpyAsync(lists.data(), (uint32_t *)rx->lists + 2u * r.nblk, total * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return 0;
+}
+
+int nrq_rx_lists(nrq_rx *rx, uint32_t *h_nlost, uint32_t *h_nrep, uint32_t *h_lost, uint32_t *h_rep_esi) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const ing_rx &r = rx->r;
+  std::vector<uint32_t> cnt, lists;
+  int rc = rx_fetch_lists(rx, cnt, lists);
+  if (rc) return rc;
+  size_t off = 0;
+  for (uint32_t b = 0; b < r.nblk; b++) {
+    const uint32_t ng = cnt[b], nr = cnt[r.nblk + b];
+    if (h_nlost) h_nlost[b] = ng;
+    if (h_nrep) h_nrep[b] = nr;
+    if (h_rep_esi) memcpy(h_rep_esi + (size_t)b * r.rep_cap, lists.data() + off, (size_t)nr * 4u);
+    if (h_lost) memcpy(h_lost + (size_t)b * r.K, lists.data() + off + nr, (size_t)ng * 4u);
+    off += (size_t)ng + nr;
+  }
+  return 0;
+}
+
+int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  if (!h_status) return fail(ctx, -1, "nrq_rx_decode: h_status is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const ing_rx &r = rx->r;
+  std::vector<uint32_t> cnt, lists;
+  int rc = rx_fetch_lists(rx, cnt, lists);
+  if (rc) return rc;
+  /* the blocks that can be decoded now, by the rules of nanorq_repair_block: gaps, at least as many repair symbols as gaps,
+   * and no more extra symbols than the rows beyond L (max_esi - K) */
+  std::vector<uint32_t> sel, lost, resi, nlost, nuse, navail, used;
+  std::vector<uint64_t> sv, rv;
+  std::vector<size_t> offs(r.nblk);
+  uint32_t lost_cap = 1, rep_cap = 1;
+  size_t off = 0;
+  for (uint32_t b = 0; b < r.nblk; b++) {
+    offs[b] = off;
+    const uint32_t ng = cnt[b], nr = cnt[r.nblk + b];
+    off += (size_t)ng + nr;
+    h_status[b] = ng == 0 ? 1 : 0;
+    if (h_used) h_used[b] = 0;
+    if (ng == 0 || nr < ng || nr - ng > r.max_esi - r.K) continue;
+    sel.push_back(b);
+    lost_cap = std::max(lost_cap, ng);
+    rep_cap = std::max(rep_cap, nr);
+  }
+  if (sel.empty()) return 0;
+  const size_t ns = sel.size();
+  lost.assign(ns * lost_cap, 0); resi.assign(ns * rep_cap, 0);
+  nlost.resize(ns); nuse.resize(ns); navail.resize(ns); used.assign(ns, 0); sv.resize(ns); rv.resize(ns);
+  for (size_t i = 0; i < ns; i++) {
+    const uint32_t b = sel[i], ng = cnt[b], nr = cnt[r.nblk + b];
+    memcpy(resi.data() + i * rep_cap, lists.data() + offs[b], (size_t)nr * 4u);
+    memcpy(lost.data() + i * lost_cap, lists.data() + offs[b] + nr, (size_t)ng * 4u);
+    nlost[i] = ng;
+    nuse[i] = nr - ng > 2u ? ng + 2u : nr; /* as the object layer: two extra symbols up front, the rest on demand */
+    navail[i] = nr;
+    sv[i] = (uint64_t)(uintptr_t)(r.src + b * r.src_stride);
+    rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
+  }
+  std::vector<int> st(ns, 0);
+  rc = nrq_decode_blocks_v(ctx, r.K, rx->Kp, r.T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
+                           navail.data(), rep_cap, rv.data(), st.data(), used.data());
+  if (rc) return rc;
+  ing_mask m{};
+  bool any = false;
+  for (size_t i = 0; i < ns; i++) {
+    h_status[sel[i]] = st[i];
+    if (h_used) h_used[sel[i]] = used[i];
+    if (st[i]) { m.w[sel[i] >> 5] |= 1u << (sel[i] & 31u); any = true; }
+  }
+  if (any) {
+    hipLaunchKernelGGL(nrq_ing_mark_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, m);
+    HIPCHK(ctx, hipGetLastError());
+  }
   return 0;
 }
 
