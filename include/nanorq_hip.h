@@ -65,7 +65,8 @@ int nrq_ctx_set_planner(nrq_ctx *ctx, int device_planner);
  * "reserve_cus", "solve_grid", "big_wg", "map_spread", "no_tiny", "tiny_div", "wide_g", "small_waves4", "no_plan_split",
  * "plan_split_force", "plan_small_state", "plan_big_wg", "encplan_dev_min_l", "no_lists" (one solve launch per batch at the width every block fits, no second block list), "lds_max" (tests: LDS bytes a strip
  * image may take when the block lists are formed), "plan_ucap" (inactive columns the device
- * planner has room for; a block that needs more is re-planned on the host).  Results never depend on them, only speed.
+ * planner has room for; a block that needs more is re-planned on the host), "tx_dword" (the sender's emit kernel takes its 4-byte
+ * path also where its 16-byte one applies: A/B runs).  Results never depend on them, only speed.
  * Fault injection for tests: "fail_after" n -- the n-th checked runtime call of the context from now on (allocation, copy,
  * event / stream operation, the error check behind a launch) is not made and fails instead, once (0 = off);
  * "faults_injected" returns the number of failures injected so far.  "fail_after" exists only on a context created with
@@ -263,6 +264,32 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used);
 void *nrq_rx_src(nrq_rx *rx);
 void *nrq_rx_rep(nrq_rx *rx);
 int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the rows keep their bytes */
+
+/* ---- device-resident sender: packets (an optional FEC Payload ID and a payload, at a packet stride) written straight into
+ * device memory -- for a GPU-direct NIC, or a kernel that sends from device memory -- for any list of (SBN, ESI) ----
+ * A transmission is nblk blocks of equal (K, K', T) with SBNs sbn0 .. sbn0+nblk-1 (an object with two block classes is two
+ * transmissions).  Block b's source row e lies at d_src + b*src_stride + e*T (src_stride 0 = K*T); the source rows are read by
+ * nrq_tx_encode AND by every emit (a source packet is a copy of its row), so they must stay unchanged until the last emit has
+ * completed.  The intermediate symbols (nblk * L * T bytes) come from the context's pool.  Kp 0 = the row RFC 6330 assigns to K.
+ * Every call is enqueue-only on the context's stream; a transmission belongs to its context and is destroyed before it.
+ * The payload of (SBN, ESI) is bit-exact with nanorq_encode (ESI < K: source row ESI; else LT(C, ESI + K' - K)). */
+typedef struct nrq_tx nrq_tx;
+#define NRQ_TX_TAG_INLINE 1u /* packet = the RFC 6330 section 3.2 FEC Payload ID (SBN 8 bits, ESI 24 bits, network byte order), then the
+                              * payload at +4 (pkt_stride >= T + 4) */
+int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, const void *d_src, size_t src_stride,
+                  nrq_tx **out);
+void nrq_tx_destroy(nrq_tx *tx);
+/* solve every block (nrq_encode_blocks): the intermediate symbols into the transmission's own buffer; emits before it: -1 */
+int nrq_tx_encode(nrq_tx *tx);
+/* Packet k for tag d_tags[k] (nanorq_tag() form, device memory) at d_pkts + k*pkt_stride (pkt_stride >= T, + 4 inline).
+ * d_results (device, nullable): 0 = written, -1 = SBN outside the transmission (the packet is left untouched). */
+int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
+/* ESIs esi0 .. esi0+n-1 of EVERY block (n * nblk packets, no tag list): order 0 = block-major (packet k -> block k / n, ESI
+ * esi0 + k % n), 1 = interleaved (packet k -> block k % nblk, ESI esi0 + k / nblk); d_tags_out (device, nullable) receives each
+ * packet's tag. */
+int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                      uint32_t *d_tags_out);
+void *nrq_tx_inter(nrq_tx *tx); /* block b's L intermediate symbols at + b*L*T (valid after nrq_tx_encode) */
 
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()

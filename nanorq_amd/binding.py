@@ -86,6 +86,14 @@ def lib():
     L.nrq_rx_rep.argtypes = [vp]
     L.nrq_rx_rep.restype = vp
     L.nrq_rx_reset.argtypes = [vp]
+    L.nrq_tx_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, sz, C.POINTER(vp)]
+    L.nrq_tx_destroy.argtypes = [vp]
+    L.nrq_tx_destroy.restype = None
+    L.nrq_tx_encode.argtypes = [vp]
+    L.nrq_tx_emit.argtypes = [vp, vp, C.c_uint32, vp, sz, C.c_uint32, vp]
+    L.nrq_tx_emit_range.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, vp, sz, C.c_uint32, vp]
+    L.nrq_tx_inter.argtypes = [vp]
+    L.nrq_tx_inter.restype = vp
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -410,6 +418,81 @@ class Receiver:
 
     def reset(self):
         self.ctx._chk(self._L.nrq_rx_reset(self._h))
+
+
+TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
+
+
+class Sender:
+    """A device-resident transmission (nrq_tx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
+    whose packets are written straight into device memory.  src: the source rows (a torch HIP tensor or a raw device address),
+    block b at src + b*src_stride (0 = K*T); they are read by encode() and by every emit, so they must not change until the last
+    emit has completed.  Every call is enqueue-only on the context's stream."""
+
+    def __init__(self, ctx, K, T, nblk, src, src_stride=0, sbn0=0, Kp=0):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.K, self.T, self.nblk, self.sbn0 = K, T, nblk, sbn0
+        self._keep = src  # the tensor stays alive as long as the transmission
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_tx_create(ctx._h, K, Kp, T, nblk, sbn0, C.c_void_p(_dptr(src)), src_stride, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._L.nrq_tx_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def inter_ptr(self):
+        """device address of the intermediate symbols (block b's L rows at + b*L*T)"""
+        return self._L.nrq_tx_inter(self._h) or 0
+
+    def stride(self, inline=False):
+        """the packet stride of out=None: T, or T + 4 rounded up to 16 with the inline header"""
+        return (self.T + 4 + 15) // 16 * 16 if inline else self.T
+
+    def _out(self, n, inline, out):
+        if out is not None:
+            return out, out.stride(0) * out.element_size()
+        import torch
+        out = torch.empty((n, self.stride(inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        return out, out.shape[1]
+
+    def encode(self):
+        """solve every block (the intermediate symbols stay in device memory); needed before any emit"""
+        self.ctx._chk(self._L.nrq_tx_encode(self._h))
+
+    def emit(self, tags, out=None, inline=False, results=None):
+        """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form) in row k of out ([n, stride] uint8 device
+        tensor; None: a new one).  results: optional [n] int32 device tensor (0 written, -1 SBN outside the transmission, whose
+        packet is left untouched).  Returns out."""
+        n = int(tags.shape[0])
+        out, stride = self._out(n, inline, out)
+        self.ctx._chk(self._L.nrq_tx_emit(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
+                                          TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+        return out
+
+    def emit_range(self, esi0, n, interleave=True, inline=False, out=None, tags_out=None):
+        """ESIs esi0 .. esi0+n-1 of every block: n * nblk packets, interleaved (packet k: block k % nblk, ESI esi0 + k // nblk) or
+        block-major (block k // n, ESI esi0 + k % n).  tags_out: optional [n * nblk] int32 device tensor for each packet's tag.
+        Returns out ([n * nblk, stride] uint8)."""
+        out, stride = self._out(n * self.nblk, inline, out)
+        self.ctx._chk(self._L.nrq_tx_emit_range(self._h, esi0, n, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
+                                                TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
+        return out
 
 
 def plan_ops(plan, header=None):

@@ -18,6 +18,7 @@ LIB = os.path.join(HERE, "libnanorq_hip.so")
 EMU = os.path.join(ROOT, "tests", "emu", "libsolve_emu.so")
 PEMU = os.path.join(ROOT, "tests", "emu", "libplanner_emu.so")
 IEMU = os.path.join(ROOT, "tests", "emu", "libingest_emu.so")
+XEMU = os.path.join(ROOT, "tests", "emu", "libemit_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -130,9 +131,19 @@ def build_ingest_emu(force=False):
     return IEMU
 
 
+def build_emit_emu(force=False):
+    """tests/emu/libemit_emu.so: CPU emulation of the device-resident sender's emit kernels (emit_body.h)."""
+    src = os.path.join(ROOT, "tests", "emu", "emit_emu.cpp")
+    deps = [src, os.path.join(CSRC, "emit_body.h"), os.path.join(CSRC, "rq_math.h")]
+    if force or _newer(XEMU, deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", XEMU, src], check=True)
+    return XEMU
+
+
 if __name__ == "__main__":
     build_lib(force="-f" in sys.argv, verbose=True)
     build_emu(force="-f" in sys.argv)
     build_planner_emu(force="-f" in sys.argv)
     build_ingest_emu(force="-f" in sys.argv)
+    build_emit_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

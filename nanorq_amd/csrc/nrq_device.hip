@@ -33,7 +33,9 @@
 #include "solve_body.h"
 #include "planner_body.h"
 #include "ingest_body.h"
+#include "emit_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
+static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
 
 #define NRQ_LDS_MAX 163840u /* 160 KiB per workgroup on gfx950 */
 /* ... handed out in pieces of 320 dwords (LLVM getLdsDwGranularity for the 160 KiB parts): what a workgroup asks for is rounded
@@ -1098,6 +1100,7 @@ struct Tuning {
   bool plan_split_force = false; /* "plan_split_force": every block planned in two parts + helper kernels (tests) */
   bool no_plan_split = false;  /* NRQ_NO_PLAN_SPLIT: big blocks planned by one kernel (no helper kernels for the HDPC fold / W transposition) */
   bool no_plan_stream = false; /* NRQ_NO_PLAN_STREAM: planner kernel on the caller's stream (no overlap with the solve before it) */
+  bool tx_dword = false;       /* "tx_dword" (A/B runs): the emit kernels' 4-byte path also where the 16-byte one applies */
   bool plan_no_wg128 = false;  /* NRQ_PLAN_NO_WG128: the smallest blocks' planner workgroups stay at 256 threads */
   bool plan_wrong_instance = false; /* "plan_wrong_instance" (tests): blocks whose peeling state fits the LDS are given to the planner instance for
                                      * the others -- pl_init_a must notice (PL_PEEL_FORM_OK) and the blocks go to the host planner */
@@ -2154,6 +2157,7 @@ int nrq_ctx_set_option(nrq_ctx *ctx, const char *name, long long value) {
   else if (n == "plan_ucap") t.plan_ucap = (uint32_t)value;
   else if (n == "plan_wrong_instance") t.plan_wrong_instance = value != 0;
   else if (n == "plan_no_wg128") t.plan_no_wg128 = value != 0;
+  else if (n == "tx_dword") t.tx_dword = value != 0;
   else if (n == "fail_after" && ctx->fault_inject_armed) ctx->fail_after = value > 0 ? value : 0;
   else if (n == "faults_injected") return (int)ctx->faults_injected; /* (read: injected failures so far) */
   else return fail(ctx, -1, "unknown option %s", name);
@@ -3630,6 +3634,280 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
     HIPCHK(ctx, hipGetLastError());
   }
   return 0;
+}
+
+} /* extern "C" */
+
+/* ================================================ device-resident sender (nrq_tx_*, emit_body.h) ==== */
+#define TX_WAVES 4u        /* waves per emit workgroup */
+#define TX_BIN_TILE 4096u  /* packets per workgroup of the bucketing passes */
+
+/* payload paths of the emit kernel, chosen per call from the alignment of the rows, the packets and T */
+enum : int {
+  TX_V16 = 0,       /* 16-byte loads and stores (payload at +0) */
+  TX_V16_SHIFT = 1, /* 16-byte loads and stores under an inline header: the payload moves up one dword across the lanes */
+  TX_DWORD = 2,     /* 4-byte loads and stores */
+  TX_BYTE = 3
+};
+
+/* One wave per TX_WAVE_PKTS work items, in block-major order: each lane builds the column list of one item into LDS, then the
+ * wave writes the items' packets one after the other, a 16/4/1-byte word of the payload per lane (the XOR of the item's rows,
+ * four rows in flight). */
+template <int MODE>
+__global__ __launch_bounds__(256) void nrq_tx_emit_kernel(tx_blk t, tx_call c) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
+  if (w0 + lane < c.n) {
+    const uint32_t k = tx_work_packet(&t, &c, (uint32_t)(w0 + lane));
+    const uint32_t tag = k < c.n ? tx_packet_tag(&t, &c, k) : 0u;
+    const uint32_t n = k < c.n ? tx_rows(&t, tag, s_cols[wv][lane]) : 0u; /* (k < n always: the work order is a permutation) */
+    s_n[wv][lane] = n;
+    s_tag[wv][lane] = tag;
+    s_k[wv][lane] = k;
+    if (k < c.n && c.results) c.results[k] = n ? 0 : -1;
+    if (k < c.n && c.tags_out) c.tags_out[k] = tag;
+  }
+  __syncthreads();
+  const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
+  const uint32_t T = t.T;
+  for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
+    const uint32_t n = s_n[wv][i];
+    if (!n) continue; /* foreign SBN: the packet stays untouched */
+    const uint32_t tag = s_tag[wv][i];
+    const uint32_t *cols = s_cols[wv][i];
+    const uint8_t *__restrict__ base = tx_base(&t, tag);
+    uint8_t *__restrict__ P = c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride;
+    if constexpr (MODE == TX_V16) {
+      for (uint32_t off = lane * 16u; off < T; off += 64u * 16u)
+        *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols, n, off);
+    } else if constexpr (MODE == TX_V16_SHIFT) {
+      /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-1 .. 4j+2: the previous lane's .w (the header for j = 0, the
+       * wave's last lane of the previous round for its first lane), then this chunk's .x .y .z; the last .w goes to +T */
+      const uint32_t nch = T >> 4;
+      uint32_t carry = tx_header_word(tag);
+      for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
+        const uint32_t j = j0 + lane;
+        const bool act = j < nch;
+        tx_u128 v{0u, 0u, 0u, 0u};
+        if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
+        uint32_t prev = __shfl_up(v.w, 1u);
+        if (lane == 0) prev = carry;
+        if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
+        if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + T) = v.w;
+        carry = __shfl(v.w, 63);
+      }
+    } else if constexpr (MODE == TX_DWORD) {
+      if (c.inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
+      uint8_t *D = P + (c.inl ? 4u : 0u);
+      for (uint32_t off = lane * 4u; off < T; off += 64u * 4u)
+        *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols, n, off);
+    } else {
+      if (c.inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
+      uint8_t *D = P + (c.inl ? 4u : 0u);
+      for (uint32_t off = lane; off < T; off += 64u) D[off] = tx_gather<uint8_t>(base, T, cols, n, off);
+    }
+  }
+}
+
+/* tag-list bucketing: packets per bucket (tx_bin), a histogram in LDS per tile of TX_BIN_TILE packets, added to cnt[] */
+__global__ __launch_bounds__(256) void nrq_tx_hist_kernel(tx_blk t, const uint32_t *tags, uint32_t n, uint32_t *cnt) {
+  __shared__ uint32_t h[257];
+  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) h[i] = 0;
+  __syncthreads();
+  const uint32_t k0 = blockIdx.x * TX_BIN_TILE, k1 = min(n, k0 + TX_BIN_TILE);
+  for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256u) atomicAdd(&h[tx_bin(&t, tags[k])], 1u);
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u)
+    if (h[i]) atomicAdd(&cnt[i], h[i]);
+}
+
+/* counts -> exclusive offsets, in place (nblk + 1 <= 257 buckets: one lane) */
+__global__ __launch_bounds__(64) void nrq_tx_scan_kernel(uint32_t nbins, uint32_t *cnt) {
+  if (threadIdx.x) return;
+  uint32_t run = 0;
+  for (uint32_t i = 0; i < nbins; i++) { const uint32_t v = cnt[i]; cnt[i] = run; run += v; }
+}
+
+/* each tile reserves its packets' places in every bucket (one atomic per bucket and tile), then writes order[] */
+__global__ __launch_bounds__(256) void nrq_tx_place_kernel(tx_blk t, const uint32_t *tags, uint32_t n, uint32_t *cursor, uint32_t *order) {
+  __shared__ uint32_t h[257], base[257];
+  constexpr uint32_t PER = TX_BIN_TILE / 256u;
+  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) h[i] = 0;
+  __syncthreads();
+  const uint32_t k0 = blockIdx.x * TX_BIN_TILE;
+  uint32_t bin[PER], rank[PER];
+#pragma unroll
+  for (uint32_t r = 0; r < PER; r++) {
+    const uint32_t k = k0 + r * 256u + threadIdx.x;
+    bin[r] = k < n ? tx_bin(&t, tags[k]) : TX_NONE;
+    rank[r] = bin[r] != TX_NONE ? atomicAdd(&h[bin[r]], 1u) : 0u;
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) base[i] = h[i] ? atomicAdd(&cursor[i], h[i]) : 0u;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < PER; r++)
+    if (bin[r] != TX_NONE) order[base[bin[r]] + rank[r]] = k0 + r * 256u + threadIdx.x;
+}
+
+struct nrq_tx {
+  nrq_ctx *ctx;
+  tx_blk t;
+  void *own_inter;
+  bool encoded;
+  void *scratch; /* list mode: bucket counts, then the work order */
+  size_t scratch_cap;
+};
+
+extern "C" {
+
+int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, const void *d_src, size_t src_stride,
+                  nrq_tx **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_tx_create: out is NULL");
+  *out = nullptr;
+  uint32_t prm[10];
+  if (nrq_params(K, prm) != 0) return fail(ctx, -1, "nrq_tx_create: K=%u out of range", K);
+  if (Kp == 0) Kp = prm[0];
+  if (Kp < prm[0] || nrq_params(Kp, prm) != 0 || prm[0] != Kp) return fail(ctx, -1, "nrq_tx_create: K'=%u is not a table row for K=%u", Kp, K);
+  if (T == 0 || nblk == 0 || nblk > 256u || sbn0 + nblk > 256u) return fail(ctx, -1, "nrq_tx_create: bad T / nblk / sbn0 (%u %u %u)", T, nblk, sbn0);
+  if (!d_src) return fail(ctx, -1, "nrq_tx_create: d_src is NULL");
+  if (src_stride == 0) src_stride = (size_t)K * T;
+  if (src_stride < (size_t)K * T) return fail(ctx, -1, "nrq_tx_create: src_stride %zu shorter than a block", src_stride);
+  nrq_tx *tx = new (std::nothrow) nrq_tx();
+  if (!tx) return fail(ctx, -1, "nrq_tx_create: out of host memory");
+  tx->ctx = ctx;
+  tx_blk &t = tx->t;
+  int rc = block_params(ctx, K, Kp, &t.p);
+  if (rc) { delete tx; return rc; }
+  t.K = K; t.T = T; t.nblk = nblk; t.sbn0 = sbn0;
+  t.src = (const uint8_t *)d_src; t.src_stride = src_stride;
+  t.inter_stride = (uint64_t)t.p.L * T;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)nblk * t.inter_stride, &tx->own_inter))) {
+    delete tx;
+    return rc;
+  }
+  t.inter = (const uint8_t *)tx->own_inter;
+  *out = tx;
+  return 0;
+}
+
+void nrq_tx_destroy(nrq_tx *tx) {
+  if (!tx) return;
+  nrq_ctx *ctx = tx->ctx;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {tx->own_inter, tx->scratch})
+    if (p) nrq_dev_free(ctx, p);
+  delete tx;
+}
+
+int nrq_tx_encode(nrq_tx *tx) {
+  if (!tx) return -1;
+  const tx_blk &t = tx->t;
+  tx->encoded = false;
+  const int rc = nrq_encode_blocks(tx->ctx, t.K, t.p.Kp, t.T, t.nblk, t.src, t.src_stride, (void *)t.inter, t.inter_stride, 0, nullptr,
+                                   nullptr, 0);
+  tx->encoded = rc == 0;
+  return rc;
+}
+
+void *nrq_tx_inter(nrq_tx *tx) { return tx ? (void *)tx->t.inter : nullptr; }
+
+} /* extern "C" */
+
+/* checks shared by both emit calls, then the launch of the emit kernel at the widest path the addresses allow */
+static int tx_check(nrq_tx *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
+  nrq_ctx *ctx = tx->ctx;
+  if (!tx->encoded) return fail(ctx, -1, "%s: the transmission is not encoded (nrq_tx_encode)", who);
+  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
+  if (pkt_stride < (size_t)tx->t.T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
+  return 0;
+}
+
+static int tx_launch(nrq_tx *tx, tx_call &c) {
+  nrq_ctx *ctx = tx->ctx;
+  const tx_blk &t = tx->t;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | t.T | reinterpret_cast<uintptr_t>(t.src) | t.src_stride |
+                       reinterpret_cast<uintptr_t>(t.inter);
+  const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
+  if ((al & 15u) == 0 && !ctx->tune.tx_dword) {
+    if (c.inl) hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_V16_SHIFT>, grid, wg, 0, ctx->stream, t, c);
+    else hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_V16>, grid, wg, 0, ctx->stream, t, c);
+  } else if ((al & 3u) == 0) {
+    hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_DWORD>, grid, wg, 0, ctx->stream, t, c);
+  } else {
+    hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_BYTE>, grid, wg, 0, ctx->stream, t, c);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = tx_check(tx, "nrq_tx_emit", d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit: bad tags (n=%u)", n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const tx_blk &t = tx->t;
+  const uint32_t nbins = t.nblk + 1u;
+  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
+  if (tx->scratch_cap < need) {
+    if (tx->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, tx->scratch);
+      tx->scratch = nullptr;
+      tx->scratch_cap = 0;
+    }
+    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
+    tx->scratch_cap = need;
+  }
+  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, t, d_tags, n, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, t, d_tags, n, cnt, order);
+  HIPCHK(ctx, hipGetLastError());
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.tags = d_tags;
+  c.order = order;
+  c.results = d_results;
+  return tx_launch(tx, c);
+}
+
+int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = tx_check(tx, "nrq_tx_emit_range", d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (order != 0 && order != 1) return fail(ctx, -1, "nrq_tx_emit_range: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
+  if (n == 0) return 0;
+  if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "nrq_tx_emit_range: ESIs %u + %u reach past 2^24", esi0, n);
+  if ((uint64_t)n * tx->t.nblk > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit_range: %u packets per block is too many", n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n * tx->t.nblk;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.esi0 = esi0;
+  c.per_blk = n;
+  c.interleave = (uint32_t)order;
+  c.tags_out = d_tags_out;
+  return tx_launch(tx, c);
 }
 
 } /* extern "C" */

@@ -1,0 +1,81 @@
+"""CPU tier of the device-resident sender (nrq_tx_*): the emulated emit kernels (tests/emu/emit_emu.cpp running the bodies of
+nanorq_amd/csrc/emit_body.h) on the oracle's intermediate symbols, against the oracle's source and repair symbols byte for byte:
+tag lists mixing source ESIs, repair ESIs near K and ESIs near 2^24, foreign SBNs, inline headers, several strides, and both
+emit_range orders against the equivalent tag list."""
+import numpy as np
+import pytest
+
+import nanorq_amd
+from tx_support import (FILL, check_packets, emu_emit, emu_emit_range, oracle_blocks, random_tags, range_tags)
+
+
+def _setup(orc, K, T, nblk, Kp, tags, seed, src_pad=0):
+    rng = np.random.default_rng(seed)
+    src = rng.integers(0, 256, (nblk, K * T + src_pad), dtype=np.uint8)
+    reps = [[int(t) & 0xFFFFFF for t in tags if (int(t) >> 24) == sb and (int(t) & 0xFFFFFF) >= K] for sb in range(nblk)]
+    blocks = oracle_blocks(orc, src, K, T, Kp, reps)
+    inter = np.stack([b[0] for b in blocks])
+    return src, blocks, inter
+
+
+def _stride(kind, T, inline):
+    need = T + (4 if inline else 0)
+    return {"tight": need, "pad4": need + 4, "r16": (need + 15) // 16 * 16, "odd": need + 3 if need % 2 == 0 else need + 2}[kind]
+
+
+@pytest.mark.parametrize("K,T,nblk,sbn0,kp_of", [
+    (10, 16, 2, 0, None),
+    (100, 13, 3, 5, None),       # K' > K, T not a multiple of 4
+    (100, 16, 2, 1, 1000),       # an object's larger K' (block 0's row coded into a short block)
+    (1000, 20, 2, 254, None),    # SBNs up to 255, T a multiple of 4 but not of 16
+    (300, 48, 3, 0, None),
+])
+@pytest.mark.parametrize("inline", [False, True])
+@pytest.mark.parametrize("stride_kind", ["tight", "pad4", "r16", "odd"])
+def test_emulated_emit_matches_oracle(orc, K, T, nblk, sbn0, kp_of, inline, stride_kind):
+    Kp = nanorq_amd.params(kp_of or K)["Kp"]
+    rng = np.random.default_rng(K + T + nblk)
+    tags = random_tags(rng, K, nblk, sbn0, 300)
+    local = np.array([((int(t) >> 24) - sbn0) << 24 | (int(t) & 0xFFFFFF) for t in tags], np.int64)
+    src, blocks, inter = _setup(orc, K, T, nblk, Kp, [t for t in local if 0 <= (t >> 24) < nblk], seed=K)
+    stride = _stride(stride_kind, T, inline)
+    pk, res = emu_emit(K, Kp, T, src, inter, tags, inline, stride, sbn0=sbn0)
+    assert set(res.tolist()) == {0, -1}
+    check_packets(pk, tags, src, blocks, K, T, nblk, sbn0, inline, res)
+
+
+def test_source_stride_longer_than_a_block(orc):
+    K, T, nblk, Kp = 100, 12, 3, nanorq_amd.params(100)["Kp"]
+    tags = random_tags(np.random.default_rng(2), K, nblk, 0, 200, foreign=False)
+    src, blocks, inter = _setup(orc, K, T, nblk, Kp, tags, seed=3, src_pad=40)
+    pk, res = emu_emit(K, Kp, T, src, inter, tags, True, T + 4)
+    check_packets(pk, tags, src, blocks, K, T, nblk, 0, True, res)
+
+
+@pytest.mark.parametrize("interleave", [False, True])
+@pytest.mark.parametrize("K,T,nblk,sbn0,esi0,n,inline,stride", [
+    (10, 16, 3, 0, 0, 25, True, 32),        # source and repair ESIs in one range
+    (100, 13, 4, 7, 90, 33, False, 15),
+    (100, 16, 5, 0, (1 << 24) - 9, 9, True, 21),  # the last ESIs there are
+])
+def test_emulated_range_equals_tag_list(orc, K, T, nblk, sbn0, esi0, n, inline, stride, interleave):
+    Kp = nanorq_amd.params(K)["Kp"]
+    want_tags = range_tags(nblk, sbn0, esi0, n, interleave)
+    local = [((int(t) >> 24) - sbn0) << 24 | (int(t) & 0xFFFFFF) for t in want_tags]
+    src, blocks, inter = _setup(orc, K, T, nblk, Kp, local, seed=n)
+    pk_r, tg = emu_emit_range(K, Kp, T, src, inter, esi0, n, interleave, inline, stride, sbn0=sbn0)
+    assert np.array_equal(tg, want_tags)
+    pk_l, res = emu_emit(K, Kp, T, src, inter, want_tags, inline, stride, sbn0=sbn0)
+    assert (res == 0).all()
+    assert np.array_equal(pk_r, pk_l)
+    check_packets(pk_r, want_tags, src, blocks, K, T, nblk, sbn0, inline)
+
+
+def test_emulated_emit_leaves_other_packets_alone(orc):
+    K, T, nblk, sbn0, Kp = 10, 8, 1, 3, nanorq_amd.params(10)["Kp"]
+    tags = np.array([(2 << 24) | 1, (3 << 24) | 12, (4 << 24) | 0, (3 << 24) | 2], np.uint32)
+    src, blocks, inter = _setup(orc, K, T, nblk, Kp, [12], seed=1)
+    pk, res = emu_emit(K, Kp, T, src, inter, tags, False, T, sbn0=sbn0)
+    assert res.tolist() == [-1, 0, -1, 0]
+    assert (pk[0] == FILL).all() and (pk[2] == FILL).all()
+    check_packets(pk, tags, src, blocks, K, T, nblk, sbn0, False, res)
