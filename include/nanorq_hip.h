@@ -291,6 +291,66 @@ int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_
                       uint32_t *d_tags_out);
 void *nrq_tx_inter(nrq_tx *tx); /* block b's L intermediate symbols at + b*L*T (valid after nrq_tx_encode) */
 
+/* ---- whole objects (RFC 6330 section 4.4.1.2) on the device: an object of F bytes and its OTI, sent and received through the
+ * sender and receiver above without the caller partitioning it ----
+ * The object is Z source blocks: ZL blocks of KL symbols (SBN 0 .. ZL-1), then ZS of KS (SBN ZL .. Z-1); each block is coded
+ * with K' = KpL / KpS (block 0's row for both classes unless NANORQ_EXT_PER_BLOCK_KP).  A symbol of T bytes is N sub-symbols,
+ * NL of TL bytes then NS of TS bytes; sub-block j of block b is one stretch of K_b * T_j bytes of the object, and row e of the
+ * block is the concatenation of row e of its sub-blocks (nanorq_api.c's symbol_offset).  Bytes of the object at offset >= F
+ * read as zero.  These are the parameters nanorq_encoder_new_ext / nanorq_decoder_new_ext derive, computed without a GPU. */
+typedef struct nrq_obj_params {
+  uint64_t F;
+  uint32_t T, Al, Z, N, Kt;
+  uint32_t ZL, KL, KpL;  /* first block class (ZL may be 0) */
+  uint32_t ZS, KS, KpS;  /* second block class */
+  uint32_t NL, TL, NS, TS; /* sub-blocks: NL of TL bytes, then NS of TS bytes (NL may be 0) */
+  uint32_t flags;        /* NANORQ_EXT_* */
+  uint32_t max_esi;      /* 2 * K' of block 0, the decoder's default */
+  uint64_t oti_common;   /* nanorq_oti_common / nanorq_oti_scheme_specific of such an object */
+  uint32_t oti_specific;
+} nrq_obj_params;
+/* the parameters of nanorq_encoder_new_ext(F, T, K, Z, N, Al, flags); -1 where it returns NULL */
+int nrq_obj_params_enc(uint64_t F, uint32_t T, uint32_t K, uint32_t Z, uint32_t N, uint32_t Al, uint32_t flags, nrq_obj_params *out);
+/* the parameters of nanorq_decoder_new_ext(common, specific, flags); -1 where it returns NULL */
+int nrq_obj_params_oti(uint64_t common, uint32_t specific, uint32_t flags, nrq_obj_params *out);
+
+/* The layout step alone (enqueue only): to_obj 0 = the object (F bytes at d_obj) into the blocks' row images (Kt * T bytes at d_rows,
+ * block b's at + its object offset; bytes past F read as zero), 1 = the row images into the object (nothing at or past F written). */
+int nrq_obj_layout(nrq_ctx *ctx, const nrq_obj_params *prm, void *d_obj, void *d_rows, int to_obj);
+
+/* Object sender.  d_obj: the object, F bytes of device memory, as it is.  N = 1: the blocks are read in place, only a last block
+ * that the object does not fill is staged (zero-padded) in the context's pool; N > 1: the blocks' row images are laid out from the
+ * object into the pool by a kernel.  In both cases the object must stay unchanged until the last emit has completed.
+ * Every call but create / destroy / oti is enqueue-only on the context's stream; the sender belongs to its context. */
+typedef struct nrq_otx nrq_otx;
+int nrq_otx_create(nrq_ctx *ctx, const nrq_obj_params *prm, const void *d_obj, nrq_otx **out);
+void nrq_otx_destroy(nrq_otx *tx);
+int nrq_otx_encode(nrq_otx *tx); /* every block (nrq_encode_blocks per class); emits before it: -1 */
+/* Packet k for tag d_tags[k] over all blocks of the object, as nrq_tx_emit (payloads bit-exact with nanorq_encode of
+ * nanorq_encoder_new_ext with the same arguments); d_results[k]: 0 written, -1 SBN >= Z (packet left untouched). */
+int nrq_otx_emit(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
+/* ESIs 0 .. K_b + nrep - 1 of every block b (its source symbols, then nrep repair symbols): sum_b (K_b + nrep) packets.
+ * order 0 = block-major (block 0's packets, then block 1's, ...), 1 = interleaved (the pairs (sbn, i) with i < K_sbn + nrep
+ * sorted by (i, sbn)).  d_tags_out (device, nullable) receives each packet's tag. */
+int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out);
+int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific);
+
+/* Object receiver: the blocks' row images in the context's pool, one reception (nrq_rx) per block class, both with the
+ * object's max_esi.  rep_cap: repair rows per block. */
+typedef struct nrq_orx nrq_orx;
+int nrq_orx_create(nrq_ctx *ctx, const nrq_obj_params *prm, uint32_t rep_cap, nrq_orx **out);
+void nrq_orx_destroy(nrq_orx *rx);
+/* as nrq_rx_add over the whole object: every packet gets the code nanorq_decoder_add_symbol of a decoder made from the same OTI
+ * and flags would give it, in packet order, or NRQ_RX_FULL.  (SBN >= Z: NANORQ_SYM_ERR for an ESI above max_esi, else
+ * NANORQ_SYM_IGN -- the object layer's block of no symbols.) */
+int nrq_orx_add(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results);
+int nrq_orx_counts(nrq_orx *rx, uint32_t *h_nlost, uint32_t *h_nrep); /* Z entries each */
+int nrq_orx_decode(nrq_orx *rx, int *h_status, uint32_t *h_used);    /* as nrq_rx_decode, Z entries */
+/* every complete block into d_out (F bytes, device) in the object's layout; bytes past F and the bytes of incomplete blocks are
+ * left untouched.  Returns the number of blocks still incomplete (>= 0), or < 0 on error.  Waits for the counts, enqueues the
+ * copy. */
+int nrq_orx_write(nrq_orx *rx, void *d_out);
+
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()
  * synchronises, returns the durations of the launches since the last read/enable in launch order. */

@@ -12,6 +12,16 @@ class NrqError(RuntimeError):
     pass
 
 
+class ObjParams(C.Structure):
+    """nrq_obj_params (include/nanorq_hip.h): an object's partition into blocks and sub-blocks, K' per class, max_esi, OTI"""
+    _fields_ = [("F", C.c_uint64)] + [(n, C.c_uint32) for n in
+                                       ("T", "Al", "Z", "N", "Kt", "ZL", "KL", "KpL", "ZS", "KS", "KpS", "NL", "TL", "NS", "TS",
+                                        "flags", "max_esi")] + [("oti_common", C.c_uint64), ("oti_specific", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class CallStats(C.Structure):
     _fields_ = [("plan_ms", C.c_double), ("host_ms", C.c_double), ("strip_bytes", C.c_uint32),
                 ("lds_bytes", C.c_uint32), ("grid", C.c_uint32), ("planner", C.c_uint32),
@@ -94,6 +104,24 @@ def lib():
     L.nrq_tx_emit_range.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int, vp, sz, C.c_uint32, vp]
     L.nrq_tx_inter.argtypes = [vp]
     L.nrq_tx_inter.restype = vp
+    opp = C.POINTER(ObjParams)
+    L.nrq_obj_params_enc.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, opp]
+    L.nrq_obj_params_oti.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, opp]
+    L.nrq_obj_layout.argtypes = [vp, opp, vp, vp, C.c_int]
+    L.nrq_otx_create.argtypes = [vp, opp, vp, C.POINTER(vp)]
+    L.nrq_otx_destroy.argtypes = [vp]
+    L.nrq_otx_destroy.restype = None
+    L.nrq_otx_encode.argtypes = [vp]
+    L.nrq_otx_emit.argtypes = [vp, vp, C.c_uint32, vp, sz, C.c_uint32, vp]
+    L.nrq_otx_emit_all.argtypes = [vp, C.c_uint32, C.c_int, vp, sz, C.c_uint32, vp]
+    L.nrq_otx_oti.argtypes = [vp, C.POINTER(C.c_uint64), u32p]
+    L.nrq_orx_create.argtypes = [vp, opp, C.c_uint32, C.POINTER(vp)]
+    L.nrq_orx_destroy.argtypes = [vp]
+    L.nrq_orx_destroy.restype = None
+    L.nrq_orx_add.argtypes = [vp, vp, sz, vp, C.c_uint32, C.c_uint32, vp]
+    L.nrq_orx_counts.argtypes = [vp, u32p, u32p]
+    L.nrq_orx_decode.argtypes = [vp, ip, u32p]
+    L.nrq_orx_write.argtypes = [vp, vp]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -493,6 +521,185 @@ class Sender:
         self.ctx._chk(self._L.nrq_tx_emit_range(self._h, esi0, n, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
                                                 TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
         return out
+
+
+EXT_RFC_OTI = 1       # NANORQ_EXT_RFC_OTI (include/nanorq_ext.h)
+EXT_PER_BLOCK_KP = 2  # NANORQ_EXT_PER_BLOCK_KP
+EXT_SUBBLOCKS = 4     # NANORQ_EXT_SUBBLOCKS
+
+
+def obj_params_enc(F, T, K=0, Z=0, N=1, Al=8, flags=0):
+    """the object parameters nanorq_encoder_new_ext(F, T, K, Z, N, Al, flags) derives (ObjParams), or None where it refuses"""
+    p = ObjParams()
+    return p if lib().nrq_obj_params_enc(F, T, K, Z, N, Al, flags, C.byref(p)) == 0 else None
+
+
+def obj_params_oti(common, specific, flags=0):
+    """the object parameters nanorq_decoder_new_ext(common, specific, flags) derives (ObjParams), or None where it refuses"""
+    p = ObjParams()
+    return p if lib().nrq_obj_params_oti(common, specific, flags, C.byref(p)) == 0 else None
+
+
+def _blocks(p):
+    return [(p.KL, p.KpL)] * p.ZL + [(p.KS, p.KpS)] * p.ZS
+
+
+class ObjectSender:
+    """A whole object sent from device memory (nrq_otx, include/nanorq_hip.h): obj is a 1-D uint8 HIP tensor of F bytes, partitioned
+    as nanorq_encoder_new_ext(F, T, K, Z, N, Al, flags) does.  The object must not change until the last emit has completed.
+    Every call but the constructor is enqueue-only on the context's stream."""
+
+    def __init__(self, ctx, obj, T, K=0, Z=0, N=1, Al=8, flags=0):
+        if obj.dim() != 1 or obj.element_size() != 1 or not obj.is_contiguous():
+            raise ValueError("obj must be a contiguous 1-D uint8 device tensor")
+        self.ctx = ctx
+        self._L = ctx._L
+        self.params = obj_params_enc(obj.shape[0], T, K, Z, N, Al, flags)
+        if self.params is None:
+            raise NrqError("the object parameters are refused (as nanorq_encoder_new_ext would)")
+        self.T = self.params.T
+        self._keep = obj
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_otx_create(ctx._h, C.byref(self.params), C.c_void_p(_dptr(obj)), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._L.nrq_otx_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def oti(self):
+        """(common, scheme-specific) OTI words for the receiver"""
+        c, s = C.c_uint64(), C.c_uint32()
+        self.ctx._chk(self._L.nrq_otx_oti(self._h, C.byref(c), C.byref(s)))
+        return c.value, s.value
+
+    @property
+    def blocks(self):
+        """(K, K') of every block, SBN 0 .. Z-1"""
+        return _blocks(self.params)
+
+    def stride(self, inline=False):
+        return (self.T + 4 + 15) // 16 * 16 if inline else self.T
+
+    def _out(self, n, inline, out):
+        if out is not None:
+            return out, out.stride(0) * out.element_size()
+        import torch
+        out = torch.empty((n, self.stride(inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        return out, out.shape[1]
+
+    def encode(self):
+        self.ctx._chk(self._L.nrq_otx_encode(self._h))
+
+    def emit(self, tags, out=None, inline=False, results=None):
+        """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form, any SBN of the object) in row k of out.
+        results: optional [n] int32 device tensor (0 written, -1 SBN >= Z: packet left untouched).  Returns out."""
+        n = int(tags.shape[0])
+        out, stride = self._out(n, inline, out)
+        self.ctx._chk(self._L.nrq_otx_emit(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
+                                           TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+        return out
+
+    def count_all(self, nrep):
+        p = self.params
+        return p.ZL * (p.KL + nrep) + p.ZS * (p.KS + nrep)
+
+    def emit_all(self, nrep, interleave=True, inline=False, out=None, tags_out=None):
+        """ESIs 0 .. K_b + nrep - 1 of every block b, block-major or interleaved (sorted by (ESI, SBN)).  Returns out."""
+        out, stride = self._out(self.count_all(nrep), inline, out)
+        self.ctx._chk(self._L.nrq_otx_emit_all(self._h, nrep, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
+                                               TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
+        return out
+
+
+class ObjectReceiver:
+    """A whole object received into device memory (nrq_orx, include/nanorq_hip.h), from its OTI words and the flags of
+    nanorq_decoder_new_ext.  rep_cap: repair rows per block (default: 10 % of the larger K, at least 16)."""
+
+    def __init__(self, ctx, common, specific, flags=0, rep_cap=None):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.params = obj_params_oti(common, specific, flags)
+        if self.params is None:
+            raise NrqError("the OTI is refused (as nanorq_decoder_new_ext would)")
+        p = self.params
+        self.F, self.Z = p.F, p.Z
+        self.rep_cap = max(16, max(p.KL, p.KS) // 10) if rep_cap is None else rep_cap
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_orx_create(ctx._h, C.byref(p), self.rep_cap, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self._L.nrq_orx_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def blocks(self):
+        return _blocks(self.params)
+
+    def add(self, payload, tags=None, inline=False, results=None, n=None, stride=None):
+        """as Receiver.add, over every block of the object (SBN >= Z: the host decoder's codes, ERR above max_esi, else IGN)"""
+        if hasattr(payload, "data_ptr"):
+            n = payload.shape[0] if n is None else n
+            stride = payload.stride(0) * payload.element_size() if stride is None else stride
+        if n is None or stride is None:
+            raise ValueError("a raw payload address needs n and stride")
+        if inline == (tags is not None):
+            raise ValueError("give either tags or inline=True")
+        self.ctx._chk(self._L.nrq_orx_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(tags)), n,
+                                          RX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+
+    def counts(self):
+        nl = np.zeros(self.Z, np.uint32)
+        nr = np.zeros(self.Z, np.uint32)
+        self.ctx._chk(self._L.nrq_orx_counts(self._h, _u32(nl), _u32(nr)))
+        return nl, nr
+
+    def decode(self):
+        st = np.zeros(self.Z, np.int32)
+        used = np.zeros(self.Z, np.uint32)
+        self.ctx._chk(self._L.nrq_orx_decode(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
+        return st, used
+
+    def write(self, out=None):
+        """Every complete block into out (a uint8 device tensor of at least F bytes; None: a new one of F bytes, zeroed) in the
+        object's layout; bytes past F and incomplete blocks are left untouched.  Returns (out, blocks still incomplete)."""
+        if out is None:
+            import torch
+            out = torch.zeros(self.F, dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            torch.cuda.synchronize()  # (torch's stream and the library's are not ordered)
+        elif out.numel() * out.element_size() < self.F:
+            raise ValueError("out is shorter than the object")
+        rc = self._L.nrq_orx_write(self._h, C.c_void_p(_dptr(out)))
+        self.ctx._chk(min(rc, 0))
+        return out, rc
 
 
 def plan_ops(plan, header=None):

@@ -19,6 +19,7 @@ EMU = os.path.join(ROOT, "tests", "emu", "libsolve_emu.so")
 PEMU = os.path.join(ROOT, "tests", "emu", "libplanner_emu.so")
 IEMU = os.path.join(ROOT, "tests", "emu", "libingest_emu.so")
 XEMU = os.path.join(ROOT, "tests", "emu", "libemit_emu.so")
+OEMU = os.path.join(ROOT, "tests", "emu", "libobj_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -140,10 +141,20 @@ def build_emit_emu(force=False):
     return XEMU
 
 
+def build_obj_emu(force=False):
+    """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
+    src = os.path.join(ROOT, "tests", "emu", "obj_emu.cpp")
+    deps = [src] + [os.path.join(CSRC, f) for f in ("obj_body.h", "emit_body.h", "rq_math.h")]
+    if force or _newer(OEMU, deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", OEMU, src], check=True)
+    return OEMU
+
+
 if __name__ == "__main__":
     build_lib(force="-f" in sys.argv, verbose=True)
     build_emu(force="-f" in sys.argv)
     build_planner_emu(force="-f" in sys.argv)
     build_ingest_emu(force="-f" in sys.argv)
     build_emit_emu(force="-f" in sys.argv)
+    build_obj_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

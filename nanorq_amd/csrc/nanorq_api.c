@@ -349,21 +349,51 @@ static void warm(nanorq *rq, int encoder) {
   }
 }
 
-nanorq *nanorq_encoder_new_ext(size_t len, uint16_t T16, uint16_t K, uint16_t Z16, uint16_t N16, uint8_t Al8, uint32_t flags) {
+/* The parts of the object parameters both constructors share: the two partitions, K' per class, max_esi and the OTI words.
+ * (an empty object still gets the smallest parameter row for block 0, as in the reference) */
+static int obj_fill(uint64_t F, size_t T, size_t Al, size_t Z, size_t N, size_t Kt, uint32_t flags, nrq_obj_params *o) {
+  const struct part sp = partition(Kt, Z), up = partition(T / Al, N);
+  uint32_t pr[10];
+  memset(o, 0, sizeof(*o));
+  o->F = F; o->T = (uint32_t)T; o->Al = (uint32_t)Al; o->Z = (uint32_t)Z; o->N = (uint32_t)N; o->Kt = (uint32_t)Kt; o->flags = flags;
+  o->ZL = (uint32_t)sp.JL; o->KL = (uint32_t)sp.IL; o->ZS = (uint32_t)sp.JS; o->KS = (uint32_t)sp.IS;
+  o->NL = (uint32_t)up.JL; o->TL = (uint32_t)(up.IL * Al); o->NS = (uint32_t)up.JS; o->TS = (uint32_t)(up.IS * Al);
+  const size_t k0 = sp.JL ? sp.IL : (sp.JS ? sp.IS : 0);
+  if (nrq_params((uint32_t)(k0 ? k0 : 1), pr) != 0) return -1;
+  const uint32_t Kp0 = pr[0];
+  o->KpL = o->ZL ? Kp0 : 0;
+  o->KpS = o->ZS ? Kp0 : 0;
+  if (flags & NANORQ_EXT_PER_BLOCK_KP) { /* (nanorq_block_kprime) */
+    if (o->ZL && o->KL && nrq_params(o->KL, pr) == 0) o->KpL = pr[0];
+    if (o->ZS && o->KS && nrq_params(o->KS, pr) == 0) o->KpS = pr[0];
+  }
+  o->max_esi = 2u * Kp0;
+  if (flags & NANORQ_EXT_RFC_OTI) { /* RFC 6330 section 3.3.2 / 3.3.3 */
+    o->oti_common = (F << 24) | (T & 0xffff);
+    o->oti_specific = (uint32_t)((Z & 0xff) << 24) | (uint32_t)((N & 0xffff) << 8) | (uint32_t)Al;
+  } else { /* nanorq.c:309-324 */
+    o->oti_common = (F << 24) | ((T - 1) & 0xffff);
+    o->oti_specific = (uint32_t)((Z - 1) << 24) | (uint32_t)((N - 1) << 8) | (uint32_t)Al;
+  }
+  return 0;
+}
+
+int nrq_obj_params_enc(uint64_t len, uint32_t T32, uint32_t K, uint32_t Z32, uint32_t N32, uint32_t Al32, uint32_t flags, nrq_obj_params *out) {
   /* nanorq.c:241-296 */
   static const uint8_t aligns[4] = {8, 4, 2, 1};
-  size_t T = T16, Z = Z16, Al = Al8;
-  if (len > NANORQ_MAX_TRANSFER) return NULL;
+  if (!out || T32 > 0xffff || K > 0xffff || Z32 > 0xffff || N32 > 0xffff || Al32 > 0xff) return -1; /* (the constructor's argument types) */
+  size_t T = T32, Z = Z32, Al = Al32;
+  if (len > NANORQ_MAX_TRANSFER) return -1;
   for (int a = 0; a < 4; a++)
     if (Al >= aligns[a]) { Al = aligns[a]; break; }
   if (Al == 0) Al = 1;
   if (T < Al) T = Al; else T -= T % Al;
   while (ceil_div(len, T) > (size_t)NRQ_Z_MAX * NRQ_K_MAX) {
-    if (Al == 1 || T * Al > 0xffff) return NULL; /* the reference would spin / overflow here */
+    if (Al == 1 || T * Al > 0xffff) return -1; /* the reference would spin / overflow here */
     T *= Al;
   }
   size_t Kt = ceil_div(len, T), Kn = K;
-  if (Kt == 0) return NULL;
+  if (Kt == 0) return -1;
   if (K == 0) {
     Kn = Kt;
     if (Z == 0) {
@@ -373,31 +403,20 @@ nanorq *nanorq_encoder_new_ext(size_t len, uint16_t T16, uint16_t K, uint16_t Z1
     Kn = ceil_div(Kt, Z);
   }
   Z = ceil_div(Kt, Kn);
-  if (Z == 0 || Z > NRQ_Z_MAX || ceil_div(Kt, Z) > NRQ_K_MAX) return NULL;
+  if (Z == 0 || Z > NRQ_Z_MAX || ceil_div(Kt, Z) > NRQ_K_MAX) return -1;
   size_t N = 1; /* nanorq.c:78 "disable interleaving" */
   if (flags & NANORQ_EXT_SUBBLOCKS) {
-    N = N16 ? N16 : 1;
-    if (N > T / Al) return NULL; /* a sub-symbol is at least Al bytes (RFC 6330 section 4.4.1.2) */
+    N = N32 ? N32 : 1;
+    if (N > T / Al) return -1; /* a sub-symbol is at least Al bytes (RFC 6330 section 4.4.1.2) */
   }
-  if ((flags & NANORQ_EXT_RFC_OTI) && (Z > 255 || T > 0xffff)) return NULL;
-  nanorq *rq = calloc(1, sizeof(nanorq));
-  if (!rq) return NULL;
-  pthread_mutex_init(&rq->io_lock, NULL);
-  rq->F = len; rq->T = T; rq->Al = Al; rq->Z = Z; rq->N = N; rq->Kt = Kt; rq->flags = flags;
-  rq->src_part = partition(Kt, Z);
-  rq->sub_part = partition(T / Al, rq->N);
-  if (!set_block_params(rq)) { free(rq); return NULL; }
-  warm(rq, 1);
-  return rq;
+  if ((flags & NANORQ_EXT_RFC_OTI) && (Z > 255 || T > 0xffff)) return -1;
+  return obj_fill(len, T, Al, Z, N, Kt, flags, out);
 }
-nanorq *nanorq_encoder_new_ex(size_t len, uint16_t T, uint16_t K, uint16_t Z, uint8_t Al) {
-  return nanorq_encoder_new_ext(len, T, K, Z, 1, Al, 0);
-}
-nanorq *nanorq_encoder_new(size_t len, uint16_t T, uint8_t Al) { return nanorq_encoder_new_ex(len, T, 0, 0, Al); }
 
-nanorq *nanorq_decoder_new_ext(uint64_t common, uint32_t specific, uint32_t flags) { /* nanorq.c:336-377 */
+int nrq_obj_params_oti(uint64_t common, uint32_t specific, uint32_t flags, nrq_obj_params *out) { /* nanorq.c:336-377 */
   uint64_t F = common >> 24;
   size_t T, Z, N, Al = specific & 0xff;
+  if (!out) return -1;
   if (flags & NANORQ_EXT_RFC_OTI) {
     T = (size_t)(common & 0xffff);
     Z = (specific >> 24) & 0xff;
@@ -407,20 +426,44 @@ nanorq *nanorq_decoder_new_ext(uint64_t common, uint32_t specific, uint32_t flag
     Z = ((specific >> 24) & 0xff) + 1;
     N = ((specific >> 8) & 0xffff) + 1;
   }
-  if (F > NANORQ_MAX_TRANSFER) return NULL;
-  if (T == 0 || Z == 0 || N == 0 || Al == 0 || T < Al || T % Al != 0) return NULL;
-  if (!(flags & NANORQ_EXT_SUBBLOCKS) && (flags & NANORQ_EXT_RFC_OTI) && N != 1) return NULL;
-  if (N > T / Al) return NULL;
+  if (F > NANORQ_MAX_TRANSFER) return -1;
+  if (T == 0 || Z == 0 || N == 0 || Al == 0 || T < Al || T % Al != 0) return -1;
+  if (!(flags & NANORQ_EXT_SUBBLOCKS) && (flags & NANORQ_EXT_RFC_OTI) && N != 1) return -1;
+  if (N > T / Al) return -1;
   size_t Kt = ceil_div(F, T);
-  if (ceil_div(Kt, Z) > NRQ_K_MAX) return NULL;
+  if (ceil_div(Kt, Z) > NRQ_K_MAX) return -1;
+  return obj_fill(F, T, Al, Z, N, Kt, flags, out);
+}
+
+static nanorq *obj_new(const nrq_obj_params *o) {
   nanorq *rq = calloc(1, sizeof(nanorq));
   if (!rq) return NULL;
   pthread_mutex_init(&rq->io_lock, NULL);
-  rq->F = F; rq->T = T; rq->Al = Al; rq->Z = Z; rq->N = N; rq->Kt = Kt; rq->flags = flags;
-  rq->src_part = partition(Kt, Z);
-  rq->sub_part = partition(T / Al, N);
+  rq->F = o->F; rq->T = o->T; rq->Al = o->Al; rq->Z = o->Z; rq->N = o->N; rq->Kt = o->Kt; rq->flags = o->flags;
+  rq->src_part = partition(rq->Kt, rq->Z);
+  rq->sub_part = partition(rq->T / rq->Al, rq->N);
   if (!set_block_params(rq)) { free(rq); return NULL; }
-  rq->max_esi = 2 * rq->Kp;
+  return rq;
+}
+
+nanorq *nanorq_encoder_new_ext(size_t len, uint16_t T, uint16_t K, uint16_t Z, uint16_t N, uint8_t Al, uint32_t flags) {
+  nrq_obj_params o;
+  if (nrq_obj_params_enc(len, T, K, Z, N, Al, flags, &o) != 0) return NULL;
+  nanorq *rq = obj_new(&o);
+  if (rq) warm(rq, 1);
+  return rq;
+}
+nanorq *nanorq_encoder_new_ex(size_t len, uint16_t T, uint16_t K, uint16_t Z, uint8_t Al) {
+  return nanorq_encoder_new_ext(len, T, K, Z, 1, Al, 0);
+}
+nanorq *nanorq_encoder_new(size_t len, uint16_t T, uint8_t Al) { return nanorq_encoder_new_ex(len, T, 0, 0, Al); }
+
+nanorq *nanorq_decoder_new_ext(uint64_t common, uint32_t specific, uint32_t flags) {
+  nrq_obj_params o;
+  if (nrq_obj_params_oti(common, specific, flags, &o) != 0) return NULL;
+  nanorq *rq = obj_new(&o);
+  if (!rq) return NULL;
+  rq->max_esi = o.max_esi;
   warm(rq, 0);
   return rq;
 }

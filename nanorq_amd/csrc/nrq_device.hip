@@ -34,6 +34,7 @@
 #include "planner_body.h"
 #include "ingest_body.h"
 #include "emit_body.h"
+#include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
 
@@ -3650,6 +3651,41 @@ enum : int {
   TX_BYTE = 3
 };
 
+/* the packet of `tag` at P: its payload is the XOR of rows cols[0..n) from base (one wave; a 16/4/1-byte word per lane) */
+template <int MODE>
+__device__ __forceinline__ void tx_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t *cols, uint32_t n, uint32_t tag,
+                                           uint8_t *__restrict__ P, uint32_t inl, uint32_t lane) {
+  if constexpr (MODE == TX_V16) {
+    for (uint32_t off = lane * 16u; off < T; off += 64u * 16u)
+      *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols, n, off);
+  } else if constexpr (MODE == TX_V16_SHIFT) {
+    /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-1 .. 4j+2: the previous lane's .w (the header for j = 0, the
+     * wave's last lane of the previous round for its first lane), then this chunk's .x .y .z; the last .w goes to +T */
+    const uint32_t nch = T >> 4;
+    uint32_t carry = tx_header_word(tag);
+    for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
+      const uint32_t j = j0 + lane;
+      const bool act = j < nch;
+      tx_u128 v{0u, 0u, 0u, 0u};
+      if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
+      uint32_t prev = __shfl_up(v.w, 1u);
+      if (lane == 0) prev = carry;
+      if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
+      if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + T) = v.w;
+      carry = __shfl(v.w, 63);
+    }
+  } else if constexpr (MODE == TX_DWORD) {
+    if (inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
+    uint8_t *D = P + (inl ? 4u : 0u);
+    for (uint32_t off = lane * 4u; off < T; off += 64u * 4u)
+      *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols, n, off);
+  } else {
+    if (inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
+    uint8_t *D = P + (inl ? 4u : 0u);
+    for (uint32_t off = lane; off < T; off += 64u) D[off] = tx_gather<uint8_t>(base, T, cols, n, off);
+  }
+}
+
 /* One wave per TX_WAVE_PKTS work items, in block-major order: each lane builds the column list of one item into LDS, then the
  * wave writes the items' packets one after the other, a 16/4/1-byte word of the payload per lane (the XOR of the item's rows,
  * four rows in flight). */
@@ -3677,37 +3713,7 @@ __global__ __launch_bounds__(256) void nrq_tx_emit_kernel(tx_blk t, tx_call c) {
     if (!n) continue; /* foreign SBN: the packet stays untouched */
     const uint32_t tag = s_tag[wv][i];
     const uint32_t *cols = s_cols[wv][i];
-    const uint8_t *__restrict__ base = tx_base(&t, tag);
-    uint8_t *__restrict__ P = c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride;
-    if constexpr (MODE == TX_V16) {
-      for (uint32_t off = lane * 16u; off < T; off += 64u * 16u)
-        *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols, n, off);
-    } else if constexpr (MODE == TX_V16_SHIFT) {
-      /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-1 .. 4j+2: the previous lane's .w (the header for j = 0, the
-       * wave's last lane of the previous round for its first lane), then this chunk's .x .y .z; the last .w goes to +T */
-      const uint32_t nch = T >> 4;
-      uint32_t carry = tx_header_word(tag);
-      for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
-        const uint32_t j = j0 + lane;
-        const bool act = j < nch;
-        tx_u128 v{0u, 0u, 0u, 0u};
-        if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
-        uint32_t prev = __shfl_up(v.w, 1u);
-        if (lane == 0) prev = carry;
-        if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
-        if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + T) = v.w;
-        carry = __shfl(v.w, 63);
-      }
-    } else if constexpr (MODE == TX_DWORD) {
-      if (c.inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
-      uint8_t *D = P + (c.inl ? 4u : 0u);
-      for (uint32_t off = lane * 4u; off < T; off += 64u * 4u)
-        *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols, n, off);
-    } else {
-      if (c.inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
-      uint8_t *D = P + (c.inl ? 4u : 0u);
-      for (uint32_t off = lane; off < T; off += 64u) D[off] = tx_gather<uint8_t>(base, T, cols, n, off);
-    }
+    tx_payload<MODE>(tx_base(&t, tag), T, cols, n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
   }
 }
 
@@ -3908,6 +3914,439 @@ int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_
   c.interleave = (uint32_t)order;
   c.tags_out = d_tags_out;
   return tx_launch(tx, c);
+}
+
+} /* extern "C" */
+
+/* ================================================ whole objects on the device (nrq_otx_* / nrq_orx_*, obj_body.h) ==== */
+/* the object <-> row-image layout: blockIdx.y = block, OBJ_UNROLL windows of 16 bytes per work item */
+template <typename W>
+__global__ __launch_bounds__(OBJ_WG) void nrq_obj_layout_kernel(obj_lay l) {
+  const uint32_t b = blockIdx.y;
+  uint32_t mw = 0; /* (the mask word picked by value: no dynamic index into the kernel arguments) */
+#pragma unroll
+  for (uint32_t i = 0; i < 8u; i++) mw = i == (b >> 5) ? l.mask[i] : mw;
+  if (l.to_obj && !((mw >> (b & 31u)) & 1u)) return;
+  obj_move<W>(&l, b, blockIdx.x * (OBJ_WG * OBJ_UNROLL) + threadIdx.x, OBJ_WG);
+}
+
+/* the two RFC 6330 section 4.4.1.2 partitions: Partition[Kt, Z] = (KL, KS, ZL, ZS) and Partition[T / Al, N] = (TL, TS, NL, NS) / Al
+ * (the emit_all index maps rely on KL = KS + 1 when ZL > 0) */
+static bool obj_partition_ok(const nrq_obj_params *p) {
+  if (p->Z == 0 || p->N == 0 || p->Al == 0 || p->T % p->Al) return false;
+  auto part = [](uint32_t I, uint32_t J, uint32_t &IL, uint32_t &IS, uint32_t &JL, uint32_t &JS) {
+    IS = I / J; JL = I - IS * J; JS = J - JL; IL = JL ? IS + 1u : 0u;
+  };
+  uint32_t IL, IS, JL, JS;
+  part(p->Kt, p->Z, IL, IS, JL, JS);
+  if (IL != p->KL || IS != p->KS || JL != p->ZL || JS != p->ZS) return false;
+  part(p->T / p->Al, p->N, IL, IS, JL, JS);
+  return IL * p->Al == p->TL && IS * p->Al == p->TS && JL == p->NL && JS == p->NS;
+}
+
+/* the consistency a parameter set from nrq_obj_params_* has (a hand-made one is refused before it can send a kernel astray) */
+static int obj_check(nrq_ctx *ctx, const char *who, const nrq_obj_params *p) {
+  if (!p) return fail(ctx, -1, "%s: params is NULL", who);
+  uint32_t pr[10];
+  const bool rowL = p->ZL == 0 || (p->KL && nrq_params(p->KpL, pr) == 0 && pr[0] == p->KpL && p->KpL >= p->KL);
+  const bool rowS = p->ZS == 0 || (p->KS && nrq_params(p->KpS, pr) == 0 && pr[0] == p->KpS && p->KpS >= p->KS);
+  if (p->Z == 0 || p->Z > 256u || p->ZL + p->ZS != p->Z || p->T == 0 || p->Kt == 0 ||
+      (uint64_t)p->ZL * p->KL + (uint64_t)p->ZS * p->KS != p->Kt || p->NL + p->NS != p->N || p->TS == 0 ||
+      (uint64_t)p->NL * p->TL + (uint64_t)p->NS * p->TS != p->T || p->F == 0 || p->F > (uint64_t)p->Kt * p->T ||
+      p->F <= (uint64_t)(p->Kt - 1u) * p->T || !rowL || !rowS || (uint64_t)std::max(p->KL, p->KS) * p->T > 0xFFFFFFFFull ||
+      p->max_esi < std::max(p->KpL, p->KpS) || p->max_esi >= (1u << 24) || !obj_partition_ok(p))
+    return fail(ctx, -1, "%s: inconsistent object parameters (use nrq_obj_params_enc / _oti)", who);
+  return 0;
+}
+
+static obj_lay obj_lay_of(const nrq_obj_params *p, void *obj, void *rows, uint32_t to_obj) {
+  obj_lay l{};
+  l.obj = (uint8_t *)obj; l.rows = (uint8_t *)rows; l.F = p->F;
+  l.T = p->T; l.Z = p->Z; l.ZL = p->ZL; l.KL = p->KL; l.KS = p->KS;
+  l.NL = p->NL; l.TL = p->TL; l.NS = p->NS; l.TS = p->TS;
+  l.to_obj = to_obj;
+  l.obj_vec = (reinterpret_cast<uintptr_t>(obj) & 15u) == 0;
+  for (uint32_t &w : l.mask) w = 0xFFFFFFFFu;
+  return l;
+}
+
+/* enqueue the layout kernel at the widest piece width the shape allows */
+static int obj_layout_launch(nrq_ctx *ctx, const obj_lay &l) {
+  uint32_t maxw = 0;
+  for (uint32_t b = 0; b < l.Z; b++) maxw = std::max(maxw, obj_windows(&l, b));
+  const dim3 grid((maxw + OBJ_WG * OBJ_UNROLL - 1u) / (OBJ_WG * OBJ_UNROLL), l.Z), wg(OBJ_WG);
+  switch (obj_width(&l)) {
+    case 16: hipLaunchKernelGGL(nrq_obj_layout_kernel<tx_u128>, grid, wg, 0, ctx->stream, l); break;
+    case 8: hipLaunchKernelGGL(nrq_obj_layout_kernel<uint64_t>, grid, wg, 0, ctx->stream, l); break;
+    case 4: hipLaunchKernelGGL(nrq_obj_layout_kernel<uint32_t>, grid, wg, 0, ctx->stream, l); break;
+    case 2: hipLaunchKernelGGL(nrq_obj_layout_kernel<uint16_t>, grid, wg, 0, ctx->stream, l); break;
+    default: hipLaunchKernelGGL(nrq_obj_layout_kernel<uint8_t>, grid, wg, 0, ctx->stream, l); break;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* the object emit: nrq_tx_emit_kernel with each packet's rows taken from the class-table segment of its SBN */
+template <int MODE>
+__global__ __launch_bounds__(256) void nrq_otx_emit_kernel(otx_obj o, tx_call c) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
+  if (w0 + lane < c.n) {
+    const uint32_t k = otx_work_packet(&o, &c, (uint32_t)(w0 + lane));
+    const uint32_t tag = k < c.n ? otx_packet_tag(&o, &c, k) : 0u;
+    const uint32_t sg = k < c.n ? otx_seg(&o, tag) : OTX_SEGS;
+    tx_blk sb = o.seg[0]; /* (selected by value: no dynamic index into the kernel arguments) */
+    if (sg == 1u) sb = o.seg[1];
+    else if (sg == 2u) sb = o.seg[2];
+    const uint32_t n = sg < OTX_SEGS ? tx_rows(&sb, tag, s_cols[wv][lane]) : 0u;
+    s_n[wv][lane] = n;
+    s_tag[wv][lane] = tag;
+    s_k[wv][lane] = k;
+    s_seg[wv][lane] = sg;
+    if (k < c.n && c.results) c.results[k] = n ? 0 : -1;
+    if (k < c.n && c.tags_out) c.tags_out[k] = tag;
+  }
+  __syncthreads();
+  const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
+  const uint32_t T = o.seg[0].T;
+  for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
+    const uint32_t n = s_n[wv][i];
+    if (!n) continue; /* SBN >= Z: the packet stays untouched */
+    const uint32_t tag = s_tag[wv][i];
+    /* the rows' base rebuilt from the kernel arguments with a wave-uniform segment (a pointer kept in LDS would come back as a
+     * generic one: flat loads, and waits that also cover the LDS reads) */
+    const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][i]);
+    const uint8_t *base = sg == 0u ? tx_base(&o.seg[0], tag) : sg == 1u ? tx_base(&o.seg[1], tag) : tx_base(&o.seg[2], tag);
+    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
+  }
+}
+
+/* the receiver's code for packets of SBN >= Z, as nanorq_decoder_add_symbol gives it (such a block has no symbols, hence no
+ * gaps): ING_ERR (NANORQ_SYM_ERR) for an ESI above max_esi, else ING_IGN */
+__global__ __launch_bounds__(256) void nrq_orx_foreign_kernel(const uint8_t *pkts, uint64_t pkt_stride, const uint32_t *tags, uint32_t n,
+                                                              uint32_t Z, uint32_t max_esi, int32_t *results) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  uint32_t tag;
+  if (tags) {
+    tag = tags[k];
+  } else { /* the FEC Payload ID, network byte order */
+    const uint8_t *p = pkts + (uint64_t)k * pkt_stride;
+    tag = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+  }
+  if ((tag >> 24) >= Z) results[k] = (tag & 0xFFFFFFu) > max_esi ? ING_ERR : ING_IGN;
+}
+
+struct nrq_otx {
+  nrq_ctx *ctx;
+  nrq_obj_params prm;
+  otx_obj o;
+  void *own_rows;  /* N > 1: every block's row image; N = 1: the staged last block (or nothing) */
+  void *own_inter;
+  bool encoded;
+  void *scratch;   /* list mode: bucket counts, then the work order */
+  size_t scratch_cap;
+};
+
+struct nrq_orx {
+  nrq_ctx *ctx;
+  nrq_obj_params prm;
+  nrq_rx *rx[2];   /* class L (SBN 0 ..), class S (SBN ZL ..); null for an empty class */
+  void *rows;      /* every block's row image, block b's at + boff(b) */
+};
+
+extern "C" {
+
+int nrq_obj_layout(nrq_ctx *ctx, const nrq_obj_params *prm, void *d_obj, void *d_rows, int to_obj) {
+  if (!ctx) return -1;
+  int rc = obj_check(ctx, "nrq_obj_layout", prm);
+  if (rc) return rc;
+  if (!d_obj || !d_rows || (to_obj != 0 && to_obj != 1)) return fail(ctx, -1, "nrq_obj_layout: bad buffers or direction");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return obj_layout_launch(ctx, obj_lay_of(prm, d_obj, d_rows, (uint32_t)to_obj));
+}
+
+int nrq_otx_create(nrq_ctx *ctx, const nrq_obj_params *prm, const void *d_obj, nrq_otx **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_otx_create: out is NULL");
+  *out = nullptr;
+  int rc = obj_check(ctx, "nrq_otx_create", prm);
+  if (rc) return rc;
+  if (!d_obj) return fail(ctx, -1, "nrq_otx_create: d_obj is NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const nrq_obj_params &p = *prm;
+  rq_params pL{}, pS{};
+  if (p.ZL && (rc = block_params(ctx, p.KL, p.KpL, &pL))) return rc;
+  if (p.ZS && (rc = block_params(ctx, p.KS, p.KpS, &pS))) return rc;
+  nrq_otx *tx = new (std::nothrow) nrq_otx();
+  if (!tx) return fail(ctx, -1, "nrq_otx_create: out of host memory");
+  tx->ctx = ctx;
+  tx->prm = p;
+  otx_obj &o = tx->o;
+  o.Z = p.Z; o.ZL = p.ZL; o.KL = p.KL; o.KS = p.KS;
+  const uint64_t T = p.T, LL = (uint64_t)pL.L * T, LS = (uint64_t)pS.L * T;
+  const uint32_t last = p.Z - 1u, Klast = last < p.ZL ? p.KL : p.KS;
+  const uint64_t olast = (uint64_t)(p.Kt - Klast) * T;
+  const bool stage = p.N == 1u && p.F < (uint64_t)p.Kt * T;
+  const uint8_t *rows = (const uint8_t *)d_obj;
+  uint8_t *inter = nullptr;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)(p.ZL * LL + p.ZS * LS), &tx->own_inter))) goto bad;
+  inter = (uint8_t *)tx->own_inter;
+  if (p.N > 1u) {
+    if ((rc = nrq_dev_alloc(ctx, (size_t)p.Kt * T, &tx->own_rows))) goto bad;
+    if ((rc = obj_layout_launch(ctx, obj_lay_of(&p, (void *)d_obj, tx->own_rows, 0)))) goto bad;
+    rows = (const uint8_t *)tx->own_rows;
+  } else if (stage) {
+    const size_t have = (size_t)(p.F - olast), full = (size_t)Klast * T;
+    if ((rc = nrq_dev_alloc(ctx, full, &tx->own_rows))) goto bad;
+    hipError_t e = nrq_inject(ctx) ? hipErrorUnknown
+                                   : hipMemcpyAsync(tx->own_rows, (const uint8_t *)d_obj + olast, have, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = nrq_inject(ctx) ? hipErrorUnknown : hipMemsetAsync((uint8_t *)tx->own_rows + have, 0, full - have, ctx->stream);
+    if (e != hipSuccess) {
+      rc = fail(ctx, -10, "nrq_otx_create: staging the last block failed: %s", hipGetErrorString(e));
+      goto bad;
+    }
+  }
+  {
+    /* segments: class L, class S, each without a staged last block, then that block */
+    auto seg = [&](uint32_t sbn0, uint32_t nblk, const rq_params &bp, uint32_t K, const uint8_t *src, uint64_t Lb) {
+      if (!nblk) return;
+      tx_blk &t = o.seg[o.nseg++];
+      t.p = bp; t.K = K; t.T = p.T; t.nblk = nblk; t.sbn0 = sbn0;
+      t.src = src; t.src_stride = (uint64_t)K * T;
+      t.inter = inter + (sbn0 < p.ZL ? sbn0 * LL : p.ZL * LL + (sbn0 - p.ZL) * LS); t.inter_stride = Lb;
+    };
+    const uint32_t cutL = stage && last < p.ZL ? 1u : 0u, cutS = stage && last >= p.ZL ? 1u : 0u;
+    seg(0, p.ZL - cutL, pL, p.KL, rows, LL);
+    seg(p.ZL, p.ZS - cutS, pS, p.KS, rows + (uint64_t)p.ZL * p.KL * T, LS);
+    if (stage) seg(last, 1, last < p.ZL ? pL : pS, Klast, (const uint8_t *)tx->own_rows, last < p.ZL ? LL : LS);
+  }
+  *out = tx;
+  return 0;
+bad:
+  nrq_otx_destroy(tx);
+  return rc;
+}
+
+void nrq_otx_destroy(nrq_otx *tx) {
+  if (!tx) return;
+  nrq_ctx *ctx = tx->ctx;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {tx->own_rows, tx->own_inter, tx->scratch})
+    if (p) nrq_dev_free(ctx, p);
+  delete tx;
+}
+
+int nrq_otx_encode(nrq_otx *tx) {
+  if (!tx) return -1;
+  tx->encoded = false;
+  for (uint32_t s = 0; s < tx->o.nseg; s++) {
+    const tx_blk &t = tx->o.seg[s];
+    const int rc = nrq_encode_blocks(tx->ctx, t.K, t.p.Kp, t.T, t.nblk, t.src, t.src_stride, (void *)t.inter, t.inter_stride, 0, nullptr,
+                                     nullptr, 0);
+    if (rc) return rc;
+  }
+  tx->encoded = true;
+  return 0;
+}
+
+int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific) {
+  if (!tx) return -1;
+  if (common) *common = tx->prm.oti_common;
+  if (specific) *specific = tx->prm.oti_specific;
+  return 0;
+}
+
+} /* extern "C" */
+
+static int otx_launch(nrq_otx *tx, const otx_obj &o, tx_call &c) {
+  nrq_ctx *ctx = tx->ctx;
+  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | tx->prm.T;
+  for (uint32_t s = 0; s < o.nseg; s++)
+    al |= reinterpret_cast<uintptr_t>(o.seg[s].src) | o.seg[s].src_stride | reinterpret_cast<uintptr_t>(o.seg[s].inter) | o.seg[s].inter_stride;
+  const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
+  if ((al & 15u) == 0 && !ctx->tune.tx_dword) {
+    if (c.inl) hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_V16_SHIFT>, grid, wg, 0, ctx->stream, o, c);
+    else hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_V16>, grid, wg, 0, ctx->stream, o, c);
+  } else if ((al & 3u) == 0) {
+    hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_DWORD>, grid, wg, 0, ctx->stream, o, c);
+  } else {
+    hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_BYTE>, grid, wg, 0, ctx->stream, o, c);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+static int otx_check(nrq_otx *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
+  nrq_ctx *ctx = tx->ctx;
+  if (!tx->encoded) return fail(ctx, -1, "%s: the object is not encoded (nrq_otx_encode)", who);
+  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
+  if (pkt_stride < (size_t)tx->prm.T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
+  return 0;
+}
+
+extern "C" {
+
+int nrq_otx_emit(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = otx_check(tx, "nrq_otx_emit", d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_otx_emit: bad tags (n=%u)", n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  tx_blk all{}; /* the bucketing passes see the object as one run of Z blocks */
+  all.sbn0 = 0;
+  all.nblk = tx->prm.Z;
+  const uint32_t nbins = all.nblk + 1u;
+  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
+  if (tx->scratch_cap < need) {
+    if (tx->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, tx->scratch);
+      tx->scratch = nullptr;
+      tx->scratch_cap = 0;
+    }
+    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
+    tx->scratch_cap = need;
+  }
+  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, all, d_tags, n, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, all, d_tags, n, cnt, order);
+  HIPCHK(ctx, hipGetLastError());
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.tags = d_tags;
+  c.order = order;
+  c.results = d_results;
+  return otx_launch(tx, tx->o, c);
+}
+
+int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = otx_check(tx, "nrq_otx_emit_all", d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (order != 0 && order != 1) return fail(ctx, -1, "nrq_otx_emit_all: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
+  const nrq_obj_params &p = tx->prm;
+  const uint64_t kmax = std::max(p.ZL ? p.KL : 0u, p.KS);
+  if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "nrq_otx_emit_all: ESIs up to %llu + %u reach past 2^24", (unsigned long long)kmax, nrep);
+  const uint64_t total = (uint64_t)p.ZL * (p.KL + (uint64_t)nrep) + (uint64_t)p.ZS * (p.KS + (uint64_t)nrep);
+  if (total > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_otx_emit_all: %llu packets are too many", (unsigned long long)total);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  otx_obj o = tx->o;
+  o.nrep = nrep;
+  o.interleave = (uint32_t)order;
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = (uint32_t)total;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.tags_out = d_tags_out;
+  return otx_launch(tx, o, c);
+}
+
+int nrq_orx_create(nrq_ctx *ctx, const nrq_obj_params *prm, uint32_t rep_cap, nrq_orx **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_orx_create: out is NULL");
+  *out = nullptr;
+  int rc = obj_check(ctx, "nrq_orx_create", prm);
+  if (rc) return rc;
+  if (rep_cap == 0) return fail(ctx, -1, "nrq_orx_create: rep_cap is 0");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const nrq_obj_params &p = *prm;
+  nrq_orx *rx = new (std::nothrow) nrq_orx();
+  if (!rx) return fail(ctx, -1, "nrq_orx_create: out of host memory");
+  rx->ctx = ctx;
+  rx->prm = p;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)p.Kt * p.T, &rx->rows))) goto bad;
+  if (p.ZL && (rc = nrq_rx_create(ctx, p.KL, p.KpL, p.T, p.ZL, 0, p.max_esi, rep_cap, rx->rows, (size_t)p.KL * p.T, nullptr, 0, &rx->rx[0])))
+    goto bad;
+  if (p.ZS && (rc = nrq_rx_create(ctx, p.KS, p.KpS, p.T, p.ZS, p.ZL, p.max_esi, rep_cap, (uint8_t *)rx->rows + (size_t)p.ZL * p.KL * p.T,
+                                  (size_t)p.KS * p.T, nullptr, 0, &rx->rx[1])))
+    goto bad;
+  *out = rx;
+  return 0;
+bad:
+  nrq_orx_destroy(rx);
+  return rc;
+}
+
+void nrq_orx_destroy(nrq_orx *rx) {
+  if (!rx) return;
+  for (nrq_rx *r : rx->rx) nrq_rx_destroy(r);
+  if (rx->rows) nrq_dev_free(rx->ctx, rx->rows); /* (nrq_rx_destroy waited for the stream) */
+  delete rx;
+}
+
+int nrq_orx_add(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  for (nrq_rx *r : rx->rx) {
+    if (!r) continue;
+    const int rc = nrq_rx_add(r, d_pkts, pkt_stride, d_tags, n, flags, d_results);
+    if (rc) return rc;
+  }
+  if (n == 0 || !d_results) return 0;
+  hipLaunchKernelGGL(nrq_orx_foreign_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint8_t *)d_pkts,
+                     (uint64_t)pkt_stride, d_tags, n, rx->prm.Z, rx->prm.max_esi, d_results);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int nrq_orx_counts(nrq_orx *rx, uint32_t *h_nlost, uint32_t *h_nrep) {
+  if (!rx) return -1;
+  const uint32_t sbn0[2] = {0, rx->prm.ZL};
+  for (int c = 0; c < 2; c++) {
+    if (!rx->rx[c]) continue;
+    const int rc = nrq_rx_counts(rx->rx[c], h_nlost ? h_nlost + sbn0[c] : nullptr, h_nrep ? h_nrep + sbn0[c] : nullptr);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int nrq_orx_decode(nrq_orx *rx, int *h_status, uint32_t *h_used) {
+  if (!rx) return -1;
+  if (!h_status) return fail(rx->ctx, -1, "nrq_orx_decode: h_status is NULL");
+  const uint32_t sbn0[2] = {0, rx->prm.ZL};
+  for (int c = 0; c < 2; c++) {
+    if (!rx->rx[c]) continue;
+    const int rc = nrq_rx_decode(rx->rx[c], h_status + sbn0[c], h_used ? h_used + sbn0[c] : nullptr);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int nrq_orx_write(nrq_orx *rx, void *d_out) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  if (!d_out) return fail(ctx, -1, "nrq_orx_write: d_out is NULL");
+  const uint32_t Z = rx->prm.Z;
+  std::vector<uint32_t> gaps(Z, 0);
+  int rc = nrq_orx_counts(rx, gaps.data(), nullptr);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  obj_lay l = obj_lay_of(&rx->prm, d_out, rx->rows, 1);
+  int incomplete = 0;
+  for (uint32_t &w : l.mask) w = 0;
+  for (uint32_t b = 0; b < Z; b++) {
+    if (gaps[b]) incomplete++;
+    else l.mask[b >> 5] |= 1u << (b & 31u);
+  }
+  if (incomplete < (int)Z && (rc = obj_layout_launch(ctx, l))) return rc;
+  return incomplete;
 }
 
 } /* extern "C" */
