@@ -45,6 +45,11 @@ typedef struct nrq_call_stats {
   uint32_t plan_ahead;  /* 1: the decode found its planner run already issued (nrq_decode_plan_ahead) */
   uint32_t strip_bytes_b, blocks_b; /* the batch's SECOND block list: blocks whose LDS image does not fit at strip_bytes run in a launch
                                      * of their own at this narrower width (0 / 0: one list) */
+  uint32_t plan_wg_threads;  /* decode: threads per workgroup of the planner kernel run (1024 / 256 / 128; 0: planned on the host) */
+  uint32_t plan_compact_state; /* 1: that run took the planner instance that keeps the peeling state in the workspace (big blocks) */
+  uint32_t plan_segmented;   /* 1: that run was segmented into parts (the biggest blocks) */
+  uint32_t backsub_strip;    /* bytes per strip of the back-substitution kernel after a narrow-strip solve (32 / 16; 0: no split) */
+  uint32_t encplan_device;   /* encode: the plan in use was built by the planner kernel (else by the host planner) */
 } nrq_call_stats;
 
 /* One context per GPU (one process per GPU: no cross-device state).  `stream` is a hipStream_t the
@@ -108,7 +113,9 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
  *            row esi, rows of missing symbols are overwritten with the recovered symbols
  *   h_lost   host: missing source ESIs of block b, ascending, at h_lost[b*lost_cap .. + h_nlost[b])
  *   h_rep_esi host: ESIs (>= K) of block b's received repair symbols in ARRIVAL order at
- *            h_rep_esi[b*rep_cap .. + h_nrep[b]); symbol q at d_rep + b*rep_stride + q*T
+ *            h_rep_esi[b*rep_cap .. + h_nrep[b]); symbol q at d_rep + b*rep_stride + q*T.  Any ESI up to 2^24 - 1, in any
+ *            order; an ESI < K (or >= 2^24) fails the block, which is left untouched.  An ESI may repeat: the copy adds no
+ *            rank, so verdict and bytes are those of the list without it (as nanorq_decoder_add_symbol drops it)
  *   d_inter  device or NULL: intermediate symbols out
  *   h_status host out: 1 = block recovered, 0 = not decodable (fewer repair symbols than gaps, or
  *            rank deficient: the caller may add symbols and retry, as with nanorq_repair_block)

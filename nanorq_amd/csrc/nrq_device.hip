@@ -1052,6 +1052,7 @@ struct EncPlan {
   hipEvent_t ready = nullptr;
   uint32_t rb_bytes = 0;  /* device build: bytes of the arena's front (header .. colslot) read back */
   double t_launch = 0;
+  bool dev_built = false; /* the plan in use came from the planner kernel (nrq_call_stats::encplan_device) */
 };
 
 inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -1318,9 +1319,14 @@ bool plan_is_segmented(const nrq_ctx *ctx, const rq_params &p, uint32_t Mcap) {
   return pl_state_in_lds(p.L, Mcap, dyn) == 0u && !ctx->tune.no_plan_split;
 }
 
+/* the planner form a run launched (nrq_call_stats::plan_wg_threads, plan_compact_state, plan_segmented) */
+struct PlanForm {
+  uint32_t wg_threads = 0, compact = 0, segmented = 0;
+};
+
 int launch_plan_kernel(nrq_ctx *ctx, hipStream_t ps, const rq_params &p, const uint8_t *d_kc, const nrq_planjob *d_pj,
                        nrq_job *d_jobs, uint32_t nblk, uint32_t Mcap, uint32_t npcap, uint32_t ucap, unsigned long long *pprof,
-                       uint32_t nnzcap) {
+                       uint32_t nnzcap, PlanForm *form = nullptr) {
   /* The workgroup state (pl_shared and the arrays behind it: frontier queues, claim lists, per-thread scratch, Gauss-Jordan
    * flags) is sized by the launch: 25 KB for big blocks; a small block's frontier and dense stage need a fraction, and
    * with 8 KB of it four 256-thread planner workgroups share a CU instead of two (the planner is latency bound: twice
@@ -1377,6 +1383,11 @@ int launch_plan_kernel(nrq_ctx *ctx, hipStream_t ps, const rq_params &p, const u
     const uint32_t part = seg ? parts_seg[pi] : 0u;
     const bool hbm_state = pl_state_in_lds(p.L, Mcap, dyn_bytes) == 0u; /* (pl_ctx_setup's rule) */
     if (part && (tiny_wg || small_wg || !hbm_state)) return fail(ctx, -2, "planner: a segmented run needs the instance for big blocks");
+    if (form) {
+      form->wg_threads = tiny_wg ? (uint32_t)PL_NT_TINY : small_wg ? (uint32_t)PL_NT_MIN : (uint32_t)PL_NT;
+      form->compact = !tiny_wg && !small_wg && (hbm_state || ctx->tune.plan_wrong_instance) ? 1u : 0u;
+      form->segmented = seg ? 1u : 0u;
+    }
     if (tiny_wg)
       hipLaunchKernelGGL(nrq_plan_kernel<(int)PL_NT_TINY>, dim3(nblk), dim3(PL_NT_TINY), dyn_bytes + sh_bytes, ps, p, d_kc, d_pj, d_jobs,
                          nblk, Mcap, npcap, ucap, dyn_bytes, pprof, part, qcap, lowcap);
@@ -1465,6 +1476,7 @@ int encplan_host_build(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc,
   ep.dev = ep.devbuf[0];
   ep.valid = true;
   ep.pending = false;
+  ep.dev_built = false;
   ep.build_ms = now_ms() - t0;
   return 0;
 }
@@ -1548,6 +1560,7 @@ int encplan_finish(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc, Enc
   ep.cur = ep.pend;
   ep.dev = ep.devbuf[ep.cur];
   ep.valid = true;
+  ep.dev_built = true;
   ep.build_ms = now_ms() - ep.t_launch;
   return 0;
 }
@@ -1769,6 +1782,7 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     ctx->stats.movers_aligned = al ? 1u : 0u;
   }
   HIPCHK(ctx, hipGetLastError());
+  uint32_t backsub_strip = 0;
   if (split) {
     /* 32-byte strips while the tables (4 KiB per W word) leave room for two workgroups per CU, 16-byte strips beyond */
     const bool wide = max_wpr <= 20u;
@@ -1777,6 +1791,7 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     uint32_t nchunks = (2048u + nsb * nblk - 1u) / (nsb * nblk);
     if (nchunks < 1u) nchunks = 1u;
     if (nchunks > 16u) nchunks = 16u;
+    backsub_strip = sb;
     if (wide)
       hipLaunchKernelGGL(nrq_backsub_kernel<32>, dim3(nsb, nchunks, nblk), dim3(256), tbl, ctx->stream, d_jobs, T, ybuf, ybuf_stride, nchunks);
     else
@@ -1824,6 +1839,7 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
   ctx->stats.wg_threads = nt;
   ctx->stats.strips_per_slot = 1u << lsub;
   ctx->stats.wg_waves_per_simd = tiny ? (uint32_t)NRQ_TINY_WV : five ? 5u : small ? (uint32_t)NRQ_SMALL_WV : 1u;
+  ctx->stats.backsub_strip = backsub_strip;
   return 0;
 }
 
@@ -2222,6 +2238,7 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
   ctx->stats.xor_ops = (uint64_t)ep->hdr.n_xor_ops * nblk;
   ctx->stats.npiv = ep->hdr.npiv; ctx->stats.u = ep->hdr.u; ctx->stats.nlev = ep->hdr.nlev;
   ctx->stats.nfree = ep->hdr.nfree;
+  ctx->stats.encplan_device = ep->dev_built ? 1u : 0u;
 
   /* per-call arrays: [jobs][isi->(cptr, cols, row)] */
   std::vector<uint32_t> isis(nrep), cptr;
@@ -2459,6 +2476,7 @@ struct PlanRun {
   size_t src_stride = 0, rep_stride = 0, inter_stride = 0;
   bool has_avail = false;
   std::vector<uint32_t> lost, nlost, resi, nrep, avail;
+  PlanForm form;
 };
 
 static void plan_ahead_drop(nrq_ctx *ctx) {
@@ -2593,7 +2611,7 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
   }
   if ((rc = launch_plan_kernel(ctx, ps, p, kc->dev, reinterpret_cast<const nrq_planjob *>(ds + off_pj),
                                reinterpret_cast<nrq_job *>(ctx->plan_jobs[ab].p), nblk, Mcap, npcap, ucap, pprof,
-                               kh->nnz + npcap * PL_PATCH_STRIDE)))
+                               kh->nnz + npcap * PL_PATCH_STRIDE, &r.form)))
     return rc;
   if (pe1) HIPCHK(ctx, hipEventRecord(pe1, ps));
   if (pprof) {
@@ -2679,6 +2697,9 @@ static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   HIPCHK(ctx, hipEventSynchronize(ctx->planned[ab]));
   ctx->stats.plan_ms = now_ms() - t_begin;
   ctx->stats.plan_ahead = ahead ? 1 : 0;
+  ctx->stats.plan_wg_threads = run->form.wg_threads;
+  ctx->stats.plan_compact_state = run->form.compact;
+  ctx->stats.plan_segmented = run->form.segmented;
   const nrq_plan_hdr *hd = reinterpret_cast<const nrq_plan_hdr *>(hs + off_hdrs);
   std::vector<const nrq_plan_hdr *> hdrs;
   std::vector<uint32_t> hblk; /* block of every header in hdrs (pick_and_launch: the batch's two block lists) */

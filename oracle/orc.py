@@ -49,6 +49,8 @@ def lib():
                                           C.POINTER(Stats)]
         L.orc_decode_block_kp.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u8p, u8p,
                                           C.POINTER(Stats)]
+        L.orc_decode_block_kpm.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u8p, u8p,
+                                           C.POINTER(Stats), C.c_uint32]
         L.orc_plan_probe.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(Stats)]
         L.orc_encode_block_cached.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_uint32, u32p, u8p]
         _LIB = L
@@ -145,13 +147,14 @@ def encode_block_cached(src, K, T, repair_esis=(), Kp=0):
     return rep[:len(esis)]
 
 
-def decode_block(esis, syms, K, T, Kp=0):
-    """esis[n] / syms[n,T] in arrival order. Returns (ok, out[K,T], stats)."""
+def decode_block(esis, syms, K, T, Kp=0, max_esi=0):
+    """esis[n] / syms[n,T] in arrival order; symbols with an ESI above max_esi (0: 2 K', the object layer's default) are refused.
+    Returns (ok, out[K,T], stats)."""
     esis = np.ascontiguousarray(esis, dtype=np.uint32)
     syms = np.ascontiguousarray(syms, dtype=np.uint8).reshape(len(esis), T)
     out = np.zeros((K, T), np.uint8)
     st = Stats()
-    ok = lib().orc_decode_block_kp(K, Kp, T, len(esis), _u32(esis), _u8(syms), _u8(out), C.byref(st))
+    ok = lib().orc_decode_block_kpm(K, Kp, T, len(esis), _u32(esis), _u8(syms), _u8(out), C.byref(st), max_esi)
     return bool(ok), out, st.as_dict()
 
 

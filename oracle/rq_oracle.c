@@ -830,18 +830,20 @@ int orc_encode_block_cached(uint32_t K, uint32_t Kp, uint32_t T, const uint8_t *
  *   esis[n], syms[n*T]; out: K*T bytes (received source symbols are written through, recovered
  *   ones after the solve).  returns 1 = block complete, 0 = not decodable (too few symbols or
  *   rank(A) < L). */
-int orc_decode_block_kp(uint32_t K, uint32_t Kp, uint32_t T, uint32_t n, const uint32_t *esis, const uint8_t *syms,
-                        uint8_t *out, orc_stats *st) {
+/* max_esi: symbols with a larger ESI are refused (0: 2 K', the object layer's default, reference nanorq.c:374; the device ABI
+ * itself takes ESIs up to 2^24 - 1) */
+int orc_decode_block_kpm(uint32_t K, uint32_t Kp, uint32_t T, uint32_t n, const uint32_t *esis, const uint8_t *syms,
+                         uint8_t *out, orc_stats *st, uint32_t max_esi) {
   orc_params_t p;
   gf_init();
   if (st) memset(st, 0, sizeof(*st));
   if (!derive_params_kp(K, Kp, &p) || T == 0) return 0;
-  uint32_t max_esi = 2 * p.Kp; /* reference nanorq.c:374 */
+  if (!max_esi) max_esi = 2 * p.Kp;
   uint8_t *seen = (uint8_t *)calloc((size_t)max_esi + 1, 1);
   uint32_t *rep_idx = (uint32_t *)malloc(sizeof(uint32_t) * (n ? n : 1));
   uint32_t nrep = 0, have_src = 0;
   size_t ld = ((size_t)T + 31u) & ~(size_t)31u;
-  size_t drows = (size_t)p.L + (max_esi - K);
+  size_t drows = (size_t)p.L + n; /* (every symbol past the first L rows is an extra row at most) */
   uint8_t *D = (uint8_t *)aligned_alloc(64, drows * ld);
   memset(D, 0, drows * ld);
   for (uint32_t k = 0; k < n; k++) {
@@ -904,6 +906,11 @@ int orc_decode_block_kp(uint32_t K, uint32_t Kp, uint32_t T, uint32_t n, const u
 done:
   free(D); free(seen); free(rep_idx);
   return ok;
+}
+
+int orc_decode_block_kp(uint32_t K, uint32_t Kp, uint32_t T, uint32_t n, const uint32_t *esis, const uint8_t *syms,
+                        uint8_t *out, orc_stats *st) {
+  return orc_decode_block_kpm(K, Kp, T, n, esis, syms, out, st, 0);
 }
 int orc_decode_block(uint32_t K, uint32_t T, uint32_t n, const uint32_t *esis, const uint8_t *syms, uint8_t *out,
                      orc_stats *st) {

@@ -1,39 +1,80 @@
-"""Helpers for the -m gpu tier: run the HIP path through the C ABI with numpy in/out."""
+"""Helpers for the -m gpu tier: run the HIP path through the C ABI with numpy in/out.
+
+Two shared contexts: "forced" (ctx(), the options below pin the device planner and every small workgroup form) and
+"default" (default_ctx(), no option set: the launch choices a product caller gets).  gpu_encode / gpu_decode take
+kind= to pick one; bound(kind) gives a module-like view with the same three functions bound to it."""
 import numpy as np
 
 import nanorq_amd
 
-_CTX = None
+KINDS = ("forced", "default")
+_CTXS = {}
 
 
-def ctx():
-    global _CTX
-    if _CTX is None:
-        # Tests that keep blocks in HBM use torch tensors.  torch brings its own copy of the HIP runtime, and it only
-        # finds the GPU if it initialises BEFORE the runtime libnanorq_hip.so is linked against opens the device
-        # (bench.py has the same order): bring torch up first.
-        try:
-            import torch
-            if torch.cuda.is_available():
-                torch.cuda.init()
-                torch.empty(1, device="cuda")
-        except ImportError:
-            pass
-        _CTX = nanorq_amd.Context(0)
+def _torch_up():
+    # Tests that keep blocks in HBM use torch tensors.  torch brings its own copy of the HIP runtime, and it only
+    # finds the GPU if it initialises BEFORE the runtime libnanorq_hip.so is linked against opens the device
+    # (bench.py has the same order): bring torch up first.
+    try:
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.init()
+            torch.empty(1, device="cuda")
+    except ImportError:
+        pass
+
+
+def ctx(kind="forced"):
+    c = _CTXS.get(kind)
+    if c is not None:
+        return c
+    if kind not in KINDS:
+        raise ValueError("unknown context kind %r" % kind)
+    _torch_up()
+    c = nanorq_amd.Context(0)
+    if kind == "forced":
         # the parity tests are about the DEVICE planner at every size and block count; a product context gives calls of one or two small
         # blocks to the host planner (nrq_decode_blocks_lazy "host_small"), which test_small_calls_take_the_host_planner covers
-        _CTX.set_option("host_plan_auto", 0)
+        c.set_option("host_plan_auto", 0)
         # ... and about every FORM of it: a product context gives a batch of at most one block per compute unit the 1024-thread planner
         # workgroup; the 256- and 128-thread forms that batches of thousands of small blocks use are exercised here at a few blocks
-        _CTX.set_option("plan_pack", 1)
+        c.set_option("plan_pack", 1)
         # ... and the single-wave solve workgroups, which a product context keeps for launches of more than ~500 strips
-        _CTX.set_option("tiny_any", 1)
-    return _CTX
+        c.set_option("tiny_any", 1)
+    _CTXS[kind] = c
+    return c
 
 
-def gpu_encode(src_blocks, K, T, esis, want_inter=False, Kp=0):
+def default_ctx():
+    """A context with no option set: the launch shapes real callers get (lone workgroups, the host planner for small calls,
+    the 1024-thread planner for batches of at most one block per CU)."""
+    return ctx("default")
+
+
+class bound:
+    """ctx / gpu_encode / gpu_decode on the context of one kind: a test body written against this module runs unchanged on it."""
+
+    def __init__(self, kind):
+        self.kind = kind
+
+    def __repr__(self):
+        return "bound(%r)" % self.kind
+
+    def ctx(self):
+        return ctx(self.kind)
+
+    def gpu_encode(self, *a, **k):
+        k.setdefault("kind", self.kind)
+        return gpu_encode(*a, **k)
+
+    def gpu_decode(self, *a, **k):
+        k.setdefault("kind", self.kind)
+        return gpu_decode(*a, **k)
+
+
+def gpu_encode(src_blocks, K, T, esis, want_inter=False, Kp=0, kind="forced"):
     """src_blocks: [nblk, K, T] uint8 -> (repair [nblk, nrep, T], inter [nblk, L, T] or None)"""
-    c = ctx()
+    c = ctx(kind)
     src_blocks = np.ascontiguousarray(src_blocks, np.uint8)
     nblk = src_blocks.shape[0]
     esis = np.ascontiguousarray(esis, np.uint32)
@@ -56,10 +97,10 @@ def gpu_encode(src_blocks, K, T, esis, want_inter=False, Kp=0):
     return rep, inter
 
 
-def gpu_decode(work_blocks, K, T, lost_lists, rep_esi_lists, rep_syms_lists, want_inter=False, Kp=0):
+def gpu_decode(work_blocks, K, T, lost_lists, rep_esi_lists, rep_syms_lists, want_inter=False, Kp=0, kind="forced"):
     """work_blocks: [nblk, K, T] with received source symbols in place (missing rows arbitrary).
     Returns (status[nblk], recovered blocks [nblk,K,T], inter or None)."""
-    c = ctx()
+    c = ctx(kind)
     work_blocks = np.ascontiguousarray(work_blocks, np.uint8)
     nblk = work_blocks.shape[0]
     lost_cap = max(1, max(len(x) for x in lost_lists))

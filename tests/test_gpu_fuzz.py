@@ -17,6 +17,13 @@ def G():
     return gpu_support
 
 
+@pytest.fixture(scope="module")
+def GD():
+    """gpu_support bound to a product-default context (no option set): the *_on_a_default_context tests run the same cases there"""
+    import gpu_support
+    return gpu_support.bound("default")
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_random_shapes(G, orc, seed):
     """(Seeds 6 and 7 with 12-byte strips forced -- the width of K ~ 8500-12000 -- on these small shapes: every symbol size that ends
@@ -27,6 +34,11 @@ def test_random_shapes(G, orc, seed):
         _random_shapes(G, orc, seed)
     finally:
         G.ctx().set_option("max_wb", 16)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_random_shapes_on_a_default_context(GD, orc, seed):
+    test_random_shapes(GD, orc, seed)
 
 
 def _random_shapes(G, orc, seed):

@@ -19,6 +19,13 @@ def G():
     return gpu_support
 
 
+@pytest.fixture(scope="module")
+def GD():
+    """gpu_support bound to a product-default context (no option set): the *_on_a_default_context tests run the same cases there"""
+    import gpu_support
+    return gpu_support.bound("default")
+
+
 def test_survey_small_symbols(G):
     s = SURVEY["small"]
     rep, _ = G.gpu_encode(kat_payload(s["K"] * s["T"]).reshape(1, s["K"], s["T"]), s["K"], s["T"], [int(e) for e in s["symbols"]])
@@ -41,6 +48,11 @@ def test_encode_vectors(G, c):
     assert GS.sha(inter[0]) == c["sha256_intermediate"], "intermediate symbols"
 
 
+@pytest.mark.parametrize("c", VEC["encode"], ids=lambda c: "K%d_Kp%d_T%d" % (c["K"], c["Kp"], c["T"]))
+def test_encode_vectors_on_a_default_context(GD, c):
+    test_encode_vectors(GD, c)
+
+
 @pytest.mark.parametrize("c", VEC["decode"], ids=lambda c: "K%d_Kp%d_oh%d_%s" % (c["K"], c["Kp"], c["overhead"], c["order"]))
 def test_decode_vectors(G, c):
     """Repair symbols come from the HIP encoder (already pinned by test_encode_vectors); the i-th missing ESI takes
@@ -57,6 +69,11 @@ def test_decode_vectors(G, c):
         assert GS.sha(out[0]) == c["sha256_recovered"]
 
 
+@pytest.mark.parametrize("c", VEC["decode"], ids=lambda c: "K%d_Kp%d_oh%d_%s" % (c["K"], c["Kp"], c["overhead"], c["order"]))
+def test_decode_vectors_on_a_default_context(GD, c):
+    test_decode_vectors(GD, c)
+
+
 def test_failure_sweep_vectors(G):
     fs = VEC["failure_sweep"]
     K, T, n = fs["K"], fs["T"], len(fs["cases"])
@@ -71,6 +88,10 @@ def test_failure_sweep_vectors(G):
     assert [bool(x) for x in st] == [c["decodable"] for c in fs["cases"]]
     for b in range(n):
         assert np.array_equal(out[b], src if st[b] else work[b])
+
+
+def test_failure_sweep_vectors_on_a_default_context(GD):
+    test_failure_sweep_vectors(GD)
 
 
 def test_every_table2_row_on_the_hip_encoder(G):

@@ -383,6 +383,13 @@ def test_headline_round_trip(ctx, torch, N):
 
 
 @pytest.mark.gpu
+def test_headline_round_trip_on_a_default_context(torch):
+    """test_headline_round_trip (N = 1) on a context with no option set: the launch choices an ObjectReceiver user gets"""
+    import gpu_support as G
+    test_headline_round_trip(G.default_ctx(), torch, 1)
+
+
+@pytest.mark.gpu
 def test_inconsistent_params_refused(ctx, torch):
     """hand-made parameter sets that break a partition (or its sums) are refused by create, before any kernel sees them"""
     F, T = 302 * 64 - 5, 64

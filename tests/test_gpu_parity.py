@@ -20,6 +20,13 @@ def G():
     return gpu_support
 
 
+@pytest.fixture(scope="module")
+def GD():
+    """gpu_support bound to a product-default context (no option set): the *_on_a_default_context tests run the same cases there"""
+    import gpu_support
+    return gpu_support.bound("default")
+
+
 def test_kat_small(G):
     rep, _ = G.gpu_encode(kat_payload(80).reshape(1, 10, 8), 10, 8, [10, 11, 12])
     assert {10 + k: rep[0, k].tobytes().hex() for k in range(3)} == KAT_SMALL
@@ -31,8 +38,10 @@ def test_kat_sha(G, K, T, lo, hi, sha):
     assert hashlib.sha256(rep[0].tobytes()).hexdigest() == sha
 
 
-@pytest.mark.parametrize("K,T", [(10, 8), (10, 40), (55, 4), (100, 1024), (101, 20), (500, 72), (1024, 1280),
-                                 (1033, 16), (4000, 48)])
+ENCODE_SHAPES = [(10, 8), (10, 40), (55, 4), (100, 1024), (101, 20), (500, 72), (1024, 1280), (1033, 16), (4000, 48)]
+
+
+@pytest.mark.parametrize("K,T", ENCODE_SHAPES)
 def test_encode_matches_oracle(G, orc, K, T):
     nblk = 3
     src = np.stack([payload(K * T, seed=3, block=b).reshape(K, T) for b in range(nblk)])
@@ -44,9 +53,11 @@ def test_encode_matches_oracle(G, orc, K, T):
         assert np.array_equal(rep[b], r_rep)
 
 
-@pytest.mark.parametrize("K,T,p,oh", [(10, 16, 0.3, 0), (100, 1024, 0.06, 0), (100, 64, 0.06, 3), (100, 8, 0.5, 40),
-                                      (1024, 1280, 0.05, 0), (1024, 1280, 0.06, 52), (1024, 24, 0.3, 1),
-                                      (8192, 32, 0.1, 0), (8192, 32, 0.1, 2), (8192, 32, 0.1, 11)])
+DECODE_CASES = [(10, 16, 0.3, 0), (100, 1024, 0.06, 0), (100, 64, 0.06, 3), (100, 8, 0.5, 40), (1024, 1280, 0.05, 0),
+                (1024, 1280, 0.06, 52), (1024, 24, 0.3, 1), (8192, 32, 0.1, 0), (8192, 32, 0.1, 2), (8192, 32, 0.1, 11)]
+
+
+@pytest.mark.parametrize("K,T,p,oh", DECODE_CASES)
 def test_decode_matches_oracle(G, orc, K, T, p, oh):
     nblk = 4
     src = np.stack([payload(K * T, seed=9, block=b).reshape(K, T) for b in range(nblk)])
@@ -69,6 +80,16 @@ def test_decode_matches_oracle(G, orc, K, T, p, oh):
             assert np.array_equal(out[b], src[b]), "block %d" % b
         else:
             assert np.array_equal(out[b], work[b])  # an undecodable block is left untouched
+
+
+@pytest.mark.parametrize("K,T", ENCODE_SHAPES)
+def test_encode_matches_oracle_on_a_default_context(GD, orc, K, T):
+    test_encode_matches_oracle(GD, orc, K, T)
+
+
+@pytest.mark.parametrize("K,T,p,oh", DECODE_CASES)
+def test_decode_matches_oracle_on_a_default_context(GD, orc, K, T, p, oh):
+    test_decode_matches_oracle(GD, orc, K, T, p, oh)
 
 
 def test_decode_too_few_symbols_and_retry(G, orc):
@@ -108,6 +129,10 @@ def test_failure_parity_sweep(G, orc):
             assert np.array_equal(out[b], src)
 
 
+def test_failure_parity_sweep_on_a_default_context(GD, orc):
+    test_failure_parity_sweep(GD, orc)
+
+
 def test_gen_symbols_from_hbm(G, orc):
     K, T, nblk = 300, 96, 2
     p = orc.params(K)
@@ -143,7 +168,10 @@ def _roundtrip(G, K, T, nblk, p, oh, seed):
     return st, out, src
 
 
-@pytest.mark.parametrize("K,T,nblk", [(100, 200, 70), (333, 1, 9), (64, 136, 130), (1024, 1288, 16)])
+LAUNCH_SHAPES = [(100, 200, 70), (333, 1, 9), (64, 136, 130), (1024, 1288, 16)]
+
+
+@pytest.mark.parametrize("K,T,nblk", LAUNCH_SHAPES)
 def test_launch_shapes(G, orc, K, T, nblk):
     """Work distribution of the persistent solve kernel: block counts that are / are not multiples of 8 (blocks are
     dealt to XCDs by octets), symbol sizes whose last 128-byte line group is partial, a single byte column; every
@@ -156,6 +184,11 @@ def test_launch_shapes(G, orc, K, T, nblk):
     for b in (0, nblk // 2, nblk - 1):
         r_rep, r_int, _ = orc.encode_block(src[b], K, T, esis, want_inter=True)
         assert np.array_equal(inter[b], r_int) and np.array_equal(rep[b], r_rep), "block %d" % b
+
+
+@pytest.mark.parametrize("K,T,nblk", LAUNCH_SHAPES)
+def test_launch_shapes_on_a_default_context(GD, orc, K, T, nblk):
+    test_launch_shapes(GD, orc, K, T, nblk)
 
 
 @pytest.mark.parametrize("K,T,nblk", [(256, 80, 300), (700, 80, 90), (1500, 80, 40), (2048, 144, 24), (2300, 80, 24),

@@ -166,6 +166,12 @@ def test_round_trip(ctx, torch, orc, K, T, nblk, inline):
         assert ok and np.array_equal(r_out, want[b])
 
 
+def test_round_trip_on_a_default_context(torch, orc):
+    """test_round_trip at the product shape on a context with no option set: the launch choices a Receiver user gets"""
+    import gpu_support as G
+    test_round_trip(G.default_ctx(), torch, orc, 8192, 1280, 256, False)
+
+
 def _singular_case(K, seed0=1):
     """a loss pattern and as many repair ESIs whose system is rank deficient (host planner), and one more repair ESI"""
     kc = nanorq_amd.host_kconst(K)

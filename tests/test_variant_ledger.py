@@ -1,0 +1,80 @@
+"""CPU tier: every kernel instantiation compiled into libnanorq_hip.so has a row in tests/variant_ledger.py -- pinned at a
+default-option shape (tests/test_gpu_variants.py), covered by a named test that forces it, or recorded as never launched with
+the reason.  A variant added without a row fails here."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+import variant_ledger as V
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_SYM = re.compile(r"\bvoid (%s)<([^<>]*)>\(" % "|".join(V.KERNELS))
+
+
+def _instantiations():
+    from nanorq_amd import build
+    path = build.build_lib()
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-C", path], check=True, capture_output=True, text=True).stdout
+    found = set()
+    for line in out.splitlines():
+        if "__device_stub__" in line:
+            continue
+        m = _SYM.search(line)
+        if m:
+            found.add((m.group(1), tuple(a.strip() for a in m.group(2).split(","))))
+    return found
+
+
+@pytest.fixture(scope="module")
+def inst():
+    return _instantiations()
+
+
+def _test_exists(ref):
+    path, name = ref.split("::")
+    with open(os.path.join(ROOT, path)) as f:
+        return re.search(r"(?m)^def %s\(" % re.escape(name), f.read()) is not None
+
+
+def test_every_kernel_family_is_compiled(inst):
+    assert {k for k, _ in inst} == set(V.KERNELS)
+    assert sum(1 for k, _ in inst if k == "nrq_solve_kernel") >= 37
+
+
+def test_every_instantiation_has_a_ledger_row(inst):
+    missing = sorted("%s<%s>" % (k, ", ".join(a)) for k, a in inst if V.ledger_row(k, a) is None)
+    assert not missing, "kernel variants without a row in tests/variant_ledger.py: %s" % missing
+
+
+def test_ledger_rows_are_well_formed(inst):
+    for k, a in sorted(inst):
+        row = V.ledger_row(k, a)
+        what = "%s<%s>" % (k, ", ".join(a))
+        assert row["status"] in ("default", "forced", "never"), what
+        if row["status"] == "never":
+            assert row.get("why"), what
+        elif row["status"] == "forced":
+            assert row.get("why") and _test_exists(row["test"]), what
+        elif "test" in row:
+            assert _test_exists(row["test"]), what
+        else:
+            assert "shape" in row or "via" in row, what
+    for name, row in V.FEATURES.items():
+        assert "shape" in row if row["status"] == "default" else _test_exists(row["test"]), name
+
+
+def test_ledger_has_no_stale_rows(inst):
+    """a row for a variant that is no longer compiled is a claim about nothing"""
+    keys = {(k, a) for k, a in inst}
+    rows = set()
+    for key in V.SOLVE:
+        wb, nt, wv, g, al = key
+        args = (str(wb), str(nt), str(wv), str(g)) + (("true" if al else "false"),)
+        rows.add(("nrq_solve_kernel", args))
+    rows |= {("nrq_backsub_kernel", (str(s),)) for s in V.BACKSUB}
+    rows |= {("nrq_plan_kernel", (str(n), str(c))) for n, c in V.PLAN}
+    assert rows <= keys, sorted(rows - keys)
