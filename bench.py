@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- RaptorQ encode+decode throughput of the MI355X path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: the headline and what
+the timed steps themselves recorded (launch times, planner and strip statistics).  Everything else below -- the checks of
+what was timed, `e2e`, `cpu_baseline`, the roofline's op counts and live counters, the other decode-plan form's step time and
+`one_object` -- runs with --full only; --cpu-sample, --alg-sample, --pmc, --no-e2e and --one-object shape what --full runs.
 
 N > 1: under torch.distributed.run (RANK / WORLD_SIZE set) this process is one rank; run on its own it starts the N ranks
 itself (nanorq_amd.shard.spawn_ranks) and refuses (exit code 2) when fewer than N GPUs are visible.
@@ -19,7 +24,7 @@ already resident in HBM when the timed region starts.  Blocks shard across GPUs 
 collective (weak scaling); rank 0 prints ONE JSON line.
 
 `value` = 8 * (payload bytes encoded and decoded) / wall time, whole job.
-Proof of work: every step destroys the lost rows of every block's receiver copy over their FULL width, poisons a few
+Proof of work (its checks: --full): every step destroys the lost rows of every block's receiver copy over their FULL width, poisons a few
 full-width rows of EVERY block's repair and intermediate symbols (which rows changes with the step) and leaves a
 column-weighted digest of them and of sampled decoded rows of every block.  After the timed region every block is verified
 in full on the device (decoded block == source; source symbols regenerated from the intermediate symbols == source; repair
@@ -82,16 +87,20 @@ def parse():
     ap.add_argument("--loss", type=float, default=0.10)
     ap.add_argument("--overhead", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0, help="host planner threads per rank (0 = cores / ranks)")
-    ap.add_argument("--cpu-sample", type=int, default=6, help="blocks timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run what it does not need: the checks of what was timed (every block in full on "
+                         "the device, every step's digest, the oracle), the end-to-end leg, the CPU baseline, the roofline's op "
+                         "counts and live counters, the other decode-plan form's step time and, at N > 1, the one-object run")
+    ap.add_argument("--cpu-sample", type=int, default=6, help="--full: blocks timed on the CPU oracle (0 = skip)")
     ap.add_argument("--alg-sample", type=int, default=2,
-                    help="with --cpu-sample 0: blocks whose reference-equivalent op counts (SURVEY 8d) the oracle forms on a "
+                    help="--full with --cpu-sample 0: blocks whose reference-equivalent op counts (SURVEY 8d) the oracle forms on a "
                          "32-byte column slice, so that roofline.frac is there without the full-width CPU leg (0 = skip)")
     ap.add_argument("--no-replan", action="store_true", help="keep the encode plan cached across steps")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams per GPU: the step's blocks are split into this many groups, each on its own stream")
     ap.add_argument("--pmc", choices=("auto", "off"), default="auto",
-                    help="auto: at 1 GPU, collect HBM / LDS / issue counters of the solve kernel with rocprofv3 passes of this "
-                         "command after the timed run (falls back to the committed profiles/ file); off: skip")
+                    help="--full, auto: at 1 GPU, collect HBM / LDS / issue counters of the solve kernel with rocprofv3 passes of "
+                         "this command after the timed run (falls back to the committed profiles/ file); off: skip")
     ap.add_argument("--plan-ahead-depth", type=int, default=2, help="planner runs kept in flight ahead of their decode (1 or 2)")
     ap.add_argument("--plan-ahead", choices=("auto", "on", "off"), default="auto",
                     help="issue the decode planner run of the NEXT step while this step's decode is being solved (the symbolic stage "
@@ -105,9 +114,9 @@ def parse():
     ap.add_argument("--no-wb12", action="store_true", help="round 5's strip widths for comparison (16, 8, 4, 2 bytes: K ~ 8500-12000 on 8-byte strips)")
     ap.add_argument("--replan-late", action="store_true", help="rebuild the next step's encode plan behind the decode launch (where it was until late in "
                                                                "round 6) instead of behind the encode launch: for comparison")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffers-to-host-buffers leg")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-buffers-to-host-buffers leg")
     ap.add_argument("--one-object", choices=("auto", "on", "off"), default="auto",
-                    help="ONE object over all N GPUs from rank 0's process (NANORQ_HIP_DEVICES=0..N-1, a host thread per device: "
+                    help="--full: ONE object over all N GPUs from rank 0's process (NANORQ_HIP_DEVICES=0..N-1, a host thread per device: "
                          "SURVEY 8(e)'s placement for cfg4 / cfg5) next to the process-sharded line; auto = when N > 1")
     ap.add_argument("--one-object-K", type=int, default=56403, help="block size of that object (cfg5: 56403, 8 blocks per GPU)")
     ap.add_argument("--one-object-T", type=int, default=1280)
@@ -289,8 +298,8 @@ def pmc_collect(args):
     if not os.path.exists(exe):
         return None, "rocprofv3 not found"
     import sqlite3
-    inner = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--alg-sample", "0", "--pmc", "off",
-             "--no-e2e", "--K", str(args.K), "--T", str(args.T), "--blocks", str(args.blocks), "--loss", str(args.loss), "--overhead", str(args.overhead)]
+    inner = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--alg-sample", "0",
+             "--pmc", "off", "--no-e2e", "--K", str(args.K), "--T", str(args.T), "--blocks", str(args.blocks), "--loss", str(args.loss), "--overhead", str(args.overhead)]
     if args.no_replan:
         inner.append("--no-replan")
     if args.no_wb12:
@@ -489,7 +498,7 @@ def main():
     if args.force_device < 0 and local >= torch.cuda.device_count():
         sys.stderr.write("bench.py: rank %d has no GPU (%d visible)\n" % (rank, torch.cuda.device_count()))
         raise SystemExit(2)
-    e2e = e2e_leg(args) if (rank == 0 and world == 1 and not args.no_e2e and args.streams <= 1) else None
+    e2e = e2e_leg(args) if (args.full and rank == 0 and world == 1 and not args.no_e2e and args.streams <= 1) else None
     if args.force_device >= 0:
         local = args.force_device
     torch.cuda.set_device(local)
@@ -733,10 +742,10 @@ def main():
     rdev = dev if args.dist_backend == "nccl" else None
     elapsed = shard.reduce_max(elapsed, world, device=rdev)   # the slowest rank defines the step time
     # the same step with the decode plan built INSIDE the decode call (a receiver that learns the reception pattern when it
-    # decodes): reported beside the headline, never `value`.  The runs still waiting are consumed first (untimed).
+    # decodes): reported beside the headline by --full, never `value`.  The runs still waiting are consumed first (untimed).
     ms_plan_in_call = None
     ms_plan_ahead = None
-    if not plan_ahead and world == 1 and args.steps >= 2 and nstreams == 1 and args.plan_ahead == "auto":
+    if args.full and not plan_ahead and world == 1 and args.steps >= 2 and nstreams == 1 and args.plan_ahead == "auto":
         # the other form beside the headline: planner runs issued two steps ahead (never `value`)
         for c_ in ctxs:
             c_.ktime_enable(False)
@@ -751,7 +760,7 @@ def main():
         ms_plan_ahead = (time.perf_counter() - t1) / nplain * 1e3
         step(ahead=False)   # (discards the runs still waiting)
         torch.cuda.synchronize(dev)
-    if plan_ahead and world == 1 and args.steps >= 2:
+    if args.full and plan_ahead and world == 1 and args.steps >= 2:
         for c_ in ctxs:
             c_.ktime_enable(False)
         for _ in range(ahead_depth + 1):
@@ -765,11 +774,13 @@ def main():
         ms_plan_in_call = (time.perf_counter() - t1) / nplain * 1e3   # (these steps' digests are checked with the others)
     retries_total = int(shard.reduce_sum(retries, world, device=rdev))
 
-    # ---- correctness of what was timed ----
-    assert torch.equal(work, src), "decoded blocks differ from the source blocks"
-    check = {"blocks": chk, "steps_digested": len(digests), "oracle": False, "all_blocks_verified": False,
+    # ---- correctness of what was timed: --full (every step forms its digest either way, a plain run does not compare them) ----
+    check = {"blocks": chk, "steps_digested": 0, "oracle": False, "all_blocks_verified": False,
              "rows_per_block_per_step": {"repair": REP_S, "intermediate": INT_S, "decoded": WRK_S} if ph_rep else None}
-    if ph_rep:
+    if args.full:
+        assert torch.equal(work, src), "decoded blocks differ from the source blocks"
+        check["steps_digested"] = len(digests)
+    if args.full and ph_rep:
         # every block in full, on the device: the source symbols regenerated from the block's intermediate symbols must be
         # the block (systematic property, RFC 6330 5.3.3.4.2), and its repair symbols regenerated must be the ones the
         # encode left.  (The decode's output was compared with `src` above.)
@@ -797,7 +808,7 @@ def main():
             if ph not in expect:
                 expect[ph] = digest_of(ph, src_rows)
             assert torch.equal(d, expect[ph]), "a timed step left poisoned or wrong rows behind (phase %d)" % ph
-    if chk:
+    if args.full and chk:
         import oracle
         for b in chk:   # the oracle's repair + intermediate symbols of the checked blocks, byte for byte
             sb = src[b].cpu().numpy()
@@ -815,7 +826,7 @@ def main():
     # own (the object layer reads its device list once) while the other ranks wait at the closing barrier ----
     one_object = None
     shard.finalize(world)   # (the last collective is behind us: the other ranks leave, rank 0 may take its time)
-    if rank == 0 and (args.one_object == "on" or (args.one_object == "auto" and world > 1)) and args.force_device < 0:
+    if args.full and rank == 0 and (args.one_object == "on" or (args.one_object == "auto" and world > 1)) and args.force_device < 0:
         for c_ in ctxs:
             c_.sync()
         torch.cuda.empty_cache()
@@ -846,10 +857,10 @@ def main():
         payload_step = world * NB * K * T
         value = 8.0 * payload_step * args.steps / elapsed / 1e9
         cpu, balg_enc, balg_dec = (None, None, None)
-        if args.cpu_sample > 0 and world == 1:   # (the CPU baseline is a one-GPU-run entry; N > 1 keeps the op counts for the roofline only)
+        if args.full and args.cpu_sample > 0 and world == 1:   # (the CPU baseline is a one-GPU-run entry; N > 1 keeps the op counts for the roofline only)
             src_np = src[:args.cpu_sample].cpu().numpy()
             cpu, balg_enc, balg_dec = cpu_baseline(args, src_np, lost, nrep)
-        elif args.alg_sample > 0:
+        elif args.full and args.alg_sample > 0:
             balg_enc, balg_dec = algorithmic_sample(args, lost, nrep, args.alg_sample)
         # solve-kernel launches in the timed region: [encode, decode(, retries...)] per step
         roof = None
@@ -876,7 +887,7 @@ def main():
             stage_dec = NB * T * ((L + args.overhead) + gaps)
             compulsory, staging = 0.5 * (comp_enc + comp_dec), 0.5 * (stage_enc + stage_dec)
             counters, csrc = (None, "off")
-            if args.pmc == "auto" and world == 1 and nstreams == 1:
+            if args.full and args.pmc == "auto" and world == 1 and nstreams == 1:
                 for c_ in ctxs:
                     c_.sync()
                 counters, csrc = pmc_collect(args)
@@ -943,7 +954,7 @@ def main():
                                      "--kernel-trace reports)"})
         out = {
             "metric": "Gbit/s encode+decode, K=%d T=%d" % (K, T), "value": value, "unit": "Gbit/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": "%s: K=%d T=%d, %d blocks/GPU/step, %.0f%% loss, overhead %d, encode(+%d repair)"

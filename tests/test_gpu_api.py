@@ -183,8 +183,8 @@ def test_two_ranks_through_the_real_library(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--K", "1024", "--T", "256", "--steps", "1", "--warmup", "1", "--cpu-sample", "0",
-            "--pmc", "off", "--no-e2e", "--force-device", "0", "--dist-backend", "gloo"]
+    base = [sys.executable, os.path.join(root, "bench.py"), "--full", "--K", "1024", "--T", "256", "--steps", "1", "--warmup", "1",
+            "--cpu-sample", "0", "--pmc", "off", "--no-e2e", "--force-device", "0", "--dist-backend", "gloo"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(base + ["--gpus", "2", "--blocks", "8", "--digest-out", str(tmp_path / "two.json")], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600)
@@ -213,14 +213,14 @@ def test_two_ranks_through_the_real_library(tmp_path):
 def test_bench_dumps_the_same_outputs_run_after_run(tmp_path):
     """bench.py --dump-outputs: the last timed step's decoded / repair / intermediate rows (a fixed sample) and the symbols each
     decode used, as float32 / float64 .npy files under 64 MB; two runs with the same arguments write the same arrays, and the
-    line reports the --steps it was given with its ms_per_step."""
+    line reports the --steps it was given with its ms_per_step.  Without --full the run does nothing beyond its steps."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--K", "1024", "--T", "256", "--blocks", "4", "--steps", "3",
-           "--warmup", "1", "--cpu-sample", "0", "--alg-sample", "0", "--pmc", "off", "--no-e2e"]
+           "--warmup", "1"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     dumps = []
     for run in ("a", "b"):
@@ -228,6 +228,10 @@ def test_bench_dumps_the_same_outputs_run_after_run(tmp_path):
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         line = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
         assert line["steps"] == 3 and line["ms_per_step"] > 0
+        # a plain run (no --full) times the steps and nothing more
+        assert line["full"] is False and line["e2e"] is None and line["cpu_baseline"] is None and not line["check"]["oracle"]
+        assert line["roofline"]["traffic_source"] == "off" and line["roofline"]["achieved"] is None
+        assert line["config"]["ms_per_step_plan_inside_decode_call"] is None and line["config"]["ms_per_step_plans_issued_ahead"] is None
         files = sorted(os.listdir(tmp_path / run))
         assert files == sorted(["decode_symbols_used.npy"] + ["%s%s.npy" % (n, s) for n in ("decoded", "repair", "intermediate")
                                                                for s in ("", "_rows")])

@@ -11,7 +11,7 @@ run() { # name K T blocks loss overhead [cpu-sample] [further bench.py arguments
   local name=$1 K=$2 T=$3 B=$4 P=$5 OH=$6 CS=${7:-2}
   if [ -n "$ONLY" ] && ! [[ "$name" =~ $ONLY ]]; then return 0; fi
   shift 7 2>/dev/null || shift $#
-  timeout 900 python $REPO/bench.py --K $K --T $T --blocks $B --loss $P --overhead $OH --steps 5 --warmup 2 --cpu-sample $CS "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
+  timeout 900 python $REPO/bench.py --full --K $K --T $T --blocks $B --loss $P --overhead $OH --steps 5 --warmup 2 --cpu-sample $CS "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
   set -- $name
   python3 - "$OUT/${TAG}_bench_$1.json" <<'PY'
 import json, sys

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Runs ON THE GPU BOX (through gpurun): the default bench line (with its own live PMC passes), the rocprofv3 kernel trace
+# Runs on a machine with an MI355X: the full bench line (--full: with its own live PMC passes), the rocprofv3 kernel trace
 # of the same command, the PMC passes again as a stand-alone file, and the other BASELINE configs -- all into
 # gpurun_out/prof/ (copy what you want judged into profiles/).
 #   /usr/local/graft/bin/gpurun --timeout 2400 -- 'bash tools/collect_profiles.sh r3'
@@ -11,7 +11,7 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 BENCH="python $REPO/bench.py --steps 3 --warmup 1 --cpu-sample 0 --pmc off --no-e2e"
 cd /tmp
-timeout 900 python $REPO/bench.py > "$OUT/${TAG}_bench_1gpu.json" 2> "$OUT/bench_1gpu.err"
+timeout 900 python $REPO/bench.py --full > "$OUT/${TAG}_bench_1gpu.json" 2> "$OUT/bench_1gpu.err"
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -- $BENCH > "$OUT/trace.log" 2>&1
 python $REPO/tools/rocprof_summary.py stats $(find "$OUT/trace" -name '*.db' | head -1) > "$OUT/${TAG}_kernel_stats.txt"
 echo "# (avg_us is over ALL launches of the run: 1 warm-up step + 3 timed steps, i.e. it includes the cold first launch -- the max column; steady_avg_us leaves the warm-up step's launches out and is the figure that roofline.avg_launch_ms of ${TAG}_bench_1gpu.json must agree with)" >> "$OUT/${TAG}_kernel_stats.txt"
