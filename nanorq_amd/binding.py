@@ -358,11 +358,35 @@ def _dptr(x):
     return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
 
 
-class Receiver:
+class _Handle:
+    """The lifecycle of a device handle: close() (also by `with` and on collection) calls the library's <_api>_destroy once."""
+    _api = None
+    _h = None
+
+    def close(self):
+        if self._h and getattr(self.ctx, "_h", None):
+            getattr(self._L, self._api + "_destroy")(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Receiver(_Handle):
     """A device-resident reception (nrq_rx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
     fed with packets that are already in device memory.  Buffers are torch HIP tensors or raw device addresses.  src None: the
     source rows are a torch tensor of the reception's own (`source`, [nblk, K, T] uint8); rep None: the repair rows come from the
     context's pool."""
+    _api = "nrq_rx"
 
     def __init__(self, ctx, K, T, nblk, rep_cap, sbn0=0, max_esi=0, Kp=0, src=None, src_stride=0, rep=None, rep_stride=0):
         self.ctx = ctx
@@ -378,23 +402,6 @@ class Receiver:
         ctx._chk(self._L.nrq_rx_create(ctx._h, K, Kp, T, nblk, sbn0, max_esi, rep_cap, C.c_void_p(_dptr(src)), src_stride,
                                        C.c_void_p(_dptr(rep)), rep_stride, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._L.nrq_rx_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     @property
     def src_ptr(self):
@@ -453,42 +460,8 @@ class Receiver:
 TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
 
 
-class Sender:
-    """A device-resident transmission (nrq_tx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
-    whose packets are written straight into device memory.  src: the source rows (a torch HIP tensor or a raw device address),
-    block b at src + b*src_stride (0 = K*T); they are read by encode() and by every emit, so they must not change until the last
-    emit has completed.  Every call is enqueue-only on the context's stream."""
-
-    def __init__(self, ctx, K, T, nblk, src, src_stride=0, sbn0=0, Kp=0):
-        self.ctx = ctx
-        self._L = ctx._L
-        self.K, self.T, self.nblk, self.sbn0 = K, T, nblk, sbn0
-        self._keep = src  # the tensor stays alive as long as the transmission
-        h = C.c_void_p()
-        ctx._chk(self._L.nrq_tx_create(ctx._h, K, Kp, T, nblk, sbn0, C.c_void_p(_dptr(src)), src_stride, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._L.nrq_tx_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def inter_ptr(self):
-        """device address of the intermediate symbols (block b's L rows at + b*L*T)"""
-        return self._L.nrq_tx_inter(self._h) or 0
+class _Emitter(_Handle):
+    """What Sender and ObjectSender share: the packet buffers, encode and the tag-list emit (<_api>_encode, <_api>_emit)."""
 
     def stride(self, inline=False):
         """the packet stride of out=None: T, or T + 4 rounded up to 16 with the inline header"""
@@ -503,17 +476,39 @@ class Sender:
 
     def encode(self):
         """solve every block (the intermediate symbols stay in device memory); needed before any emit"""
-        self.ctx._chk(self._L.nrq_tx_encode(self._h))
+        self.ctx._chk(getattr(self._L, self._api + "_encode")(self._h))
 
     def emit(self, tags, out=None, inline=False, results=None):
         """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form) in row k of out ([n, stride] uint8 device
-        tensor; None: a new one).  results: optional [n] int32 device tensor (0 written, -1 SBN outside the transmission, whose
-        packet is left untouched).  Returns out."""
+        tensor; None: a new one).  results: optional [n] int32 device tensor (0 written, -1 SBN outside the transmission or the
+        object, whose packet is left untouched).  Returns out."""
         n = int(tags.shape[0])
         out, stride = self._out(n, inline, out)
-        self.ctx._chk(self._L.nrq_tx_emit(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
-                                          TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+        self.ctx._chk(getattr(self._L, self._api + "_emit")(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
+                                                            TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
         return out
+
+
+class Sender(_Emitter):
+    """A device-resident transmission (nrq_tx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
+    whose packets are written straight into device memory.  src: the source rows (a torch HIP tensor or a raw device address),
+    block b at src + b*src_stride (0 = K*T); they are read by encode() and by every emit, so they must not change until the last
+    emit has completed.  Every call is enqueue-only on the context's stream."""
+    _api = "nrq_tx"
+
+    def __init__(self, ctx, K, T, nblk, src, src_stride=0, sbn0=0, Kp=0):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.K, self.T, self.nblk, self.sbn0 = K, T, nblk, sbn0
+        self._keep = src  # the tensor stays alive as long as the transmission
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_tx_create(ctx._h, K, Kp, T, nblk, sbn0, C.c_void_p(_dptr(src)), src_stride, C.byref(h)))
+        self._h = h
+
+    @property
+    def inter_ptr(self):
+        """device address of the intermediate symbols (block b's L rows at + b*L*T)"""
+        return self._L.nrq_tx_inter(self._h) or 0
 
     def emit_range(self, esi0, n, interleave=True, inline=False, out=None, tags_out=None):
         """ESIs esi0 .. esi0+n-1 of every block: n * nblk packets, interleaved (packet k: block k % nblk, ESI esi0 + k // nblk) or
@@ -546,10 +541,11 @@ def _blocks(p):
     return [(p.KL, p.KpL)] * p.ZL + [(p.KS, p.KpS)] * p.ZS
 
 
-class ObjectSender:
+class ObjectSender(_Emitter):
     """A whole object sent from device memory (nrq_otx, include/nanorq_hip.h): obj is a 1-D uint8 HIP tensor of F bytes, partitioned
     as nanorq_encoder_new_ext(F, T, K, Z, N, Al, flags) does.  The object must not change until the last emit has completed.
     Every call but the constructor is enqueue-only on the context's stream."""
+    _api = "nrq_otx"
 
     def __init__(self, ctx, obj, T, K=0, Z=0, N=1, Al=8, flags=0):
         if obj.dim() != 1 or obj.element_size() != 1 or not obj.is_contiguous():
@@ -565,23 +561,6 @@ class ObjectSender:
         ctx._chk(self._L.nrq_otx_create(ctx._h, C.byref(self.params), C.c_void_p(_dptr(obj)), C.byref(h)))
         self._h = h
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._L.nrq_otx_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     @property
     def oti(self):
         """(common, scheme-specific) OTI words for the receiver"""
@@ -593,28 +572,6 @@ class ObjectSender:
     def blocks(self):
         """(K, K') of every block, SBN 0 .. Z-1"""
         return _blocks(self.params)
-
-    def stride(self, inline=False):
-        return (self.T + 4 + 15) // 16 * 16 if inline else self.T
-
-    def _out(self, n, inline, out):
-        if out is not None:
-            return out, out.stride(0) * out.element_size()
-        import torch
-        out = torch.empty((n, self.stride(inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
-        return out, out.shape[1]
-
-    def encode(self):
-        self.ctx._chk(self._L.nrq_otx_encode(self._h))
-
-    def emit(self, tags, out=None, inline=False, results=None):
-        """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form, any SBN of the object) in row k of out.
-        results: optional [n] int32 device tensor (0 written, -1 SBN >= Z: packet left untouched).  Returns out."""
-        n = int(tags.shape[0])
-        out, stride = self._out(n, inline, out)
-        self.ctx._chk(self._L.nrq_otx_emit(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
-                                           TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
-        return out
 
     def count_all(self, nrep):
         p = self.params
@@ -628,9 +585,10 @@ class ObjectSender:
         return out
 
 
-class ObjectReceiver:
+class ObjectReceiver(_Handle):
     """A whole object received into device memory (nrq_orx, include/nanorq_hip.h), from its OTI words and the flags of
     nanorq_decoder_new_ext.  rep_cap: repair rows per block (default: 10 % of the larger K, at least 16)."""
+    _api = "nrq_orx"
 
     def __init__(self, ctx, common, specific, flags=0, rep_cap=None):
         self.ctx = ctx
@@ -644,23 +602,6 @@ class ObjectReceiver:
         h = C.c_void_p()
         ctx._chk(self._L.nrq_orx_create(ctx._h, C.byref(p), self.rep_cap, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self._L.nrq_orx_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     @property
     def blocks(self):

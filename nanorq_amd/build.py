@@ -133,8 +133,8 @@ def build_ingest_emu(force=False):
 
 
 def build_emit_emu(force=False):
-    """tests/emu/libemit_emu.so: CPU emulation of the device-resident sender's emit kernels (emit_body.h)."""
-    src = os.path.join(ROOT, "tests", "emu", "emit_emu.cpp")
+    """tests/emu/libemit_emu.so: CPU emulation of the device-resident emit kernel (csrc/emit_emu.cpp over emit_body.h)."""
+    src = os.path.join(CSRC, "emit_emu.cpp")
     deps = [src, os.path.join(CSRC, "emit_body.h"), os.path.join(CSRC, "rq_math.h")]
     if force or _newer(XEMU, deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", XEMU, src], check=True)

@@ -1,17 +1,22 @@
 /*
- * emit_body.h -- the per-packet bodies of the device-resident sender (nrq_tx_*, include/nanorq_hip.h): packets -- an optional
- * 4-byte RFC 6330 FEC Payload ID and a payload at a packet stride -- written straight into device memory for a transmission of
- * nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1, whose intermediate symbols are already in device memory.
+ * emit_body.h -- the per-packet bodies of the device-resident emit (nrq_tx_* and nrq_otx_*, include/nanorq_hip.h): packets -- an
+ * optional 4-byte RFC 6330 FEC Payload ID and a payload at a packet stride -- written straight into device memory from the
+ * intermediate symbols of blocks that are already in device memory.
+ *
+ * The source of an emit is a table (tx_src) of up to TX_SEGS segments: consecutive SBN ranges of equal (K, K', T) and uniform
+ * row strides (tx_blk), which together cover the span of Z blocks from SBN sbn0, the first ZL of them of the larger class.  A
+ * transmission (nrq_tx) is one segment with Z = ZL = nblk; an object (nrq_otx) has class L, class S and a last block staged
+ * apart (N = 1, F < Kt * T).
  *
  * Payload of (block b, ESI e), bit-exact with nanorq_encode (nanorq_api.c):
  *   e <  K   source row e of block b (the caller's rows)
  *   e >= K   LT(C_b, e + K' - K): the XOR of the intermediate symbols rq_lt_columns names
- * nrq_device.hip instantiates these bodies in its emit kernels; tests/emu/emit_emu.cpp runs them sequentially on the CPU.
+ * nrq_device.hip instantiates these bodies in its emit kernel; emit_emu.cpp runs them sequentially on the CPU.
  *
- * Work order.  A packet's repair gathers hit its block's L x T bytes of intermediate symbols; the kernels walk packets BLOCK-MAJOR
- * (work item w -> packet tx_work_packet(w)) so that a block's packets run together and its rows are served from the caches, in
- * whatever order the packets lie in the output.  emit_range maps analytically; a tag list is first bucketed by block
- * (tx_bin: one bucket per block, one more for foreign SBNs) into c->order.
+ * Work order.  A packet's repair gathers hit its block's L x T bytes of intermediate symbols; the kernel walks packets BLOCK-MAJOR
+ * (work item w -> packet tx_packet_of(w)) so that a block's packets run together and its rows are served from the caches, in
+ * whatever order the packets lie in the output.  Range mode maps analytically; a tag list is first bucketed by block (tx_bin:
+ * one bucket per block of the span, one more for SBNs outside it) into c->order.
  */
 #ifndef NRQ_EMIT_BODY_H
 #define NRQ_EMIT_BODY_H
@@ -31,7 +36,9 @@
                        * in LDS starts on its own bank) */
 #define TX_WAVE_PKTS 64u /* work items one wave takes: one per lane for the column lists, then one after the other for the payload */
 
-/* the transmission (device addresses; the emulation passes host arrays) */
+#define TX_SEGS 3u /* segments of an emit source: block class L, class S, and a last block staged apart */
+
+/* one segment: nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1 (device addresses; the emulation passes host arrays) */
 struct tx_blk {
   rq_params p;            /* of K' (p.K = K) */
   uint32_t K, T, nblk, sbn0;
@@ -39,6 +46,13 @@ struct tx_blk {
   uint64_t src_stride;
   const uint8_t *inter;   /* block b's intermediate symbol i at inter + b*inter_stride + i*T */
   uint64_t inter_stride;
+};
+
+/* the emit source: segments seg[0 .. nseg) over the span of Z blocks from SBN sbn0, the first ZL of them of the larger class */
+struct tx_src {
+  struct tx_blk seg[TX_SEGS];
+  uint32_t nseg;
+  uint32_t sbn0, Z, ZL;
 };
 
 /* one emit call */
@@ -49,51 +63,99 @@ struct tx_call {
   uint32_t inl;           /* 1: FEC Payload ID at +0, payload at +4 */
   const uint32_t *tags;   /* list mode: tag of packet k (nanorq_tag form); NULL: range mode */
   const uint32_t *order;  /* list mode: packet of work item w (bucketed by block) */
-  int32_t *results;       /* list mode, nullable: 0 written, -1 SBN outside the transmission */
-  uint32_t esi0, per_blk, interleave; /* range mode: per_blk ESIs esi0.. of every block; packet k -> (k % nblk, k / nblk) or
-                                       * (k / per_blk, k % per_blk) */
+  int32_t *results;       /* list mode, nullable: 0 written, -1 SBN outside the span */
+  uint32_t esi0, nL, nS;  /* range mode: ESIs esi0 .. esi0+nL-1 of each of the first ZL blocks, esi0 .. esi0+nS-1 of the rest */
+  uint32_t interleave;    /* range mode: 0 block-major, 1 sorted by (ESI, SBN) */
   uint32_t *tags_out;     /* range mode, nullable: the tag of each packet */
 };
 
 TX_HD uint32_t tx_tag(uint32_t sbn, uint32_t esi) { return (sbn << 24) | esi; }
 
-/* block of a tag inside the transmission, or TX_NONE */
-TX_HD uint32_t tx_block(const struct tx_blk *t, uint32_t tag) {
+/* block of a tag inside SBNs sbn0 .. sbn0+nblk-1, or TX_NONE */
+TX_HD uint32_t tx_index(uint32_t sbn0, uint32_t nblk, uint32_t tag) {
   const uint32_t sbn = tag >> 24;
-  return (sbn >= t->sbn0 && sbn - t->sbn0 < t->nblk) ? sbn - t->sbn0 : TX_NONE;
+  return (sbn >= sbn0 && sbn - sbn0 < nblk) ? sbn - sbn0 : TX_NONE;
+}
+TX_HD uint32_t tx_block(const struct tx_blk *t, uint32_t tag) { return tx_index(t->sbn0, t->nblk, tag); }
+
+/* list mode bucket: the block in the span, or nblk for an SBN outside it */
+TX_HD uint32_t tx_bin(uint32_t sbn0, uint32_t nblk, uint32_t tag) {
+  const uint32_t b = tx_index(sbn0, nblk, tag);
+  return b == TX_NONE ? nblk : b;
 }
 
-/* list mode bucket: the block, or nblk for a foreign SBN */
-TX_HD uint32_t tx_bin(const struct tx_blk *t, uint32_t tag) {
-  const uint32_t b = tx_block(t, tag);
-  return b == TX_NONE ? t->nblk : b;
+/* the segment holding the SBN of `tag`, or TX_SEGS (outside the span); MULTI = false: a one-segment table */
+template <bool MULTI>
+TX_HD uint32_t tx_seg(const struct tx_src *s, uint32_t tag) {
+  const uint32_t nseg = MULTI ? s->nseg : 1u;
+  for (uint32_t g = 0; g < nseg; g++)
+    if (tx_block(&s->seg[g], tag) != TX_NONE) return g;
+  return TX_SEGS;
 }
 
-/* packet index of work item w */
-TX_HD uint32_t tx_work_packet(const struct tx_blk *t, const struct tx_call *c, uint32_t w) {
+/* segment g, selected by value (no dynamic index into the kernel arguments) */
+TX_HD struct tx_blk tx_pick(const struct tx_src *s, uint32_t g) {
+  struct tx_blk t = s->seg[0];
+  if (g == 1u) t = s->seg[1];
+  else if (g == 2u) t = s->seg[2];
+  return t;
+}
+
+/* Range mode.  Block-major: block b's packets (nL or nS of them) one after the other.  Interleaved: round i holds ESI esi0 + i of
+ * every block while i < nlo, later rounds only the first ZL blocks' (nL >= nS).  MULTI = false: a one-segment table, i.e. one
+ * block class, where every block has nL packets (the launcher passes nL = nS) and the maps reduce to (w / nL, w % nL) and
+ * (k % Z, k / Z). */
+TX_HD uint32_t tx_nlo(const struct tx_src *s, const struct tx_call *c) { return s->Z - s->ZL ? c->nS : c->nL; }
+
+/* block-major position w -> (block, i) */
+template <bool MULTI>
+TX_HD void tx_bm(const struct tx_src *s, const struct tx_call *c, uint32_t w, uint32_t *b, uint32_t *i) {
+  const uint32_t aL = s->ZL * c->nL;
+  if (!MULTI || w < aL) { *b = w / c->nL; *i = w - *b * c->nL; }
+  else { const uint32_t w2 = w - aL, q = w2 / c->nS; *b = s->ZL + q; *i = w2 - q * c->nS; }
+}
+
+/* interleaved packet index of (block, i), and back */
+template <bool MULTI>
+TX_HD uint32_t tx_il_index(const struct tx_src *s, const struct tx_call *c, uint32_t b, uint32_t i) {
+  const uint32_t nlo = tx_nlo(s, c);
+  return !MULTI || i < nlo ? i * s->Z + b : nlo * s->Z + (i - nlo) * s->ZL + b;
+}
+template <bool MULTI>
+TX_HD void tx_il_pair(const struct tx_src *s, const struct tx_call *c, uint32_t k, uint32_t *b, uint32_t *i) {
+  const uint32_t nlo = tx_nlo(s, c), a = nlo * s->Z;
+  if (!MULTI || k < a) { *i = k / s->Z; *b = k - *i * s->Z; }
+  else { const uint32_t k2 = k - a, r = k2 / s->ZL; *i = nlo + r; *b = k2 - r * s->ZL; }
+}
+
+/* packet index of work item w (work in block-major order) */
+template <bool MULTI>
+TX_HD uint32_t tx_packet_of(const struct tx_src *s, const struct tx_call *c, uint32_t w) {
   if (c->tags) return c->order[w];
   if (!c->interleave) return w;
-  const uint32_t b = w / c->per_blk, i = w - b * c->per_blk;
-  return i * t->nblk + b;
+  uint32_t b, i;
+  tx_bm<MULTI>(s, c, w, &b, &i);
+  return tx_il_index<MULTI>(s, c, b, i);
 }
 
 /* tag of packet k */
-TX_HD uint32_t tx_packet_tag(const struct tx_blk *t, const struct tx_call *c, uint32_t k) {
+template <bool MULTI>
+TX_HD uint32_t tx_tag_of(const struct tx_src *s, const struct tx_call *c, uint32_t k) {
   if (c->tags) return c->tags[k];
   uint32_t b, i;
-  if (c->interleave) { i = k / t->nblk; b = k - i * t->nblk; }
-  else { b = k / c->per_blk; i = k - b * c->per_blk; }
-  return tx_tag(t->sbn0 + b, c->esi0 + i);
+  if (c->interleave) tx_il_pair<MULTI>(s, c, k, &b, &i);
+  else tx_bm<MULTI>(s, c, k, &b, &i);
+  return tx_tag(s->sbn0 + b, c->esi0 + i);
 }
 
-/* the rows a packet of `tag` (inside the transmission) is made of: the block's source rows or its intermediate symbols */
+/* the rows a packet of `tag` (inside the segment) is made of: the block's source rows or its intermediate symbols */
 TX_HD const uint8_t *tx_base(const struct tx_blk *t, uint32_t tag) {
   const uint32_t b = tx_block(t, tag);
   return (tag & 0xFFFFFFu) < t->K ? t->src + (uint64_t)b * t->src_stride : t->inter + (uint64_t)b * t->inter_stride;
 }
 
 /* The rows whose XOR is the payload of `tag`, as indices (times T) from tx_base into cols[TX_COLS]; returns their count, 0 for
- * a foreign SBN. */
+ * an SBN outside the segment. */
 TX_HD uint32_t tx_rows(const struct tx_blk *t, uint32_t tag, uint32_t *cols) {
   const uint32_t esi = tag & 0xFFFFFFu;
   if (tx_block(t, tag) == TX_NONE) return 0;

@@ -3660,7 +3660,7 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
 
 } /* extern "C" */
 
-/* ================================================ device-resident sender (nrq_tx_*, emit_body.h) ==== */
+/* ================================================ device-resident emit (nrq_tx_* / nrq_otx_*, emit_body.h) ==== */
 #define TX_WAVES 4u        /* waves per emit workgroup */
 #define TX_BIN_TILE 4096u  /* packets per workgroup of the bucketing passes */
 
@@ -3709,44 +3709,59 @@ __device__ __forceinline__ void tx_payload(const uint8_t *__restrict__ base, uin
 
 /* One wave per TX_WAVE_PKTS work items, in block-major order: each lane builds the column list of one item into LDS, then the
  * wave writes the items' packets one after the other, a 16/4/1-byte word of the payload per lane (the XOR of the item's rows,
- * four rows in flight). */
-template <int MODE>
-__global__ __launch_bounds__(256) void nrq_tx_emit_kernel(tx_blk t, tx_call c) {
+ * four rows in flight).  Each packet's rows come from the table segment of its SBN; MULTI = false is the form for a one-segment
+ * table (no segment search, no select, no segment index in LDS). */
+template <int MODE, bool MULTI>
+__global__ __launch_bounds__(256) void nrq_emit_kernel(tx_src s, tx_call c) {
   __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
   __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS]; /* (MULTI only: unused LDS is not allocated) */
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
   if (w0 + lane < c.n) {
-    const uint32_t k = tx_work_packet(&t, &c, (uint32_t)(w0 + lane));
-    const uint32_t tag = k < c.n ? tx_packet_tag(&t, &c, k) : 0u;
-    const uint32_t n = k < c.n ? tx_rows(&t, tag, s_cols[wv][lane]) : 0u; /* (k < n always: the work order is a permutation) */
+    const uint32_t k = tx_packet_of<MULTI>(&s, &c, (uint32_t)(w0 + lane));
+    const uint32_t tag = k < c.n ? tx_tag_of<MULTI>(&s, &c, k) : 0u;
+    const uint32_t sg = k < c.n ? tx_seg<MULTI>(&s, tag) : TX_SEGS; /* (k < n always: the work order is a permutation) */
+    const tx_blk sb = MULTI ? tx_pick(&s, sg) : s.seg[0];
+    const uint32_t n = sg < TX_SEGS ? tx_rows(&sb, tag, s_cols[wv][lane]) : 0u;
     s_n[wv][lane] = n;
     s_tag[wv][lane] = tag;
     s_k[wv][lane] = k;
+    if (MULTI) s_seg[wv][lane] = sg;
     if (k < c.n && c.results) c.results[k] = n ? 0 : -1;
     if (k < c.n && c.tags_out) c.tags_out[k] = tag;
   }
   __syncthreads();
   const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
-  const uint32_t T = t.T;
+  const uint32_t T = s.seg[0].T;
   for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
     const uint32_t n = s_n[wv][i];
-    if (!n) continue; /* foreign SBN: the packet stays untouched */
+    if (!n) continue; /* SBN outside the span: the packet stays untouched */
     const uint32_t tag = s_tag[wv][i];
-    const uint32_t *cols = s_cols[wv][i];
-    tx_payload<MODE>(tx_base(&t, tag), T, cols, n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
+    const uint8_t *base;
+    if constexpr (MULTI) {
+      /* the rows' base rebuilt from the kernel arguments with a wave-uniform segment (a pointer kept in LDS would come back as a
+       * generic one: flat loads, and waits that also cover the LDS reads); only the chosen segment's fields are read (segment
+       * 0's base, replaced after a test, costs two dependent argument loads per packet) */
+      const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][i]);
+      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
+    } else {
+      base = tx_base(&s.seg[0], tag);
+    }
+    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
   }
 }
 
-/* tag-list bucketing: packets per bucket (tx_bin), a histogram in LDS per tile of TX_BIN_TILE packets, added to cnt[] */
-__global__ __launch_bounds__(256) void nrq_tx_hist_kernel(tx_blk t, const uint32_t *tags, uint32_t n, uint32_t *cnt) {
+/* tag-list bucketing over the span of nblk blocks from sbn0: packets per bucket (tx_bin), a histogram in LDS per tile of
+ * TX_BIN_TILE packets, added to cnt[] */
+__global__ __launch_bounds__(256) void nrq_tx_hist_kernel(uint32_t sbn0, uint32_t nblk, const uint32_t *tags, uint32_t n, uint32_t *cnt) {
   __shared__ uint32_t h[257];
-  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) h[i] = 0;
+  for (uint32_t i = threadIdx.x; i <= nblk; i += 256u) h[i] = 0;
   __syncthreads();
   const uint32_t k0 = blockIdx.x * TX_BIN_TILE, k1 = min(n, k0 + TX_BIN_TILE);
-  for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256u) atomicAdd(&h[tx_bin(&t, tags[k])], 1u);
+  for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256u) atomicAdd(&h[tx_bin(sbn0, nblk, tags[k])], 1u);
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u)
+  for (uint32_t i = threadIdx.x; i <= nblk; i += 256u)
     if (h[i]) atomicAdd(&cnt[i], h[i]);
 }
 
@@ -3758,35 +3773,156 @@ __global__ __launch_bounds__(64) void nrq_tx_scan_kernel(uint32_t nbins, uint32_
 }
 
 /* each tile reserves its packets' places in every bucket (one atomic per bucket and tile), then writes order[] */
-__global__ __launch_bounds__(256) void nrq_tx_place_kernel(tx_blk t, const uint32_t *tags, uint32_t n, uint32_t *cursor, uint32_t *order) {
+__global__ __launch_bounds__(256) void nrq_tx_place_kernel(uint32_t sbn0, uint32_t nblk, const uint32_t *tags, uint32_t n, uint32_t *cursor,
+                                                           uint32_t *order) {
   __shared__ uint32_t h[257], base[257];
   constexpr uint32_t PER = TX_BIN_TILE / 256u;
-  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) h[i] = 0;
+  for (uint32_t i = threadIdx.x; i <= nblk; i += 256u) h[i] = 0;
   __syncthreads();
   const uint32_t k0 = blockIdx.x * TX_BIN_TILE;
   uint32_t bin[PER], rank[PER];
 #pragma unroll
   for (uint32_t r = 0; r < PER; r++) {
     const uint32_t k = k0 + r * 256u + threadIdx.x;
-    bin[r] = k < n ? tx_bin(&t, tags[k]) : TX_NONE;
+    bin[r] = k < n ? tx_bin(sbn0, nblk, tags[k]) : TX_NONE;
     rank[r] = bin[r] != TX_NONE ? atomicAdd(&h[bin[r]], 1u) : 0u;
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i <= t.nblk; i += 256u) base[i] = h[i] ? atomicAdd(&cursor[i], h[i]) : 0u;
+  for (uint32_t i = threadIdx.x; i <= nblk; i += 256u) base[i] = h[i] ? atomicAdd(&cursor[i], h[i]) : 0u;
   __syncthreads();
 #pragma unroll
   for (uint32_t r = 0; r < PER; r++)
     if (bin[r] != TX_NONE) order[base[bin[r]] + rank[r]] = k0 + r * 256u + threadIdx.x;
 }
 
-struct nrq_tx {
+/* what both senders are: an emit source and the device buffers behind it.  nrq_tx and nrq_otx (distinct in the header) are this
+ * plus, for an object, its parameters; their create calls fill it, everything after that is shared. */
+struct tx_sender {
   nrq_ctx *ctx;
-  tx_blk t;
-  void *own_inter;
+  tx_src s;
+  void *own[2];          /* device buffers it owns: the intermediate symbols; an object's row images or staged last block */
   bool encoded;
-  void *scratch; /* list mode: bucket counts, then the work order */
+  const char *unencoded; /* the emit calls' refusal before the encode */
+  void *scratch;         /* list mode: bucket counts, then the work order */
   size_t scratch_cap;
 };
+
+struct nrq_tx : tx_sender {};
+
+template <class S>
+static void tx_destroy(S *tx) {
+  if (!tx) return;
+  nrq_ctx *ctx = tx->ctx;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {tx->own[0], tx->own[1], tx->scratch})
+    if (p) nrq_dev_free(ctx, p);
+  delete tx;
+}
+
+/* solve every block of every segment */
+static int tx_encode(tx_sender *tx) {
+  if (!tx) return -1;
+  tx->encoded = false;
+  for (uint32_t g = 0; g < tx->s.nseg; g++) {
+    const tx_blk &t = tx->s.seg[g];
+    const int rc = nrq_encode_blocks(tx->ctx, t.K, t.p.Kp, t.T, t.nblk, t.src, t.src_stride, (void *)t.inter, t.inter_stride, 0, nullptr,
+                                     nullptr, 0);
+    if (rc) return rc;
+  }
+  tx->encoded = true;
+  return 0;
+}
+
+/* checks shared by every emit call */
+static int tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
+  nrq_ctx *ctx = tx->ctx;
+  if (!tx->encoded) return fail(ctx, -1, "%s: %s", who, tx->unencoded);
+  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
+  if (pkt_stride < (size_t)tx->s.seg[0].T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
+  return 0;
+}
+
+/* the emit kernel at the widest path the addresses allow, in its one-segment form for a one-segment table */
+static int tx_launch(tx_sender *tx, const tx_call &c) {
+  using emit_fn = void (*)(tx_src, tx_call);
+  static const emit_fn kern[2][4] = { /* [multi-segment][mode] */
+      {nrq_emit_kernel<TX_V16, false>, nrq_emit_kernel<TX_V16_SHIFT, false>, nrq_emit_kernel<TX_DWORD, false>,
+       nrq_emit_kernel<TX_BYTE, false>},
+      {nrq_emit_kernel<TX_V16, true>, nrq_emit_kernel<TX_V16_SHIFT, true>, nrq_emit_kernel<TX_DWORD, true>,
+       nrq_emit_kernel<TX_BYTE, true>}};
+  nrq_ctx *ctx = tx->ctx;
+  const tx_src &s = tx->s;
+  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | s.seg[0].T;
+  for (uint32_t g = 0; g < s.nseg; g++)
+    al |= reinterpret_cast<uintptr_t>(s.seg[g].src) | s.seg[g].src_stride | reinterpret_cast<uintptr_t>(s.seg[g].inter) | s.seg[g].inter_stride;
+  const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (c.inl ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
+  const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
+  hipLaunchKernelGGL(kern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, c);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* list mode: the tags bucketed by block of the span into the scratch's work order, then the emit */
+static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                        int32_t *d_results) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u)", who, n);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
+  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
+  if (tx->scratch_cap < need) {
+    if (tx->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, tx->scratch);
+      tx->scratch = nullptr;
+      tx->scratch_cap = 0;
+    }
+    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
+    tx->scratch_cap = need;
+  }
+  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt, order);
+  HIPCHK(ctx, hipGetLastError());
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.tags = d_tags;
+  c.order = order;
+  c.results = d_results;
+  return tx_launch(tx, c);
+}
+
+/* range mode (the caller has checked its arguments): ESIs esi0 .. esi0+nL-1 of each of the span's first ZL blocks, esi0 ..
+ * esi0+nS-1 of the rest, block-major (order 0) or interleaved (1) */
+static int tx_emit_span(tx_sender *tx, uint32_t esi0, uint32_t nL, uint32_t nS, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                        uint32_t *d_tags_out) {
+  nrq_ctx *ctx = tx->ctx;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = tx->s.ZL * nL + (tx->s.Z - tx->s.ZL) * nS;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.esi0 = esi0;
+  c.nL = tx->s.ZL ? nL : nS; /* (a table of one class has nL packets per block: the one-segment maps) */
+  c.nS = nS;
+  c.interleave = (uint32_t)order;
+  c.tags_out = d_tags_out;
+  return tx_launch(tx, c);
+}
 
 extern "C" {
 
@@ -3806,113 +3942,32 @@ int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nb
   nrq_tx *tx = new (std::nothrow) nrq_tx();
   if (!tx) return fail(ctx, -1, "nrq_tx_create: out of host memory");
   tx->ctx = ctx;
-  tx_blk &t = tx->t;
+  tx->unencoded = "the transmission is not encoded (nrq_tx_encode)";
+  tx->s.nseg = 1;
+  tx->s.sbn0 = sbn0; tx->s.Z = tx->s.ZL = nblk;
+  tx_blk &t = tx->s.seg[0];
   int rc = block_params(ctx, K, Kp, &t.p);
   if (rc) { delete tx; return rc; }
   t.K = K; t.T = T; t.nblk = nblk; t.sbn0 = sbn0;
   t.src = (const uint8_t *)d_src; t.src_stride = src_stride;
   t.inter_stride = (uint64_t)t.p.L * T;
-  if ((rc = nrq_dev_alloc(ctx, (size_t)nblk * t.inter_stride, &tx->own_inter))) {
+  if ((rc = nrq_dev_alloc(ctx, (size_t)nblk * t.inter_stride, &tx->own[0]))) {
     delete tx;
     return rc;
   }
-  t.inter = (const uint8_t *)tx->own_inter;
+  t.inter = (const uint8_t *)tx->own[0];
   *out = tx;
   return 0;
 }
 
-void nrq_tx_destroy(nrq_tx *tx) {
-  if (!tx) return;
-  nrq_ctx *ctx = tx->ctx;
-  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {tx->own_inter, tx->scratch})
-    if (p) nrq_dev_free(ctx, p);
-  delete tx;
-}
+void nrq_tx_destroy(nrq_tx *tx) { tx_destroy(tx); }
 
-int nrq_tx_encode(nrq_tx *tx) {
-  if (!tx) return -1;
-  const tx_blk &t = tx->t;
-  tx->encoded = false;
-  const int rc = nrq_encode_blocks(tx->ctx, t.K, t.p.Kp, t.T, t.nblk, t.src, t.src_stride, (void *)t.inter, t.inter_stride, 0, nullptr,
-                                   nullptr, 0);
-  tx->encoded = rc == 0;
-  return rc;
-}
+int nrq_tx_encode(nrq_tx *tx) { return tx_encode(tx); }
 
-void *nrq_tx_inter(nrq_tx *tx) { return tx ? (void *)tx->t.inter : nullptr; }
-
-} /* extern "C" */
-
-/* checks shared by both emit calls, then the launch of the emit kernel at the widest path the addresses allow */
-static int tx_check(nrq_tx *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
-  nrq_ctx *ctx = tx->ctx;
-  if (!tx->encoded) return fail(ctx, -1, "%s: the transmission is not encoded (nrq_tx_encode)", who);
-  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
-  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
-  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
-  if (pkt_stride < (size_t)tx->t.T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
-  return 0;
-}
-
-static int tx_launch(nrq_tx *tx, tx_call &c) {
-  nrq_ctx *ctx = tx->ctx;
-  const tx_blk &t = tx->t;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | t.T | reinterpret_cast<uintptr_t>(t.src) | t.src_stride |
-                       reinterpret_cast<uintptr_t>(t.inter);
-  const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
-  if ((al & 15u) == 0 && !ctx->tune.tx_dword) {
-    if (c.inl) hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_V16_SHIFT>, grid, wg, 0, ctx->stream, t, c);
-    else hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_V16>, grid, wg, 0, ctx->stream, t, c);
-  } else if ((al & 3u) == 0) {
-    hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_DWORD>, grid, wg, 0, ctx->stream, t, c);
-  } else {
-    hipLaunchKernelGGL(nrq_tx_emit_kernel<TX_BYTE>, grid, wg, 0, ctx->stream, t, c);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-extern "C" {
+void *nrq_tx_inter(nrq_tx *tx) { return tx ? (void *)tx->s.seg[0].inter : nullptr; }
 
 int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
-  if (!tx) return -1;
-  nrq_ctx *ctx = tx->ctx;
-  int rc = tx_check(tx, "nrq_tx_emit", d_pkts, pkt_stride, flags);
-  if (rc) return rc;
-  if (n == 0) return 0;
-  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit: bad tags (n=%u)", n);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const tx_blk &t = tx->t;
-  const uint32_t nbins = t.nblk + 1u;
-  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if (tx->scratch_cap < need) {
-    if (tx->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, tx->scratch);
-      tx->scratch = nullptr;
-      tx->scratch_cap = 0;
-    }
-    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
-    tx->scratch_cap = need;
-  }
-  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
-  hipStream_t st = ctx->stream;
-  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
-  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, t, d_tags, n, cnt);
-  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
-  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, t, d_tags, n, cnt, order);
-  HIPCHK(ctx, hipGetLastError());
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
-  c.tags = d_tags;
-  c.order = order;
-  c.results = d_results;
-  return tx_launch(tx, c);
+  return tx_emit_list(tx, "nrq_tx_emit", d_tags, n, d_pkts, pkt_stride, flags, d_results);
 }
 
 int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out) {
@@ -3923,18 +3978,8 @@ int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_
   if (order != 0 && order != 1) return fail(ctx, -1, "nrq_tx_emit_range: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
   if (n == 0) return 0;
   if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "nrq_tx_emit_range: ESIs %u + %u reach past 2^24", esi0, n);
-  if ((uint64_t)n * tx->t.nblk > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit_range: %u packets per block is too many", n);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n * tx->t.nblk;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
-  c.esi0 = esi0;
-  c.per_blk = n;
-  c.interleave = (uint32_t)order;
-  c.tags_out = d_tags_out;
-  return tx_launch(tx, c);
+  if ((uint64_t)n * tx->s.Z > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit_range: %u packets per block is too many", n);
+  return tx_emit_span(tx, esi0, n, n, order, d_pkts, pkt_stride, flags, d_tags_out);
 }
 
 } /* extern "C" */
@@ -4007,44 +4052,6 @@ static int obj_layout_launch(nrq_ctx *ctx, const obj_lay &l) {
   return 0;
 }
 
-/* the object emit: nrq_tx_emit_kernel with each packet's rows taken from the class-table segment of its SBN */
-template <int MODE>
-__global__ __launch_bounds__(256) void nrq_otx_emit_kernel(otx_obj o, tx_call c) {
-  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
-  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
-  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
-  if (w0 + lane < c.n) {
-    const uint32_t k = otx_work_packet(&o, &c, (uint32_t)(w0 + lane));
-    const uint32_t tag = k < c.n ? otx_packet_tag(&o, &c, k) : 0u;
-    const uint32_t sg = k < c.n ? otx_seg(&o, tag) : OTX_SEGS;
-    tx_blk sb = o.seg[0]; /* (selected by value: no dynamic index into the kernel arguments) */
-    if (sg == 1u) sb = o.seg[1];
-    else if (sg == 2u) sb = o.seg[2];
-    const uint32_t n = sg < OTX_SEGS ? tx_rows(&sb, tag, s_cols[wv][lane]) : 0u;
-    s_n[wv][lane] = n;
-    s_tag[wv][lane] = tag;
-    s_k[wv][lane] = k;
-    s_seg[wv][lane] = sg;
-    if (k < c.n && c.results) c.results[k] = n ? 0 : -1;
-    if (k < c.n && c.tags_out) c.tags_out[k] = tag;
-  }
-  __syncthreads();
-  const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
-  const uint32_t T = o.seg[0].T;
-  for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
-    const uint32_t n = s_n[wv][i];
-    if (!n) continue; /* SBN >= Z: the packet stays untouched */
-    const uint32_t tag = s_tag[wv][i];
-    /* the rows' base rebuilt from the kernel arguments with a wave-uniform segment (a pointer kept in LDS would come back as a
-     * generic one: flat loads, and waits that also cover the LDS reads) */
-    const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][i]);
-    const uint8_t *base = sg == 0u ? tx_base(&o.seg[0], tag) : sg == 1u ? tx_base(&o.seg[1], tag) : tx_base(&o.seg[2], tag);
-    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
-  }
-}
-
 /* the receiver's code for packets of SBN >= Z, as nanorq_decoder_add_symbol gives it (such a block has no symbols, hence no
  * gaps): ING_ERR (NANORQ_SYM_ERR) for an ESI above max_esi, else ING_IGN */
 __global__ __launch_bounds__(256) void nrq_orx_foreign_kernel(const uint8_t *pkts, uint64_t pkt_stride, const uint32_t *tags, uint32_t n,
@@ -4061,15 +4068,8 @@ __global__ __launch_bounds__(256) void nrq_orx_foreign_kernel(const uint8_t *pkt
   if ((tag >> 24) >= Z) results[k] = (tag & 0xFFFFFFu) > max_esi ? ING_ERR : ING_IGN;
 }
 
-struct nrq_otx {
-  nrq_ctx *ctx;
+struct nrq_otx : tx_sender {
   nrq_obj_params prm;
-  otx_obj o;
-  void *own_rows;  /* N > 1: every block's row image; N = 1: the staged last block (or nothing) */
-  void *own_inter;
-  bool encoded;
-  void *scratch;   /* list mode: bucket counts, then the work order */
-  size_t scratch_cap;
 };
 
 struct nrq_orx {
@@ -4105,27 +4105,29 @@ int nrq_otx_create(nrq_ctx *ctx, const nrq_obj_params *prm, const void *d_obj, n
   nrq_otx *tx = new (std::nothrow) nrq_otx();
   if (!tx) return fail(ctx, -1, "nrq_otx_create: out of host memory");
   tx->ctx = ctx;
+  tx->unencoded = "the object is not encoded (nrq_otx_encode)";
   tx->prm = p;
-  otx_obj &o = tx->o;
-  o.Z = p.Z; o.ZL = p.ZL; o.KL = p.KL; o.KS = p.KS;
+  tx_src &o = tx->s;
+  o.sbn0 = 0; o.Z = p.Z; o.ZL = p.ZL;
   const uint64_t T = p.T, LL = (uint64_t)pL.L * T, LS = (uint64_t)pS.L * T;
   const uint32_t last = p.Z - 1u, Klast = last < p.ZL ? p.KL : p.KS;
   const uint64_t olast = (uint64_t)(p.Kt - Klast) * T;
   const bool stage = p.N == 1u && p.F < (uint64_t)p.Kt * T;
   const uint8_t *rows = (const uint8_t *)d_obj;
+  void *&own_rows = tx->own[1]; /* N > 1: every block's row image; N = 1: the staged last block (or nothing) */
   uint8_t *inter = nullptr;
-  if ((rc = nrq_dev_alloc(ctx, (size_t)(p.ZL * LL + p.ZS * LS), &tx->own_inter))) goto bad;
-  inter = (uint8_t *)tx->own_inter;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)(p.ZL * LL + p.ZS * LS), &tx->own[0]))) goto bad;
+  inter = (uint8_t *)tx->own[0];
   if (p.N > 1u) {
-    if ((rc = nrq_dev_alloc(ctx, (size_t)p.Kt * T, &tx->own_rows))) goto bad;
-    if ((rc = obj_layout_launch(ctx, obj_lay_of(&p, (void *)d_obj, tx->own_rows, 0)))) goto bad;
-    rows = (const uint8_t *)tx->own_rows;
+    if ((rc = nrq_dev_alloc(ctx, (size_t)p.Kt * T, &own_rows))) goto bad;
+    if ((rc = obj_layout_launch(ctx, obj_lay_of(&p, (void *)d_obj, own_rows, 0)))) goto bad;
+    rows = (const uint8_t *)own_rows;
   } else if (stage) {
     const size_t have = (size_t)(p.F - olast), full = (size_t)Klast * T;
-    if ((rc = nrq_dev_alloc(ctx, full, &tx->own_rows))) goto bad;
+    if ((rc = nrq_dev_alloc(ctx, full, &own_rows))) goto bad;
     hipError_t e = nrq_inject(ctx) ? hipErrorUnknown
-                                   : hipMemcpyAsync(tx->own_rows, (const uint8_t *)d_obj + olast, have, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = nrq_inject(ctx) ? hipErrorUnknown : hipMemsetAsync((uint8_t *)tx->own_rows + have, 0, full - have, ctx->stream);
+                                   : hipMemcpyAsync(own_rows, (const uint8_t *)d_obj + olast, have, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = nrq_inject(ctx) ? hipErrorUnknown : hipMemsetAsync((uint8_t *)own_rows + have, 0, full - have, ctx->stream);
     if (e != hipSuccess) {
       rc = fail(ctx, -10, "nrq_otx_create: staging the last block failed: %s", hipGetErrorString(e));
       goto bad;
@@ -4143,7 +4145,7 @@ int nrq_otx_create(nrq_ctx *ctx, const nrq_obj_params *prm, const void *d_obj, n
     const uint32_t cutL = stage && last < p.ZL ? 1u : 0u, cutS = stage && last >= p.ZL ? 1u : 0u;
     seg(0, p.ZL - cutL, pL, p.KL, rows, LL);
     seg(p.ZL, p.ZS - cutS, pS, p.KS, rows + (uint64_t)p.ZL * p.KL * T, LS);
-    if (stage) seg(last, 1, last < p.ZL ? pL : pS, Klast, (const uint8_t *)tx->own_rows, last < p.ZL ? LL : LS);
+    if (stage) seg(last, 1, last < p.ZL ? pL : pS, Klast, (const uint8_t *)own_rows, last < p.ZL ? LL : LS);
   }
   *out = tx;
   return 0;
@@ -4152,27 +4154,9 @@ bad:
   return rc;
 }
 
-void nrq_otx_destroy(nrq_otx *tx) {
-  if (!tx) return;
-  nrq_ctx *ctx = tx->ctx;
-  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {tx->own_rows, tx->own_inter, tx->scratch})
-    if (p) nrq_dev_free(ctx, p);
-  delete tx;
-}
+void nrq_otx_destroy(nrq_otx *tx) { tx_destroy(tx); }
 
-int nrq_otx_encode(nrq_otx *tx) {
-  if (!tx) return -1;
-  tx->encoded = false;
-  for (uint32_t s = 0; s < tx->o.nseg; s++) {
-    const tx_blk &t = tx->o.seg[s];
-    const int rc = nrq_encode_blocks(tx->ctx, t.K, t.p.Kp, t.T, t.nblk, t.src, t.src_stride, (void *)t.inter, t.inter_stride, 0, nullptr,
-                                     nullptr, 0);
-    if (rc) return rc;
-  }
-  tx->encoded = true;
-  return 0;
-}
+int nrq_otx_encode(nrq_otx *tx) { return tx_encode(tx); }
 
 int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific) {
   if (!tx) return -1;
@@ -4181,84 +4165,14 @@ int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific) {
   return 0;
 }
 
-} /* extern "C" */
-
-static int otx_launch(nrq_otx *tx, const otx_obj &o, tx_call &c) {
-  nrq_ctx *ctx = tx->ctx;
-  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | tx->prm.T;
-  for (uint32_t s = 0; s < o.nseg; s++)
-    al |= reinterpret_cast<uintptr_t>(o.seg[s].src) | o.seg[s].src_stride | reinterpret_cast<uintptr_t>(o.seg[s].inter) | o.seg[s].inter_stride;
-  const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
-  if ((al & 15u) == 0 && !ctx->tune.tx_dword) {
-    if (c.inl) hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_V16_SHIFT>, grid, wg, 0, ctx->stream, o, c);
-    else hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_V16>, grid, wg, 0, ctx->stream, o, c);
-  } else if ((al & 3u) == 0) {
-    hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_DWORD>, grid, wg, 0, ctx->stream, o, c);
-  } else {
-    hipLaunchKernelGGL(nrq_otx_emit_kernel<TX_BYTE>, grid, wg, 0, ctx->stream, o, c);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-static int otx_check(nrq_otx *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
-  nrq_ctx *ctx = tx->ctx;
-  if (!tx->encoded) return fail(ctx, -1, "%s: the object is not encoded (nrq_otx_encode)", who);
-  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
-  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
-  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
-  if (pkt_stride < (size_t)tx->prm.T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
-  return 0;
-}
-
-extern "C" {
-
 int nrq_otx_emit(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
-  if (!tx) return -1;
-  nrq_ctx *ctx = tx->ctx;
-  int rc = otx_check(tx, "nrq_otx_emit", d_pkts, pkt_stride, flags);
-  if (rc) return rc;
-  if (n == 0) return 0;
-  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_otx_emit: bad tags (n=%u)", n);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  tx_blk all{}; /* the bucketing passes see the object as one run of Z blocks */
-  all.sbn0 = 0;
-  all.nblk = tx->prm.Z;
-  const uint32_t nbins = all.nblk + 1u;
-  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if (tx->scratch_cap < need) {
-    if (tx->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, tx->scratch);
-      tx->scratch = nullptr;
-      tx->scratch_cap = 0;
-    }
-    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
-    tx->scratch_cap = need;
-  }
-  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
-  hipStream_t st = ctx->stream;
-  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
-  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, all, d_tags, n, cnt);
-  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
-  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, all, d_tags, n, cnt, order);
-  HIPCHK(ctx, hipGetLastError());
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
-  c.tags = d_tags;
-  c.order = order;
-  c.results = d_results;
-  return otx_launch(tx, tx->o, c);
+  return tx_emit_list(tx, "nrq_otx_emit", d_tags, n, d_pkts, pkt_stride, flags, d_results);
 }
 
 int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out) {
   if (!tx) return -1;
   nrq_ctx *ctx = tx->ctx;
-  int rc = otx_check(tx, "nrq_otx_emit_all", d_pkts, pkt_stride, flags);
+  int rc = tx_check(tx, "nrq_otx_emit_all", d_pkts, pkt_stride, flags);
   if (rc) return rc;
   if (order != 0 && order != 1) return fail(ctx, -1, "nrq_otx_emit_all: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
   const nrq_obj_params &p = tx->prm;
@@ -4266,17 +4180,7 @@ int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t
   if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "nrq_otx_emit_all: ESIs up to %llu + %u reach past 2^24", (unsigned long long)kmax, nrep);
   const uint64_t total = (uint64_t)p.ZL * (p.KL + (uint64_t)nrep) + (uint64_t)p.ZS * (p.KS + (uint64_t)nrep);
   if (total > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_otx_emit_all: %llu packets are too many", (unsigned long long)total);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  otx_obj o = tx->o;
-  o.nrep = nrep;
-  o.interleave = (uint32_t)order;
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = (uint32_t)total;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
-  c.tags_out = d_tags_out;
-  return otx_launch(tx, o, c);
+  return tx_emit_span(tx, 0, p.KL + nrep, p.KS + nrep, order, d_pkts, pkt_stride, flags, d_tags_out);
 }
 
 int nrq_orx_create(nrq_ctx *ctx, const nrq_obj_params *prm, uint32_t rep_cap, nrq_orx **out) {

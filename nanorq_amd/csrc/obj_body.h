@@ -15,16 +15,13 @@
  * 16, 8, 4, 2, 1 dividing T, TL and TS: a piece then never straddles a sub-block row, and its row-side address is V-aligned.
  * A window that a block boundary or F cuts goes a byte at a time on the object side, only the block's own bytes.
  * nrq_device.hip instantiates these bodies in nrq_obj_layout_kernel; tests/emu/obj_emu.cpp runs them on the CPU.
- *
- * The object sender's class table (otx_obj) is here too: the packets of one emit span both block classes of an object, and the
- * per-packet bodies of emit_body.h run against the table entry (segment) that holds the packet's SBN.
  */
 #ifndef NRQ_OBJ_BODY_H
 #define NRQ_OBJ_BODY_H
 
 #include <stdint.h>
 
-#include "emit_body.h"
+#include "emit_body.h" /* (TX_HD) */
 
 #define OBJ_WIN 16u       /* bytes per object window */
 #define OBJ_UNROLL 4u     /* windows per work item (all loaded before any is stored) */
@@ -162,65 +159,6 @@ TX_HD void obj_move(const struct obj_lay *l, uint32_t b, uint32_t q0, uint32_t s
       obj_store_window<W>(l, ws[u], full[u], own[u], v[u]);
     }
   }
-}
-
-/* ---- the object sender's class table ---- */
-#define OTX_SEGS 3u /* block class L, class S, and a last block staged apart (N = 1, F < Kt * T) */
-
-struct otx_obj {
-  struct tx_blk seg[OTX_SEGS]; /* consecutive SBN ranges of equal (K, K') and uniform row strides */
-  uint32_t nseg;
-  uint32_t Z, ZL, KL, KS;
-  uint32_t nrep, interleave;   /* emit_all: ESIs 0 .. K_b + nrep - 1 of every block; order */
-};
-
-/* the segment holding the SBN of `tag`, or OTX_SEGS (SBN >= Z) */
-TX_HD uint32_t otx_seg(const struct otx_obj *o, uint32_t tag) {
-  for (uint32_t s = 0; s < o->nseg; s++)
-    if (tx_block(&o->seg[s], tag) != TX_NONE) return s;
-  return OTX_SEGS;
-}
-
-/* emit_all: packets per block of each class, and the ESI count below which every block takes part in an interleaved round */
-TX_HD uint32_t otx_nL(const struct otx_obj *o) { return o->KL + o->nrep; }
-TX_HD uint32_t otx_nS(const struct otx_obj *o) { return o->KS + o->nrep; }
-TX_HD uint32_t otx_nlo(const struct otx_obj *o) { return o->Z - o->ZL ? otx_nS(o) : otx_nL(o); }
-TX_HD uint32_t otx_total(const struct otx_obj *o) { return o->ZL * otx_nL(o) + (o->Z - o->ZL) * otx_nS(o); }
-
-/* block-major position w -> (block, i) */
-TX_HD void otx_bm(const struct otx_obj *o, uint32_t w, uint32_t *b, uint32_t *i) {
-  const uint32_t nL = otx_nL(o), nS = otx_nS(o), aL = o->ZL * nL;
-  if (w < aL) { *b = w / nL; *i = w - *b * nL; }
-  else { const uint32_t w2 = w - aL, q = w2 / nS; *b = o->ZL + q; *i = w2 - q * nS; }
-}
-
-/* interleaved packet index of (block, i), and back (rounds i < nlo hold every block, later rounds only class L's) */
-TX_HD uint32_t otx_il_index(const struct otx_obj *o, uint32_t b, uint32_t i) {
-  const uint32_t nlo = otx_nlo(o);
-  return i < nlo ? i * o->Z + b : nlo * o->Z + (i - nlo) * o->ZL + b;
-}
-TX_HD void otx_il_pair(const struct otx_obj *o, uint32_t k, uint32_t *b, uint32_t *i) {
-  const uint32_t nlo = otx_nlo(o), a = nlo * o->Z;
-  if (k < a) { *i = k / o->Z; *b = k - *i * o->Z; }
-  else { const uint32_t k2 = k - a, r = k2 / o->ZL; *i = nlo + r; *b = k2 - r * o->ZL; }
-}
-
-/* packet index of work item w (work in block-major order) */
-TX_HD uint32_t otx_work_packet(const struct otx_obj *o, const struct tx_call *c, uint32_t w) {
-  if (c->tags) return c->order[w];
-  if (!o->interleave) return w;
-  uint32_t b, i;
-  otx_bm(o, w, &b, &i);
-  return otx_il_index(o, b, i);
-}
-
-/* tag of packet k */
-TX_HD uint32_t otx_packet_tag(const struct otx_obj *o, const struct tx_call *c, uint32_t k) {
-  if (c->tags) return c->tags[k];
-  uint32_t b, i;
-  if (o->interleave) otx_il_pair(o, k, &b, &i);
-  else otx_bm(o, k, &b, &i);
-  return tx_tag(b, i);
 }
 
 #endif /* NRQ_OBJ_BODY_H */

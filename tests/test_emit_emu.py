@@ -1,12 +1,13 @@
-"""CPU tier of the device-resident sender (nrq_tx_*): the emulated emit kernels (tests/emu/emit_emu.cpp running the bodies of
-nanorq_amd/csrc/emit_body.h) on the oracle's intermediate symbols, against the oracle's source and repair symbols byte for byte:
-tag lists mixing source ESIs, repair ESIs near K and ESIs near 2^24, foreign SBNs, inline headers, several strides, and both
-emit_range orders against the equivalent tag list."""
+"""CPU tier of the device-resident senders (nrq_tx_*, nrq_otx_*): the emulated emit kernel (nanorq_amd/csrc/emit_emu.cpp
+running the bodies of emit_body.h) on the oracle's intermediate symbols, against the oracle's source and repair symbols byte
+for byte: tag lists mixing source ESIs, repair ESIs near K and ESIs near 2^24, foreign SBNs, inline headers, several strides, and
+both emit_range orders against the equivalent tag list; and an object's class table of three segments (emit_all in both orders,
+a tag list)."""
 import numpy as np
 import pytest
 
 import nanorq_amd
-from tx_support import (FILL, check_packets, emu_emit, emu_emit_range, oracle_blocks, random_tags, range_tags)
+from tx_support import (FILL, check_packets, emu_emit, emu_emit_range, emu_emit_table, oracle_blocks, random_tags, range_tags)
 
 
 def _setup(orc, K, T, nblk, Kp, tags, seed, src_pad=0):
@@ -79,3 +80,55 @@ def test_emulated_emit_leaves_other_packets_alone(orc):
     assert res.tolist() == [-1, 0, -1, 0]
     assert (pk[0] == FILL).all() and (pk[2] == FILL).all()
     check_packets(pk, tags, src, blocks, K, T, nblk, sbn0, False, res)
+
+
+@pytest.mark.parametrize("sbn0", [0, 3])
+@pytest.mark.parametrize("inline,stride_kind", [(False, "tight"), (True, "odd"), (True, "r16")])
+def test_emulated_class_table(orc, sbn0, inline, stride_kind):
+    """A table as nrq_otx_create builds it for an object with a short last block: class L (K = 11, K' = 12), class S (K = 10,
+    K' = 10) and the last block staged apart in rows of its own.  emit_all (ESIs 0 .. K_b + nrep - 1 of every block) block-major
+    and interleaved against a numpy model of the order, and a tag list with SBNs below and past the span; every payload against
+    the oracle."""
+    T, Z, ZL, KL, KS, nrep = 12, 5, 2, 11, 10, 7
+    Ks = [KL] * ZL + [KS] * (Z - ZL)
+    Kps = {K: nanorq_amd.params(K)["Kp"] for K in (KL, KS)}
+    rng = np.random.default_rng(sbn0 + T)
+    src = [rng.integers(0, 256, K * T, dtype=np.uint8) for K in Ks]
+    want_bm = np.array([(sbn0 + b) << 24 | i for b in range(Z) for i in range(Ks[b] + nrep)], np.uint32)
+    want_il = np.array(sorted(want_bm.tolist(), key=lambda t: (t & 0xFFFFFF, t >> 24)), np.uint32)
+    tags = random_tags(rng, KS, Z + 1, sbn0, 300)
+    # the oracle's blocks, with every repair ESI either emit asks for
+    reps = [list(range(Ks[b], Ks[b] + nrep)) + [int(t) & 0xFFFFFF for t in tags if (int(t) >> 24) == sbn0 + b and (int(t) & 0xFFFFFF) >= Ks[b]]
+            for b in range(Z)]
+    blocks = [oracle_blocks(orc, src[b][None], Ks[b], T, Kps[Ks[b]], [reps[b]])[0] for b in range(Z)]
+
+    def seg(b0, nb):
+        K = Ks[b0]
+        return (K, Kps[K], sbn0 + b0, np.stack([src[b].copy() for b in range(b0, b0 + nb)]),
+                np.stack([blocks[b][0] for b in range(b0, b0 + nb)]))
+    segs = [seg(0, ZL), seg(ZL, Z - ZL - 1), seg(Z - 1, 1)]
+    span = (sbn0, Z, ZL)
+    stride = _stride(stride_kind, T, inline)
+    off = 4 if inline else 0
+
+    def check(pk, tgs, res=None):
+        for k, t in enumerate(tgs):
+            b, esi = (int(t) >> 24) - sbn0, int(t) & 0xFFFFFF
+            if not 0 <= b < Z:
+                assert res[k] == -1 and (pk[k] == FILL).all(), k
+                continue
+            assert res is None or res[k] == 0, k
+            want = src[b][esi * T:(esi + 1) * T] if esi < Ks[b] else blocks[b][1][esi]
+            assert np.array_equal(pk[k, off:off + T], want), (k, hex(int(t)))
+            assert not inline or bytes(pk[k, :4]) == int(t).to_bytes(4, "big"), k
+            assert (pk[k, off + T:] == FILL).all(), k
+
+    for interleave, want in ((0, want_bm), (1, want_il)):
+        pk, got = emu_emit_table(segs, span, T, inline, stride, rng=(0, KL + nrep, KS + nrep, interleave))
+        assert np.array_equal(got, want), interleave
+        check(pk, want)
+        pk_l, res = emu_emit_table(segs, span, T, inline, stride, tags=want)
+        assert (res == 0).all() and np.array_equal(pk_l, pk), interleave
+    pk, res = emu_emit_table(segs, span, T, inline, stride, tags=tags)
+    assert set(res.tolist()) == {0, -1}
+    check(pk, tags, res)

@@ -167,8 +167,9 @@ def _object(torch, case, seed):
 
 
 def test_object_emit_modes(D, torch_mod, orc):
-    """nrq_otx_emit_kernel in each of its four modes (the alignment of the packet rows picks it: otx_launch), against
-    nanorq_encode of the object layer: byte rows (odd stride), 4-byte rows, 16-byte rows, 16-byte rows behind an inline header"""
+    """nrq_emit_kernel<MODE, true> (a table of three segments: class L, class S, the staged last block) in each of its four
+    modes (the alignment of the packet rows picks it: tx_launch), against nanorq_encode of the object layer: byte rows (odd
+    stride), 4-byte rows, 16-byte rows, 16-byte rows behind an inline header"""
     from capi import api
     from test_gpu_obj import FILL, _host_encoder, _host_payload, _tags
     import nanorq_amd

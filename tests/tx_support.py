@@ -1,5 +1,6 @@
-"""Test support for the device-resident sender (nrq_tx_*): the CPU emulation of its emit kernels (tests/emu/emit_emu.cpp over
-nanorq_amd/csrc/emit_body.h), the packets the oracle says a transmission must produce, and tag lists."""
+"""Test support for the device-resident senders (nrq_tx_*, nrq_otx_*): the CPU emulation of their emit kernel
+(nanorq_amd/csrc/emit_emu.cpp over emit_body.h), the packets the oracle says a transmission must produce, and tag
+lists."""
 import ctypes as C
 
 import numpy as np
@@ -19,6 +20,7 @@ def emu_lib():
         vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
         L.emu_tx_emit.argtypes = [vp, vp, u64, vp, u64, vp, u32, u32, vp, u64, vp]
         L.emu_tx_emit_range.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp, u64, vp]
+        L.emu_emit_table.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, u64, vp, vp]
         _EMU = L
     return _EMU
 
@@ -61,6 +63,38 @@ def emu_emit_range(K, Kp, T, src, inter, esi0, n, interleave, inline, stride, sb
                                      int(interleave), int(inline), _p(pkts), stride, _p(tags))
     assert rc == 0, rc
     return pkts, tags
+
+
+def emu_emit_table(segs, span, T, inline, stride, tags=None, rng=None):
+    """The emit from a table of segments, each (K, Kp, sbn0, src [nblk, K*T or more], inter [nblk, L, T]), over the span
+    (sbn0, Z, ZL): a tag list (tags) or range mode (rng = (esi0, nL, nS, interleave)) -> (packets [n, stride], results [n] or the
+    tags [n] range mode wrote)"""
+    srcs = [np.ascontiguousarray(s[3].reshape(s[3].shape[0], -1), np.uint8) for s in segs]
+    inters = [np.ascontiguousarray(s[4], np.uint8) for s in segs]
+    prm = np.array([[K, Kp, T, src.shape[0], sbn0] for (K, Kp, sbn0, _, _), src in zip(segs, srcs)], np.uint32)
+    nseg = len(segs)
+
+    def per_seg(ctype, vals):
+        return (ctype * nseg)(*vals)
+    sbn0, Z, ZL = span
+    if tags is not None:
+        tags = np.ascontiguousarray(tags, np.uint32)
+        n = len(tags)
+        out = np.full(n, 77, np.int32)
+        res, tags_out, range_ = out, None, None
+    else:
+        esi0, nL, nS, _ = rng
+        n = ZL * nL + (Z - ZL) * nS
+        out = np.zeros(n, np.uint32)
+        res, tags_out, range_ = None, out, np.array(rng, np.uint32)
+    pkts = np.full((n, stride), FILL, np.uint8)
+    rc = emu_lib().emu_emit_table(_p(prm), nseg, _p(np.array(span, np.uint32)),
+                                  per_seg(C.c_void_p, [a.ctypes.data for a in srcs]), per_seg(C.c_uint64, [a.shape[1] for a in srcs]),
+                                  per_seg(C.c_void_p, [a.ctypes.data for a in inters]),
+                                  per_seg(C.c_uint64, [a.shape[1] * T for a in inters]), _p(tags), n if tags is not None else 0,
+                                  _p(range_), int(inline), _p(pkts), stride, _p(res), _p(tags_out))
+    assert rc == 0, rc
+    return pkts, out
 
 
 def range_tags(nblk, sbn0, esi0, n, interleave):

@@ -99,15 +99,18 @@ FEATURES = {
                             why="one block in a few thousand at K=8192 needs the second list; the test forces it with lds_max"),
 }
 
-# the device sender / object sender / object layout kernels: each instance and a test that launches it
-TX_MODES = {0: "TX_BYTE", 1: "TX_DWORD", 2: "TX_V16", 3: "TX_V16_SHIFT"}
-TX_EMIT = {
-    0: dict(status="default", test="tests/test_gpu_tx.py::test_device_emit_matches_emulation", why="T odd / odd stride"),
-    1: dict(status="default", test="tests/test_gpu_tx.py::test_device_emit_matches_emulation", why="stride a multiple of 4"),
-    2: dict(status="default", test="tests/test_gpu_tx.py::test_device_emit_matches_emulation", why="16-byte rows, tags in a list"),
-    3: dict(status="default", test="tests/test_gpu_tx.py::test_device_emit_matches_emulation", why="16-byte rows, inline header"),
+# the emit kernel nrq_emit_kernel<MODE, MULTI> (one-segment and multi-segment tables) and the object layout kernel: each
+# instance and a test that launches it
+TX_MODES = {0: "TX_V16", 1: "TX_V16_SHIFT", 2: "TX_DWORD", 3: "TX_BYTE"}
+_TX_TEST = "tests/test_gpu_tx.py::test_device_emit_matches_emulation"
+EMIT = {
+    (0, False): dict(status="default", test=_TX_TEST, why="16-byte rows, tags in a list"),
+    (1, False): dict(status="default", test=_TX_TEST, why="16-byte rows, inline header"),
+    (2, False): dict(status="default", test=_TX_TEST, why="stride a multiple of 4"),
+    (3, False): dict(status="default", test=_TX_TEST, why="T odd / odd stride"),
 }
-OTX_EMIT = {m: dict(status="default", test="tests/test_gpu_variants.py::test_object_emit_modes", why=TX_MODES[m]) for m in range(4)}
+EMIT.update({(m, True): dict(status="default", test="tests/test_gpu_variants.py::test_object_emit_modes",
+                             why=TX_MODES[m] + ", an object of three segments") for m in TX_MODES})
 OBJ_LAYOUT = {
     16: dict(status="default", test="tests/test_gpu_obj.py::test_receiver_matches_host_decoder", why="T = 64, N = 1"),
     8: dict(status="default", test="tests/test_gpu_obj.py::test_receiver_matches_host_decoder", why="T = 1280, N = 3, Al = 8"),
@@ -128,14 +131,11 @@ def ledger_row(kernel, args):
         return BACKSUB.get(int(args[0]))
     if kernel == "nrq_plan_kernel":
         return PLAN.get((int(args[0]), int(args[1]) if len(args) > 1 else 0))
-    if kernel == "nrq_tx_emit_kernel":
-        return TX_EMIT.get(int(args[0]))
-    if kernel == "nrq_otx_emit_kernel":
-        return OTX_EMIT.get(int(args[0]))
+    if kernel == "nrq_emit_kernel":
+        return EMIT.get((int(args[0]), args[1] == "true"))
     if kernel == "nrq_obj_layout_kernel":
         return OBJ_LAYOUT.get(OBJ_WORD.get(args[0]))
     raise KeyError(kernel)
 
 
-KERNELS = ("nrq_solve_kernel", "nrq_backsub_kernel", "nrq_plan_kernel", "nrq_tx_emit_kernel", "nrq_otx_emit_kernel",
-           "nrq_obj_layout_kernel")
+KERNELS = ("nrq_solve_kernel", "nrq_backsub_kernel", "nrq_plan_kernel", "nrq_emit_kernel", "nrq_obj_layout_kernel")

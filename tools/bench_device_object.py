@@ -4,6 +4,8 @@
                                    3 (432 / 424-byte sub-symbols, 8-byte pieces), against the floor 2*F / 6.29 TB/s
   emit_all_ms vs sender_ms         ObjectSender.emit_all(911, interleaved, inline) of a 256 x 8192 object against one-class
                                    Sender.emit_range of the same blocks (equal bytes), alternated rep by rep
+  emit_all_headline_ms             ObjectSender.emit_all(911, interleaved, inline) of the headline object (two classes and the
+                                   last block staged apart: a table of three segments)
   orx_add_ms vs rx_add_ms          ObjectReceiver.add against one-class Receiver.add on the same packets (the 256 x 8192 object:
                                    one class, one reception inside), alternated
   orx_add_headline_ms              ObjectReceiver.add of the headline object's own emit_all(911) packets (two classes: a reception
@@ -104,6 +106,14 @@ if not a.skip_emit or not a.skip_add:
         stats("emit_all_ms", t_o)
         stats("sender_ms", t_s)
         res["emit_all_vs_sender"] = round(float(np.median(t_o) / np.median(t_s)), 3)
+        with nanorq_amd.ObjectSender(ctx, obj, T, Z=Z) as htx:
+            htx.encode()
+            pk_h = torch.empty((htx.count_all(NREP), stride), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            t_h = [timed(lambda: htx.emit_all(NREP, interleave=True, inline=True, out=pk_h)) for _ in range(a.reps)]
+            stats("emit_all_headline_ms", t_h)
+            ctx.sync()
+        del pk_h
     del pk_s
     otx.close()
     tx.close()
