@@ -168,7 +168,19 @@ typedef struct nrq_plan_hdr {
   uint32_t off_augt;    /* u32[lpr * aug_stride]: word w of reduced row p at [w * aug_stride + p] */
   uint32_t lpr;         /* words per row: ceil(nlow / 32); 0: the combinations are ops of the stream (blocks of L < NRQ_AUG_MATRIX_MIN_L) */
   uint32_t aug_stride;  /* >= r2, multiple of 4 */
+  /* The pivots a decode that asks for no intermediate symbols needs: those whose slot occurs in the out lists of the missing
+   * symbols (the only slots ph_store then reads).  After the dense stage a pivot's value depends on its own row and C_u alone, so
+   * the back-substitution may run over these pivots only.  A view of the full one above, which stays complete; off_needslot == 0:
+   * no such view (encode plans, segmented runs, host-built plans), the solve takes the full one. */
+  uint32_t nneed;       /* needed pivots, ascending in k */
+  uint32_t need_pad;    /* stride (in needed pivots) of off_wneed, multiple of 64 */
+  uint32_t off_needslot;/* u16[nneed]: slot of needed pivot j */
+  uint32_t off_wneed;   /* u32[wpr*need_pad]: word w of needed pivot j's W row at [w*need_pad + j] (the form of off_wt) */
 } nrq_plan_hdr;
+/* (emu_device_plan and plan_header read the header from the first 256 bytes of a plan) */
+#ifdef __cplusplus
+static_assert(sizeof(nrq_plan_hdr) <= 256u, "nrq_plan_hdr is read as a 256-byte prefix");
+#endif
 
 /* Per-K' constants shared by every plan of that K': the HDPC block (RFC 6330 section 5.3.3.3) and the
  * "base" constraint structure -- the S LDPC rows and the LT rows of ISI 0..K'-1 (reference

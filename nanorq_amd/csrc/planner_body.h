@@ -317,7 +317,7 @@ SB_HD uint32_t pl_arena_bound(uint32_t L, uint32_t Mcap, uint32_t ucap, uint32_t
   if (pl_bin_in_stream(L)) ops += 2u * ucap * 64u;             /* (the GF(2) combinations as ops of the stream) */
   else ops += ((ucap + 3u) & ~3u) * ((PL_LOWCAP + 31u) / 32u) + 16u; /* (or as words of a bit matrix) */
   uint32_t b = 256u + L * 2u * 3u + (L + 16u) * 2u + ucap * 2u * 4u + ucap * 4u * 2u + PL_MAXH * ucap +
-               NRQ_MAX_FREE * PL_MAXH + wprcap * npad * 4u + ops * 4u +
+               NRQ_MAX_FREE * PL_MAXH + wprcap * npad * 4u * 2u + npad * 2u + 16u + ops * 4u +
                Mcap * 4u + (nlost_cap + 1u) * 8u + nlost_cap * PL_PATCH_STRIDE * 2u + 1024u;
   return pl_r16(b);
 }
@@ -3076,6 +3076,13 @@ template <int Z> SB_HD void pl_mark_failed(PlanCtx &c, uint32_t tid, uint32_t nt
 }
 
 /* =============================== phase 8: maps, W image, job ================================= */
+/* The needed-pivot view (plan.h off_needslot): built for device-planned decodes that want no intermediate symbols, when a bit
+ * per slot fits the claim lists (free after peeling) */
+SB_HD bool pl_need_wanted(const PlanCtx &c) {
+  return (c.job.mode & 0xFFu) == 0u && c.job.inter == 0u && c.sh->npiv != 0u &&
+         (c.sh->M + 31u) / 32u * 4u <= 4u * c.qcap;
+}
+SB_HD uint32_t *pl_need_marks(const PlanCtx &c) { uint32_t *q = reinterpret_cast<uint32_t *>(c.claim_l()); PL_ASSUME_LDS(q); return q; }
 template <int Z> SB_HD void pl_final_a(PlanCtx &c, uint32_t tid, uint32_t nt) {
   pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
   if (sh->status) return;
@@ -3128,6 +3135,10 @@ template <int Z> SB_HD void pl_final_b(PlanCtx &c, uint32_t tid, uint32_t nt) {
     c.part()[2] = o; o = pl_r16(o + (nl + 1u) * 4u);                   /* out_cptr */
     c.part()[3] = o; o = pl_r16(o + nl * 4u + 4u);                     /* out_row */
     c.part()[4] = o; o = pl_r16(o + nl * PL_PATCH_STRIDE * 2u + NRQ_STORE_SLACK);  /* out_slots (+ what ph_store reads past a list) */
+    const uint32_t need = pl_need_wanted(c);
+    c.part()[5] = need ? o : 0u; if (need) o = pl_r16(o + sh->tmp0 * 2u);                 /* needslot (room for every pivot) */
+    c.part()[6] = need ? o : 0u; if (need) o = pl_r16(o + sh->wpr * sh->tmp0 * 4u);       /* wneed */
+    c.part()[7] = need;
     sh->arena_top = o;
     if (o > c.job.arena_cap) (sh->fail_site = __LINE__, sh->status = PL_FAIL_CAPACITY);
     sh->tmp1 = 0; /* (sum of the level groups' op counts: pl_final_c) */
@@ -3216,6 +3227,8 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
     }
     if (tid == 0) cptr[nl] = ps[nt];
   }
+  if (!sh->status && c.part()[7]) /* (the marks of pl_final_e: one bit per slot) */
+    for (uint32_t i = tid; i < (sh->M + 31u) / 32u; i += nt) pl_need_marks(c)[i] = 0u;
   if (tid != 0) return;
   nrq_plan_hdr h;
   memset(&h, 0, sizeof(h));
@@ -3272,6 +3285,15 @@ SB_HD void pl_wt_fill(uint8_t *arena, const uint32_t *wrows, uint32_t e0, uint32
     const uint32_t w = e / stride, k = e - w * stride;
     wt[e] = k < npiv ? wrows[(size_t)pivslot[k] * wpr + w] : 0u;
   }
+  if (!h->off_needslot) return;
+  /* (the needed-pivot view's W rows: pl_need_b left them to this pass) */
+  const uint32_t pad = h->need_pad, nneed = h->nneed;
+  const uint16_t *nslot = reinterpret_cast<const uint16_t *>(arena + h->off_needslot);
+  uint32_t *wneed = reinterpret_cast<uint32_t *>(arena + h->off_wneed);
+  for (uint32_t e = e0; e < wpr * pad; e += step) {
+    const uint32_t w = e / pad, j = e - w * pad;
+    wneed[e] = j < nneed ? wrows[(size_t)nslot[j] * wpr + w] : 0u;
+  }
 }
 
 /* the missing source symbols' LT neighbour lists, translated to slots (uses cptr from the step before) */
@@ -3282,6 +3304,7 @@ template <int Z> SB_HD void pl_final_e(PlanCtx &c, uint32_t tid, uint32_t nt) {
   const uint32_t nl = c.job.nlost;
   const uint32_t *cptr = reinterpret_cast<const uint32_t *>(c.arena + c.part()[2]);
   uint16_t *osl = reinterpret_cast<uint16_t *>(c.arena + c.part()[4]);
+  uint32_t *marks = c.part()[7] ? pl_need_marks(c) : nullptr; /* (uniform) */
   for (uint32_t g = tid; g < nl; g += nt) {
     const uint32_t e = c.lost[g], a = c.b_rptr[p.S + p.H + e], n = c.b_rptr[p.S + p.H + e + 1] - a, o = cptr[g];
     constexpr uint32_t CB = 8; /* entries whose two dependent loads are in flight together */
@@ -3293,7 +3316,80 @@ template <int Z> SB_HD void pl_final_e(PlanCtx &c, uint32_t tid, uint32_t nt) {
       for (uint32_t q = 0; q < CB; q++) sl[q] = c.colslot[col[q]];
 #pragma unroll
       for (uint32_t q = 0; q < CB; q++)
-        if (k0 + q < n) osl[o + k0 + q] = (uint16_t)sl[q];
+        if (k0 + q < n) {
+          osl[o + k0 + q] = (uint16_t)sl[q];
+          if (marks) PL_ATOM_OR(&marks[sl[q] >> 5], 1u << (sl[q] & 31u));
+        }
+    }
+  }
+}
+
+/* The needed pivots (plan.h off_needslot): the pivots k whose slot pl_final_e marked, ascending in k.  The pivot range is dealt
+ * out in contiguous chunks, one per wave; a wave takes 64 pivots a trip and ranks them by ballot (the emulator, whose threads run
+ * one after the other, walks a chunk with the wave's first thread), so the view does not depend on the order in which the waves
+ * run.  The chunks' counts go to part()[8 ..] (at most 16 waves; [0, 8) hold the arena offsets).  pl_need_a counts
+ * every chunk, pl_need_b writes the slots and the W rows of the chunk behind those of the chunks before it (a segmented run leaves
+ * the W rows to nrq_wt_kernel, pl_wt_fill, with the rest of the W image). */
+#define PL_NEED_UNIT 64u
+SB_HD bool pl_need_marked(const PlanCtx &c, uint32_t k, uint32_t end) {
+  if (k >= end) return false;
+  const uint32_t s = c.pivslot[k];
+  return ((pl_need_marks(c)[s >> 5] >> (s & 31u)) & 1u) != 0u;
+}
+template <int Z> SB_HD void pl_need_a(PlanCtx &c, uint32_t tid, uint32_t nt) {
+  pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
+  if (sh->status || !c.part()[7]) return;
+  const uint32_t unit = tid / PL_NEED_UNIT, nunit = nt / PL_NEED_UNIT, np = sh->npiv;
+  const uint32_t per = ((np + nunit - 1u) / nunit + PL_NEED_UNIT - 1u) / PL_NEED_UNIT * PL_NEED_UNIT;
+  const uint32_t a = unit * per < np ? unit * per : np, b = a + per < np ? a + per : np;
+  uint32_t n = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (uint32_t k0 = a; k0 < b; k0 += PL_NEED_UNIT) n += (uint32_t)__popcll(__ballot(pl_need_marked(c, k0 + (tid & 63u), b)));
+#else
+  if (tid % PL_NEED_UNIT) return;
+  for (uint32_t k = a; k < b; k++) n += pl_need_marked(c, k, b) ? 1u : 0u;
+#endif
+  if (tid % PL_NEED_UNIT == 0u) c.part()[8u + unit] = n;
+}
+template <int Z> SB_HD void pl_need_b(PlanCtx &c, uint32_t tid, uint32_t nt) {
+  pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
+  if (sh->status || !c.part()[7]) return;
+  const uint32_t unit = tid / PL_NEED_UNIT, nunit = nt / PL_NEED_UNIT, np = sh->npiv, wpr = sh->wpr;
+  const uint32_t per = ((np + nunit - 1u) / nunit + PL_NEED_UNIT - 1u) / PL_NEED_UNIT * PL_NEED_UNIT;
+  const uint32_t a = unit * per < np ? unit * per : np, b = a + per < np ? a + per : np;
+  const uint32_t *cnt = c.part() + 8u;
+  uint32_t base = 0, nneed = 0;
+  for (uint32_t v = 0; v < nunit; v++) { const uint32_t x = cnt[v]; base += v < unit ? x : 0u; nneed += x; }
+  const uint32_t pad = (nneed + 63u) & ~63u;
+  uint16_t *nslot = reinterpret_cast<uint16_t *>(c.arena + c.part()[5]);
+  uint32_t *wneed = reinterpret_cast<uint32_t *>(c.arena + c.part()[6]);
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (uint32_t k0 = a; k0 < b; k0 += PL_NEED_UNIT) {
+    const uint32_t k = k0 + (tid & 63u);
+    const bool on = pl_need_marked(c, k, b);
+    const unsigned long long m = __ballot(on);
+    const uint32_t j = base + (uint32_t)__popcll(m & ((1ull << (tid & 63u)) - 1ull));
+    base += (uint32_t)__popcll(m);
+#else
+  for (uint32_t k = a; k < b && tid % PL_NEED_UNIT == 0u; k++) {
+    const bool on = pl_need_marked(c, k, b);
+    const uint32_t j = base;
+    base += on ? 1u : 0u;
+#endif
+    if (!on) continue;
+    const uint32_t s = c.pivslot[k];
+    nslot[j] = (uint16_t)s;
+    if (!sh->defer_wt)
+      for (uint32_t w = 0; w < wpr; w++) wneed[(size_t)w * pad + j] = c.wrows[(size_t)s * wpr + w]; /* (one W row: a line or two) */
+  }
+  if (!sh->defer_wt)
+    for (uint32_t e = tid; e < (pad - nneed) * wpr; e += nt) wneed[(size_t)(e / (pad - nneed)) * pad + nneed + e % (pad - nneed)] = 0u;
+  if (tid == 0) {
+    nrq_plan_hdr *h = c.hdr;
+    h->nneed = nneed; h->need_pad = pad; h->off_needslot = c.part()[5]; h->off_wneed = c.part()[6];
+    if (c.job.hdr_out) {
+      nrq_plan_hdr *ho = PL_HBM(nrq_plan_hdr, c.job.hdr_out);
+      ho->nneed = nneed; ho->need_pad = pad; ho->off_needslot = c.part()[5]; ho->off_wneed = c.part()[6];
     }
   }
 }

@@ -234,5 +234,7 @@
   if (PL_SEG != 1 && PL_SEG != 3 && PL_SEG != 4) {
     PL_PHASE(pl_final_d);
     PL_PHASE(pl_final_e);
+    PL_PHASE(pl_need_a); /* (the needed-pivot view: device-planned decodes without intermediate symbols) */
+    PL_PHASE(pl_need_b);
   }
 }

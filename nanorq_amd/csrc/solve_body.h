@@ -1571,12 +1571,17 @@ SB_HD void backsub_one(const StripCtx<WB, G> &c, const uint8_t *t4, uint32_t slo
   lds_put<WB, G>(c.slots(), slot, acc);
 }
 
-template <int WB, int NW, int G = 1, bool FAST = true> SB_HD void backsub_fixed(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt) {
+/* need: the pivots phase 5b runs over are those a decode without intermediate symbols reads (plan.h off_needslot), not all */
+#define NRQ_BACKSUB_VIEW(c, need)                                                                                            \
+  const NRQ_GAS uint16_t *pivslot = (c).template arr<uint16_t>((need) ? (c).h->off_needslot : (c).h->off_pivslot);      \
+  const NRQ_GAS uint32_t *wt = (c).template arr<uint32_t>((need) ? (c).h->off_wneed : (c).h->off_wt);                   \
+  const uint32_t stride = (need) ? (c).h->need_pad : (c).h->npiv_pad, npiv = (need) ? (c).h->nneed : (c).h->npiv
+template <int WB, int NW, int G = 1, bool FAST = true>
+SB_HD void backsub_fixed(const StripCtx<WB, G> &c, bool need, uint32_t tid, uint32_t nt) {
   if constexpr (!FAST) { /* the small workgroups: both register sets loaded, then both used (fewer live registers) */
 
-  const NRQ_GAS uint16_t *pivslot = c.template arr<uint16_t>(c.h->off_pivslot);
-  const NRQ_GAS uint32_t *wt = c.template arr<uint32_t>(c.h->off_wt);
-  const uint32_t wpr = c.h->wpr, stride = c.h->npiv_pad, npiv = c.h->npiv;
+  NRQ_BACKSUB_VIEW(c, need);
+  const uint32_t wpr = c.h->wpr;
   const uint8_t *t4 = c.t4();
   for (uint32_t k = tid; k < npiv; k += 2 * nt) {
     const uint32_t k2 = k + nt;
@@ -1592,9 +1597,8 @@ template <int WB, int NW, int G = 1, bool FAST = true> SB_HD void backsub_fixed(
   }
     return;
   }
-  const NRQ_GAS uint16_t *pivslot = c.template arr<uint16_t>(c.h->off_pivslot);
-  const NRQ_GAS uint32_t *wt = c.template arr<uint32_t>(c.h->off_wt);
-  const uint32_t wpr = c.h->wpr, stride = c.h->npiv_pad, npiv = c.h->npiv;
+  NRQ_BACKSUB_VIEW(c, need);
+  const uint32_t wpr = c.h->wpr;
   const uint8_t *t4 = c.t4();
   /* two register sets, filled alternately: the W words of the NEXT pivot are requested before the current one starts its
    * table lookups, so a trip to L2 is never waited for with nothing else to do (it was: both sets loaded, then both used) */
@@ -1622,16 +1626,18 @@ template <int WB, int NW, int G = 1, bool FAST = true> SB_HD void backsub_fixed(
   }
 }
 
+/* A pivot's value is Y_k ^ W_k * C_u: it depends on no other pivot by now, so a job that reads only the out lists' slots (no
+ * intermediate symbols) computes only the pivots the plan names as needed -- a third of them at 10 % loss -- and leaves the
+ * others' slots as they are (ph_park still writes all u inactive columns) */
 template <int WB, int G = 1, bool FAST = true> SB_HD void ph_backsub(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt) {
   const uint32_t wpr = c.h->wpr;
-  if (wpr <= 4) backsub_fixed<WB, 4, G, FAST>(c, tid, nt);
-  else if (wpr <= 8) backsub_fixed<WB, 8, G, FAST>(c, tid, nt);
-  else if (wpr <= 12) backsub_fixed<WB, 12, G, FAST>(c, tid, nt);
-  else if (wpr <= 24) backsub_fixed<WB, 24, G, FAST>(c, tid, nt);
+  const bool need = c.job->inter == 0 && c.h->off_needslot != 0u; /* (chosen once per strip) */
+  if (wpr <= 4) backsub_fixed<WB, 4, G, FAST>(c, need, tid, nt);
+  else if (wpr <= 8) backsub_fixed<WB, 8, G, FAST>(c, need, tid, nt);
+  else if (wpr <= 12) backsub_fixed<WB, 12, G, FAST>(c, need, tid, nt);
+  else if (wpr <= 24) backsub_fixed<WB, 24, G, FAST>(c, need, tid, nt);
   else {
-    const NRQ_GAS uint16_t *pivslot = c.template arr<uint16_t>(c.h->off_pivslot);
-    const NRQ_GAS uint32_t *wt = c.template arr<uint32_t>(c.h->off_wt);
-    const uint32_t stride = c.h->npiv_pad, npiv = c.h->npiv;
+    NRQ_BACKSUB_VIEW(c, need);
     const uint8_t *t4 = c.t4();
     for (uint32_t k = tid; k < npiv; k += nt) {
       uint32_t s = pivslot[k];
