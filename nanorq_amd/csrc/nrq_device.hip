@@ -1015,26 +1015,42 @@ double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-struct DevBuf {
+/* What the host side holds of the runtime is owned by the member that names it: move-only, released by its destructor.
+ * ACQUISITION stays with the code that needs the thing (ensure_dev / ensure_pin, the checked create calls), and so does
+ * every ORDERING question -- a destructor synchronises nothing (nrq_ctx_destroy does, before the members go). */
+template <auto Release> struct Buf {
   uint8_t *p = nullptr;
   size_t cap = 0;
+  Buf() = default;
+  Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Buf &operator=(Buf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~Buf() { if (p) (void)Release(p); }
 };
-struct PinBuf {
-  uint8_t *p = nullptr;
-  size_t cap = 0;
+using DevBuf = Buf<hipFree>;
+using PinBuf = Buf<hipHostFree>;
+using HostBuf = Buf<nrq_host_free>; /* what planner_host.cpp hands out (cap is not used) */
+
+template <class H, auto Release> struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+  Handle &operator=(Handle &&o) noexcept { std::swap(h, o.h); return *this; }
+  ~Handle() { if (h) (void)Release(h); }
+  operator H() const { return h; }
 };
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using TimingPool = std::vector<std::pair<Event, Event>>;
 
 struct KConst {
-  uint8_t *host = nullptr;
-  uint8_t *dev = nullptr;
+  HostBuf host;
+  DevBuf dev;
   uint32_t bytes = 0;
 };
 
 struct EncPlan {
   bool valid = false;     /* false after nrq_plan_cache_clear: rebuilt on next use, buffers are kept */
-  size_t dev_cap = 0;
-  uint8_t *pin = nullptr; /* host planner: pinned image for the asynchronous upload; device planner: what comes back */
-  size_t pin_cap = 0;
+  PinBuf pin;             /* host planner: pinned image for the asynchronous upload; device planner: what comes back */
   uint8_t *dev = nullptr; /* the plan in use: plan arena and rowsrc (one of devbuf[]) */
   uint32_t plan_bytes = 0;
   uint32_t rowsrc_off = 0;
@@ -1044,20 +1060,54 @@ struct EncPlan {
   /* Two device buffers: a plan that is rebuilt ON THE DEVICE (big K', encplan_device_launch) goes to the buffer that is
    * not in use, on a stream of its own, while solves may still read the other one.  The host planner keeps to buffer 0
    * (its upload is ordered on the caller's stream). */
-  uint8_t *devbuf[2] = {nullptr, nullptr};
-  size_t devcap[2] = {0, 0};
-  hipEvent_t used[2] = {nullptr, nullptr}; /* last solve launch that reads devbuf[i] */
+  DevBuf devbuf[2];
+  Event used[2]; /* last solve launch that reads devbuf[i] */
   bool used_set[2] = {false, false};
   int cur = 0;
   bool pending = false;   /* a device build is in flight into devbuf[pend]; encplan_finish() completes it */
   int pend = 0;
-  hipEvent_t ready = nullptr;
+  Event ready;
   uint32_t rb_bytes = 0;  /* device build: bytes of the arena's front (header .. colslot) read back */
   double t_launch = 0;
   bool dev_built = false; /* the plan in use came from the planner kernel (nrq_call_stats::encplan_device) */
 };
 
 inline size_t r16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+/* The symbol rows of a call, T bytes each, one run per block: base + b * stride, or an address per block (the _v entry points). */
+struct Rows {
+  const void *base = nullptr;
+  size_t stride = 0;
+  const uint64_t *vec = nullptr;
+  explicit operator bool() const { return base || vec; }
+  bool operator==(const Rows &o) const { return base == o.base && stride == o.stride && vec == o.vec; }
+  uint64_t of(uint32_t b) const { return vec ? vec[b] : (uint64_t)(uintptr_t)((const uint8_t *)base + (size_t)b * stride); }
+  /* every row starts 16-byte aligned */
+  bool aligned(uint32_t nblk, uint32_t T) const {
+    uintptr_t bits = vec ? 0 : (reinterpret_cast<uintptr_t>(base) | (uintptr_t)stride);
+    for (uint32_t b = 0; vec && b < nblk; b++) bits |= (uintptr_t)vec[b];
+    return ((bits | (uintptr_t)T) & 15u) == 0;
+  }
+};
+
+/* What a decode call IS: the entry points build one and everything below them takes it.  Pointers, not copies -- the lists
+ * are the caller's for the length of the call (PlanRun, which outlives its call, points them into vectors of its own). */
+struct DecodeCall {
+  uint32_t K = 0, Kp = 0, T = 0, nblk = 0;
+  Rows src, rep, inter; /* source rows (recovered symbols go back into them), repair rows, intermediate symbols (optional) */
+  const uint32_t *h_lost = nullptr, *h_nlost = nullptr; /* per block: lost_cap ESIs, ascending, and how many of them count */
+  const uint32_t *h_rep_esi = nullptr, *h_nrep = nullptr; /* per block: rep_cap repair ESIs, how many to use ... */
+  const uint32_t *h_avail = nullptr;                     /* ... and how many may be used if those leave the system rank deficient (optional) */
+  uint32_t lost_cap = 0, rep_cap = 0;
+  int *h_status = nullptr;    /* out, per block: 1 = decoded */
+  uint32_t *h_used = nullptr; /* out, per block: repair symbols used (optional) */
+  uint32_t chunk_blocks = 0;  /* nrq_decode_blocks_vc: blocks per solve launch (0: one launch for all) ... */
+  void *const *chunk_done = nullptr, *const *chunk_up = nullptr; /* ... with an event to record behind / to wait for ahead of each */
+  bool io_aligned = false; /* every symbol row of the call is 16-byte aligned: the solve's movers take their aligned-only form */
+  uint64_t src_of(uint32_t b) const { return src.of(b); }
+  uint64_t rep_of(uint32_t b) const { return rep.of(b); }
+  uint64_t inter_of(uint32_t b) const { return inter ? inter.of(b) : 0; }
+};
 
 } // namespace
 
@@ -1143,22 +1193,21 @@ struct nrq_ctx {
   std::map<uint64_t, EncPlan> encplans; /* by (K', K) */
   DevBuf scratch[2];                    /* per-call device arrays (double-buffered across calls) */
   PinBuf staging[2];
-  hipEvent_t staged[2] = {nullptr, nullptr};
+  Event staged[2];
   int flip = 0;
   int threads = 0;
   nrq_call_stats stats;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  hipEvent_t encplan_uploaded = nullptr;
+  Event t0, t1;
+  Event encplan_uploaded;
   bool attr_set[5] = {false, false, false, false, false};
   /* optional per-launch timing of the solve kernel (HIP events on the launch stream) */
   bool ktime_on = false;
   bool ktime_outer = false; /* the solve launches in flight are bracketed by their caller's pair of events */
-  hipEvent_t ktime_base = nullptr; /* recorded by nrq_ktime_enable: origin of the launch intervals */
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ktime_pool;
+  Event ktime_base; /* recorded by nrq_ktime_enable: origin of the launch intervals */
+  TimingPool ktime_pool;
   size_t ktime_used = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ptime_pool; /* same for the planner launches (all kernels of a planner run) */
+  TimingPool ptime_pool; /* same for the planner launches (all kernels of a planner run) */
   size_t ptime_used = 0;
-  unsigned long long *prof = nullptr; /* NRQ_PROF=1 */
   /* device planner */
   int planner = 1; /* 1 = device planner for decode (default), 0 = host planner */
   /* Planner runs may be issued AHEAD of their decode call (nrq_decode_plan_ahead), up to NRQ_PLAN_AHEAD_MAX of them: plan
@@ -1175,19 +1224,14 @@ struct nrq_ctx {
    * device-wide synchronisation points).  Freed blocks are reused for requests of up to 1.25x less; reuse is safe
    * because all work on a block is ordered on the context's streams and the object layer waits for its copy
    * streams before it frees. */
-  const uint64_t *vec_inter = nullptr; /* nrq_encode_blocks_v: per-block addresses of the intermediate symbols */
-  const uint64_t *vec_src = nullptr, *vec_rep = nullptr; /* nrq_decode_blocks_v: per-block buffer addresses instead of base + stride */
-  bool io_aligned = false;              /* set by the entry points: every symbol row of the call is 16-byte aligned (base addresses and strides) */
-  uint32_t chunk_blocks = 0;            /* nrq_decode_blocks_vc: blocks per solve launch (0: one launch for all) */
-  void *const *chunk_done = nullptr, *const *chunk_up = nullptr;
   std::multimap<size_t, void *> pool_free;
   std::map<void *, size_t> pool_size;
   size_t pool_cached = 0;
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr}; /* streams of the object layer: [0] host -> device copies, [1] device -> host copies,
-                                                     * [2] kernels that sort uploaded packets into rows beside both */
+  Stream aux[3]; /* streams of the object layer: [0] host -> device copies, [1] device -> host copies,
+                  * [2] kernels that sort uploaded packets into rows beside both */
   DevBuf scat_dev[2];
   PinBuf scat_pin[2];
-  hipEvent_t scat_ev[2] = {nullptr, nullptr};
+  Event scat_ev[2];
   int scat_flip = 0;
   bool plan_attr = false;
   /* The planner kernel runs on a stream of its own: it depends on the reception pattern only, not on the symbols, so
@@ -1195,17 +1239,17 @@ struct nrq_ctx {
    * `planned`: planner + header download done (the host waits for it, the solve launch on the caller's stream is
    * ordered behind it); `arena_free`: the solve that reads the plan arenas / job records has finished -- the next
    * planner launch overwrites them and waits for it. */
-  hipStream_t plan_stream = nullptr;
-  hipStream_t plan_stream_b = nullptr; /* the second planner stream (runs issued ahead alternate) */
-  hipEvent_t planned[3] = {nullptr, nullptr, nullptr}, arena_free[3] = {nullptr, nullptr, nullptr};
+  Stream plan_stream;
+  Stream plan_stream_b; /* the second planner stream (runs issued ahead alternate) */
+  Event planned[3], arena_free[3];
   bool arena_busy[3] = {false, false, false};
   int aflip = 0;
   std::deque<struct PlanRun *> ahead; /* planner runs issued by nrq_decode_plan_ahead and not yet consumed, oldest first */
-  hipStream_t plan_stream2 = nullptr; /* encode plans built on the device (encplan_device_launch): beside both of the above */
+  Stream plan_stream2; /* encode plans built on the device (encplan_device_launch): beside both of the above */
   DevBuf encplan_work;                /* planner workspace of that build */
   DevBuf pscratch[4]; /* planner inputs: buffers of their own (the per-call arrays above belong to the caller's stream) */
   PinBuf pstaging[4];
-  hipEvent_t pstaged[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event pstaged[4];
   int pflip = 0;
 };
 
@@ -1247,22 +1291,40 @@ static inline bool nrq_inject(nrq_ctx *ctx);
                                       __FILE__, __LINE__);                                                  \
   } while (0)
 
-int ensure_dev(nrq_ctx *ctx, DevBuf &b, size_t bytes) {
+/* grow a buffer to `bytes` at least: the old one is freed, `want` bytes are allocated (0: the per-call arrays' margin, a
+ * quarter and a page; the encode plans, one size per K', ask for an eighth) */
+int ensure_dev(nrq_ctx *ctx, DevBuf &b, size_t bytes, size_t want = 0) {
   if (b.cap >= bytes) return 0;
   if (b.p) HIPCHK(ctx, hipFree(b.p));
   b.p = nullptr; b.cap = 0;
-  size_t want = bytes + bytes / 4 + 4096;
+  if (!want) want = bytes + bytes / 4 + 4096;
   HIPCHK(ctx, hipMalloc((void **)&b.p, want));
   b.cap = want;
   return 0;
 }
-int ensure_pin(nrq_ctx *ctx, PinBuf &b, size_t bytes) {
+int ensure_pin(nrq_ctx *ctx, PinBuf &b, size_t bytes, size_t want = 0) {
   if (b.cap >= bytes) return 0;
   if (b.p) HIPCHK(ctx, hipHostFree(b.p));
   b.p = nullptr; b.cap = 0;
-  size_t want = bytes + bytes / 4 + 4096;
+  if (!want) want = bytes + bytes / 4 + 4096;
   HIPCHK(ctx, hipHostMalloc((void **)&b.p, want, hipHostMallocDefault));
   b.cap = want;
+  return 0;
+}
+
+/* The next pair of timing events of a pool (created on first use): the first is recorded on `st`, the second is handed back
+ * for the caller to record behind its launches.  A caller that cannot do so gives the pair back (used--): the readers
+ * (nrq_ktime_read, ...) take the elapsed time of every pair in use, and an event that was never recorded has none. */
+int timing_pair(nrq_ctx *ctx, TimingPool &pool, size_t &used, hipStream_t st, hipEvent_t *ev_end) {
+  if (used == pool.size()) {
+    Event a, b;
+    HIPCHK(ctx, hipEventCreate(&a.h));
+    HIPCHK(ctx, hipEventCreate(&b.h));
+    pool.emplace_back(std::move(a), std::move(b));
+  }
+  HIPCHK(ctx, hipEventRecord(pool[used].first, st));
+  *ev_end = pool[used].second;
+  used++;
   return 0;
 }
 
@@ -1301,10 +1363,11 @@ int get_kconst(nrq_ctx *ctx, uint32_t K, KConst **out) {
   auto it = ctx->kconst.find(p.Kp);
   if (it == ctx->kconst.end()) {
     KConst kc;
-    if (nrq_host_kconst_build(K, &kc.host, &kc.bytes) != 0) return fail(ctx, -2, "kconst build failed");
-    HIPCHK(ctx, hipMalloc((void **)&kc.dev, kc.bytes));
-    HIPCHK(ctx, hipMemcpy(kc.dev, kc.host, kc.bytes, hipMemcpyHostToDevice));
-    it = ctx->kconst.emplace(p.Kp, kc).first;
+    if (nrq_host_kconst_build(K, &kc.host.p, &kc.bytes) != 0) return fail(ctx, -2, "kconst build failed");
+    HIPCHK(ctx, hipMalloc((void **)&kc.dev.p, kc.bytes));
+    kc.dev.cap = kc.bytes;
+    HIPCHK(ctx, hipMemcpy(kc.dev.p, kc.host.p, kc.bytes, hipMemcpyHostToDevice));
+    it = ctx->kconst.emplace(p.Kp, std::move(kc)).first;
   }
   *out = &it->second;
   return 0;
@@ -1429,53 +1492,40 @@ int launch_plan_kernel(nrq_ctx *ctx, hipStream_t ps, const rq_params &p, const u
   return 0;
 }
 
-int ensure_encbuf(nrq_ctx *ctx, EncPlan &ep, int i, size_t total) {
-  if (ep.devcap[i] >= total) return 0;
-  if (ep.devbuf[i]) HIPCHK(ctx, hipFree(ep.devbuf[i]));
-  ep.devbuf[i] = nullptr; ep.devcap[i] = 0;
-  HIPCHK(ctx, hipMalloc((void **)&ep.devbuf[i], total + total / 8));
-  ep.devcap[i] = total + total / 8;
-  return 0;
-}
-
 /* host planner: build, stage in pinned memory, upload on the caller's stream (buffer 0) */
 int encplan_host_build(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc, EncPlan &ep) {
   double t0 = now_ms();
   std::vector<uint32_t> isis(p.Kp);
   for (uint32_t j = 0; j < p.Kp; j++) isis[j] = j;
-  uint8_t *arena = nullptr;
+  HostBuf arena;
   uint32_t bytes = 0;
-  if (nrq_host_plan_build(p.Kp, p.Kp, isis.data(), kc->host, &arena, &bytes) != 0)
+  if (nrq_host_plan_build(p.Kp, p.Kp, isis.data(), kc->host.p, &arena.p, &bytes) != 0)
     return fail(ctx, -2, "encode plan build failed for K=%u", K);
-  memcpy(&ep.hdr, arena, sizeof(ep.hdr));
-  if (ep.hdr.status) { nrq_host_free(arena); return fail(ctx, -3, "encode matrix singular for K=%u (cannot happen)", K); }
+  memcpy(&ep.hdr, arena.p, sizeof(ep.hdr));
+  if (ep.hdr.status) return fail(ctx, -3, "encode matrix singular for K=%u (cannot happen)", K);
   ep.plan_bytes = bytes;
-  ep.colslot.assign(reinterpret_cast<const uint16_t *>(arena + ep.hdr.off_colslot),
-                    reinterpret_cast<const uint16_t *>(arena + ep.hdr.off_colslot) + p.L);
+  ep.colslot.assign(reinterpret_cast<const uint16_t *>(arena.p + ep.hdr.off_colslot),
+                    reinterpret_cast<const uint16_t *>(arena.p + ep.hdr.off_colslot) + p.L);
   ep.rowsrc_off = (uint32_t)r16(bytes);
   const size_t total = ep.rowsrc_off + (size_t)p.L * 4;
   /* device and pinned buffers survive a cache clear (same K => same size class); the upload is
    * asynchronous on the context's stream, so rebuilding a plan never waits for the GPU */
-  int rc = ensure_encbuf(ctx, ep, 0, total);
-  if (rc) { nrq_host_free(arena); return rc; }
-  if (ep.pin_cap < total) {
-    if (ep.pin) HIPCHK(ctx, hipHostFree(ep.pin));
-    ep.pin = nullptr;
-    HIPCHK(ctx, hipHostMalloc((void **)&ep.pin, total + total / 8, hipHostMallocDefault));
-    ep.pin_cap = total + total / 8;
+  int rc = ensure_dev(ctx, ep.devbuf[0], total, total + total / 8);
+  if (rc) return rc;
+  if (ep.pin.cap < total) {
+    if ((rc = ensure_pin(ctx, ep.pin, total, total + total / 8))) return rc;
   } else {
     /* the previous upload from this pinned image must have been consumed */
     HIPCHK(ctx, hipEventSynchronize(ctx->encplan_uploaded));
   }
-  memcpy(ep.pin, arena, bytes);
-  uint32_t *rowsrc = reinterpret_cast<uint32_t *>(ep.pin + ep.rowsrc_off);
+  memcpy(ep.pin.p, arena.p, bytes);
+  uint32_t *rowsrc = reinterpret_cast<uint32_t *>(ep.pin.p + ep.rowsrc_off);
   for (uint32_t r = 0; r < p.L; r++) rowsrc[r] = NRQ_ROW_ZERO;
   for (uint32_t j = 0; j < K; j++) rowsrc[p.S + p.H + j] = j;
-  nrq_host_free(arena);
-  HIPCHK(ctx, hipMemcpyAsync(ep.devbuf[0], ep.pin, total, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ep.devbuf[0].p, ep.pin.p, total, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipEventRecord(ctx->encplan_uploaded, ctx->stream));
   ep.cur = 0;
-  ep.dev = ep.devbuf[0];
+  ep.dev = ep.devbuf[0].p;
   ep.valid = true;
   ep.pending = false;
   ep.dev_built = false;
@@ -1488,7 +1538,7 @@ int encplan_host_build(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc,
  * plan_stream2, into the buffer that is not in use; encplan_finish() waits for it and reads the header, the job
  * record and colslot[] back.  (reference: nanorq_precalculate, lib/nanorq.c:393-401) */
 int encplan_device_launch(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc, EncPlan &ep) {
-  const nrq_kconst_hdr *kh = reinterpret_cast<const nrq_kconst_hdr *>(kc->host);
+  const nrq_kconst_hdr *kh = reinterpret_cast<const nrq_kconst_hdr *>(kc->host.p);
   uint32_t ucap = p.P + 768u;
   if (ucap > 1280u) ucap = 1280u;
   if (ucap < p.P + 32u) return 1; /* not for the device planner */
@@ -1499,39 +1549,34 @@ int encplan_device_launch(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *
   const uint32_t rb = (uint32_t)(r16(r16(r16(r16(sizeof(nrq_plan_hdr)) + p.L * 2u) + p.L * 2u) + p.L * 2u));
   const size_t off_pj = arena_cap, off_job = off_pj + r16(sizeof(nrq_planjob)), dev_total = off_job + r16(sizeof(nrq_job));
   const size_t pin_pj = 0, pin_rb = r16(sizeof(nrq_planjob)), pin_job = pin_rb + rb, pin_total = pin_job + r16(sizeof(nrq_job));
-  const int buf = (ep.devbuf[ep.cur] && (ep.valid || ep.used_set[ep.cur])) ? ep.cur ^ 1 : ep.cur;
+  const int buf = (ep.devbuf[ep.cur].p && (ep.valid || ep.used_set[ep.cur])) ? ep.cur ^ 1 : ep.cur;
   int rc;
-  if ((rc = ensure_encbuf(ctx, ep, buf, dev_total))) return rc;
+  if ((rc = ensure_dev(ctx, ep.devbuf[buf], dev_total, dev_total + dev_total / 8))) return rc;
   if ((rc = ensure_dev(ctx, ctx->encplan_work, wl.total))) return rc;
   /* (the pinned image may still be the source of a host-built plan's asynchronous upload: encplan_host_build after a failed
    * device build -- wait for it before the job record is written over its first bytes) */
   HIPCHK(ctx, hipEventSynchronize(ctx->encplan_uploaded));
-  if (ep.pin_cap < pin_total) {
-    if (ep.pin) HIPCHK(ctx, hipHostFree(ep.pin));
-    ep.pin = nullptr;
-    HIPCHK(ctx, hipHostMalloc((void **)&ep.pin, pin_total + pin_total / 8, hipHostMallocDefault));
-    ep.pin_cap = pin_total + pin_total / 8;
-  }
-  if (!ep.ready) HIPCHK(ctx, hipEventCreateWithFlags(&ep.ready, hipEventDisableTiming));
+  if ((rc = ensure_pin(ctx, ep.pin, pin_total, pin_total + pin_total / 8))) return rc;
+  if (!ep.ready) HIPCHK(ctx, hipEventCreateWithFlags(&ep.ready.h, hipEventDisableTiming));
   for (int i = 0; i < 2; i++)
-    if (!ep.used[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ep.used[i], hipEventDisableTiming));
+    if (!ep.used[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ep.used[i].h, hipEventDisableTiming));
   hipStream_t ps = ctx->plan_stream2;
   if (ep.used_set[buf]) HIPCHK(ctx, hipStreamWaitEvent(ps, ep.used[buf], 0));
-  nrq_planjob *pj = reinterpret_cast<nrq_planjob *>(ep.pin + pin_pj);
+  nrq_planjob *pj = reinterpret_cast<nrq_planjob *>(ep.pin.p + pin_pj);
   memset(pj, 0, sizeof(*pj));
   pj->work = (uint64_t)(uintptr_t)ctx->encplan_work.p;
-  pj->arena = (uint64_t)(uintptr_t)ep.devbuf[buf];
+  pj->arena = (uint64_t)(uintptr_t)ep.devbuf[buf].p;
   pj->arena_cap = arena_cap;
   pj->mode = 1u | (plan_is_segmented(ctx, p, Mcap) ? (ctx->tune.no_wentry ? 0x100u : 0x300u) : 0u);
-  HIPCHK(ctx, hipMemcpyAsync(ep.devbuf[buf] + off_pj, pj, sizeof(*pj), hipMemcpyHostToDevice, ps));
+  HIPCHK(ctx, hipMemcpyAsync(ep.devbuf[buf].p + off_pj, pj, sizeof(*pj), hipMemcpyHostToDevice, ps));
   rq_params pk = p;
   pk.K = K;
-  if ((rc = launch_plan_kernel(ctx, ps, pk, kc->dev, reinterpret_cast<const nrq_planjob *>(ep.devbuf[buf] + off_pj),
-                               reinterpret_cast<nrq_job *>(ep.devbuf[buf] + off_job), 1u, Mcap, npcap, ucap, nullptr,
+  if ((rc = launch_plan_kernel(ctx, ps, pk, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ep.devbuf[buf].p + off_pj),
+                               reinterpret_cast<nrq_job *>(ep.devbuf[buf].p + off_job), 1u, Mcap, npcap, ucap, nullptr,
                                kh->nnz + npcap * PL_PATCH_STRIDE)))
     return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ep.pin + pin_rb, ep.devbuf[buf], rb, hipMemcpyDeviceToHost, ps));
-  HIPCHK(ctx, hipMemcpyAsync(ep.pin + pin_job, ep.devbuf[buf] + off_job, sizeof(nrq_job), hipMemcpyDeviceToHost, ps));
+  HIPCHK(ctx, hipMemcpyAsync(ep.pin.p + pin_rb, ep.devbuf[buf].p, rb, hipMemcpyDeviceToHost, ps));
+  HIPCHK(ctx, hipMemcpyAsync(ep.pin.p + pin_job, ep.devbuf[buf].p + off_job, sizeof(nrq_job), hipMemcpyDeviceToHost, ps));
   HIPCHK(ctx, hipEventRecord(ep.ready, ps));
   ep.pending = true;
   ep.pend = buf;
@@ -1544,12 +1589,12 @@ int encplan_finish(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc, Enc
   if (!ep.pending) return 0;
   HIPCHK(ctx, hipEventSynchronize(ep.ready));
   ep.pending = false;
-  const uint8_t *rbp = ep.pin + r16(sizeof(nrq_planjob));
+  const uint8_t *rbp = ep.pin.p + r16(sizeof(nrq_planjob));
   nrq_plan_hdr hd;
   memcpy(&hd, rbp, sizeof(hd));
   nrq_job jb;
   memcpy(&jb, rbp + ep.rb_bytes, sizeof(jb));
-  if (hd.magic != NRQ_PLAN_MAGIC || hd.status != 0 || hd.off_colslot + p.L * 2u > ep.rb_bytes || jb.plan != (uint64_t)(uintptr_t)ep.devbuf[ep.pend]) {
+  if (hd.magic != NRQ_PLAN_MAGIC || hd.status != 0 || hd.off_colslot + p.L * 2u > ep.rb_bytes || jb.plan != (uint64_t)(uintptr_t)ep.devbuf[ep.pend].p) {
     /* a planner capacity was exceeded (or worse): the host planner takes over */
     if (ctx->tune.prof) fprintf(stderr, "[NRQ_PROF] encode plan K'=%u: device build failed (status %u, planner_body.h:%u), host planner\n",
                                 p.Kp, hd.reserved[0], hd.fail_site);
@@ -1560,7 +1605,7 @@ int encplan_finish(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc, Enc
   ep.plan_bytes = hd.total_bytes;
   ep.rowsrc_off = (uint32_t)(jb.rowsrc - jb.plan);
   ep.cur = ep.pend;
-  ep.dev = ep.devbuf[ep.cur];
+  ep.dev = ep.devbuf[ep.cur].p;
   ep.valid = true;
   ep.dev_built = true;
   ep.build_ms = now_ms() - ep.t_launch;
@@ -1610,7 +1655,7 @@ void build_out_lists(const rq_params &p, const uint16_t *colslot, uint32_t n, co
 
 template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, uint32_t nblk, uint32_t T,
                                 const uint8_t *d_kc, uint32_t lds_bytes, uint32_t max_slots, uint32_t max_out, uint32_t max_u,
-                                uint32_t max_wpr, const std::vector<const nrq_plan_hdr *> &hdrs) {
+                                uint32_t max_wpr, const std::vector<const nrq_plan_hdr *> &hdrs, bool io_aligned) {
   /* WIDE strips (G lanes per element, 16 * G bytes per strip; solve_body.h) -- an experiment for small blocks, whose levels
    * hold a dozen ops and whose HDPC / dense phases a dozen rows, so that most lanes of a wave idle through them on a
    * 16-byte strip.  Measured (K=100 / 500 / 1000, G = 8 / 4 / 2, two or three 256-thread workgroups per CU): 270-313 /
@@ -1742,38 +1787,31 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     }
     ctx->attr_set[slot] = true;
   }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev1 = nullptr;
   if (ctx->ktime_on && !ctx->ktime_outer) { /* (ktime_outer: pick_and_launch brackets the launches of both block lists itself) */
-    if (ctx->ktime_used == ctx->ktime_pool.size()) {
-      hipEvent_t a, b;
-      HIPCHK(ctx, hipEventCreate(&a));
-      HIPCHK(ctx, hipEventCreate(&b));
-      ctx->ktime_pool.emplace_back(a, b);
-    }
-    ev0 = ctx->ktime_pool[ctx->ktime_used].first;
-    ev1 = ctx->ktime_pool[ctx->ktime_used].second;
-    ctx->ktime_used++;
-    HIPCHK(ctx, hipEventRecord(ev0, ctx->stream));
+    int rc_ = timing_pair(ctx, ctx->ktime_pool, ctx->ktime_used, ctx->stream, &ev1);
+    if (rc_) return rc_;
   }
   const uint32_t nprof = (uint32_t)((grid + 15) / 16);
+  DevBuf prof; /* NRQ_PROF=1: the workgroups' shader-clock marks, for the length of this launch */
   if (ctx->tune.prof) {
-    if (ctx->prof) { (void)hipFree(ctx->prof); ctx->prof = nullptr; }
-    HIPCHK(ctx, hipMalloc((void **)&ctx->prof, (size_t)nprof * 16 * 8));
-    HIPCHK(ctx, hipMemsetAsync(ctx->prof, 0, (size_t)nprof * 16 * 8, ctx->stream));
+    HIPCHK(ctx, hipMalloc((void **)&prof.p, (size_t)nprof * 16 * 8));
+    HIPCHK(ctx, hipMemsetAsync(prof.p, 0, (size_t)nprof * 16 * 8, ctx->stream));
   }
+  unsigned long long *const d_prof = reinterpret_cast<unsigned long long *>(prof.p);
 #define NRQ_LAUNCH_WIDE(GG)                                                                                                          \
   hipLaunchKernelGGL((nrq_solve_kernel<16, 256, 4, GG>), dim3((uint32_t)grid), dim3(256), lds_bytes, ctx->stream, d_jobs, nblk, T, nstrips, \
-                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, ctx->prof,     \
+                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, d_prof,        \
                      ybuf, ybuf_stride)
   if (WB == 16 && G == 8) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(8); }
   else if (WB == 16 && G == 4) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(4); }
   else if (WB == 16 && G == 2) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(2); }
   else {
     /* (the movers' aligned-only form; 12-byte strips: whole dwords, solve_body.h g_get_al12) */
-    const bool al = ctx->io_aligned && G == 1 && WB >= 4 && T % (uint32_t)(WB == 12 ? 4 : WB) == 0u;
+    const bool al = io_aligned && G == 1 && WB >= 4 && T % (uint32_t)(WB == 12 ? 4 : WB) == 0u;
 #define NRQ_LAUNCH(NTT, WVV, ALL)                                                                                                        \
   hipLaunchKernelGGL((nrq_solve_kernel<WB, NTT, WVV, 1, ALL>), dim3((uint32_t)grid), dim3(NTT), lds_bytes, ctx->stream, d_jobs, nblk, T, nstrips, \
-                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, ctx->prof, ybuf,   \
+                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, d_prof, ybuf,      \
                      ybuf_stride)
     if constexpr (WB == 12) { if (al) NRQ_LAUNCH(NRQ_WG, 1, true); else NRQ_LAUNCH(NRQ_WG, 1, false); }
     else if (tiny) { if (al) NRQ_LAUNCH(64, NRQ_TINY_WV, true); else NRQ_LAUNCH(64, NRQ_TINY_WV, false); }
@@ -1805,9 +1843,9 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     }
   }
   if (ev1) HIPCHK(ctx, hipEventRecord(ev1, ctx->stream));
-  if (ctx->prof) {
+  if (d_prof) {
     std::vector<unsigned long long> hp((size_t)nprof * 16);
-    HIPCHK(ctx, hipMemcpyAsync(hp.data(), ctx->prof, hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hp.data(), d_prof, hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     static const char *names[8] = {"load", "fwd", "hdpc", "bin", "dense", "tables", "backsub", "store"};
     double sum[8] = {0}, tot = 0;
@@ -1832,8 +1870,6 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     fprintf(stderr, " | marks since fwd end:");
     for (int k = 0; k < 7; k++) fprintf(stderr, " %.0f", cnt ? ext[k] / cnt : 0.0);
     fprintf(stderr, "\n");
-    (void)hipFree(ctx->prof);
-    ctx->prof = nullptr;
   }
   ctx->stats.strip_bytes = WBE;
   ctx->stats.lds_bytes = lds_bytes;
@@ -1845,20 +1881,9 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
   return 0;
 }
 
-/* every row of a base + b * stride array of T-byte rows starts 16-byte aligned */
-inline bool rows_aligned(const void *base, size_t stride, uint32_t T) {
-  return ((reinterpret_cast<uintptr_t>(base) | (uintptr_t)stride | (uintptr_t)T) & 15u) == 0;
-}
-inline bool vec_aligned(const uint64_t *v, uint32_t n, uint32_t T) {
-  if (T & 15u) return false;
-  for (uint32_t b = 0; b < n; b++)
-    if (v[b] & 15u) return false;
-  return true;
-}
-
 /* widest strip whose LDS image fits for every plan header in hdrs */
 static int launch_list(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs, const nrq_job *d_jobs, uint32_t nblk,
-                       uint32_t T, const uint8_t *d_kc, uint32_t max_out, uint32_t wb, uint32_t need) {
+                       uint32_t T, const uint8_t *d_kc, uint32_t max_out, uint32_t wb, uint32_t need, bool io_aligned) {
   uint32_t max_slots = 0, max_u = 0, max_wpr = 0;
   for (const nrq_plan_hdr *h : hdrs) {
     if (h->status) continue;
@@ -1867,11 +1892,11 @@ static int launch_list(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hd
     if (h->wpr > max_wpr) max_wpr = h->wpr;
   }
   switch (wb) {
-    case 16: return launch_wb<16>(ctx, 0, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs);
-    case 12: return launch_wb<12>(ctx, 4, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs);
-    case 8: return launch_wb<8>(ctx, 1, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs);
-    case 4: return launch_wb<4>(ctx, 2, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs);
-    default: return launch_wb<2>(ctx, 3, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs);
+    case 16: return launch_wb<16>(ctx, 0, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
+    case 12: return launch_wb<12>(ctx, 4, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
+    case 8: return launch_wb<8>(ctx, 1, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
+    case 4: return launch_wb<4>(ctx, 2, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
+    default: return launch_wb<2>(ctx, 3, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
   }
 }
 /* widest width at which the image of h fits the LDS (0: none) and its size there */
@@ -1897,7 +1922,7 @@ static uint32_t widest_fit(const nrq_ctx *ctx, const nrq_plan_hdr *h, uint32_t *
  * side by side first (a handful of small device-to-device copies, only when a batch splits).
  * blk_of_hdr: index in d_jobs of every header (nullptr: all blocks share one plan, nothing to split). */
 int pick_and_launch(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs, const nrq_job *d_jobs, uint32_t nblk,
-                    uint32_t T, const uint8_t *d_kc, uint32_t max_out, const std::vector<uint32_t> *blk_of_hdr = nullptr) {
+                    uint32_t T, const uint8_t *d_kc, uint32_t max_out, bool io_aligned, const std::vector<uint32_t> *blk_of_hdr = nullptr) {
   uint32_t wa = 0, need_a = 0, wb_ = 16, need_b = 0, na = 0, nsolv = 0;
   std::vector<uint32_t> wd(hdrs.size(), 0), nd(hdrs.size(), 0);
   for (size_t i = 0; i < hdrs.size(); i++) {
@@ -1922,7 +1947,7 @@ int pick_and_launch(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs,
     uint32_t need = 0;
     for (const nrq_plan_hdr *h : hdrs)
       if (!h->status) { const uint32_t t = nrq_lds_plan(h, w).total; if (t > need) need = t; }
-    return launch_list(ctx, hdrs, d_jobs, nblk, T, d_kc, max_out, w, need);
+    return launch_list(ctx, hdrs, d_jobs, nblk, T, d_kc, max_out, w, need, io_aligned);
   }
   /* two lists */
   std::vector<const nrq_plan_hdr *> ha, hb;
@@ -1957,22 +1982,17 @@ int pick_and_launch(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs,
   /* one pair of timing events around both launches (bench.py reads one interval per call) */
   hipEvent_t ev1 = nullptr;
   if (ctx->ktime_on) {
-    if (ctx->ktime_used == ctx->ktime_pool.size()) {
-      hipEvent_t a, b;
-      HIPCHK(ctx, hipEventCreate(&a));
-      HIPCHK(ctx, hipEventCreate(&b));
-      ctx->ktime_pool.emplace_back(a, b);
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ktime_pool[ctx->ktime_used].first, ctx->stream));
-    ev1 = ctx->ktime_pool[ctx->ktime_used].second;
-    ctx->ktime_used++;
+    if ((rc = timing_pair(ctx, ctx->ktime_pool, ctx->ktime_used, ctx->stream, &ev1))) return rc;
     ctx->ktime_outer = true;
   }
-  rc = launch_list(ctx, hb, jb, (uint32_t)ib.size(), T, d_kc, max_out, wb_, need_b);
+  rc = launch_list(ctx, hb, jb, (uint32_t)ib.size(), T, d_kc, max_out, wb_, need_b, io_aligned);
   const uint32_t sb_b = ctx->stats.strip_bytes;
-  if (!rc) rc = launch_list(ctx, ha, ja, na_blocks, T, d_kc, max_out, wa, need_a); /* (last: the call's stats describe the wide list) */
+  if (!rc) rc = launch_list(ctx, ha, ja, na_blocks, T, d_kc, max_out, wa, need_a, io_aligned); /* (last: the call's stats describe the wide list) */
   ctx->ktime_outer = false;
-  if (rc) return rc;
+  if (rc) {
+    if (ev1) ctx->ktime_used--; /* (the pair's second event will not be recorded) */
+    return rc;
+  }
   if (ev1) HIPCHK(ctx, hipEventRecord(ev1, ctx->stream));
   ctx->stats.strip_bytes_b = sb_b;
   ctx->stats.blocks_b = (uint32_t)ib.size();
@@ -2015,29 +2035,16 @@ int nrq_ctx_create(int device, void *stream, nrq_ctx **out) {
     ctx->fault_inject_armed = fi && *fi == '1';
   }
   memset(&ctx->stats, 0, sizeof(ctx->stats));
-  if (hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->plan_stream_b, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->plan_stream2, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->aux[0], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->aux[1], hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->aux[2], hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->scat_ev[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->scat_ev[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->planned[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->planned[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->planned[2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->arena_free[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->arena_free[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->arena_free[2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->pstaged[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->pstaged[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->pstaged[2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->pstaged[3], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&ctx->t0) != hipSuccess || hipEventCreate(&ctx->t1) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->encplan_uploaded, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->staged[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->staged[1], hipEventDisableTiming) != hipSuccess) {
-    delete ctx;
+  bool ok = true;
+  for (Stream *st : {&ctx->plan_stream, &ctx->plan_stream_b, &ctx->plan_stream2, &ctx->aux[0], &ctx->aux[1], &ctx->aux[2]})
+    ok = ok && hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking) == hipSuccess;
+  for (Event *ev : {&ctx->scat_ev[0], &ctx->scat_ev[1], &ctx->planned[0], &ctx->planned[1], &ctx->planned[2], &ctx->arena_free[0],
+                    &ctx->arena_free[1], &ctx->arena_free[2], &ctx->pstaged[0], &ctx->pstaged[1], &ctx->pstaged[2], &ctx->pstaged[3],
+                    &ctx->encplan_uploaded, &ctx->staged[0], &ctx->staged[1]})
+    ok = ok && hipEventCreateWithFlags(&ev->h, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreate(&ctx->t0.h) == hipSuccess && hipEventCreate(&ctx->t1.h) == hipSuccess;
+  if (!ok) {
+    delete ctx; /* (what was created goes with it) */
     return -23;
   }
   *out = ctx;
@@ -2052,69 +2059,21 @@ void nrq_plan_cache_clear(nrq_ctx *ctx) {
 static void encplans_release(nrq_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->plan_stream2) (void)hipStreamSynchronize(ctx->plan_stream2);
-  for (auto &kv : ctx->encplans) {
-    for (int i = 0; i < 2; i++) {
-      if (kv.second.devbuf[i]) (void)hipFree(kv.second.devbuf[i]);
-      if (kv.second.used[i]) (void)hipEventDestroy(kv.second.used[i]);
-    }
-    if (kv.second.ready) (void)hipEventDestroy(kv.second.ready);
-    if (kv.second.pin) (void)hipHostFree(kv.second.pin);
-  }
   ctx->encplans.clear();
 }
 
 void nrq_ctx_destroy(nrq_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
+  /* ORDERING first, spelled out: the work on every stream is over and the planner runs issued ahead are through before
+   * anything is released ... */
   (void)hipStreamSynchronize(ctx->stream);
   encplans_release(ctx);
-  if (ctx->encplan_uploaded) (void)hipEventDestroy(ctx->encplan_uploaded);
-  for (auto &kv : ctx->kconst) {
-    if (kv.second.dev) (void)hipFree(kv.second.dev);
-    nrq_host_free(kv.second.host);
-  }
   plan_ahead_drop(ctx);
-  if (ctx->plan_stream) { (void)hipStreamSynchronize(ctx->plan_stream); (void)hipStreamDestroy(ctx->plan_stream); }
-  if (ctx->plan_stream_b) { (void)hipStreamSynchronize(ctx->plan_stream_b); (void)hipStreamDestroy(ctx->plan_stream_b); }
-  if (ctx->plan_stream2) { (void)hipStreamSynchronize(ctx->plan_stream2); (void)hipStreamDestroy(ctx->plan_stream2); }
-  if (ctx->encplan_work.p) (void)hipFree(ctx->encplan_work.p);
-  for (int i = 0; i < 2; i++) {
-    if (ctx->aux[i]) { (void)hipStreamSynchronize(ctx->aux[i]); (void)hipStreamDestroy(ctx->aux[i]); }
-    if (i == 0 && ctx->aux[2]) { (void)hipStreamSynchronize(ctx->aux[2]); (void)hipStreamDestroy(ctx->aux[2]); }
-    if (ctx->scat_dev[i].p) (void)hipFree(ctx->scat_dev[i].p);
-    if (ctx->scat_pin[i].p) (void)hipHostFree(ctx->scat_pin[i].p);
-    if (ctx->scat_ev[i]) (void)hipEventDestroy(ctx->scat_ev[i]);
-  }
+  for (const Stream *st : {&ctx->plan_stream, &ctx->plan_stream_b, &ctx->plan_stream2, &ctx->aux[0], &ctx->aux[1], &ctx->aux[2]})
+    if (*st) (void)hipStreamSynchronize(*st);
+  /* ... then RELEASE: the pool's blocks (cached, or never given back by the caller) here, everything else by the members' destructors */
   for (auto &kv : ctx->pool_size) (void)hipFree(kv.first);
-  ctx->pool_size.clear(); ctx->pool_free.clear();
-  for (int i = 0; i < 3; i++) {
-    if (ctx->planned[i]) (void)hipEventDestroy(ctx->planned[i]);
-    if (ctx->arena_free[i]) (void)hipEventDestroy(ctx->arena_free[i]);
-    if (ctx->plan_arena[i].p) (void)hipFree(ctx->plan_arena[i].p);
-    if (ctx->plan_jobs[i].p) (void)hipFree(ctx->plan_jobs[i].p);
-  }
-  for (int i = 0; i < 2; i++)
-    if (ctx->plan_work[i].p) (void)hipFree(ctx->plan_work[i].p);
-  for (int i = 2; i < 4; i++) {
-    if (ctx->pscratch[i].p) (void)hipFree(ctx->pscratch[i].p);
-    if (ctx->pstaging[i].p) (void)hipHostFree(ctx->pstaging[i].p);
-    if (ctx->pstaged[i]) (void)hipEventDestroy(ctx->pstaged[i]);
-  }
-  if (ctx->stage.p) (void)hipFree(ctx->stage.p);
-  if (ctx->ybuf.p) (void)hipFree(ctx->ybuf.p);
-  for (int i = 0; i < 2; i++) {
-    if (ctx->pscratch[i].p) (void)hipFree(ctx->pscratch[i].p);
-    if (ctx->pstaging[i].p) (void)hipHostFree(ctx->pstaging[i].p);
-    if (ctx->pstaged[i]) (void)hipEventDestroy(ctx->pstaged[i]);
-    if (ctx->scratch[i].p) (void)hipFree(ctx->scratch[i].p);
-    if (ctx->staging[i].p) (void)hipHostFree(ctx->staging[i].p);
-    if (ctx->staged[i]) (void)hipEventDestroy(ctx->staged[i]);
-  }
-  for (auto &pr : ctx->ktime_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (auto &pr : ctx->ptime_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (ctx->ktime_base) (void)hipEventDestroy(ctx->ktime_base);
-  if (ctx->t0) (void)hipEventDestroy(ctx->t0);
-  if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   delete ctx;
 }
 
@@ -2212,11 +2171,10 @@ int nrq_warm(nrq_ctx *ctx, uint32_t K, uint32_t Kp, int encode_plan) {
   return rc;
 }
 
-int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_src, size_t src_stride,
-                      void *d_inter, size_t inter_stride, uint32_t nrep, const uint32_t *h_esis, void *d_rep,
-                      size_t rep_stride) {
-  if (!ctx) return -1;
-  if (!d_src || T == 0 || nblk == 0 || (nrep && (!h_esis || !d_rep))) return fail(ctx, -1, "bad arguments");
+/* nrq_encode_blocks / nrq_encode_blocks_v: the intermediate symbols (optional) go to base + stride or to an address per block */
+static int encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const Rows &src, const Rows &inter, uint32_t nrep,
+                         const uint32_t *h_esis, const Rows &rep) {
+  if (!src || T == 0 || nblk == 0 || (nrep && (!h_esis || !rep))) return fail(ctx, -1, "bad arguments");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const double t_begin = now_ms();
   rq_params p;
@@ -2224,8 +2182,7 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
   if (rc) return rc;
   for (uint32_t q = 0; q < nrep; q++)
     if (h_esis[q] < K || h_esis[q] >= (1u << 24)) return fail(ctx, -1, "repair ESI %u out of range", h_esis[q]);
-  ctx->io_aligned = rows_aligned(d_src, src_stride, T) && (!nrep || rows_aligned(d_rep, rep_stride, T)) &&
-                    (ctx->vec_inter ? vec_aligned(ctx->vec_inter, nblk, T) : (!d_inter || rows_aligned(d_inter, inter_stride, T)));
+  const bool io_aligned = src.aligned(nblk, T) && (!nrep || rep.aligned(nblk, T)) && (!inter || inter.aligned(nblk, T));
   KConst *kc;
   rc = get_kconst(ctx, p.Kp, &kc);
   if (rc) return rc;
@@ -2267,10 +2224,10 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
     memset(&j, 0, sizeof(j));
     j.plan = (uint64_t)(uintptr_t)ep->dev;
     j.rowsrc = (uint64_t)(uintptr_t)(ep->dev + ep->rowsrc_off);
-    j.src = (uint64_t)(uintptr_t)((const uint8_t *)d_src + (size_t)b * src_stride);
+    j.src = src.of(b);
     j.rep = 0;
-    j.inter = ctx->vec_inter ? ctx->vec_inter[b] : d_inter ? (uint64_t)(uintptr_t)((uint8_t *)d_inter + (size_t)b * inter_stride) : 0;
-    j.out = nrep ? (uint64_t)(uintptr_t)((uint8_t *)d_rep + (size_t)b * rep_stride) : 0;
+    j.inter = inter ? inter.of(b) : 0;
+    j.out = nrep ? rep.of(b) : 0;
     j.out_cptr = (uint64_t)(uintptr_t)(ds + off_cptr);
     j.out_slots = (uint64_t)(uintptr_t)(ds + off_cols);
     j.out_row = (uint64_t)(uintptr_t)(ds + off_row);
@@ -2279,7 +2236,7 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
   HIPCHK(ctx, hipMemcpyAsync(ds, hs, total, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipEventRecord(ctx->staged[f], ctx->stream));
   std::vector<const nrq_plan_hdr *> hdrs(1, &ep->hdr);
-  rc = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ds + off_jobs), nblk, T, kc->dev, ((d_inter || ctx->vec_inter) ? p.L : 0u) + nrep);
+  rc = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ds + off_jobs), nblk, T, kc->dev.p, (inter ? p.L : 0u) + nrep, io_aligned);
   if (ep->used[ep->cur]) { /* (device-built plans: the next build may not overwrite this buffer before the launch is done) */
     HIPCHK(ctx, hipEventRecord(ep->used[ep->cur], ctx->stream));
     ep->used_set[ep->cur] = true;
@@ -2288,13 +2245,25 @@ int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
   return rc;
 }
 
-static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
-                      const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi,
-                      const uint32_t *h_nrep, const uint32_t *h_avail, uint32_t *h_used, uint32_t rep_cap, const void *d_rep, size_t rep_stride, void *d_inter,
-                      size_t inter_stride, int *h_status) {
+int nrq_encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_src, size_t src_stride,
+                      void *d_inter, size_t inter_stride, uint32_t nrep, const uint32_t *h_esis, void *d_rep,
+                      size_t rep_stride) {
+  if (!ctx) return -1;
+  return encode_blocks(ctx, K, Kp, T, nblk, Rows{d_src, src_stride}, Rows{d_inter, inter_stride}, nrep, h_esis, Rows{d_rep, rep_stride});
+}
+
+int nrq_encode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_src, size_t src_stride,
+                        const uint64_t *d_inter_v) {
+  if (!ctx || !d_inter_v) return -1;
+  return encode_blocks(ctx, K, Kp, T, nblk, Rows{d_src, src_stride}, Rows{nullptr, 0, d_inter_v}, 0, nullptr, Rows{});
+}
+
+/* decode with the symbolic stage on the host; select: the blocks to do (nullptr: all of them), the others' status is left alone */
+static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select) {
+  const uint32_t K = c.K, T = c.T, nblk = c.nblk;
   const double t_begin = now_ms();
   rq_params p;
-  int rc = block_params(ctx, K, Kp, &p);
+  int rc = block_params(ctx, K, c.Kp, &p);
   if (rc) return rc;
   KConst *kc;
   rc = get_kconst(ctx, p.Kp, &kc);
@@ -2302,7 +2271,7 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
   if (!select) memset(&ctx->stats, 0, sizeof(ctx->stats));
 
   struct Prep {
-    uint8_t *plan = nullptr;
+    HostBuf plan; /* the host-built plan arena */
     uint32_t plan_bytes = 0;
     std::vector<uint32_t> rowsrc, cptr, orow;
     std::vector<uint16_t> cols;
@@ -2311,23 +2280,19 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
     size_t off_plan = 0, off_rowsrc = 0, off_cptr = 0, off_row = 0, off_cols = 0;
   };
   std::vector<Prep> prep(nblk);
-  struct PrepGuard { /* the host-built plan arenas are released on every way out of this function */
-    std::vector<Prep> &v;
-    ~PrepGuard() { for (auto &pr : v) if (pr.plan) { nrq_host_free(pr.plan); pr.plan = nullptr; } }
-  } prep_guard{prep};
   const uint32_t pad = p.Kp - K;
 
   auto prepare = [&](uint32_t b) {
     Prep &pr = prep[b];
-    const uint32_t nl = h_nlost[b], nr = h_nrep[b];
+    const uint32_t nl = c.h_nlost[b], nr = c.h_nrep[b];
     if (select && !select[b]) { pr.state = 2; return; } /* not ours: leave its status alone */
     if (nl == 0) { pr.state = 0; return; }             /* nothing missing (nanorq.c:605-606) */
-    if (nr < nl || nl > lost_cap || nr > rep_cap) { pr.state = -1; return; } /* nanorq.c:607-608 */
-    const uint32_t *lost = h_lost + (size_t)b * lost_cap;
-    const uint32_t *resi = h_rep_esi + (size_t)b * rep_cap;
-    uint32_t avail = h_avail ? h_avail[b] : nr;
+    if (nr < nl || nl > c.lost_cap || nr > c.rep_cap) { pr.state = -1; return; } /* nanorq.c:607-608 */
+    const uint32_t *lost = c.h_lost + (size_t)b * c.lost_cap;
+    const uint32_t *resi = c.h_rep_esi + (size_t)b * c.rep_cap;
+    uint32_t avail = c.h_avail ? c.h_avail[b] : nr;
     if (avail < nr) avail = nr;
-    if (avail > rep_cap) avail = rep_cap;
+    if (avail > c.rep_cap) avail = c.rep_cap;
     /* use nr symbols; while the system is rank deficient and the caller holds more, take one more and re-plan */
     for (uint32_t use = nr;; use++) {
       const uint32_t overhead = use - nl;
@@ -2347,15 +2312,15 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
         isis[p.Kp + e] = resi[nl + e] + pad;
         pr.rowsrc[p.L + e] = NRQ_ROW_REP | (nl + e);
       }
-      if (pr.plan) { nrq_host_free(pr.plan); pr.plan = nullptr; }
-      if (nrq_host_plan_build(p.Kp, p.Kp + overhead, isis.data(), kc->host, &pr.plan, &pr.plan_bytes) != 0) {
+      pr.plan = HostBuf();
+      if (nrq_host_plan_build(p.Kp, p.Kp + overhead, isis.data(), kc->host.p, &pr.plan.p, &pr.plan_bytes) != 0) {
         pr.state = -1;
         return;
       }
-      if (reinterpret_cast<const nrq_plan_hdr *>(pr.plan)->status == 0) { pr.used = use; break; }
+      if (reinterpret_cast<const nrq_plan_hdr *>(pr.plan.p)->status == 0) { pr.used = use; break; }
       if (use + 1 > avail) { pr.state = -1; return; } /* rank(A) < L with everything the caller holds */
     }
-    build_out_lists(p, reinterpret_cast<const uint16_t *>(pr.plan + reinterpret_cast<const nrq_plan_hdr *>(pr.plan)->off_colslot),
+    build_out_lists(p, reinterpret_cast<const uint16_t *>(pr.plan.p + reinterpret_cast<const nrq_plan_hdr *>(pr.plan.p)->off_colslot),
                     nl, lost, pr.cptr, pr.cols); /* ISI of a source symbol is its ESI */
     pr.orow.assign(lost, lost + nl);
     pr.state = 1;
@@ -2392,7 +2357,7 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
   uint32_t nsolve = 0;
   for (uint32_t b = 0; b < nblk; b++) {
     Prep &pr = prep[b];
-    if (pr.state != 2) { h_status[b] = pr.state >= 0 ? 1 : 0; if (h_used) h_used[b] = pr.state == 1 ? pr.used : 0; }
+    if (pr.state != 2) { c.h_status[b] = pr.state >= 0 ? 1 : 0; if (c.h_used) c.h_used[b] = pr.state == 1 ? pr.used : 0; }
     if (pr.state != 1) continue;
     nsolve++;
     pr.off_plan = off;   off = r16(off + pr.plan_bytes);
@@ -2424,7 +2389,7 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
       memset(&j, 0, sizeof(j));
       if (pr.state != 1) { j.plan = (uint64_t)(uintptr_t)(ds + off_dummy); continue; }
       hblk.push_back(b);
-      memcpy(hs + pr.off_plan, pr.plan, pr.plan_bytes);
+      memcpy(hs + pr.off_plan, pr.plan.p, pr.plan_bytes);
       memcpy(hs + pr.off_rowsrc, pr.rowsrc.data(), pr.rowsrc.size() * 4);
       memcpy(hs + pr.off_cptr, pr.cptr.data(), pr.cptr.size() * 4);
       memcpy(hs + pr.off_row, pr.orow.data(), pr.orow.size() * 4);
@@ -2438,9 +2403,9 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
       ctx->stats.plan_bytes += pr.plan_bytes;
       j.plan = (uint64_t)(uintptr_t)(ds + pr.off_plan);
       j.rowsrc = (uint64_t)(uintptr_t)(ds + pr.off_rowsrc);
-      j.src = (ctx->vec_src ? ctx->vec_src[b] : (uint64_t)(uintptr_t)((uint8_t *)d_src + (size_t)b * src_stride));
-      j.rep = (ctx->vec_rep ? ctx->vec_rep[b] : (uint64_t)(uintptr_t)((const uint8_t *)d_rep + (size_t)b * rep_stride));
-      j.inter = d_inter ? (uint64_t)(uintptr_t)((uint8_t *)d_inter + (size_t)b * inter_stride) : 0;
+      j.src = c.src_of(b);
+      j.rep = c.rep_of(b);
+      j.inter = c.inter_of(b);
       j.out = j.src; /* recovered symbols go back into the block's own rows */
       j.out_cptr = (uint64_t)(uintptr_t)(ds + pr.off_cptr);
       j.out_slots = (uint64_t)(uintptr_t)(ds + pr.off_cols);
@@ -2454,7 +2419,7 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
       uint32_t max_out = 0;
       for (uint32_t b = 0; b < nblk; b++)
         if (prep[b].state == 1 && prep[b].orow.size() > max_out) max_out = (uint32_t)prep[b].orow.size();
-      result = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ds), nblk, T, kc->dev, (d_inter ? p.L : 0u) + max_out, &hblk);
+      result = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ds), nblk, T, kc->dev.p, (c.inter ? p.L : 0u) + max_out, c.io_aligned, &hblk);
     }
   }
   ctx->stats.host_ms += now_ms() - t_begin;
@@ -2463,20 +2428,17 @@ static int decode_host(nrq_ctx *ctx, const uint8_t *select, uint32_t K, uint32_t
 
 
 /* One planner run of a batch of decode blocks: what its launch leaves for the half that waits for it and launches the solve.
- * Kept in the context between nrq_decode_plan_ahead and the decode call it was issued for (`key_*`: that call's arguments). */
+ * Kept in the context between nrq_decode_plan_ahead and the decode call it was issued for (`call`: that call's record). */
 struct PlanRun {
   rq_params p;
   KConst *kc = nullptr;
-  uint32_t K = 0, Kp = 0, T = 0, nblk = 0, lost_cap = 0, rep_cap = 0;
   uint32_t ucap = 0, Mcap = 0, npcap = 0, arena_cap = 0, max_nl = 0;
   size_t off_hdrs = 0;
   int f = 0, ab = 0; /* staging set, arena set */
   hipStream_t ps = nullptr;
   double t_begin = 0;
-  /* the call this run was issued for */
-  const void *d_src = nullptr, *d_rep = nullptr, *d_inter = nullptr;
-  size_t src_stride = 0, rep_stride = 0, inter_stride = 0;
-  bool has_avail = false;
+  /* the call this run was issued for: its lists point into the copies beside it */
+  DecodeCall call;
   std::vector<uint32_t> lost, nlost, resi, nrep, avail;
   PlanForm form;
 };
@@ -2491,26 +2453,23 @@ static void plan_ahead_drop(nrq_ctx *ctx) {
 }
 
 /* first half: inputs down, planner kernels and the headers' way back enqueued on the planner stream */
-static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
-                       const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi,
-                       const uint32_t *h_nrep, uint32_t rep_cap, const void *d_rep, size_t rep_stride, void *d_inter,
-                       size_t inter_stride, const uint32_t *h_avail) {
+static int plan_launch(nrq_ctx *ctx, PlanRun &r, const DecodeCall &c) {
+  const uint32_t K = c.K, nblk = c.nblk;
   r.t_begin = now_ms();
   rq_params &p = r.p;
-  int rc = block_params(ctx, K, Kp, &p);
+  int rc = block_params(ctx, K, c.Kp, &p);
   if (rc) return rc;
   KConst *kc;
   rc = get_kconst(ctx, p.Kp, &kc);
   if (rc) return rc;
   r.kc = kc;
-  r.K = K; r.Kp = Kp; r.T = T; r.nblk = nblk; r.lost_cap = lost_cap; r.rep_cap = rep_cap;
-  const nrq_kconst_hdr *kh = reinterpret_cast<const nrq_kconst_hdr *>(kc->host);
+  const nrq_kconst_hdr *kh = reinterpret_cast<const nrq_kconst_hdr *>(kc->host.p);
   uint32_t max_oh = 0, max_nrep = 0, max_nl = 0;
   for (uint32_t b = 0; b < nblk; b++) {
-    const uint32_t nl = h_nlost[b];
-    uint32_t nr = h_nrep[b];
-    if (nl == 0 || nr < nl || nl > lost_cap || nr > rep_cap) continue;
-    if (h_avail && h_avail[b] > nr) nr = h_avail[b] < rep_cap ? h_avail[b] : rep_cap; /* sizing: everything it may use */
+    const uint32_t nl = c.h_nlost[b];
+    uint32_t nr = c.h_nrep[b];
+    if (nl == 0 || nr < nl || nl > c.lost_cap || nr > c.rep_cap) continue;
+    if (c.h_avail && c.h_avail[b] > nr) nr = c.h_avail[b] < c.rep_cap ? c.h_avail[b] : c.rep_cap; /* sizing: everything it may use */
     if (nr - nl > max_oh) max_oh = nr - nl;
     if (nr > max_nrep) max_nrep = nr;
     if (nl > max_nl) max_nl = nl;
@@ -2543,8 +2502,8 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
   /* inputs of the planner: [planjobs][lost lists][repair ESI lists]; headers come back after them */
   const size_t off_pj = 0;
   const size_t off_lost = r16(off_pj + (size_t)nblk * sizeof(nrq_planjob));
-  const size_t off_resi = r16(off_lost + (size_t)nblk * lost_cap * 4);
-  const size_t in_bytes = r16(off_resi + (size_t)nblk * rep_cap * 4);
+  const size_t off_resi = r16(off_lost + (size_t)nblk * c.lost_cap * 4);
+  const size_t in_bytes = r16(off_resi + (size_t)nblk * c.rep_cap * 4);
   const size_t off_hdrs = in_bytes;
   const size_t total = r16(off_hdrs + (size_t)nblk * sizeof(nrq_plan_hdr));
   r.off_hdrs = off_hdrs;
@@ -2564,25 +2523,25 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
   if ((rc = ensure_dev(ctx, ctx->pscratch[f], total))) return rc; /* (inputs, and the headers side by side behind them) */
   uint8_t *hs = ctx->pstaging[f].p, *ds = ctx->pscratch[f].p;
   if (ctx->arena_busy[ab] && ps != ctx->stream) HIPCHK(ctx, hipStreamWaitEvent(ps, ctx->arena_free[ab], 0));
-  memcpy(hs + off_lost, h_lost, (size_t)nblk * lost_cap * 4);
-  memcpy(hs + off_resi, h_rep_esi, (size_t)nblk * rep_cap * 4);
+  memcpy(hs + off_lost, c.h_lost, (size_t)nblk * c.lost_cap * 4);
+  memcpy(hs + off_resi, c.h_rep_esi, (size_t)nblk * c.rep_cap * 4);
   nrq_planjob *pj = reinterpret_cast<nrq_planjob *>(hs + off_pj);
   for (uint32_t b = 0; b < nblk; b++) {
     nrq_planjob &j = pj[b];
     memset(&j, 0, sizeof(j));
-    const bool sane = h_nlost[b] <= lost_cap && h_nrep[b] <= rep_cap;
-    j.lost = (uint64_t)(uintptr_t)(ds + off_lost + (size_t)b * lost_cap * 4);
-    j.rep_esi = (uint64_t)(uintptr_t)(ds + off_resi + (size_t)b * rep_cap * 4);
+    const bool sane = c.h_nlost[b] <= c.lost_cap && c.h_nrep[b] <= c.rep_cap;
+    j.lost = (uint64_t)(uintptr_t)(ds + off_lost + (size_t)b * c.lost_cap * 4);
+    j.rep_esi = (uint64_t)(uintptr_t)(ds + off_resi + (size_t)b * c.rep_cap * 4);
     j.work = (uint64_t)(uintptr_t)(work.p + (size_t)b * wl.total);
     j.arena = (uint64_t)(uintptr_t)(ctx->plan_arena[ab].p + (size_t)b * arena_cap);
     j.hdr_out = (uint64_t)(uintptr_t)(ds + off_hdrs + (size_t)b * sizeof(nrq_plan_hdr));
-    j.src = (ctx->vec_src ? ctx->vec_src[b] : (uint64_t)(uintptr_t)((uint8_t *)d_src + (size_t)b * src_stride));
-    j.rep = (ctx->vec_rep ? ctx->vec_rep[b] : (uint64_t)(uintptr_t)((const uint8_t *)d_rep + (size_t)b * rep_stride));
-    j.inter = d_inter ? (uint64_t)(uintptr_t)((uint8_t *)d_inter + (size_t)b * inter_stride) : 0;
-    j.nlost = sane ? h_nlost[b] : 0;
-    j.nrep = sane ? h_nrep[b] : 0;
+    j.src = c.src_of(b);
+    j.rep = c.rep_of(b);
+    j.inter = c.inter_of(b);
+    j.nlost = sane ? c.h_nlost[b] : 0;
+    j.nrep = sane ? c.h_nrep[b] : 0;
     j.nrep_avail = j.nrep;
-    if (sane && h_avail && h_avail[b] > j.nrep) j.nrep_avail = h_avail[b] < rep_cap ? h_avail[b] : rep_cap;
+    if (sane && c.h_avail && c.h_avail[b] > j.nrep) j.nrep_avail = c.h_avail[b] < c.rep_cap ? c.h_avail[b] : c.rep_cap;
     j.arena_cap = arena_cap;
     j.mode = plan_is_segmented(ctx, p, Mcap) ? (ctx->tune.no_wentry ? 0x100u : 0x300u) : 0u; /* bit 8: segmented run, bit 9: entry pass by nrq_wentry_kernel */
   }
@@ -2593,25 +2552,15 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
     hipLaunchKernelGGL(nrq_ctl_copy_kernel, dim3(g ? g : 1u), dim3(256), 0, ps, reinterpret_cast<uint4 *>(ds), reinterpret_cast<const uint4 *>(hs), n16);
     HIPCHK(ctx, hipGetLastError());
   }
-  unsigned long long *pprof = nullptr;
+  DevBuf prof; /* NRQ_PROF=1: the planner's shader-clock marks, for the length of this run's launch */
   if (ctx->tune.prof) {
-    HIPCHK(ctx, hipMalloc((void **)&pprof, 64 * 8));
-    HIPCHK(ctx, hipMemsetAsync(pprof, 0, 64 * 8, ps));
+    HIPCHK(ctx, hipMalloc((void **)&prof.p, 64 * 8));
+    HIPCHK(ctx, hipMemsetAsync(prof.p, 0, 64 * 8, ps));
   }
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
-  if (ctx->ktime_on) {
-    if (ctx->ptime_used == ctx->ptime_pool.size()) {
-      hipEvent_t a, b;
-      HIPCHK(ctx, hipEventCreate(&a));
-      HIPCHK(ctx, hipEventCreate(&b));
-      ctx->ptime_pool.emplace_back(a, b);
-    }
-    pe0 = ctx->ptime_pool[ctx->ptime_used].first;
-    pe1 = ctx->ptime_pool[ctx->ptime_used].second;
-    ctx->ptime_used++;
-    HIPCHK(ctx, hipEventRecord(pe0, ps));
-  }
-  if ((rc = launch_plan_kernel(ctx, ps, p, kc->dev, reinterpret_cast<const nrq_planjob *>(ds + off_pj),
+  unsigned long long *const pprof = reinterpret_cast<unsigned long long *>(prof.p);
+  hipEvent_t pe1 = nullptr;
+  if (ctx->ktime_on && (rc = timing_pair(ctx, ctx->ptime_pool, ctx->ptime_used, ps, &pe1))) return rc;
+  if ((rc = launch_plan_kernel(ctx, ps, p, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ds + off_pj),
                                reinterpret_cast<nrq_job *>(ctx->plan_jobs[ab].p), nblk, Mcap, npcap, ucap, pprof,
                                kh->nnz + npcap * PL_PATCH_STRIDE, &r.form)))
     return rc;
@@ -2633,7 +2582,6 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
     fprintf(stderr, "\n[NRQ_PROF] chained peel: entries %llu, group clocks busy %llu (waiting for the rows %llu), claims %llu, phases %llu clocks %llu; flags trip %llu, subtraction trip %llu, claims %llu\n",
             hp[56], hp[57], hp[58], hp[59], hp[61], hp[60], hp[62], hp[63], hp[54]);
 #endif
-    (void)hipFree(pprof);
   }
   HIPCHK(ctx, hipMemcpyAsync(hs + off_hdrs, ds + off_hdrs, (size_t)nblk * sizeof(nrq_plan_hdr), hipMemcpyDeviceToHost, ps)); /* (pl_final_d's second copies) */
   HIPCHK(ctx, hipEventRecord(ctx->pstaged[f], ps));
@@ -2642,26 +2590,21 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, uint32_t K, uint32_t Kp, uint32
 }
 
 /* was this run issued for exactly this call? */
-static bool plan_run_matches(const nrq_ctx *ctx, const PlanRun &r, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_src,
-                             size_t src_stride, const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap,
-                             const uint32_t *h_rep_esi, const uint32_t *h_nrep, uint32_t rep_cap, const void *d_rep, size_t rep_stride,
-                             const void *d_inter, size_t inter_stride, const uint32_t *h_avail) {
-  if (ctx->vec_src || ctx->vec_rep || ctx->chunk_blocks) return false;
-  if (r.K != K || r.Kp != Kp || r.T != T || r.nblk != nblk || r.lost_cap != lost_cap || r.rep_cap != rep_cap) return false;
-  if (r.d_src != d_src || r.src_stride != src_stride || r.d_rep != d_rep || r.rep_stride != rep_stride || r.d_inter != d_inter ||
-      r.inter_stride != inter_stride || r.has_avail != (h_avail != nullptr))
-    return false;
-  return memcmp(r.nlost.data(), h_nlost, (size_t)nblk * 4) == 0 && memcmp(r.nrep.data(), h_nrep, (size_t)nblk * 4) == 0 &&
-         (!h_avail || memcmp(r.avail.data(), h_avail, (size_t)nblk * 4) == 0) &&
-         memcmp(r.lost.data(), h_lost, (size_t)nblk * lost_cap * 4) == 0 && memcmp(r.resi.data(), h_rep_esi, (size_t)nblk * rep_cap * 4) == 0;
+static bool plan_run_matches(const PlanRun &r, const DecodeCall &c) {
+  const DecodeCall &a = r.call;
+  if (c.src.vec || c.rep.vec || c.chunk_blocks) return false; /* (runs are issued for base + stride calls that solve in one launch) */
+  if (a.K != c.K || a.Kp != c.Kp || a.T != c.T || a.nblk != c.nblk || a.lost_cap != c.lost_cap || a.rep_cap != c.rep_cap) return false;
+  if (!(a.src == c.src) || !(a.rep == c.rep) || !(a.inter == c.inter) || (a.h_avail != nullptr) != (c.h_avail != nullptr)) return false;
+  return memcmp(a.h_nlost, c.h_nlost, (size_t)c.nblk * 4) == 0 && memcmp(a.h_nrep, c.h_nrep, (size_t)c.nblk * 4) == 0 &&
+         (!c.h_avail || memcmp(a.h_avail, c.h_avail, (size_t)c.nblk * 4) == 0) &&
+         memcmp(a.h_lost, c.h_lost, (size_t)c.nblk * c.lost_cap * 4) == 0 &&
+         memcmp(a.h_rep_esi, c.h_rep_esi, (size_t)c.nblk * c.rep_cap * 4) == 0;
 }
 
 /* decode with the symbolic stage on the GPU: one planner workgroup per block, then the solve */
-static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
-                         const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi,
-                         const uint32_t *h_nrep, uint32_t rep_cap, const void *d_rep, size_t rep_stride, void *d_inter,
-                         size_t inter_stride, int *h_status, std::vector<uint8_t> *fallback, const uint32_t *h_avail,
-                         uint32_t *h_used) {
+/* (fallback: set for the blocks that exceeded a planner capacity; the return value 1 says that there are some) */
+static int decode_device(nrq_ctx *ctx, const DecodeCall &c, std::vector<uint8_t> *fallback) {
+  const uint32_t K = c.K, T = c.T, nblk = c.nblk;
   const double t_begin = now_ms();
   memset(&ctx->stats, 0, sizeof(ctx->stats));
   ctx->stats.planner = 1;
@@ -2670,8 +2613,7 @@ static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   while (!ctx->ahead.empty()) {
     PlanRun *f = ctx->ahead.front();
     ctx->ahead.pop_front();
-    if (plan_run_matches(ctx, *f, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, rep_cap, d_rep, rep_stride,
-                         d_inter, inter_stride, h_avail)) {
+    if (plan_run_matches(*f, c)) {
       run = f; /* the planner run of this very call is already on its way (or done) */
       ahead = true;
       break;
@@ -2684,18 +2626,16 @@ static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   }
   struct Owner { PlanRun *r; ~Owner() { delete r; } } owner{ahead ? run : nullptr};
   if (!ahead) {
-    const int rc0 = plan_launch(ctx, *run, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, rep_cap, d_rep,
-                                rep_stride, d_inter, inter_stride, h_avail);
+    const int rc0 = plan_launch(ctx, *run, c);
     if (rc0) return rc0;
   }
   const rq_params &p = run->p;
   KConst *kc = run->kc;
   const int ab = run->ab;
-  const uint32_t arena_cap = run->arena_cap, max_nl = run->max_nl;
+  const uint32_t max_nl = run->max_nl;
   hipStream_t ps = run->ps;
   uint8_t *hs = ctx->pstaging[run->f].p;
   const size_t off_hdrs = run->off_hdrs;
-  (void)arena_cap;
   HIPCHK(ctx, hipEventSynchronize(ctx->planned[ab]));
   ctx->stats.plan_ms = now_ms() - t_begin;
   ctx->stats.plan_ahead = ahead ? 1 : 0;
@@ -2707,12 +2647,12 @@ static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   std::vector<uint32_t> hblk; /* block of every header in hdrs (pick_and_launch: the batch's two block lists) */
   bool need_fallback = false;
   for (uint32_t b = 0; b < nblk; b++) {
-    if (h_used) h_used[b] = 0;
-    if (h_nlost[b] == 0) { h_status[b] = 1; continue; } /* nothing missing (nanorq.c:605-606) */
+    if (c.h_used) c.h_used[b] = 0;
+    if (c.h_nlost[b] == 0) { c.h_status[b] = 1; continue; } /* nothing missing (nanorq.c:605-606) */
     if (hd[b].magic != NRQ_PLAN_MAGIC) return fail(ctx, -11, "device planner produced no header for block %u", b);
     if (hd[b].status == 0) {
-      h_status[b] = 1;
-      if (h_used) h_used[b] = h_nrep[b] + hd[b].reserved[1];
+      c.h_status[b] = 1;
+      if (c.h_used) c.h_used[b] = c.h_nrep[b] + hd[b].reserved[1];
       hdrs.push_back(&hd[b]);
       hblk.push_back(b);
       if (ctx->stats.npiv == 0) {
@@ -2721,39 +2661,39 @@ static int decode_device(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
       ctx->stats.xor_ops += hd[b].n_xor_ops;
       ctx->stats.plan_bytes += hd[b].total_bytes;
     } else if (hd[b].reserved[0] == PL_FAIL_CAPACITY) {
-      if (ctx->tune.prof || ctx->tune.diag) fprintf(stderr, "[NRQ_PROF] block %u: device planner capacity exceeded at planner_body.h:%u (npiv %u u %u nlev %u nrows %u M %u nlost %u)\n", b, hd[b].fail_site, hd[b].npiv, hd[b].u, hd[b].nlev, hd[b].nrows, hd[b].M, h_nlost[b]);
+      if (ctx->tune.prof || ctx->tune.diag) fprintf(stderr, "[NRQ_PROF] block %u: device planner capacity exceeded at planner_body.h:%u (npiv %u u %u nlev %u nrows %u M %u nlost %u)\n", b, hd[b].fail_site, hd[b].npiv, hd[b].u, hd[b].nlev, hd[b].nrows, hd[b].M, c.h_nlost[b]);
       (*fallback)[b] = 1;
       need_fallback = true;
-      h_status[b] = 0;
+      c.h_status[b] = 0;
     } else {
       if (ctx->tune.prof || ctx->tune.diag)
         fprintf(stderr, "[NRQ_PROF] block %u: not decodable: status %u reason %u site %u npiv %u u %u nlev %u nlow %u r2 %u nfree %u taken %u\n", b, hd[b].status,
                 hd[b].reserved[0], hd[b].fail_site, hd[b].npiv, hd[b].u, hd[b].nlev, hd[b].nlow, hd[b].r2, hd[b].nfree, hd[b].reserved[1]);
-      h_status[b] = 0;
+      c.h_status[b] = 0;
     }
   }
   int result = 0;
-  if (ctx->chunk_blocks) {
+  if (c.chunk_blocks) {
     /* one planner run, the solve chunk by chunk (nrq_decode_blocks_vc): an event per chunk for the caller's copy streams */
     if (ps != ctx->stream) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->planned[ab], 0));
-    const uint32_t cb = ctx->chunk_blocks;
+    const uint32_t cb = c.chunk_blocks;
     for (uint32_t c0 = 0, ci = 0; c0 < nblk && !result; c0 += cb, ci++) {
       const uint32_t m = nblk - c0 < cb ? nblk - c0 : cb;
       std::vector<const nrq_plan_hdr *> hc;
       std::vector<uint32_t> hcb;
       for (uint32_t b = c0; b < c0 + m; b++)
-        if (h_nlost[b] != 0 && hd[b].magic == NRQ_PLAN_MAGIC && hd[b].status == 0) { hc.push_back(&hd[b]); hcb.push_back(b - c0); }
-      if (ctx->chunk_up && ctx->chunk_up[ci]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)ctx->chunk_up[ci], 0));
+        if (c.h_nlost[b] != 0 && hd[b].magic == NRQ_PLAN_MAGIC && hd[b].status == 0) { hc.push_back(&hd[b]); hcb.push_back(b - c0); }
+      if (c.chunk_up && c.chunk_up[ci]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)c.chunk_up[ci], 0));
       if (!hc.empty())
-        result = pick_and_launch(ctx, hc, reinterpret_cast<const nrq_job *>(ctx->plan_jobs[ab].p) + c0, m, T, kc->dev, (d_inter ? p.L : 0u) + max_nl, &hcb);
-      if (ctx->chunk_done && ctx->chunk_done[ci]) HIPCHK(ctx, hipEventRecord((hipEvent_t)ctx->chunk_done[ci], ctx->stream));
+        result = pick_and_launch(ctx, hc, reinterpret_cast<const nrq_job *>(ctx->plan_jobs[ab].p) + c0, m, T, kc->dev.p, (c.inter ? p.L : 0u) + max_nl, c.io_aligned, &hcb);
+      if (c.chunk_done && c.chunk_done[ci]) HIPCHK(ctx, hipEventRecord((hipEvent_t)c.chunk_done[ci], ctx->stream));
     }
     HIPCHK(ctx, hipEventRecord(ctx->arena_free[ab], ctx->stream));
     ctx->arena_busy[ab] = true;
   } else if (!hdrs.empty()) {
     if (ps != ctx->stream) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->planned[ab], 0));
-    result = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ctx->plan_jobs[ab].p), nblk, T, kc->dev,
-                             (d_inter ? p.L : 0u) + max_nl, &hblk);
+    result = pick_and_launch(ctx, hdrs, reinterpret_cast<const nrq_job *>(ctx->plan_jobs[ab].p), nblk, T, kc->dev.p,
+                             (c.inter ? p.L : 0u) + max_nl, c.io_aligned, &hblk);
     /* the launch reads the plan arenas and job records: a later planner run may not overwrite this set before it is done */
     HIPCHK(ctx, hipEventRecord(ctx->arena_free[ab], ctx->stream));
     ctx->arena_busy[ab] = true;
@@ -2776,32 +2716,33 @@ int nrq_decode_plan_ahead(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uin
   if (!ctx->planner) return 0; /* host planner: nothing to issue ahead */
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->ahead.size() >= NRQ_PLAN_AHEAD_MAX) return fail(ctx, -6, "nrq_decode_plan_ahead: %u runs are already waiting for their decode calls", (unsigned)NRQ_PLAN_AHEAD_MAX);
+  DecodeCall c;
+  c.K = K; c.Kp = Kp; c.T = T; c.nblk = nblk;
+  c.src = {d_src, src_stride}; c.rep = {d_rep, rep_stride}; c.inter = {d_inter, inter_stride};
+  c.h_lost = h_lost; c.h_nlost = h_nlost; c.lost_cap = lost_cap;
+  c.h_rep_esi = h_rep_esi; c.h_nrep = h_nrep; c.h_avail = h_nrep_avail; c.rep_cap = rep_cap;
   PlanRun *r = new PlanRun();
-  const int rc = plan_launch(ctx, *r, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, rep_cap, d_rep,
-                             rep_stride, d_inter, inter_stride, h_nrep_avail);
+  const int rc = plan_launch(ctx, *r, c);
   if (rc) { delete r; return rc; }
-  r->d_src = d_src; r->src_stride = src_stride; r->d_rep = d_rep; r->rep_stride = rep_stride; r->d_inter = d_inter; r->inter_stride = inter_stride;
-  r->has_avail = h_nrep_avail != nullptr;
   r->lost.assign(h_lost, h_lost + (size_t)nblk * lost_cap);
   r->resi.assign(h_rep_esi, h_rep_esi + (size_t)nblk * rep_cap);
   r->nlost.assign(h_nlost, h_nlost + nblk);
   r->nrep.assign(h_nrep, h_nrep + nblk);
   if (h_nrep_avail) r->avail.assign(h_nrep_avail, h_nrep_avail + nblk);
+  r->call = c;
+  r->call.h_lost = r->lost.data(); r->call.h_nlost = r->nlost.data(); r->call.h_rep_esi = r->resi.data(); r->call.h_nrep = r->nrep.data();
+  if (h_nrep_avail) r->call.h_avail = r->avail.data();
   ctx->ahead.push_back(r);
   if (ctx->ahead.size() > ctx->ahead_hint) ctx->ahead_hint = (uint32_t)ctx->ahead.size();
   return 0;
 }
 
-int nrq_decode_blocks_lazy(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
-                           const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi,
-                           const uint32_t *h_nrep, const uint32_t *h_nrep_avail, uint32_t rep_cap, const void *d_rep,
-                           size_t rep_stride, void *d_inter, size_t inter_stride, int *h_status, uint32_t *h_used) {
-  if (!ctx) return -1;
-  if (!d_src || T == 0 || nblk == 0 || !h_nlost || !h_nrep || !h_status) return fail(ctx, -1, "bad arguments");
+/* every decode entry point ends here, with the call's record (completed here: io_aligned) */
+static int decode(nrq_ctx *ctx, DecodeCall &c) {
+  if (!c.src || c.T == 0 || c.nblk == 0 || !c.h_nlost || !c.h_nrep || !c.h_status) return fail(ctx, -1, "bad arguments");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  ctx->io_aligned = (ctx->vec_src ? vec_aligned(ctx->vec_src, nblk, T) : rows_aligned(d_src, src_stride, T)) &&
-                    (ctx->vec_rep ? vec_aligned(ctx->vec_rep, nblk, T) : rows_aligned(d_rep, rep_stride, T)) &&
-                    (!d_inter || rows_aligned(d_inter, inter_stride, T));
+  const uint32_t K = c.K, nblk = c.nblk;
+  c.io_aligned = c.src.aligned(nblk, c.T) && c.rep.aligned(nblk, c.T) && (!c.inter || c.inter.aligned(nblk, c.T));
   /* A call with one or two SMALL blocks (the reference's own harness: one block per call): the planner kernel is a chain of ~120
    * phases that a lone block cannot fill -- 200 us at K=100, 460 at K=1000, whatever the block count up to one per CU -- while the
    * host planner, sequential per block, needs ~0.45 us per source symbol on the GPU box's CPU.  Measured with the reference's
@@ -2809,71 +2750,38 @@ int nrq_decode_blocks_lazy(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, ui
    * 20.8 / 24.1, K=2000 22.3 / 21.8, K=2500 25.5 / 23.6, K=3000 25.7 / 23.1, K=4000 34.8 / 17.9.  So the host plans when its estimate is the shorter
    * one (option "host_plan_auto" / NRQ_HOST_PLAN_AUTO=0: never), unless plans were issued ahead or the call solves in chunks.
    * (Several small blocks: decode_host plans them one after the other -- its worker threads cost more to start than such plans take.) */
-  const bool host_small = ctx->planner && ctx->tune.host_plan_auto && ctx->ahead.empty() && !ctx->chunk_blocks &&
+  const bool host_small = ctx->planner && ctx->tune.host_plan_auto && ctx->ahead.empty() && !c.chunk_blocks &&
                           (uint64_t)38u * nblk * K < (uint64_t)20000u + (uint64_t)28u * K; /* (tools/small_calls.py: host call ~65 us + 0.3-0.4 us x K per block, planner-kernel
                                                                                                       * call ~270 us + 0.28 us x K: one block of K < 2000, two of K < 416, four of K < 161) */
   if (!ctx->planner || host_small) {
-    const int rc_ = decode_host(ctx, nullptr, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep,
-                                h_nrep_avail, h_used, rep_cap, d_rep, rep_stride, d_inter, inter_stride, h_status);
+    const int rc_ = decode_host(ctx, c, nullptr);
     if (host_small) ctx->stats.host_planned = 0; /* (a choice, not a fallback: tests read host_planned as "the device planner gave up") */
     return rc_;
   }
   std::vector<uint8_t> fallback(nblk, 0);
-  int rc = decode_device(ctx, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, rep_cap, d_rep,
-                         rep_stride, d_inter, inter_stride, h_status, &fallback, h_nrep_avail, h_used);
+  int rc = decode_device(ctx, c, &fallback);
   if (rc <= 0) return rc;
   /* blocks that exceeded a device-planner capacity are planned on the host (rare) */
   uint32_t nfb = 0;
   for (uint8_t f : fallback) nfb += f;
-  rc = decode_host(ctx, fallback.data(), K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep,
-                     h_nrep_avail, h_used, rep_cap, d_rep, rep_stride, d_inter, inter_stride, h_status);
+  rc = decode_host(ctx, c, fallback.data());
   ctx->stats.host_planned = nfb;
   if (ctx->tune.prof) fprintf(stderr, "[NRQ_PROF] %u of %u blocks re-planned on the host (device planner capacity)\n", nfb, nblk);
   return rc;
 }
 
-int nrq_encode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_src, size_t src_stride,
-                        const uint64_t *d_inter_v) {
-  if (!ctx || !d_inter_v) return -1;
-  ctx->vec_inter = d_inter_v;
-  const int rc = nrq_encode_blocks(ctx, K, Kp, T, nblk, d_src, src_stride, nullptr, 0, 0, nullptr, nullptr, 0);
-  ctx->vec_inter = nullptr;
-  return rc;
-}
-
-int nrq_decode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
-                        const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
-                        const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used) {
-  if (!ctx || !d_src_v || !d_rep_v) return -1;
-  ctx->vec_src = d_src_v;
-  ctx->vec_rep = d_rep_v;
-  const int rc = nrq_decode_blocks_lazy(ctx, K, Kp, T, nblk, (void *)(uintptr_t)16, 0, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, h_nrep_avail,
-                                        rep_cap, (const void *)(uintptr_t)16, 0, nullptr, 0, h_status, h_used);
-  ctx->vec_src = ctx->vec_rep = nullptr;
-  return rc;
-}
-
-int nrq_decode_blocks_vc(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
-                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
-                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used,
-                         uint32_t chunk_blocks, void *const *chunk_done, void *const *upload_done) {
-  if (!ctx || !chunk_blocks || !chunk_done) return -1;
-  const uint32_t nchunks = (nblk + chunk_blocks - 1u) / chunk_blocks;
-  if (!ctx->planner) {
-    /* host planner: no chunks -- everything is solved by one launch, after all uploads; every event is recorded behind it */
-    for (uint32_t i = 0; upload_done && i < nchunks; i++)
-      if (upload_done[i]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)upload_done[i], 0));
-  } else {
-    ctx->chunk_blocks = chunk_blocks; ctx->chunk_done = chunk_done; ctx->chunk_up = upload_done;
-  }
-  const int rc = nrq_decode_blocks_v(ctx, K, Kp, T, nblk, d_src_v, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, h_nrep_avail, rep_cap, d_rep_v,
-                                     h_status, h_used);
-  const bool chunked = ctx->chunk_blocks != 0 && ctx->stats.host_planned == 0;
-  ctx->chunk_blocks = 0; ctx->chunk_done = ctx->chunk_up = nullptr;
-  if (!chunked) /* (also when blocks were re-planned on the host and solved by a later launch: the events say "all done") */
-    for (uint32_t i = 0; i < nchunks; i++)
-      if (chunk_done[i]) HIPCHK(ctx, hipEventRecord((hipEvent_t)chunk_done[i], ctx->stream));
-  return rc;
+int nrq_decode_blocks_lazy(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
+                           const uint32_t *h_lost, const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi,
+                           const uint32_t *h_nrep, const uint32_t *h_nrep_avail, uint32_t rep_cap, const void *d_rep,
+                           size_t rep_stride, void *d_inter, size_t inter_stride, int *h_status, uint32_t *h_used) {
+  if (!ctx) return -1;
+  DecodeCall c;
+  c.K = K; c.Kp = Kp; c.T = T; c.nblk = nblk;
+  c.src = {d_src, src_stride}; c.rep = {d_rep, rep_stride}; c.inter = {d_inter, inter_stride};
+  c.h_lost = h_lost; c.h_nlost = h_nlost; c.lost_cap = lost_cap;
+  c.h_rep_esi = h_rep_esi; c.h_nrep = h_nrep; c.h_avail = h_nrep_avail; c.rep_cap = rep_cap;
+  c.h_status = h_status; c.h_used = h_used;
+  return decode(ctx, c);
 }
 
 int nrq_decode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, void *d_src, size_t src_stride,
@@ -2882,6 +2790,46 @@ int nrq_decode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
                       size_t inter_stride, int *h_status) {
   return nrq_decode_blocks_lazy(ctx, K, Kp, T, nblk, d_src, src_stride, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, nullptr,
                                 rep_cap, d_rep, rep_stride, d_inter, inter_stride, h_status, nullptr);
+}
+
+int nrq_decode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
+                        const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
+                        const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used) {
+  if (!ctx || !d_src_v || !d_rep_v) return -1;
+  DecodeCall c;
+  c.K = K; c.Kp = Kp; c.T = T; c.nblk = nblk;
+  c.src.vec = d_src_v; c.rep.vec = d_rep_v;
+  c.h_lost = h_lost; c.h_nlost = h_nlost; c.lost_cap = lost_cap;
+  c.h_rep_esi = h_rep_esi; c.h_nrep = h_nrep; c.h_avail = h_nrep_avail; c.rep_cap = rep_cap;
+  c.h_status = h_status; c.h_used = h_used;
+  return decode(ctx, c);
+}
+
+int nrq_decode_blocks_vc(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
+                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
+                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used,
+                         uint32_t chunk_blocks, void *const *chunk_done, void *const *upload_done) {
+  if (!ctx || !chunk_blocks || !chunk_done || !d_src_v || !d_rep_v) return -1;
+  const uint32_t nchunks = (nblk + chunk_blocks - 1u) / chunk_blocks;
+  DecodeCall c;
+  c.K = K; c.Kp = Kp; c.T = T; c.nblk = nblk;
+  c.src.vec = d_src_v; c.rep.vec = d_rep_v;
+  c.h_lost = h_lost; c.h_nlost = h_nlost; c.lost_cap = lost_cap;
+  c.h_rep_esi = h_rep_esi; c.h_nrep = h_nrep; c.h_avail = h_nrep_avail; c.rep_cap = rep_cap;
+  c.h_status = h_status; c.h_used = h_used;
+  if (!ctx->planner) {
+    /* host planner: no chunks -- everything is solved by one launch, after all uploads; every event is recorded behind it */
+    for (uint32_t i = 0; upload_done && i < nchunks; i++)
+      if (upload_done[i]) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)upload_done[i], 0));
+  } else {
+    c.chunk_blocks = chunk_blocks; c.chunk_done = chunk_done; c.chunk_up = upload_done;
+  }
+  const int rc = decode(ctx, c);
+  const bool chunked = c.chunk_blocks != 0 && ctx->stats.host_planned == 0;
+  if (!chunked) /* (also when blocks were re-planned on the host and solved by a later launch: the events say "all done") */
+    for (uint32_t i = 0; i < nchunks; i++)
+      if (chunk_done[i]) HIPCHK(ctx, hipEventRecord((hipEvent_t)chunk_done[i], ctx->stream));
+  return rc;
 }
 
 int nrq_gen_symbols(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const void *d_inter, size_t inter_stride,
@@ -3155,7 +3103,7 @@ int nrq_ktime_enable(nrq_ctx *ctx, int on) {
   ctx->ktime_used = 0;
   ctx->ptime_used = 0;
   if (on) {
-    if (!ctx->ktime_base) HIPCHK(ctx, hipEventCreate(&ctx->ktime_base));
+    if (!ctx->ktime_base) HIPCHK(ctx, hipEventCreate(&ctx->ktime_base.h));
     HIPCHK(ctx, hipEventRecord(ctx->ktime_base, ctx->stream));
   }
   return 0;
