@@ -159,6 +159,15 @@ int nrq_decode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint3
                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used);
 
+/* nrq_decode_blocks_v that also writes the intermediate symbols: block b's L symbols go to device address d_inter_v[b] (a host array of
+ * device addresses; NULL: none, and the call IS nrq_decode_blocks_v).  As in every decode that is given a place for them, all
+ * pivots are back-substituted (the needed-pivot view applies only without intermediate symbols); a block that is not recovered
+ * leaves its L * T bytes undefined.  What nrq_rx_decode calls while a relay is attached to the reception. */
+int nrq_decode_blocks_vi(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
+                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
+                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, const uint64_t *d_inter_v, int *h_status,
+                         uint32_t *h_used);
+
 /* nrq_decode_blocks_v with ONE planner run for all blocks and the solve in chunks of `chunk_blocks` blocks, in order: after
  * chunk i has been solved the event chunk_done[i] (nrq_event_new; ceil(nblk / chunk_blocks) of them) is recorded on the
  * context's stream, so that a caller can start moving the first blocks (nrq_stream_wait on a copy stream) while the later
@@ -283,13 +292,15 @@ int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the 
 typedef struct nrq_tx nrq_tx;
 #define NRQ_TX_TAG_INLINE 1u /* packet = the RFC 6330 section 3.2 FEC Payload ID (SBN 8 bits, ESI 24 bits, network byte order), then the
                               * payload at +4 (pkt_stride >= T + 4) */
+#define NRQ_TX_NOT_READY (-2) /* emit result code beside 0 and -1: a block of a relay that is not ready (the packet is left untouched) */
 int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, const void *d_src, size_t src_stride,
                   nrq_tx **out);
 void nrq_tx_destroy(nrq_tx *tx);
 /* solve every block (nrq_encode_blocks): the intermediate symbols into the transmission's own buffer; emits before it: -1 */
 int nrq_tx_encode(nrq_tx *tx);
 /* Packet k for tag d_tags[k] (nanorq_tag() form, device memory) at d_pkts + k*pkt_stride (pkt_stride >= T, + 4 inline).
- * d_results (device, nullable): 0 = written, -1 = SBN outside the transmission (the packet is left untouched). */
+ * d_results (device, nullable): 0 = written, -1 = SBN outside the transmission (the packet is left untouched); a relay also gives
+ * NRQ_TX_NOT_READY. */
 int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
 /* ESIs esi0 .. esi0+n-1 of EVERY block (n * nblk packets, no tag list): order 0 = block-major (packet k -> block k / n, ESI
  * esi0 + k % n), 1 = interleaved (packet k -> block k % nblk, ESI esi0 + k / nblk); d_tags_out (device, nullable) receives each
@@ -297,6 +308,28 @@ int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, si
 int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
                       uint32_t *d_tags_out);
 void *nrq_tx_inter(nrq_tx *tx); /* block b's L intermediate symbols at + b*L*T (valid after nrq_tx_encode) */
+/* per block (nblk entries): 1 = its packets can be emitted.  A sender: all 1 after nrq_tx_encode, all 0 before; a relay: below. */
+int nrq_tx_ready(nrq_tx *tx, uint32_t *h_ready);
+
+/* ---- relay: a transmission made FROM a reception, over the reception's own rows -- the node in the middle of a distribution tree,
+ * which receives blocks and goes on sending them, fresh repair symbols included, without solving a block twice ----
+ * The result is an ordinary nrq_tx (same emit calls, same destroy) whose source rows are the reception's, in place, and whose
+ * intermediate symbols (nblk * L * T bytes) come from the context's pool.  One relay per reception (a second call: -1).  Destroy
+ * the relay before its reception; a reception destroyed first detaches the relay, whose later calls fail with an error text.
+ * A block of the relay is READY when it is complete in the reception and its intermediate symbols are written:
+ *   - from the moment the relay is attached, nrq_rx_decode writes the intermediate symbols of every block it recovers into the
+ *     relay's buffer (nrq_decode_blocks_vi: all pivots are back-substituted), and the block is ready when the call returns;
+ *   - nrq_tx_encode on a relay makes ready every complete block that is not: it solves, with the encoder, only the blocks that
+ *     completed without a decode (nothing was missing) or were decoded before the relay was attached, leaves ready blocks alone
+ *     and launches nothing when there is nothing to do.  It may be called any number of times, after any decode (it waits for
+ *     the reception's counts);
+ *   - nrq_rx_reset makes every block not ready.
+ * nrq_tx_emit on a relay is never refused for want of an encode: a packet of a block that is not ready is left untouched and
+ * gets NRQ_TX_NOT_READY in d_results (-1 keeps meaning "SBN outside the span").  nrq_tx_emit_range needs every block ready
+ * (-1 and a text that names the blocks that are not).  Everything is enqueued on the context's stream, so an emit enqueued
+ * after a decode sees that decode's rows and intermediate symbols; a ready block never changes again (later packets for it are
+ * IGN), so its packets stay valid while the reception takes packets for other blocks. */
+int nrq_rx_relay(nrq_rx *rx, nrq_tx **out);
 
 /* ---- whole objects (RFC 6330 section 4.4.1.2) on the device: an object of F bytes and its OTI, sent and received through the
  * sender and receiver above without the caller partitioning it ----
@@ -341,6 +374,7 @@ int nrq_otx_emit(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, 
  * sorted by (i, sbn)).  d_tags_out (device, nullable) receives each packet's tag. */
 int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out);
 int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific);
+int nrq_otx_ready(nrq_otx *tx, uint32_t *h_ready); /* as nrq_tx_ready, Z entries */
 
 /* Object receiver: the blocks' row images in the context's pool, one reception (nrq_rx) per block class, both with the
  * object's max_esi.  rep_cap: repair rows per block. */
@@ -357,6 +391,14 @@ int nrq_orx_decode(nrq_orx *rx, int *h_status, uint32_t *h_used);    /* as nrq_r
  * left untouched.  Returns the number of blocks still incomplete (>= 0), or < 0 on error.  Waits for the counts, enqueues the
  * copy. */
 int nrq_orx_write(nrq_orx *rx, void *d_out);
+/* The object's relay (as nrq_rx_relay, over both block classes): an ordinary nrq_otx whose table lies over the receiver's row
+ * images -- class L at their start, class S behind it, each with its own K' under NANORQ_EXT_PER_BLOCK_KP; the Kt * T bytes of
+ * the row images make a staged last block unnecessary, and neither nrq_orx_write nor a layout pass is on the forwarding path --
+ * and whose intermediate symbols (ZL * L_L * T + ZS * L_S * T bytes) come from the context's pool.  nrq_orx_decode feeds it,
+ * nrq_otx_encode makes the remaining complete blocks ready, nrq_otx_emit gives NRQ_TX_NOT_READY per packet, nrq_otx_emit_all needs
+ * every block ready, nrq_otx_oti returns the object's OTI.  Packets are bit-exact with those of nrq_otx_create over the original
+ * object.  Destroy it before the receiver (else it is detached). */
+int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
 
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()

@@ -124,6 +124,11 @@ def lib():
     L.nrq_orx_counts.argtypes = [vp, u32p, u32p]
     L.nrq_orx_decode.argtypes = [vp, ip, u32p]
     L.nrq_orx_write.argtypes = [vp, vp]
+    if hasattr(L, "nrq_rx_relay"):  # (NANORQ_HIP_LIB may name a build from before the relays: A/B runs against it; relay() then raises)
+        L.nrq_tx_ready.argtypes = [vp, u32p]
+        L.nrq_rx_relay.argtypes = [vp, C.POINTER(vp)]
+        L.nrq_otx_ready.argtypes = [vp, u32p]
+        L.nrq_orx_relay.argtypes = [vp, C.POINTER(vp)]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -456,8 +461,14 @@ class Receiver(_Handle):
     def reset(self):
         self.ctx._chk(self._L.nrq_rx_reset(self._h))
 
+    def relay(self):
+        """A Sender over this reception's own rows (nrq_rx_relay): it emits any (SBN, ESI) of every block that is ready -- decoded
+        while the relay was attached, or complete and made ready by its encode().  One per reception."""
+        return RelaySender(self)
+
 
 TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
+TX_NOT_READY = -2   # NRQ_TX_NOT_READY
 
 
 class _Emitter(_Handle):
@@ -481,7 +492,8 @@ class _Emitter(_Handle):
     def emit(self, tags, out=None, inline=False, results=None):
         """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form) in row k of out ([n, stride] uint8 device
         tensor; None: a new one).  results: optional [n] int32 device tensor (0 written, -1 SBN outside the transmission or the
-        object, whose packet is left untouched).  Returns out."""
+        object, whose packet is left untouched; a relay: TX_NOT_READY for a block that is not ready, likewise untouched).
+        Returns out."""
         n = int(tags.shape[0])
         out, stride = self._out(n, inline, out)
         self.ctx._chk(getattr(self._L, self._api + "_emit")(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
@@ -518,6 +530,34 @@ class Sender(_Emitter):
         self.ctx._chk(self._L.nrq_tx_emit_range(self._h, esi0, n, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
                                                 TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
         return out
+
+
+class _Relay:
+    """What the two relays add to their sender class: made from a receiver (which they keep alive, so that Python tears the relay
+    down first), encode() = "make ready every complete block that is not", ready()."""
+
+    def _attach(self, rx):
+        self.ctx = rx.ctx
+        self._L = rx._L
+        self.receiver = rx
+        h = C.c_void_p()
+        self.ctx._chk(getattr(self._L, rx._api + "_relay")(rx._h, C.byref(h)))
+        self._h = h
+
+    def ready(self):
+        """numpy bool per block: its packets can be emitted"""
+        r = np.zeros(self._nblocks, np.uint32)
+        self.ctx._chk(getattr(self._L, self._api + "_ready")(self._h, _u32(r)))
+        return r.astype(bool)
+
+
+class RelaySender(_Relay, Sender):
+    """Receiver.relay(): a Sender (emit, emit_range, inter_ptr) over the reception's rows, in place."""
+
+    def __init__(self, rx):
+        self.K, self.T, self.nblk, self.sbn0 = rx.K, rx.T, rx.nblk, rx.sbn0
+        self._nblocks = rx.nblk
+        self._attach(rx)
 
 
 EXT_RFC_OTI = 1       # NANORQ_EXT_RFC_OTI (include/nanorq_ext.h)
@@ -585,6 +625,16 @@ class ObjectSender(_Emitter):
         return out
 
 
+class RelayObjectSender(_Relay, ObjectSender):
+    """ObjectReceiver.relay(): an ObjectSender (emit, emit_all, oti, blocks) over the receiver's row images, in place."""
+
+    def __init__(self, rx):
+        self.params = rx.params
+        self.T = rx.params.T
+        self._nblocks = rx.Z
+        self._attach(rx)
+
+
 class ObjectReceiver(_Handle):
     """A whole object received into device memory (nrq_orx, include/nanorq_hip.h), from its OTI words and the flags of
     nanorq_decoder_new_ext.  rep_cap: repair rows per block (default: 10 % of the larger K, at least 16)."""
@@ -630,6 +680,11 @@ class ObjectReceiver(_Handle):
         used = np.zeros(self.Z, np.uint32)
         self.ctx._chk(self._L.nrq_orx_decode(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
         return st, used
+
+    def relay(self):
+        """An ObjectSender over this receiver's row images (nrq_orx_relay): it emits any (SBN, ESI) of every block that is ready,
+        bit-exact with an ObjectSender of the original object.  One per receiver."""
+        return RelayObjectSender(self)
 
     def write(self, out=None):
         """Every complete block into out (a uint8 device tensor of at least F bytes; None: a new one of F bytes, zeroed) in the

@@ -17,6 +17,10 @@
  * (work item w -> packet tx_packet_of(w)) so that a block's packets run together and its rows are served from the caches, in
  * whatever order the packets lie in the output.  Range mode maps analytically; a tag list is first bucketed by block (tx_bin:
  * one bucket per block of the span, one more for SBNs outside it) into c->order.
+ *
+ * Ready mask.  A relay (a sender over a reception's rows) may hold blocks whose intermediate symbols are not written yet:
+ * tx_src::ready has a bit per block of the span, and a packet of a block whose bit is clear is left untouched with the result
+ * TX_NOT_READY (tx_admit).  Senders pass all ones.
  */
 #ifndef NRQ_EMIT_BODY_H
 #define NRQ_EMIT_BODY_H
@@ -38,6 +42,9 @@
 
 #define TX_SEGS 3u /* segments of an emit source: block class L, class S, and a last block staged apart */
 
+#define TX_FOREIGN (-1)   /* list mode result: SBN outside the span */
+#define TX_NOT_READY (-2) /* list mode result: a block of the span that is not ready (relays only) */
+
 /* one segment: nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1 (device addresses; the emulation passes host arrays) */
 struct tx_blk {
   rq_params p;            /* of K' (p.K = K) */
@@ -53,6 +60,8 @@ struct tx_src {
   struct tx_blk seg[TX_SEGS];
   uint32_t nseg;
   uint32_t sbn0, Z, ZL;
+  uint32_t ready[8];      /* a bit per block of the span (Z <= 256): its packets may be emitted.  All ones for a sender; a relay
+                           * (nrq_rx_relay) clears the blocks whose intermediate symbols are not there yet */
 };
 
 /* one emit call */
@@ -63,7 +72,7 @@ struct tx_call {
   uint32_t inl;           /* 1: FEC Payload ID at +0, payload at +4 */
   const uint32_t *tags;   /* list mode: tag of packet k (nanorq_tag form); NULL: range mode */
   const uint32_t *order;  /* list mode: packet of work item w (bucketed by block) */
-  int32_t *results;       /* list mode, nullable: 0 written, -1 SBN outside the span */
+  int32_t *results;       /* list mode, nullable: 0 written, TX_FOREIGN SBN outside the span, TX_NOT_READY */
   uint32_t esi0, nL, nS;  /* range mode: ESIs esi0 .. esi0+nL-1 of each of the first ZL blocks, esi0 .. esi0+nS-1 of the rest */
   uint32_t interleave;    /* range mode: 0 block-major, 1 sorted by (ESI, SBN) */
   uint32_t *tags_out;     /* range mode, nullable: the tag of each packet */
@@ -91,6 +100,28 @@ TX_HD uint32_t tx_seg(const struct tx_src *s, uint32_t tag) {
   for (uint32_t g = 0; g < nseg; g++)
     if (tx_block(&s->seg[g], tag) != TX_NONE) return g;
   return TX_SEGS;
+}
+
+/* the ready bit of the block of `tag` (a tag of the span); the mask word is picked by value (no dynamic index into the kernel
+ * arguments) */
+TX_HD uint32_t tx_ready(const struct tx_src *s, uint32_t tag) {
+  const uint32_t b = (tag >> 24) - s->sbn0;
+  uint32_t w = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (uint32_t i = 0; i < 8u; i++) w = i == (b >> 5) ? s->ready[i] : w;
+  return (w >> (b & 31u)) & 1u;
+}
+
+/* what a packet of `tag` gets: its segment, or TX_SEGS when it stays untouched -- *code says why (0: it is written) */
+template <bool MULTI>
+TX_HD uint32_t tx_admit(const struct tx_src *s, uint32_t tag, int32_t *code) {
+  const uint32_t g = tx_seg<MULTI>(s, tag);
+  if (g == TX_SEGS) { *code = TX_FOREIGN; return TX_SEGS; }
+  if (!tx_ready(s, tag)) { *code = TX_NOT_READY; return TX_SEGS; }
+  *code = 0;
+  return g;
 }
 
 /* segment g, selected by value (no dynamic index into the kernel arguments) */

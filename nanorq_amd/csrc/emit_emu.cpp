@@ -2,7 +2,7 @@
  * its work order (block-major; a tag list bucketed by block first), over a table of segments.  The payload is written a byte at a
  * time -- what the kernel's byte path does; its wider paths must give the same bytes.  Test support, not part of the library:
  * build.build_emit_emu() makes tests/emu/libemit_emu.so of it.  It lives beside the bodies it drives, and its C entry points
- * (emu_tx_emit, emu_tx_emit_range, emu_emit_table) are what the tests call. */
+ * (emu_tx_emit, emu_tx_emit_range, emu_emit_table, emu_emit_table_ready) are what the tests call. */
 #include <stdint.h>
 #include <string.h>
 
@@ -20,10 +20,11 @@ static int run(const tx_src *s, const tx_call *c) {
     if (k >= c->n || hit[k]++) return -2;
     const uint32_t tag = tx_tag_of<MULTI>(s, c, k);
     if (c->tags_out) c->tags_out[k] = tag;
-    const uint32_t g = tx_seg<MULTI>(s, tag);
+    int32_t code;
+    const uint32_t g = tx_admit<MULTI>(s, tag, &code);
     const tx_blk t = tx_pick(s, g);
     const uint32_t n = g < TX_SEGS ? tx_rows(&t, tag, cols) : 0u;
-    if (c->results) c->results[k] = n ? 0 : -1;
+    if (c->results) c->results[k] = code;
     if (n) tx_emit_bytes(&t, c, k, tag, cols, n);
   }
   return 0;
@@ -31,12 +32,27 @@ static int run(const tx_src *s, const tx_call *c) {
 
 extern "C" {
 
+/* The emit from a table of nseg segments WITH A READY MASK (a relay's table): ready = 8 words, bit b = block b of the span may
+ * be emitted; a packet of another block of the span is left untouched with the result -2.  Otherwise as emu_emit_table, which
+ * is this with all ones. */
+int emu_emit_table_ready(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
+                         const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
+                         uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out, const uint32_t *ready);
+
 /* The emit from a table of nseg segments: prm = nseg x {K, K', T, nblk, sbn0}, segment g's rows at src[g] / inter[g] with strides
  * src_stride[g] / inter_stride[g]; span = {sbn0, Z, ZL}.  List mode when tags is not NULL (n tags; results), else range mode with
  * range = {esi0, nL, nS, interleave} (tags_out; one segment: nL = nS).  -1: a bad table. */
 int emu_emit_table(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
                    const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
                    uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out) {
+  const uint32_t all[8] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+  return emu_emit_table_ready(prm, nseg, span, src, src_stride, inter, inter_stride, tags, n, range, inl, pkts, pkt_stride, results,
+                              tags_out, all);
+}
+
+int emu_emit_table_ready(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
+                         const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
+                         uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out, const uint32_t *ready) {
   tx_src s;
   memset(&s, 0, sizeof(s));
   if (nseg == 0 || nseg > TX_SEGS) return -1;
@@ -49,6 +65,7 @@ int emu_emit_table(const uint32_t *prm, uint32_t nseg, const uint32_t *span, con
     t.src = src[g]; t.src_stride = src_stride[g]; t.inter = inter[g]; t.inter_stride = inter_stride[g];
   }
   s.nseg = nseg; s.sbn0 = span[0]; s.Z = span[1]; s.ZL = span[2];
+  memcpy(s.ready, ready, sizeof(s.ready));
   tx_call c;
   memset(&c, 0, sizeof(c));
   c.pkts = pkts; c.pkt_stride = pkt_stride; c.inl = inl;

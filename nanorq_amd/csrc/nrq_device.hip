@@ -2795,10 +2795,18 @@ int nrq_decode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_
 int nrq_decode_blocks_v(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, int *h_status, uint32_t *h_used) {
+  return nrq_decode_blocks_vi(ctx, K, Kp, T, nblk, d_src_v, h_lost, h_nlost, lost_cap, h_rep_esi, h_nrep, h_nrep_avail, rep_cap, d_rep_v,
+                              nullptr, h_status, h_used);
+}
+
+int nrq_decode_blocks_vi(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, const uint64_t *d_src_v, const uint32_t *h_lost,
+                         const uint32_t *h_nlost, uint32_t lost_cap, const uint32_t *h_rep_esi, const uint32_t *h_nrep,
+                         const uint32_t *h_nrep_avail, uint32_t rep_cap, const uint64_t *d_rep_v, const uint64_t *d_inter_v, int *h_status,
+                         uint32_t *h_used) {
   if (!ctx || !d_src_v || !d_rep_v) return -1;
   DecodeCall c;
   c.K = K; c.Kp = Kp; c.T = T; c.nblk = nblk;
-  c.src.vec = d_src_v; c.rep.vec = d_rep_v;
+  c.src.vec = d_src_v; c.rep.vec = d_rep_v; c.inter.vec = d_inter_v;
   c.h_lost = h_lost; c.h_nlost = h_nlost; c.lost_cap = lost_cap;
   c.h_rep_esi = h_rep_esi; c.h_nrep = h_nrep; c.h_avail = h_nrep_avail; c.rep_cap = rep_cap;
   c.h_status = h_status; c.h_used = h_used;
@@ -3293,6 +3301,7 @@ __global__ __launch_bounds__(256) void nrq_ing_fold_kernel(ing_rx r, ing_call c)
 }
 
 struct ing_mask { uint32_t w[8]; }; /* a bit per block of the reception (nblk <= 256) */
+struct tx_sender;
 
 /* blocks a decode recovered: every source ESI counts as seen from now on (what nanorq_repair_block does to the bitmap) */
 __global__ __launch_bounds__(256) void nrq_ing_mark_kernel(ing_rx r, ing_mask m) {
@@ -3362,7 +3371,14 @@ struct nrq_rx {
   void *scratch;        /* per-call arrays */
   size_t scratch_cap;
   void *lists;          /* nrq_ing_lists_kernel output */
+  tx_sender *relay;     /* the relay attached to this reception (nrq_rx_relay / nrq_orx_relay), or null ... */
+  uint32_t relay_seg, relay_b0; /* ... in whose table this reception is segment relay_seg, its block 0 the span's block relay_b0 */
 };
+
+/* the relay's side of a reception (defined with the senders below) */
+static uint64_t relay_inter(const tx_sender *tx, uint32_t seg, uint32_t b); /* where block b of segment seg has its intermediate symbols */
+static void relay_set(tx_sender *tx, uint32_t b0, uint32_t nblk, bool valid); /* blocks b0 .. b0+nblk-1 of the span: intermediate symbols (not) written */
+static void relay_detach(tx_sender *tx);                                    /* a reception of the relay goes away */
 
 static size_t rx_al(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
@@ -3435,6 +3451,7 @@ bad:
 void nrq_rx_destroy(nrq_rx *rx) {
   if (!rx) return;
   nrq_ctx *ctx = rx->ctx;
+  if (rx->relay) relay_detach(rx->relay); /* (its later calls fail with an error text; it frees what it owns itself) */
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
   for (void *p : {rx->own_src, rx->own_rep, rx->state, rx->scratch, rx->lists})
     if (p) nrq_dev_free(ctx, p);
@@ -3444,6 +3461,7 @@ void nrq_rx_destroy(nrq_rx *rx) {
 int nrq_rx_reset(nrq_rx *rx) {
   if (!rx) return -1;
   HIPCHK(rx->ctx, hipSetDevice(rx->ctx->device));
+  if (rx->relay) relay_set(rx->relay, rx->relay_b0, rx->r.nblk, false); /* (emits enqueued before carry their mask by value) */
   return rx_init_state(rx);
 }
 
@@ -3591,8 +3609,15 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
     rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
   }
   std::vector<int> st(ns, 0);
-  rc = nrq_decode_blocks_v(ctx, r.K, rx->Kp, r.T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
-                           navail.data(), rep_cap, rv.data(), st.data(), used.data());
+  /* with a relay attached the decode also writes the intermediate symbols of every block it recovers, into the relay's buffer
+   * (and so back-substitutes all pivots); without one it asks for none, as nrq_decode_blocks_v */
+  std::vector<uint64_t> iv;
+  if (rx->relay) {
+    iv.resize(ns);
+    for (size_t i = 0; i < ns; i++) iv[i] = relay_inter(rx->relay, rx->relay_seg, sel[i]);
+  }
+  rc = nrq_decode_blocks_vi(ctx, r.K, rx->Kp, r.T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
+                            navail.data(), rep_cap, rv.data(), rx->relay ? iv.data() : nullptr, st.data(), used.data());
   if (rc) return rc;
   ing_mask m{};
   bool any = false;
@@ -3600,6 +3625,7 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
     h_status[sel[i]] = st[i];
     if (h_used) h_used[sel[i]] = used[i];
     if (st[i]) { m.w[sel[i] >> 5] |= 1u << (sel[i] & 31u); any = true; }
+    if (st[i] && rx->relay) relay_set(rx->relay, rx->relay_b0 + sel[i], 1, true);
   }
   if (any) {
     hipLaunchKernelGGL(nrq_ing_mark_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, m);
@@ -3671,14 +3697,15 @@ __global__ __launch_bounds__(256) void nrq_emit_kernel(tx_src s, tx_call c) {
   if (w0 + lane < c.n) {
     const uint32_t k = tx_packet_of<MULTI>(&s, &c, (uint32_t)(w0 + lane));
     const uint32_t tag = k < c.n ? tx_tag_of<MULTI>(&s, &c, k) : 0u;
-    const uint32_t sg = k < c.n ? tx_seg<MULTI>(&s, tag) : TX_SEGS; /* (k < n always: the work order is a permutation) */
+    int32_t code = TX_FOREIGN;
+    const uint32_t sg = k < c.n ? tx_admit<MULTI>(&s, tag, &code) : TX_SEGS; /* (k < n always: the work order is a permutation) */
     const tx_blk sb = MULTI ? tx_pick(&s, sg) : s.seg[0];
     const uint32_t n = sg < TX_SEGS ? tx_rows(&sb, tag, s_cols[wv][lane]) : 0u;
     s_n[wv][lane] = n;
     s_tag[wv][lane] = tag;
     s_k[wv][lane] = k;
     if (MULTI) s_seg[wv][lane] = sg;
-    if (k < c.n && c.results) c.results[k] = n ? 0 : -1;
+    if (k < c.n && c.results) c.results[k] = code;
     if (k < c.n && c.tags_out) c.tags_out[k] = tag;
   }
   __syncthreads();
@@ -3686,7 +3713,7 @@ __global__ __launch_bounds__(256) void nrq_emit_kernel(tx_src s, tx_call c) {
   const uint32_t T = s.seg[0].T;
   for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
     const uint32_t n = s_n[wv][i];
-    if (!n) continue; /* SBN outside the span: the packet stays untouched */
+    if (!n) continue; /* SBN outside the span, or a block that is not ready: the packet stays untouched */
     const uint32_t tag = s_tag[wv][i];
     const uint8_t *base;
     if constexpr (MULTI) {
@@ -3755,23 +3782,96 @@ struct tx_sender {
   const char *unencoded; /* the emit calls' refusal before the encode */
   void *scratch;         /* list mode: bucket counts, then the work order */
   size_t scratch_cap;
+  /* A relay (nrq_rx_relay / nrq_orx_relay): segment g's source rows are those of the reception from[g], and s.ready has the bit
+   * of every block whose intermediate symbols are written -- by a decode of the reception while the relay was attached, or by
+   * the relay's encode for a block that is complete (only complete blocks ever get the bit: ready = complete and written). */
+  bool relay, detached;  /* detached: a reception was destroyed first; every later call fails */
+  nrq_rx *from[2];
 };
 
 struct nrq_tx : tx_sender {};
+
+static uint64_t relay_inter(const tx_sender *tx, uint32_t seg, uint32_t b) {
+  const tx_blk &t = tx->s.seg[seg];
+  return (uint64_t)(uintptr_t)(t.inter + (uint64_t)b * t.inter_stride);
+}
+
+static void relay_set(tx_sender *tx, uint32_t b0, uint32_t nblk, bool valid) {
+  for (uint32_t b = b0; b < b0 + nblk; b++) {
+    if (valid) tx->s.ready[b >> 5] |= 1u << (b & 31u);
+    else tx->s.ready[b >> 5] &= ~(1u << (b & 31u));
+  }
+}
+
+static bool tx_is_ready(const tx_sender *tx, uint32_t b) { return (tx->s.ready[b >> 5] >> (b & 31u)) & 1u; }
+
+static void relay_detach(tx_sender *tx) {
+  for (nrq_rx *&r : tx->from) {
+    if (r) r->relay = nullptr;
+    r = nullptr;
+  }
+  tx->detached = true;
+  memset(tx->s.ready, 0, sizeof(tx->s.ready));
+}
 
 template <class S>
 static void tx_destroy(S *tx) {
   if (!tx) return;
   nrq_ctx *ctx = tx->ctx;
+  for (nrq_rx *r : tx->from)
+    if (r) r->relay = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
   for (void *p : {tx->own[0], tx->own[1], tx->scratch})
     if (p) nrq_dev_free(ctx, p);
   delete tx;
 }
 
+/* a relay's blocks that are not ready, as a text ("3, 7, 9 ... (12 of 256)") */
+static std::string relay_missing(const tx_sender *tx) {
+  std::string out;
+  uint32_t n = 0;
+  for (uint32_t b = 0; b < tx->s.Z; b++) {
+    if (tx_is_ready(tx, b)) continue;
+    if (n < 8u) out += (n ? ", " : "") + std::to_string(tx->s.sbn0 + b);
+    n++;
+  }
+  if (n > 8u) out += " ...";
+  return out + " (" + std::to_string(n) + " of " + std::to_string(tx->s.Z) + ")";
+}
+
+/* a relay's encode: every block that is complete in its reception but has no intermediate symbols yet -- nothing was missing,
+ * or it was decoded before the relay was attached -- is solved with the encoder, from the reception's rows; the blocks that are
+ * ready are left alone (no launch at all when there is nothing to do).  Waits for the receptions' counts. */
+static int relay_encode(tx_sender *tx) {
+  nrq_ctx *ctx = tx->ctx;
+  for (uint32_t g = 0; g < tx->s.nseg; g++) {
+    const tx_blk &t = tx->s.seg[g];
+    nrq_rx *rx = tx->from[g];
+    std::vector<uint32_t> gaps(t.nblk, 0);
+    int rc = nrq_rx_counts(rx, gaps.data(), nullptr);
+    if (rc) return rc;
+    std::vector<uint32_t> todo;
+    std::vector<uint64_t> sv, iv;
+    for (uint32_t b = 0; b < t.nblk; b++) {
+      if (gaps[b] || tx_is_ready(tx, rx->relay_b0 + b)) continue;
+      todo.push_back(b);
+      sv.push_back((uint64_t)(uintptr_t)(t.src + (uint64_t)b * t.src_stride));
+      iv.push_back(relay_inter(tx, g, b));
+    }
+    if (todo.empty()) continue;
+    rc = encode_blocks(ctx, t.K, t.p.Kp, t.T, (uint32_t)todo.size(), Rows{nullptr, 0, sv.data()}, Rows{nullptr, 0, iv.data()}, 0, nullptr,
+                       Rows{});
+    if (rc) return rc;
+    for (uint32_t b : todo) relay_set(tx, rx->relay_b0 + b, 1, true);
+  }
+  return 0;
+}
+
 /* solve every block of every segment */
 static int tx_encode(tx_sender *tx) {
   if (!tx) return -1;
+  if (tx->detached) return fail(tx->ctx, -1, "the relay's reception was destroyed");
+  if (tx->relay) return relay_encode(tx);
   tx->encoded = false;
   for (uint32_t g = 0; g < tx->s.nseg; g++) {
     const tx_blk &t = tx->s.seg[g];
@@ -3786,6 +3886,7 @@ static int tx_encode(tx_sender *tx) {
 /* checks shared by every emit call */
 static int tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
   nrq_ctx *ctx = tx->ctx;
+  if (tx->detached) return fail(ctx, -1, "%s: the relay's reception was destroyed", who);
   if (!tx->encoded) return fail(ctx, -1, "%s: %s", who, tx->unencoded);
   if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
   if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
@@ -3857,9 +3958,12 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
 
 /* range mode (the caller has checked its arguments): ESIs esi0 .. esi0+nL-1 of each of the span's first ZL blocks, esi0 ..
  * esi0+nS-1 of the rest, block-major (order 0) or interleaved (1) */
-static int tx_emit_span(tx_sender *tx, uint32_t esi0, uint32_t nL, uint32_t nS, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
-                        uint32_t *d_tags_out) {
+static int tx_emit_span(tx_sender *tx, const char *who, uint32_t esi0, uint32_t nL, uint32_t nS, int order, void *d_pkts, size_t pkt_stride,
+                        uint32_t flags, uint32_t *d_tags_out) {
   nrq_ctx *ctx = tx->ctx;
+  if (tx->relay) /* (the packet maps are analytic over all blocks: no holes) */
+    for (uint32_t b = 0; b < tx->s.Z; b++)
+      if (!tx_is_ready(tx, b)) return fail(ctx, -1, "%s: blocks of the relay are not ready: SBN %s", who, relay_missing(tx).c_str());
   HIPCHK(ctx, hipSetDevice(ctx->device));
   tx_call c{};
   c.pkts = (uint8_t *)d_pkts;
@@ -3895,6 +3999,7 @@ int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nb
   tx->unencoded = "the transmission is not encoded (nrq_tx_encode)";
   tx->s.nseg = 1;
   tx->s.sbn0 = sbn0; tx->s.Z = tx->s.ZL = nblk;
+  memset(tx->s.ready, 0xFF, sizeof(tx->s.ready));
   tx_blk &t = tx->s.seg[0];
   int rc = block_params(ctx, K, Kp, &t.p);
   if (rc) { delete tx; return rc; }
@@ -3916,6 +4021,47 @@ int nrq_tx_encode(nrq_tx *tx) { return tx_encode(tx); }
 
 void *nrq_tx_inter(nrq_tx *tx) { return tx ? (void *)tx->s.seg[0].inter : nullptr; }
 
+static int tx_ready(tx_sender *tx, const char *who, uint32_t *h_ready) {
+  if (!tx) return -1;
+  if (tx->detached) return fail(tx->ctx, -1, "%s: the relay's reception was destroyed", who);
+  if (!h_ready) return fail(tx->ctx, -1, "%s: h_ready is NULL", who);
+  for (uint32_t b = 0; b < tx->s.Z; b++) h_ready[b] = tx->relay ? tx_is_ready(tx, b) : tx->encoded;
+  return 0;
+}
+
+int nrq_tx_ready(nrq_tx *tx, uint32_t *h_ready) { return tx_ready(tx, "nrq_tx_ready", h_ready); }
+
+int nrq_rx_relay(nrq_rx *rx, nrq_tx **out) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  if (!out) return fail(ctx, -1, "nrq_rx_relay: out is NULL");
+  *out = nullptr;
+  if (rx->relay) return fail(ctx, -1, "nrq_rx_relay: the reception has a relay already");
+  const ing_rx &r = rx->r;
+  nrq_tx *tx = new (std::nothrow) nrq_tx();
+  if (!tx) return fail(ctx, -1, "nrq_rx_relay: out of host memory");
+  tx->ctx = ctx;
+  tx->relay = tx->encoded = true; /* (a relay is never "not encoded": its blocks are ready or not, one by one) */
+  tx->unencoded = "";
+  tx->s.nseg = 1;
+  tx->s.sbn0 = r.sbn0; tx->s.Z = tx->s.ZL = r.nblk;
+  tx_blk &t = tx->s.seg[0];
+  int rc = block_params(ctx, r.K, rx->Kp, &t.p);
+  if (rc) { delete tx; return rc; }
+  t.K = r.K; t.T = r.T; t.nblk = r.nblk; t.sbn0 = r.sbn0;
+  t.src = r.src; t.src_stride = r.src_stride; /* the reception's rows, in place */
+  t.inter_stride = (uint64_t)t.p.L * r.T;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)r.nblk * t.inter_stride, &tx->own[0]))) {
+    delete tx;
+    return rc;
+  }
+  t.inter = (const uint8_t *)tx->own[0];
+  tx->from[0] = rx;
+  rx->relay = tx; rx->relay_seg = 0; rx->relay_b0 = 0;
+  *out = tx;
+  return 0;
+}
+
 int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
   return tx_emit_list(tx, "nrq_tx_emit", d_tags, n, d_pkts, pkt_stride, flags, d_results);
 }
@@ -3929,7 +4075,7 @@ int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_
   if (n == 0) return 0;
   if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "nrq_tx_emit_range: ESIs %u + %u reach past 2^24", esi0, n);
   if ((uint64_t)n * tx->s.Z > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit_range: %u packets per block is too many", n);
-  return tx_emit_span(tx, esi0, n, n, order, d_pkts, pkt_stride, flags, d_tags_out);
+  return tx_emit_span(tx, "nrq_tx_emit_range", esi0, n, n, order, d_pkts, pkt_stride, flags, d_tags_out);
 }
 
 } /* extern "C" */
@@ -4059,6 +4205,7 @@ int nrq_otx_create(nrq_ctx *ctx, const nrq_obj_params *prm, const void *d_obj, n
   tx->prm = p;
   tx_src &o = tx->s;
   o.sbn0 = 0; o.Z = p.Z; o.ZL = p.ZL;
+  memset(o.ready, 0xFF, sizeof(o.ready));
   const uint64_t T = p.T, LL = (uint64_t)pL.L * T, LS = (uint64_t)pS.L * T;
   const uint32_t last = p.Z - 1u, Klast = last < p.ZL ? p.KL : p.KS;
   const uint64_t olast = (uint64_t)(p.Kt - Klast) * T;
@@ -4115,6 +4262,8 @@ int nrq_otx_oti(nrq_otx *tx, uint64_t *common, uint32_t *specific) {
   return 0;
 }
 
+int nrq_otx_ready(nrq_otx *tx, uint32_t *h_ready) { return tx_ready(tx, "nrq_otx_ready", h_ready); }
+
 int nrq_otx_emit(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
   return tx_emit_list(tx, "nrq_otx_emit", d_tags, n, d_pkts, pkt_stride, flags, d_results);
 }
@@ -4130,7 +4279,7 @@ int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t
   if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "nrq_otx_emit_all: ESIs up to %llu + %u reach past 2^24", (unsigned long long)kmax, nrep);
   const uint64_t total = (uint64_t)p.ZL * (p.KL + (uint64_t)nrep) + (uint64_t)p.ZS * (p.KS + (uint64_t)nrep);
   if (total > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_otx_emit_all: %llu packets are too many", (unsigned long long)total);
-  return tx_emit_span(tx, 0, p.KL + nrep, p.KS + nrep, order, d_pkts, pkt_stride, flags, d_tags_out);
+  return tx_emit_span(tx, "nrq_otx_emit_all", 0, p.KL + nrep, p.KS + nrep, order, d_pkts, pkt_stride, flags, d_tags_out);
 }
 
 int nrq_orx_create(nrq_ctx *ctx, const nrq_obj_params *prm, uint32_t rep_cap, nrq_orx **out) {
@@ -4157,6 +4306,51 @@ int nrq_orx_create(nrq_ctx *ctx, const nrq_obj_params *prm, uint32_t rep_cap, nr
 bad:
   nrq_orx_destroy(rx);
   return rc;
+}
+
+int nrq_orx_relay(nrq_orx *rx, nrq_otx **out) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  if (!out) return fail(ctx, -1, "nrq_orx_relay: out is NULL");
+  *out = nullptr;
+  for (nrq_rx *r : rx->rx)
+    if (r && r->relay) return fail(ctx, -1, "nrq_orx_relay: the reception has a relay already");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const nrq_obj_params &p = rx->prm;
+  int rc = 0;
+  rq_params pL{}, pS{};
+  if (p.ZL && (rc = block_params(ctx, p.KL, p.KpL, &pL))) return rc;
+  if (p.ZS && (rc = block_params(ctx, p.KS, p.KpS, &pS))) return rc;
+  nrq_otx *tx = new (std::nothrow) nrq_otx();
+  if (!tx) return fail(ctx, -1, "nrq_orx_relay: out of host memory");
+  tx->ctx = ctx;
+  tx->relay = tx->encoded = true;
+  tx->unencoded = "";
+  tx->prm = p;
+  tx_src &o = tx->s;
+  o.sbn0 = 0; o.Z = p.Z; o.ZL = p.ZL;
+  const uint64_t T = p.T, LL = (uint64_t)pL.L * T, LS = (uint64_t)pS.L * T;
+  if ((rc = nrq_dev_alloc(ctx, (size_t)(p.ZL * LL + p.ZS * LS), &tx->own[0]))) {
+    delete tx;
+    return rc;
+  }
+  /* the class table over the receptions' rows (Kt * T bytes, zero-padded behind F by the last packet's sender: no staged last
+   * block), the intermediate symbols class L first, class S behind it, as nrq_otx_create lays them out */
+  const rq_params *bp[2] = {&pL, &pS};
+  const uint64_t Lb[2] = {LL, LS}, ioff[2] = {0, p.ZL * LL};
+  for (int c = 0; c < 2; c++) {
+    nrq_rx *r = rx->rx[c];
+    if (!r) continue;
+    const uint32_t g = o.nseg++;
+    tx_blk &t = o.seg[g];
+    t.p = *bp[c]; t.K = r->r.K; t.T = p.T; t.nblk = r->r.nblk; t.sbn0 = r->r.sbn0;
+    t.src = r->r.src; t.src_stride = r->r.src_stride;
+    t.inter = (const uint8_t *)tx->own[0] + ioff[c]; t.inter_stride = Lb[c];
+    tx->from[g] = r;
+    r->relay = tx; r->relay_seg = g; r->relay_b0 = r->r.sbn0;
+  }
+  *out = tx;
+  return 0;
 }
 
 void nrq_orx_destroy(nrq_orx *rx) {
