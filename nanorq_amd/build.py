@@ -2,7 +2,7 @@
 
   libnanorq_hip.so   product: gfx950 kernels + C ABI (include/nanorq_hip.h) + drop-in nanorq.h/io.h
                      layer, compiled with hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
-  tests/emu/libsolve_emu.so   test support: CPU emulation of the solve workgroup (g++)
+  tests/emu/lib*_emu.so       test support: the kernels' phase code and the launch decisions, built by g++ for the CPU tier
 
 The .so files are git-ignored but travel to the GPU box with the working tree.
 """
@@ -20,6 +20,7 @@ PEMU = os.path.join(ROOT, "tests", "emu", "libplanner_emu.so")
 IEMU = os.path.join(ROOT, "tests", "emu", "libingest_emu.so")
 XEMU = os.path.join(ROOT, "tests", "emu", "libemit_emu.so")
 OEMU = os.path.join(ROOT, "tests", "emu", "libobj_emu.so")
+SEMU = os.path.join(ROOT, "tests", "emu", "libshape_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -107,47 +108,41 @@ def build_tools(force=False):
     return exe
 
 
+def _build_emu(target, src, headers, force):
+    """one CPU emulation library: a g++ build of `src` over the kernel bodies it includes (`headers`, in csrc)"""
+    if force or _newer(target, [src] + [os.path.join(CSRC, h) for h in headers]):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", target, src], check=True)
+    return target
+
+
 def build_emu(force=False):
-    src = os.path.join(ROOT, "tests", "emu", "solve_emu.cpp")
-    deps = [src, os.path.join(CSRC, "solve_body.h"), os.path.join(CSRC, "plan.h")]
-    if force or _newer(EMU, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", EMU, src], check=True)
-    return EMU
+    return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"), ("solve_body.h", "plan.h"), force)
 
 
 def build_planner_emu(force=False):
-    src = os.path.join(ROOT, "tests", "emu", "planner_emu.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("planner_body.h", "planner_seq.h", "solve_body.h", "plan.h", "rq_math.h")]
-    if force or _newer(PEMU, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", PEMU, src], check=True)
-    return PEMU
+    return _build_emu(PEMU, os.path.join(ROOT, "tests", "emu", "planner_emu.cpp"),
+                      ("planner_body.h", "planner_seq.h", "solve_body.h", "plan.h", "rq_math.h"), force)
 
 
 def build_ingest_emu(force=False):
     """tests/emu/libingest_emu.so: CPU emulation of the device-resident receiver's ingest kernels (ingest_body.h)."""
-    src = os.path.join(ROOT, "tests", "emu", "ingest_emu.cpp")
-    deps = [src, os.path.join(CSRC, "ingest_body.h")]
-    if force or _newer(IEMU, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", IEMU, src], check=True)
-    return IEMU
+    return _build_emu(IEMU, os.path.join(ROOT, "tests", "emu", "ingest_emu.cpp"), ("ingest_body.h",), force)
 
 
 def build_emit_emu(force=False):
     """tests/emu/libemit_emu.so: CPU emulation of the device-resident emit kernel (csrc/emit_emu.cpp over emit_body.h)."""
-    src = os.path.join(CSRC, "emit_emu.cpp")
-    deps = [src, os.path.join(CSRC, "emit_body.h"), os.path.join(CSRC, "rq_math.h")]
-    if force or _newer(XEMU, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", XEMU, src], check=True)
-    return XEMU
+    return _build_emu(XEMU, os.path.join(CSRC, "emit_emu.cpp"), ("emit_body.h", "rq_math.h"), force)
 
 
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
-    src = os.path.join(ROOT, "tests", "emu", "obj_emu.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("obj_body.h", "emit_body.h", "rq_math.h")]
-    if force or _newer(OEMU, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", OEMU, src], check=True)
-    return OEMU
+    return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
+
+
+def build_shape_emu(force=False):
+    """tests/emu/libshape_emu.so: the launch decisions (launch_shape.h) behind a C interface; host code as it is, no emulation."""
+    return _build_emu(SEMU, os.path.join(ROOT, "tests", "emu", "shape_emu.cpp"),
+                      ("launch_shape.h", "planner_body.h", "solve_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h"), force)
 
 
 if __name__ == "__main__":
@@ -157,4 +152,5 @@ if __name__ == "__main__":
     build_ingest_emu(force="-f" in sys.argv)
     build_emit_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
+    build_shape_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -38,17 +38,8 @@
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
 
-#define NRQ_LDS_MAX 163840u /* 160 KiB per workgroup on gfx950 */
-/* ... handed out in pieces of 320 dwords (LLVM getLdsDwGranularity for the 160 KiB parts): what a workgroup asks for is rounded
- * up to that, and how many workgroups share a CU follows from the rounded size.  (The HIP occupancy query divides the bytes:
- * it said nine 18 016-byte workgroups fit, eight were resident, and the ninth of every CU ran as a second round -- K=500.) */
-#define NRQ_LDS_GRANULE 1280u
-static inline uint32_t lds_alloc(uint32_t bytes) { return (bytes + NRQ_LDS_GRANULE - 1u) / NRQ_LDS_GRANULE * NRQ_LDS_GRANULE; }
-#ifndef NRQ_WG
-#define NRQ_WG 768 /* threads of the solve workgroup: 3 waves per SIMD.  One workgroup owns the CU (LDS), and its phases are
-                    * bound by instruction issue and LDS latency: measured 256 -> 512 -> 768 -> 1024 threads = 673 / 796 / 835 /
-                    * 807 Gbit/s on the headline workload */
-#endif
+#include "launch_shape.h" /* the knobs, the instance lists, what a launch looks like: host code the tests compile on their own */
+
 #define NRQ_GEN_WG 256
 
 /* ============================================================================================
@@ -58,8 +49,8 @@ static inline uint32_t lds_alloc(uint32_t bytes) { return (bytes + NRQ_LDS_GRANU
 /* Work: "line groups" -- the 128/WB strips of one block that share a 128-byte line of every symbol row.  Slot q
  * of the work list -> (block, group); workgroup g takes the slots g, g + gridDim.x, ...  With many blocks in the
  * launch (by_block) all groups of a block go to workgroups of one XCD (workgroup g runs on XCD g % 8, observed;
- * speed only), so that the block's plan -- every strip walks the whole op stream -- is served by one L2. */
-static inline bool nrq_map_by_block(uint32_t nblk) { return nblk >= 64u || (nblk >= 8u && (nblk & 7u) == 0u); }
+ * speed only), so that the block's plan -- every strip walks the whole op stream -- is served by one L2
+ * (nrq_map_by_block, launch_shape.h). */
 __device__ __forceinline__ bool nrq_map_group(uint32_t q, uint32_t nblk, uint32_t gpb, bool by_block, uint32_t *blk, uint32_t *grp) {
   if (by_block) {
     const uint32_t m = q >> 3;
@@ -72,7 +63,6 @@ __device__ __forceinline__ bool nrq_map_group(uint32_t q, uint32_t nblk, uint32_
   return *blk < nblk;
 }
 
-/* first slot >= q (stepping by gridDim.x) that holds a group of a solvable block; >= nslots if none */
 /* first slot >= q (stepping by gridDim.x) that holds a group of a solvable block; >= nslots if none */
 __device__ __forceinline__ uint32_t nrq_next_group(uint32_t q, uint32_t nslots, const nrq_job *__restrict__ jobs, uint32_t nblk,
                                                    uint32_t gpb, bool by_block) {
@@ -121,14 +111,6 @@ __device__ __forceinline__ uint32_t nrq_next_group(uint32_t q, uint32_t nslots, 
  * then compiled WITHOUT their byte-wise forms -- with both forms at every call site the kernels were half as large again
  * (persistent workgroups in different phases share the instruction cache), and a byte-wise path inside a mover loop makes the
  * compiler wait for all loads in flight where the paths join. */
-#ifndef NRQ_TINY_WV
-#define NRQ_TINY_WV 3   /* the single-wave variant: waves per SIMD it is built for (170 registers), */
-#endif
-#ifndef NRQ_TINY_OCC
-#define NRQ_TINY_OCC 12u /* and workgroups per compute unit it runs with.  Round 4, K=100 T=1024 x 8192 blocks: 5 / 18 (96 registers,
-                          * 151 of them spilled: every phase reloads its pointers from scratch) 370 Gbit/s, 4 / 16 ~385, 3 / 12 419,
-                          * 2 / 8 358; K=256 527 / 547 / 569 / 533 */
-#endif
 #ifndef NRQ_PROF_DONE
 #define NRQ_PROF_DONE 9 /* NRQ_PROF samples this strip (counted from 0) of every 16th workgroup.  It must lie behind the workgroup's FIRST work
                          * slot to see a scatter at all (the first slot has no results of a slot before it to move): strip 9 is in the second
@@ -142,9 +124,6 @@ __device__ __forceinline__ uint32_t nrq_next_group(uint32_t q, uint32_t nslots, 
 #endif
 #ifndef NRQ_W12_SW
 #define NRQ_W12_SW 2
-#endif
-#ifndef NRQ_SMALL_WV
-#define NRQ_SMALL_WV 4   /* the 256-thread variant: workgroups per compute unit = waves per SIMD it is built for */
 #endif
 template <int WB, int NT, int WV, int G = 1, bool AL = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WV)))
@@ -1111,72 +1090,6 @@ struct DecodeCall {
 
 } // namespace
 
-/* Tuning / debugging knobs from the environment, read ONCE when the context is created (the launch path does not
- * call getenv). */
-struct Tuning {
-  bool map_spread = false;   /* NRQ_MAP_SPREAD: deal line groups round-robin instead of block octets per XCD */
-  bool big_wg = false;       /* NRQ_BIG_WG: never use the 256-thread solve variants */
-  bool small_waves4 = true;  /* NRQ_SMALL_WAVES5 clears it: the 256-thread variant compiled for 5 workgroups per CU (96 registers per
-                              * thread) is used where five images fit; since the row pipeline forms its addresses ahead of the LDS wait the
-                              * 4-workgroup one (128 registers) is faster there: K=1000 930 -> 980 Gbit/s */
-  bool prof = false;         /* NRQ_PROF: per-phase shader-clock marks, printed to stderr */
-  bool diag = false;         /* NRQ_DIAG: why a block was reported not decodable, to stderr */
-  bool plan_lds_max = false; /* NRQ_PLAN_LDS_MAX: planner always takes the whole LDS */
-  bool plan_big_wg = false;  /* NRQ_PLAN_BIG_WG: planner always 1024 threads */
-  uint32_t small_div = 2;    /* NRQ_SMALL_DIV: LDS images per CU from which the 256-thread variant is used (measured: 2 beats 3) */
-  uint64_t solve_grid = 0;   /* NRQ_SOLVE_GRID: persistent workgroups of the solve launch (0 = fill the device) */
-  uint32_t max_wb = 16;      /* NRQ_MAX_WB: widest strip considered */
-  bool no_wb12 = false;      /* NRQ_NO_WB12: strip widths 16, 8, 4, 2 only (round 5's set) */
-  bool tiny_any = false;      /* "tiny_any" / NRQ_TINY_ANY: the solve's throughput forms whatever the launch size (tests): single-wave workgroups also for a
-                               * few hundred strips, 256-thread ones also for a lone mid-size block */
-  bool plan_pack = false;     /* NRQ_PLAN_PACK: small blocks' planner workgroups share a CU whatever the block count */
-  bool host_plan_auto = true; /* NRQ_HOST_PLAN_AUTO=0: a call of one or two small blocks is planned by the planner kernel like any other */
-  int prof_base = 2;         /* NRQ_PROF_BASE: stamp the free-form marks are measured from */
-  uint32_t encplan_dev_min_l = 12000; /* NRQ_ENCPLAN_DEV_MIN_L: from this many intermediate symbols on, encode plans are built by
-                              * the device planner, asynchronously (the host planner takes 25 ms at K=27000, 95 ms at K'=56403) */
-  uint32_t wide_g = 0;       /* NRQ_WIDE_G: wide strips of G = 2, 4, 8 lanes per element where two such images fit a CU */
-  bool no_wentry = false;    /* NRQ_NO_WENTRY: big blocks' entry pass by the planner workgroup itself, not by nrq_wentry_kernel */
-  bool no_tiny = false;      /* NRQ_NO_TINY: no single-wave workgroups for tiny strip images */
-  uint32_t tiny_div = 7;     /* NRQ_TINY_DIV: LDS images per CU from which the single-wave variant is used (launches with ONE plan: encode).
-                              * (Twelve until the workgroups per CU were counted by allocated LDS, lds_alloc(): between eight and
-                              * eleven images the ninth.. workgroup of a CU had run as a second round and the variant looked slow;
-                              * with the count right it wins from seven on -- K=450 +22 %, K=500 +14 %, K=600 +12 %, K=700 +2 %.) */
-  uint32_t tiny_div_dec = 7; /* NRQ_TINY_DIV_DEC: the same for launches with a plan per block (decode): every strip walks a plan of its own
-                              * through L2 / HBM, and more independent strips in flight hide more of those trips.  (Seven: at six
-                              * images per CU -- K=1000 once its plans have a few inactive columns fewer -- the single waves lose to
-                              * the 256-thread workgroups, decode 11.1 against 7.4 ms per 2048 blocks; at seven, K=700, they win 5.2 : 6.2.) */
-  bool no_split = false;     /* NRQ_NO_SPLIT: narrow strips also do their back-substitution in the solve kernel */
-  bool no_balance = false;   /* NRQ_NO_BALANCE: keep whole-line work slots even when the rounds come out uneven */
-  uint32_t lds_max = NRQ_LDS_MAX; /* "lds_max" (tests): LDS bytes a strip image may take when the batch's block lists are formed (pick_and_launch) */
-  bool no_lists = false;     /* NRQ_NO_LISTS: one solve launch per batch at the width EVERY block fits (round 5), no second list */
-  int reserve_cus = -1;      /* NRQ_RESERVE_CUS: compute units a big-block solve launch leaves to the planner (-1 = automatic) */
-  bool plan_small_state = true;  /* NRQ_PLAN_BIG_STATE clears it: small blocks' planner workgroups keep the full-size queues */
-  bool plan_split_force = false; /* "plan_split_force": every block planned in two parts + helper kernels (tests) */
-  bool no_plan_split = false;  /* NRQ_NO_PLAN_SPLIT: big blocks planned by one kernel (no helper kernels for the HDPC fold / W transposition) */
-  bool no_plan_stream = false; /* NRQ_NO_PLAN_STREAM: planner kernel on the caller's stream (no overlap with the solve before it) */
-  bool tx_dword = false;       /* "tx_dword" (A/B runs): the emit kernels' 4-byte path also where the 16-byte one applies */
-  bool plan_no_wg128 = false;  /* NRQ_PLAN_NO_WG128: the smallest blocks' planner workgroups stay at 256 threads */
-  bool plan_wrong_instance = false; /* "plan_wrong_instance" (tests): blocks whose peeling state fits the LDS are given to the planner instance for
-                                     * the others -- pl_init_a must notice (PL_PEEL_FORM_OK) and the blocks go to the host planner */
-  uint32_t plan_ucap = 0;      /* "plan_ucap": inactive-column capacity of the device planner (0 = P + 768, at most 1280); tests lower it
-                                * to send blocks through the capacity fallback (host re-plan) */
-  void read() {
-    auto flag = [](const char *n) { const char *e = getenv(n); return e != nullptr; };
-    auto num = [](const char *n, long long d) { const char *e = getenv(n); return (e && *e) ? atoll(e) : d; };
-    map_spread = flag("NRQ_MAP_SPREAD"); big_wg = flag("NRQ_BIG_WG"); small_waves4 = !flag("NRQ_SMALL_WAVES5");
-    prof = flag("NRQ_PROF"); diag = flag("NRQ_DIAG"); plan_lds_max = flag("NRQ_PLAN_LDS_MAX"); plan_big_wg = flag("NRQ_PLAN_BIG_WG");
-    small_div = (uint32_t)num("NRQ_SMALL_DIV", 2); solve_grid = (uint64_t)num("NRQ_SOLVE_GRID", 0);
-    max_wb = (uint32_t)num("NRQ_MAX_WB", 16); prof_base = (int)num("NRQ_PROF_BASE", 2);
-    encplan_dev_min_l = (uint32_t)num("NRQ_ENCPLAN_DEV_MIN_L", 12000);
-    wide_g = (uint32_t)num("NRQ_WIDE_G", 0);
-    if (wide_g != 2u && wide_g != 4u && wide_g != 8u) wide_g = 0;
-    no_wentry = flag("NRQ_NO_WENTRY"); no_tiny = flag("NRQ_NO_TINY"); tiny_div = (uint32_t)num("NRQ_TINY_DIV", 7); tiny_div_dec = (uint32_t)num("NRQ_TINY_DIV_DEC", 7);
-    no_split = flag("NRQ_NO_SPLIT"); no_balance = flag("NRQ_NO_BALANCE"); no_lists = flag("NRQ_NO_LISTS"); no_wb12 = flag("NRQ_NO_WB12"); host_plan_auto = num("NRQ_HOST_PLAN_AUTO", 1) != 0; plan_pack = flag("NRQ_PLAN_PACK"); tiny_any = flag("NRQ_TINY_ANY"); reserve_cus = (int)num("NRQ_RESERVE_CUS", -1); no_plan_stream = flag("NRQ_NO_PLAN_STREAM");
-    no_plan_split = flag("NRQ_NO_PLAN_SPLIT");
-    plan_small_state = !flag("NRQ_PLAN_BIG_STATE"); plan_no_wg128 = flag("NRQ_PLAN_NO_WG128");
-  }
-};
-
 #define NRQ_PLAN_AHEAD_MAX 2u
 struct PlanRun;
 static void plan_ahead_drop(struct nrq_ctx *ctx);
@@ -1199,7 +1112,7 @@ struct nrq_ctx {
   nrq_call_stats stats;
   Event t0, t1;
   Event encplan_uploaded;
-  bool attr_set[5] = {false, false, false, false, false};
+  uint32_t attr_widths = 0; /* bit WB: the attributes of the solve instances of that strip width are set */
   /* optional per-launch timing of the solve kernel (HIP events on the launch stream) */
   bool ktime_on = false;
   bool ktime_outer = false; /* the solve launches in flight are bracketed by their caller's pair of events */
@@ -1338,17 +1251,18 @@ int block_params(nrq_ctx *ctx, uint32_t K, uint32_t Kp, rq_params *p) {
   return 0;
 }
 
+/* nrq_plan_kernel<NT, compact>: row i is the instance of nrq_plan_keys[i] (launch_shape.h) */
+using plan_fn = void (*)(rq_params, const uint8_t *, const nrq_planjob *, nrq_job *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                         unsigned long long *, uint32_t, uint32_t, uint32_t);
+#define NRQ_PLAN_ROW(NT, PK) &nrq_plan_kernel<(int)NT, PK>,
+static const plan_fn plan_table[] = {NRQ_PLAN_INSTANCES(NRQ_PLAN_ROW)};
+#undef NRQ_PLAN_ROW
+
 /* the planner kernels may own the whole LDS of a CU (also the first touch of the code object: the runtime loads it here) */
 static int plan_attr_once(nrq_ctx *ctx) {
   if (ctx->plan_attr) return 0;
-  HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_plan_kernel<(int)PL_NT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-  HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_plan_kernel<(int)PL_NT, 1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-  HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_plan_kernel<(int)PL_NT_MIN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-  HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_plan_kernel<(int)PL_NT_TINY>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
+  for (const plan_fn fn : plan_table)
+    HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
   HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_mh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)NRQ_LDS_MAX));
   HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_wpass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1373,119 +1287,32 @@ int get_kconst(nrq_ctx *ctx, uint32_t K, KConst **out) {
   return 0;
 }
 
-/* launch geometry of the planner kernel: LDS sizing, workgroup shape (shared by the decode planner and the device
- * build of encode plans) */
-/* Big blocks, whose peeling state does not fit the LDS next to the dense-stage reserve (pl_ctx_setup's rule), run the
- * planner in two parts with helper kernels between and after them (planner_seq.h).  The jobs carry the choice in
- * bit 8 of nrq_planjob::mode (pl_final_c then leaves the W transposition to nrq_wt_kernel). */
-bool plan_is_segmented(const nrq_ctx *ctx, const rq_params &p, uint32_t Mcap) {
-  const uint32_t sh_bytes = pl_shared_bytes(PL_QCAP, PL_LOWCAP, PL_NT), dyn = NRQ_LDS_MAX - sh_bytes;
-  if (ctx->tune.plan_split_force) return true; /* (tests: the segmented path at sizes the oracle checks quickly) */
-  return pl_state_in_lds(p.L, Mcap, dyn) == 0u && !ctx->tune.no_plan_split;
-}
-
-/* the planner form a run launched (nrq_call_stats::plan_wg_threads, plan_compact_state, plan_segmented) */
-struct PlanForm {
-  uint32_t wg_threads = 0, compact = 0, segmented = 0;
-};
-
-int launch_plan_kernel(nrq_ctx *ctx, hipStream_t ps, const rq_params &p, const uint8_t *d_kc, const nrq_planjob *d_pj,
+/* One planner run as plan_shape() decided it (the decode planner and the device build of encode plans): the instance once per
+ * part, the helper kernels of a segmented run between and behind the parts (planner_seq.h). */
+int launch_plan_kernel(nrq_ctx *ctx, hipStream_t ps, const PlanShape &s, const rq_params &p, const uint8_t *d_kc, const nrq_planjob *d_pj,
                        nrq_job *d_jobs, uint32_t nblk, uint32_t Mcap, uint32_t npcap, uint32_t ucap, unsigned long long *pprof,
-                       uint32_t nnzcap, PlanForm *form = nullptr) {
-  /* The workgroup state (pl_shared and the arrays behind it: frontier queues, claim lists, per-thread scratch, Gauss-Jordan
-   * flags) is sized by the launch: 25 KB for big blocks; a small block's frontier and dense stage need a fraction, and
-   * with 8 KB of it four 256-thread planner workgroups share a CU instead of two (the planner is latency bound: twice
-   * the workgroups, half the time).  Overflowing a capacity is reported as such and re-planned on the host. */
-  uint32_t qcap = PL_QCAP, lowcap = PL_LOWCAP;
-  uint32_t sh_bytes = pl_shared_bytes(qcap, lowcap, PL_NT);
-  /* dynamic LDS: everything a CU has for a big block; for small blocks what the planner can use (peeling state plus the
-   * dense-stage reserve, or a 16-byte strip image of the W rows), so that several workgroups share a CU */
-  uint32_t dyn_bytes = NRQ_LDS_MAX - sh_bytes;
-  bool small_wg = false; /* 256-thread workgroups: a small block has no use for 1024 threads, a CU has for 4 blocks */
-  bool tiny_wg = false;  /* 128-thread workgroups (with small_wg) */
-  {
-    const uint32_t peel = 2u * pl_r16(Mcap * 4u) + pl_r16(p.L * 4u) + pl_dense_reserve(p.L);
-    const uint32_t wimg = (Mcap + 320u + NRQ_SCRATCH) * 16u;
-    const uint32_t fit = pl_r16((peel > wimg ? peel : wimg) + 2048u);
-    /* (queues / claim lists / Gauss-Jordan flags: a frontier, a round's claims and the leftover rows are at most the block's rows) */
-    const uint32_t q_s = Mcap <= 248u ? 256u : p.L <= 1500u ? 512u : 1024u, low_s = Mcap <= 248u ? 256u : p.L <= 1500u ? 384u : 768u;
-    const uint32_t sh_s = ctx->tune.plan_small_state ? pl_shared_bytes(q_s, low_s, PL_NT_MIN) : sh_bytes;
-    /* ... when there are more blocks than compute units.  A batch of at most one block per CU gains nothing from sharing: every block
-     * gets the 1024-thread workgroup and the whole LDS (round 6, planner per batch, 256-thread / 1024-thread workgroups: K=500 x 256
-     * blocks 0.55 / 0.39 ms, K=1000 x 256 0.53 / 0.44, K=2500 x 256 0.95 / 0.69, K=2500 x 64 1.15 / 0.79; one block of K=2500 through
-     * the reference's benchmark.c: decode column 24.1 -> 30.8 Gbit/s).  "plan_pack" = 1 packs regardless (tests of the small forms). */
-    const bool pack = nblk > (uint32_t)ctx->ncu || ctx->tune.plan_pack;
-    if (lds_alloc(fit + sh_s) <= NRQ_LDS_MAX / 2u && !ctx->tune.plan_lds_max) {
-      dyn_bytes = fit; /* (also for the 1024-thread workgroup of a small batch: it then leaves LDS and wave slots to a solve running beside it) */
-      small_wg = !ctx->tune.plan_big_wg && pack;
-      if (small_wg && ctx->tune.plan_small_state) { qcap = q_s; lowcap = low_s; sh_bytes = sh_s; }
-      /* The smallest blocks: 128 threads.  A planner phase is one wave's chain of instructions and trips,
-       * the other waves of the workgroup mostly wait; the registers of the kernel (~100) let a CU hold 20 waves -- five
-       * 256-thread workgroups, or as many 128-thread ones as the LDS takes (six or more from here on): more blocks in flight
-       * for the same waves. */
-      const uint32_t sh_t = pl_shared_bytes(q_s, low_s, PL_NT_TINY);
-      if (small_wg && ctx->tune.plan_small_state && !ctx->tune.plan_no_wg128 && lds_alloc(fit + sh_t) * 6u <= NRQ_LDS_MAX) { tiny_wg = true; sh_bytes = sh_t; }
-    }
-  }
-  const bool seg = plan_is_segmented(ctx, p, Mcap);
-  if (seg && ctx->tune.plan_split_force) {
-    /* a segmented run keeps nothing in LDS between its parts: its peeling state must live in the workspace, which
-     * pl_ctx_setup chooses when the dynamic region is too small for it -- so make it too small (dense stage only) */
-    const uint32_t need = 2u * pl_r16(Mcap * 4u) + pl_r16(p.L * 4u);
-    uint32_t only_dense = (pl_dense_reserve(p.L) + need - 16u) & ~15u; /* 16 bytes short of holding the peeling state */
-    if (only_dense < dyn_bytes) dyn_bytes = only_dense;
-    if (pl_state_in_lds(p.L, Mcap, dyn_bytes) != 0u) dyn_bytes = (need - 16u) & ~15u; /* (... also for the form that shares the rowstate image) */
-    small_wg = false; tiny_wg = false;
-    qcap = PL_QCAP; lowcap = PL_LOWCAP; sh_bytes = pl_shared_bytes(qcap, lowcap, PL_NT);
-  }
-  const uint32_t mh_dyn = 72u * 1024u; /* nrq_mh_kernel: MhT (16 B x u <= 20 KB) + the tiles (4 KB + 256 x wpr words <= 40 KB) */
+                       uint32_t nnzcap) {
   { int rc_ = plan_attr_once(ctx); if (rc_) return rc_; }
-  /* parts of the run: everything | 3, (entry pass), 4, (W pass, HDPC fold), 2 */
-  const bool wentry = seg && !ctx->tune.no_wentry;
-  const uint32_t parts_seg[3] = {wentry ? 3u : 1u, wentry ? 4u : 2u, 2u};
-  const uint32_t nparts_run = !seg ? 1u : wentry ? 3u : 2u;
-  for (uint32_t pi = 0; pi < nparts_run; pi++) {
-    const uint32_t part = seg ? parts_seg[pi] : 0u;
-    const bool hbm_state = pl_state_in_lds(p.L, Mcap, dyn_bytes) == 0u; /* (pl_ctx_setup's rule) */
-    if (part && (tiny_wg || small_wg || !hbm_state)) return fail(ctx, -2, "planner: a segmented run needs the instance for big blocks");
-    if (form) {
-      form->wg_threads = tiny_wg ? (uint32_t)PL_NT_TINY : small_wg ? (uint32_t)PL_NT_MIN : (uint32_t)PL_NT;
-      form->compact = !tiny_wg && !small_wg && (hbm_state || ctx->tune.plan_wrong_instance) ? 1u : 0u;
-      form->segmented = seg ? 1u : 0u;
-    }
-    if (tiny_wg)
-      hipLaunchKernelGGL(nrq_plan_kernel<(int)PL_NT_TINY>, dim3(nblk), dim3(PL_NT_TINY), dyn_bytes + sh_bytes, ps, p, d_kc, d_pj, d_jobs,
-                         nblk, Mcap, npcap, ucap, dyn_bytes, pprof, part, qcap, lowcap);
-    else if (small_wg)
-      hipLaunchKernelGGL(nrq_plan_kernel<(int)PL_NT_MIN>, dim3(nblk), dim3(PL_NT_MIN), dyn_bytes + sh_bytes, ps, p, d_kc, d_pj, d_jobs,
-                         nblk, Mcap, npcap, ucap, dyn_bytes, pprof, part, qcap, lowcap);
-    else if (hbm_state || ctx->tune.plan_wrong_instance) /* (the state stays in HBM) */
-      hipLaunchKernelGGL((nrq_plan_kernel<(int)PL_NT, 1>), dim3(nblk), dim3(PL_NT), dyn_bytes + sh_bytes, ps, p, d_kc, d_pj, d_jobs, nblk,
-                         Mcap, npcap, ucap, dyn_bytes, pprof, part, qcap, lowcap);
-    else
-      hipLaunchKernelGGL(nrq_plan_kernel<(int)PL_NT>, dim3(nblk), dim3(PL_NT), dyn_bytes + sh_bytes, ps, p, d_kc, d_pj, d_jobs, nblk,
-                         Mcap, npcap, ucap, dyn_bytes, pprof, part, qcap, lowcap);
+  if (s.err) return fail(ctx, -2, "planner: a segmented run needs the instance for big blocks");
+  const int inst = plan_key_index(s.wg_threads, s.compact);
+  if (inst < 0) return fail(ctx, -2, "planner: no instance nrq_plan_kernel<%u, %u>", s.wg_threads, s.compact);
+  for (uint32_t pi = 0; pi < s.nparts; pi++) {
+    const uint32_t part = s.parts[pi];
+    hipLaunchKernelGGL(plan_table[inst], dim3(nblk), dim3(s.wg_threads), s.dyn_bytes + s.sh_bytes, ps, p, d_kc, d_pj, d_jobs, nblk, Mcap,
+                       npcap, ucap, s.dyn_bytes, pprof, part, s.qcap, s.lowcap);
     HIPCHK(ctx, hipGetLastError());
     if (part == 3u) {
-      uint32_t nw = 64u / (nblk ? nblk : 1u); /* workgroups per block: what a batch of few big blocks finds free beside the solves */
-      if (nw < 2u) nw = 2u;
-      if (nw > 8u) nw = 8u;
-      hipLaunchKernelGGL(nrq_wentry_kernel, dim3(nw, nblk), dim3(1024), sh_bytes, ps, p, d_kc, d_pj, Mcap, npcap, ucap, dyn_bytes);
+      hipLaunchKernelGGL(nrq_wentry_kernel, dim3(s.wentry_wgs, nblk), dim3(1024), s.sh_bytes, ps, p, d_kc, d_pj, Mcap, npcap, ucap, s.dyn_bytes);
       HIPCHK(ctx, hipGetLastError());
     }
     if (part == 1u || part == 4u) {
-      const uint32_t wp_lds = (Mcap + NRQ_SCRATCH) * 2u + 64u;
-      hipLaunchKernelGGL(nrq_wpass_kernel, dim3(((ucap + 31u) / 32u) * 2u, nblk), dim3(256), wp_lds, ps, p, d_kc, d_pj, Mcap, npcap, ucap);
+      hipLaunchKernelGGL(nrq_wpass_kernel, dim3(s.wpass_wgs, nblk), dim3(256), s.wpass_lds, ps, p, d_kc, d_pj, Mcap, npcap, ucap);
       HIPCHK(ctx, hipGetLastError());
-      /* the HDPC fold: as many workgroups per block as leave the whole batch ~256 */
-      uint32_t nparts = 256u / (nblk ? nblk : 1u);
-      if (nparts < 1u) nparts = 1u;
-      if (nparts > 64u) nparts = 64u;
-      hipLaunchKernelGGL(nrq_mh_kernel, dim3(nparts, nblk), dim3(1024), mh_dyn + sh_bytes, ps, p, d_kc, d_pj, Mcap, npcap, ucap, mh_dyn);
+      hipLaunchKernelGGL(nrq_mh_kernel, dim3(s.mh_wgs, nblk), dim3(1024), s.mh_dyn + s.sh_bytes, ps, p, d_kc, d_pj, Mcap, npcap, ucap, s.mh_dyn);
       HIPCHK(ctx, hipGetLastError());
     }
   }
-  if (seg) {
+  if (s.segmented) {
     hipLaunchKernelGGL(nrq_wt_kernel, dim3(64, nblk), dim3(256), 0, ps, d_pj, p.L, Mcap, npcap, ucap, nnzcap);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -1567,11 +1394,12 @@ int encplan_device_launch(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *
   pj->work = (uint64_t)(uintptr_t)ctx->encplan_work.p;
   pj->arena = (uint64_t)(uintptr_t)ep.devbuf[buf].p;
   pj->arena_cap = arena_cap;
-  pj->mode = 1u | (plan_is_segmented(ctx, p, Mcap) ? (ctx->tune.no_wentry ? 0x100u : 0x300u) : 0u);
+  const PlanShape shape = plan_shape(ctx->tune, ctx->ncu, p, 1u, Mcap, ucap);
+  pj->mode = 1u | shape.mode;
   HIPCHK(ctx, hipMemcpyAsync(ep.devbuf[buf].p + off_pj, pj, sizeof(*pj), hipMemcpyHostToDevice, ps));
   rq_params pk = p;
   pk.K = K;
-  if ((rc = launch_plan_kernel(ctx, ps, pk, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ep.devbuf[buf].p + off_pj),
+  if ((rc = launch_plan_kernel(ctx, ps, shape, pk, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ep.devbuf[buf].p + off_pj),
                                reinterpret_cast<nrq_job *>(ep.devbuf[buf].p + off_job), 1u, Mcap, npcap, ucap, nullptr,
                                kh->nnz + npcap * PL_PATCH_STRIDE)))
     return rc;
@@ -1653,192 +1481,80 @@ void build_out_lists(const rq_params &p, const uint16_t *colslot, uint32_t n, co
   cptr[n] = (uint32_t)cols.size();
 }
 
-template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, uint32_t nblk, uint32_t T,
-                                const uint8_t *d_kc, uint32_t lds_bytes, uint32_t max_slots, uint32_t max_out, uint32_t max_u,
-                                uint32_t max_wpr, const std::vector<const nrq_plan_hdr *> &hdrs, bool io_aligned) {
-  /* WIDE strips (G lanes per element, 16 * G bytes per strip; solve_body.h) -- an experiment for small blocks, whose levels
-   * hold a dozen ops and whose HDPC / dense phases a dozen rows, so that most lanes of a wave idle through them on a
-   * 16-byte strip.  Measured (K=100 / 500 / 1000, G = 8 / 4 / 2, two or three 256-thread workgroups per CU): 270-313 /
-   * 600-619 / 727-731 Gbit/s against 326 / 613 / 881 with 16-byte strips: the LDS holds the same number of symbol bytes
-   * either way, a strip's chain of phases is no shorter for being wider, and G x fewer virtual threads make its
-   * per-thread loops longer.  Not selected automatically; NRQ_WIDE_G / "wide_g" forces it (tests keep it correct). */
-  uint32_t G = 1;
-  if (WB == 16 && ctx->tune.wide_g > 1u && T >= 16u * ctx->tune.wide_g) {
-    uint32_t need = 0;
-    for (const nrq_plan_hdr *h : hdrs)
-      if (!h->status) { const uint32_t t = nrq_lds_plan(h, 16u * ctx->tune.wide_g).total; if (t > need) need = t; }
-    if (lds_alloc(need) * 2u <= NRQ_LDS_MAX) { G = ctx->tune.wide_g; lds_bytes = need; }
+/* nrq_solve_kernel<WB, NT, WV, G, AL>: row i is the instance of nrq_solve_keys[i] (launch_shape.h) */
+using solve_fn = void (*)(const nrq_job *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t *, uint8_t *, uint32_t,
+                          uint32_t, unsigned long long *, uint8_t *, size_t);
+#define NRQ_SOLVE_ROW(WB, NT, WV, G, AL) &nrq_solve_kernel<WB, NT, WV, G, AL>,
+static const solve_fn solve_table[] = {NRQ_SOLVE_INSTANCES(NRQ_SOLVE_ROW)};
+#undef NRQ_SOLVE_ROW
+
+/* One solve launch: the blocks of d_jobs at strip width wb, as solve_shape() decides it -- buffers, attributes, the instance the
+ * shape names, the two kernels that finish a split solve, the profile, the call's stats. */
+static int launch_solve(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs, const nrq_job *d_jobs, uint32_t nblk,
+                        uint32_t T, const uint8_t *d_kc, uint32_t max_out, uint32_t wb, uint32_t need, bool io_aligned) {
+  SolveIn in;
+  in.wb = wb; in.nblk = nblk; in.T = T; in.lds_bytes = need; in.max_out = max_out; in.io_aligned = io_aligned;
+  in.hdrs = hdrs.data(); in.nhdrs = hdrs.size();
+  for (const nrq_plan_hdr *h : hdrs) {
+    if (h->status) continue;
+    if (h->M > in.max_slots) in.max_slots = h->M;
+    if (h->u > in.max_u) in.max_u = h->u;
+    if (h->wpr > in.max_wpr) in.max_wpr = h->wpr;
   }
-  const uint32_t WBE = WB * G;
-  /* narrow strips: the solve kernel stops after the dense stage, nrq_backsub_kernel / nrq_collect_kernel finish on
-   * full-width rows of a per-block work buffer (see there) */
-  const bool split = WB <= 4 && !ctx->tune.no_split;
-  const uint32_t res_elems = max_out; /* rows nrq_collect_kernel writes per block at most */
-  if (split) max_out = max_slots + max_u;
-  const uint32_t nstrips = (T + WBE - 1) / WBE, spl = nrq_group_strips(WBE);
-  const bool by_block = nrq_map_by_block(nblk) && !ctx->tune.map_spread;
-  /* workgroup shape: the full-size workgroup when a strip image needs more than half of the CU's LDS, 256-thread ones
-   * when two or more fit */
-  /* (a launch whose strips each get a CU of their own -- a lone block of the reference's harness -- takes the full-size workgroup from
-   * K ~ 1200 on: encode column of benchmark.c K=1500 208 -> 225 Gbit/s, K=3000 294 -> 315, K=4000 313 -> 333; below, the same) */
-  const bool lone = (uint64_t)nblk * ((T + WB - 1) / WB) <= (uint64_t)ctx->ncu && max_slots >= 1200u && !ctx->tune.tiny_any;
-  const bool small = WB != 12 && lds_alloc(lds_bytes) * ctx->tune.small_div <= NRQ_LDS_MAX && !ctx->tune.big_wg && !lone; /* (12-byte strips: big blocks) */
-  /* single-wave workgroups when 12 or more images fit a CU (see the kernel; K=256: +26 % over five 256-thread workgroups) */
-  const uint32_t tdiv = hdrs.size() > 1u ? ctx->tune.tiny_div_dec : ctx->tune.tiny_div;
-  /* ... and when the launch has the strips to fill them: a lone block's 80 strips each get a 256-thread workgroup and a CU of their own
-   * (the reference's benchmark.c, one block per call, K=500: encode column 81 -> 106 Gbit/s without the single-wave form; from ~1000
-   * strips on -- 16 blocks of K=500 -- the single-wave form is the faster one again: 0.07 against 0.09 ms) */
-  const bool tiny = G == 1 && small && (uint64_t)lds_alloc(lds_bytes) * tdiv <= NRQ_LDS_MAX && !ctx->tune.no_tiny &&
-                    ((uint64_t)nblk * nstrips > 2u * (uint64_t)ctx->ncu || ctx->tune.tiny_any);
-  const uint32_t nt = tiny ? 64u : small ? 256u : (uint32_t)NRQ_WG;
-  uint32_t occ = NRQ_LDS_MAX / lds_alloc(lds_bytes ? lds_bytes : 1u);
-  if (occ > 2048u / nt) occ = 2048u / nt;
-  /* registers: the 256-thread variant (one wave per SIMD) is compiled for NRQ_SMALL_WAVES waves per SIMD.  More
-   * workgroups than are resident at once would run as a second, thinner round of a statically partitioned job. */
-  const bool five = G == 1 && small && !tiny && occ >= 5u && !ctx->tune.small_waves4;
-  if (tiny) { if (occ > NRQ_TINY_OCC) occ = NRQ_TINY_OCC; } /* one wave per workgroup, compiled for 5 waves per SIMD; 20 per CU by the LDS sum, but
-                                              * measured: with 20 x 256 workgroups not all are resident and the rest runs as a second
-                                              * round (10.4 ms against 8.7 ms with 18 x 256 at K=100, T=1024, 8192 blocks) */
-  else if (small && occ > (five ? 5u : (uint32_t)NRQ_SMALL_WV)) occ = five ? 5u : (uint32_t)NRQ_SMALL_WV;
-  if (tiny && ctx->tune.diag) fprintf(stderr, "[NRQ_DIAG] single-wave workgroups: %u bytes of LDS each, %u per CU\n", lds_bytes, occ);
-  if (occ < 1u) occ = 1u;
-  /* persistent workgroups fill the device; a multiple of 8 keeps a workgroup's slots on its XCD */
-  uint64_t grid = (uint64_t)(ctx->ncu / 8) * 8 * occ;
-  /* A batch of few big blocks: leave a compute unit per block (one per XCD at least) to the planner workgroups of the
-   * decode that follows or runs beside this launch on the context's planner stream (decode_device) -- a planner
-   * workgroup needs a whole CU's LDS, and the persistent workgroups of this launch would otherwise hold every CU until
-   * they are all done.  ~3 % of the solve's throughput for 8 blocks; the planner (one workgroup per block, latency
-   * bound: 12 ms at K=27000, 36 ms at K'=56403) then hides behind the encode solve. */
-  if (!small && occ == 1u) {
-    /* (with planner runs issued ahead -- nrq_decode_plan_ahead -- up to `ahead_hint` batches' planner workgroups are resident at
-     * once, and the encode plan of a big block is built by one more workgroup on a stream of its own: without a compute unit
-     * for each of them one waits until this launch's persistent workgroups are through, and its 20-30 ms start from there) */
-    const uint32_t runs = ctx->ahead_hint > 1u ? ctx->ahead_hint : 1u;
-    uint32_t reserve = ctx->tune.reserve_cus >= 0 ? (uint32_t)ctx->tune.reserve_cus : (nblk <= 16u ? (nblk * runs + 1u + 7u) / 8u * 8u : 0u);
-    if (reserve + 64u <= grid) grid -= reserve / 8u * 8u;
-  }
-  if (ctx->tune.solve_grid) grid = ctx->tune.solve_grid / 8 * 8;
-  if (grid < 8) grid = 8;
-  /* work slots (nrq_map_group): `sub` strips of a block each -- the strips of a whole line unless that would leave
-   * workgroups idle -- incl. the empty slots of a partial block octet */
-  uint32_t lsub = 0;
-  while ((1u << lsub) < spl) lsub++;
-  auto slots_for = [&](uint32_t ls) -> uint64_t {
-    const uint32_t sub = 1u << ls, spb = (nstrips + sub - 1) / sub;
-    return by_block ? (uint64_t)((nblk + 7u) / 8u) * 8u * spb : (uint64_t)nblk * spb;
-  };
-  while (lsub > 0 && slots_for(lsub) < grid) lsub--;
+  const SolveShape s = solve_shape(ctx->tune, ctx->ncu, ctx->ahead_hint, in);
+  if (s.err == SHAPE_GRID_TOO_LARGE) return fail(ctx, -4, "grid too large");
+  if (s.key.NT == 64 && ctx->tune.diag) fprintf(stderr, "[NRQ_DIAG] single-wave workgroups: %u bytes of LDS each, %u per CU\n", s.lds_bytes, s.occ);
+  const int inst = solve_key_index(s.key);
+  if (inst < 0)
+    return fail(ctx, -2, "no solve kernel instance <%d, %d, %d, %d, %s>", s.key.WB, s.key.NT, s.key.WV, s.key.G, s.key.AL ? "true" : "false");
   {
-    /* Work is dealt statically (workgroup g takes slots g, g + grid, ...): with few big blocks the rounds do not come
-     * out even -- K'=56403, 8 blocks: 320 whole-line slots on 256 workgroups is two rounds for a quarter of them, 32
-     * strips against 20 on average.  Smaller slots even that out; what they cost is gather efficiency (pieces shorter
-     * than a 128-byte line), which matters for wide strips only: a 2- or 4-byte strip is solved at the same cost per
-     * strip as a 16-byte one, so its data movement is an eighth or a quarter of the time share. */
-    auto max_strips = [&](uint32_t ls) -> uint64_t {
-      const uint64_t ns = slots_for(ls), g = grid < ns ? grid : ns;
-      return ((ns + g - 1) / g) << ls;
-    };
-    const uint32_t min_ls = WB >= 8 ? (lsub < 2u ? lsub : 2u) : 0u;
-    uint32_t best = lsub;
-    for (uint32_t ls = lsub; ls-- > min_ls;)
-      if (max_strips(ls) * 100u < max_strips(best) * 93u) best = ls;
-    if (!ctx->tune.no_balance) lsub = best;
-  }
-  const uint64_t nslots = slots_for(lsub);
-  if (nslots > 0x7FFFFFFFull) return fail(ctx, -4, "grid too large");
-  if (grid > nslots) grid = by_block ? (nslots + 7) / 8 * 8 : nslots;
-  /* per workgroup: two sets of `spl` input staging buffers (the line group being solved, the one being gathered)
-   * and two sets of `spl` output staging buffers (the group being solved, the one being scattered) */
-  const uint32_t stage_stride = (max_slots * WBE + 255u) & ~255u, ostage_stride = (max_out * WBE + 255u) & ~255u;
-  {
-    int rc_ = ensure_dev(ctx, ctx->stage, (size_t)grid * 2u * spl * ((size_t)stage_stride + ostage_stride));
+    int rc_ = ensure_dev(ctx, ctx->stage, s.stage_bytes());
     if (rc_) return rc_;
   }
-  size_t ybuf_stride = 0;
   uint8_t *ybuf = nullptr;
-  if (split) {
-    ybuf_stride = ((size_t)(max_slots + max_u) * T + 255u) & ~(size_t)255u;
-    int rc_ = ensure_dev(ctx, ctx->ybuf, (size_t)nblk * ybuf_stride);
+  if (s.split) {
+    int rc_ = ensure_dev(ctx, ctx->ybuf, (size_t)nblk * s.ybuf_stride);
     if (rc_) return rc_;
     ybuf = ctx->ybuf.p;
   }
-  if (!ctx->attr_set[slot]) {
+  if (!(ctx->attr_widths >> wb & 1u)) { /* first launch at this width: its instances (and the back-substitution kernels) may own the LDS */
     HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_backsub_kernel<32>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
     HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_backsub_kernel<16>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-#define NRQ_SET_LDS_ATTR(...)                                                                                                              \
-    HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_solve_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)NRQ_LDS_MAX))
-    NRQ_SET_LDS_ATTR(WB, NRQ_WG, 1, 1, false); NRQ_SET_LDS_ATTR(WB, NRQ_WG, 1, 1, true);
-    if constexpr (WB != 12) {
-    NRQ_SET_LDS_ATTR(WB, 256, NRQ_SMALL_WV, 1, false);    NRQ_SET_LDS_ATTR(WB, 256, NRQ_SMALL_WV, 1, true);
-    NRQ_SET_LDS_ATTR(WB, 256, 5, 1, false);    NRQ_SET_LDS_ATTR(WB, 256, 5, 1, true);
-    NRQ_SET_LDS_ATTR(WB, 64, NRQ_TINY_WV, 1, false);     NRQ_SET_LDS_ATTR(WB, 64, NRQ_TINY_WV, 1, true);
-    }
-#undef NRQ_SET_LDS_ATTR
-    if constexpr (WB == 16) {
-      HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_solve_kernel<16, 256, 4, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-      HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_solve_kernel<16, 256, 4, 4>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-      HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&nrq_solve_kernel<16, 256, 4, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)NRQ_LDS_MAX));
-    }
-    ctx->attr_set[slot] = true;
+    for (int i = 0; i < nrq_solve_nkeys; i++)
+      if (nrq_solve_keys[i].WB == (int)wb)
+        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(solve_table[i]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)NRQ_LDS_MAX));
+    ctx->attr_widths |= 1u << wb;
   }
   hipEvent_t ev1 = nullptr;
   if (ctx->ktime_on && !ctx->ktime_outer) { /* (ktime_outer: pick_and_launch brackets the launches of both block lists itself) */
     int rc_ = timing_pair(ctx, ctx->ktime_pool, ctx->ktime_used, ctx->stream, &ev1);
     if (rc_) return rc_;
   }
-  const uint32_t nprof = (uint32_t)((grid + 15) / 16);
+  const uint32_t nprof = (s.grid + 15u) / 16u;
   DevBuf prof; /* NRQ_PROF=1: the workgroups' shader-clock marks, for the length of this launch */
   if (ctx->tune.prof) {
     HIPCHK(ctx, hipMalloc((void **)&prof.p, (size_t)nprof * 16 * 8));
     HIPCHK(ctx, hipMemsetAsync(prof.p, 0, (size_t)nprof * 16 * 8, ctx->stream));
   }
   unsigned long long *const d_prof = reinterpret_cast<unsigned long long *>(prof.p);
-#define NRQ_LAUNCH_WIDE(GG)                                                                                                          \
-  hipLaunchKernelGGL((nrq_solve_kernel<16, 256, 4, GG>), dim3((uint32_t)grid), dim3(256), lds_bytes, ctx->stream, d_jobs, nblk, T, nstrips, \
-                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, d_prof,        \
-                     ybuf, ybuf_stride)
-  if (WB == 16 && G == 8) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(8); }
-  else if (WB == 16 && G == 4) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(4); }
-  else if (WB == 16 && G == 2) { if constexpr (WB == 16) NRQ_LAUNCH_WIDE(2); }
-  else {
-    /* (the movers' aligned-only form; 12-byte strips: whole dwords, solve_body.h g_get_al12) */
-    const bool al = io_aligned && G == 1 && WB >= 4 && T % (uint32_t)(WB == 12 ? 4 : WB) == 0u;
-#define NRQ_LAUNCH(NTT, WVV, ALL)                                                                                                        \
-  hipLaunchKernelGGL((nrq_solve_kernel<WB, NTT, WVV, 1, ALL>), dim3((uint32_t)grid), dim3(NTT), lds_bytes, ctx->stream, d_jobs, nblk, T, nstrips, \
-                     by_block ? 1u : 0u, (uint32_t)nslots, lsub, d_kc, (uint8_t *)ctx->stage.p, stage_stride, ostage_stride, d_prof, ybuf,      \
-                     ybuf_stride)
-    if constexpr (WB == 12) { if (al) NRQ_LAUNCH(NRQ_WG, 1, true); else NRQ_LAUNCH(NRQ_WG, 1, false); }
-    else if (tiny) { if (al) NRQ_LAUNCH(64, NRQ_TINY_WV, true); else NRQ_LAUNCH(64, NRQ_TINY_WV, false); }
-    else if (five) { if (al) NRQ_LAUNCH(256, 5, true); else NRQ_LAUNCH(256, 5, false); }
-    else if (small) { if (al) NRQ_LAUNCH(256, NRQ_SMALL_WV, true); else NRQ_LAUNCH(256, NRQ_SMALL_WV, false); }
-    else { if (al) NRQ_LAUNCH(NRQ_WG, 1, true); else NRQ_LAUNCH(NRQ_WG, 1, false); }
-#undef NRQ_LAUNCH
-    ctx->stats.movers_aligned = al ? 1u : 0u;
-  }
+  hipLaunchKernelGGL(solve_table[inst], dim3(s.grid), dim3((uint32_t)s.key.NT), s.lds_bytes, ctx->stream, d_jobs, nblk, T, s.nstrips,
+                     s.by_block ? 1u : 0u, s.nslots, s.lsub, d_kc, (uint8_t *)ctx->stage.p, s.stage_stride, s.ostage_stride, d_prof, ybuf,
+                     s.ybuf_stride);
+  if (s.key.G == 1) ctx->stats.movers_aligned = s.key.AL ? 1u : 0u; /* (a wide-strip launch leaves it as the call's reset gave it) */
   HIPCHK(ctx, hipGetLastError());
-  uint32_t backsub_strip = 0;
-  if (split) {
-    /* 32-byte strips while the tables (4 KiB per W word) leave room for two workgroups per CU, 16-byte strips beyond */
-    const bool wide = max_wpr <= 20u;
-    const uint32_t sb = wide ? 32u : 16u, nsb = (T + sb - 1u) / sb, tbl = max_wpr * 8u * 16u * sb;
-    if (tbl > NRQ_LDS_MAX) return fail(ctx, -5, "back-substitution tables do not fit the LDS (wpr=%u)", max_wpr);
-    uint32_t nchunks = (2048u + nsb * nblk - 1u) / (nsb * nblk);
-    if (nchunks < 1u) nchunks = 1u;
-    if (nchunks > 16u) nchunks = 16u;
-    backsub_strip = sb;
-    if (wide)
-      hipLaunchKernelGGL(nrq_backsub_kernel<32>, dim3(nsb, nchunks, nblk), dim3(256), tbl, ctx->stream, d_jobs, T, ybuf, ybuf_stride, nchunks);
+  if (s.split) {
+    if (s.err == SHAPE_BACKSUB_TABLES) return fail(ctx, -5, "back-substitution tables do not fit the LDS (wpr=%u)", in.max_wpr);
+    const dim3 bgrid(s.backsub_nsb, s.nchunks, nblk);
+    if (s.backsub_strip == 32u)
+      hipLaunchKernelGGL(nrq_backsub_kernel<32>, bgrid, dim3(256), s.backsub_tbl, ctx->stream, d_jobs, T, ybuf, s.ybuf_stride, s.nchunks);
     else
-      hipLaunchKernelGGL(nrq_backsub_kernel<16>, dim3(nsb, nchunks, nblk), dim3(256), tbl, ctx->stream, d_jobs, T, ybuf, ybuf_stride, nchunks);
+      hipLaunchKernelGGL(nrq_backsub_kernel<16>, bgrid, dim3(256), s.backsub_tbl, ctx->stream, d_jobs, T, ybuf, s.ybuf_stride, s.nchunks);
     HIPCHK(ctx, hipGetLastError());
-    if (res_elems) {
-      hipLaunchKernelGGL(nrq_collect_kernel, dim3(res_elems, nblk), dim3(256), 0, ctx->stream, d_jobs, T, (const uint8_t *)ybuf, ybuf_stride);
+    if (s.res_elems) {
+      hipLaunchKernelGGL(nrq_collect_kernel, dim3(s.res_elems, nblk), dim3(256), 0, ctx->stream, d_jobs, T, (const uint8_t *)ybuf, s.ybuf_stride);
       HIPCHK(ctx, hipGetLastError());
     }
   }
@@ -1857,7 +1573,7 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
       tot += (double)(q[8] - q[0]);
       cnt++;
     }
-    fprintf(stderr, "[NRQ_PROF] WB=%d grid=%llu sampled=%u total=%.0f clk:", WB, (unsigned long long)grid, cnt,
+    fprintf(stderr, "[NRQ_PROF] WB=%u grid=%llu sampled=%u total=%.0f clk:", wb, (unsigned long long)s.grid, cnt,
             cnt ? tot / cnt : 0.0);
     for (int k = 0; k < 8; k++) fprintf(stderr, " %s=%.0f", names[k], cnt ? sum[k] / cnt : 0.0);
     /* slots 9..15: free-form marks a phase may leave through StripCtx::dbg (differences to the phase start) */
@@ -1871,91 +1587,32 @@ template <int WB> int launch_wb(nrq_ctx *ctx, int slot, const nrq_job *d_jobs, u
     for (int k = 0; k < 7; k++) fprintf(stderr, " %.0f", cnt ? ext[k] / cnt : 0.0);
     fprintf(stderr, "\n");
   }
-  ctx->stats.strip_bytes = WBE;
-  ctx->stats.lds_bytes = lds_bytes;
-  ctx->stats.grid = (uint32_t)grid;
-  ctx->stats.wg_threads = nt;
-  ctx->stats.strips_per_slot = 1u << lsub;
-  ctx->stats.wg_waves_per_simd = tiny ? (uint32_t)NRQ_TINY_WV : five ? 5u : small ? (uint32_t)NRQ_SMALL_WV : 1u;
-  ctx->stats.backsub_strip = backsub_strip;
+  ctx->stats.strip_bytes = wb * (uint32_t)s.key.G;
+  ctx->stats.lds_bytes = s.lds_bytes;
+  ctx->stats.grid = s.grid;
+  ctx->stats.wg_threads = s.wg_threads;
+  ctx->stats.strips_per_slot = 1u << s.lsub;
+  ctx->stats.wg_waves_per_simd = s.wg_waves;
+  ctx->stats.backsub_strip = s.backsub_strip;
   return 0;
 }
 
-/* widest strip whose LDS image fits for every plan header in hdrs */
-static int launch_list(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs, const nrq_job *d_jobs, uint32_t nblk,
-                       uint32_t T, const uint8_t *d_kc, uint32_t max_out, uint32_t wb, uint32_t need, bool io_aligned) {
-  uint32_t max_slots = 0, max_u = 0, max_wpr = 0;
-  for (const nrq_plan_hdr *h : hdrs) {
-    if (h->status) continue;
-    if (h->M > max_slots) max_slots = h->M;
-    if (h->u > max_u) max_u = h->u;
-    if (h->wpr > max_wpr) max_wpr = h->wpr;
-  }
-  switch (wb) {
-    case 16: return launch_wb<16>(ctx, 0, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
-    case 12: return launch_wb<12>(ctx, 4, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
-    case 8: return launch_wb<8>(ctx, 1, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
-    case 4: return launch_wb<4>(ctx, 2, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
-    default: return launch_wb<2>(ctx, 3, d_jobs, nblk, T, d_kc, need, max_slots, max_out, max_u, max_wpr, hdrs, io_aligned);
-  }
-}
-/* widest width at which the image of h fits the LDS (0: none) and its size there */
-static uint32_t widest_fit(const nrq_ctx *ctx, const nrq_plan_hdr *h, uint32_t *need) {
-  /* (12 bytes: between the 16-byte image's limit, K ~ 8500, and ~12000; below, a block that does not fit 16 bytes is the odd one
-   * of its batch -- a decode plan with many inactive columns -- and goes on the second list at 12 as well) */
-  static const uint32_t widths[5] = {16, 12, 8, 4, 2};
-  for (int s = 0; s < 5; s++) {
-    if (widths[s] > ctx->tune.max_wb) continue;
-    if (widths[s] == 12u && ctx->tune.no_wb12) continue;
-    const uint32_t t = nrq_lds_plan(h, widths[s]).total;
-    if (t <= ctx->tune.lds_max) { *need = t; return widths[s]; }
-  }
-  *need = 0;
-  return 0;
-}
-
-/* The solve launch(es) of a batch.  A launch runs at one strip width, and the widest width a block can have is set by ITS plan
- * (a decode plan's LDS image grows with its inactive columns): at K=8192 one block in a few thousand -- one launch in 40 at 10 %
- * loss, 4 in 40 at 30 % -- does not fit the 16-byte image.  Round 5 sent the whole launch to the width every block fits (8 bytes:
- * ~1.7 x the time for 256 blocks because of one); now the batch is split into at most TWO LISTS -- the blocks that fit the
- * widest width any block has, and the others, launched at the widest width THEY all fit; each list's job records are copied
- * side by side first (a handful of small device-to-device copies, only when a batch splits).
+/* The solve launch(es) of a batch: one, or -- when solve_lists() puts the blocks on two lists -- one per list, each list's job
+ * records copied side by side first (a handful of small device-to-device copies, only when a batch splits).
  * blk_of_hdr: index in d_jobs of every header (nullptr: all blocks share one plan, nothing to split). */
 int pick_and_launch(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs, const nrq_job *d_jobs, uint32_t nblk,
                     uint32_t T, const uint8_t *d_kc, uint32_t max_out, bool io_aligned, const std::vector<uint32_t> *blk_of_hdr = nullptr) {
-  uint32_t wa = 0, need_a = 0, wb_ = 16, need_b = 0, na = 0, nsolv = 0;
-  std::vector<uint32_t> wd(hdrs.size(), 0), nd(hdrs.size(), 0);
-  for (size_t i = 0; i < hdrs.size(); i++) {
-    if (hdrs[i]->status) continue;
-    nsolv++;
-    wd[i] = widest_fit(ctx, hdrs[i], &nd[i]);
-    if (!wd[i]) return fail(ctx, -5, "block too large for the LDS-resident solver");
-    if (wd[i] > wa) wa = wd[i];
-  }
-  if (!nsolv) return 0; /* nothing solvable in this batch */
-  for (size_t i = 0; i < hdrs.size(); i++) {
-    if (hdrs[i]->status) continue;
-    if (wd[i] == wa) { na++; if (nd[i] > need_a) need_a = nd[i]; }
-    else if (wd[i] < wb_) wb_ = wd[i];
-  }
-  const uint32_t nb = nsolv - na;
+  const SolveLists l = solve_lists(ctx->tune, hdrs.data(), hdrs.size(), blk_of_hdr != nullptr);
+  if (l.err) return fail(ctx, -5, "block too large for the LDS-resident solver");
+  if (!l.nsolv) return 0; /* nothing solvable in this batch */
   ctx->stats.strip_bytes_b = 0; ctx->stats.blocks_b = 0;
-  /* one list: everybody fits the widest width -- or lists are off / impossible (no block indices) / not worth it (the wide list
-   * would be the minority: then everybody runs at the narrow width, as before) */
-  if (nb == 0 || !blk_of_hdr || ctx->tune.no_lists || na < nb) {
-    const uint32_t w = nb == 0 ? wa : wb_;
-    uint32_t need = 0;
-    for (const nrq_plan_hdr *h : hdrs)
-      if (!h->status) { const uint32_t t = nrq_lds_plan(h, w).total; if (t > need) need = t; }
-    return launch_list(ctx, hdrs, d_jobs, nblk, T, d_kc, max_out, w, need, io_aligned);
-  }
-  /* two lists */
+  if (!l.two) return launch_solve(ctx, hdrs, d_jobs, nblk, T, d_kc, max_out, l.wa, l.need_a, io_aligned);
   std::vector<const nrq_plan_hdr *> ha, hb;
   std::vector<uint32_t> ib;
   for (size_t i = 0; i < hdrs.size(); i++) {
     if (hdrs[i]->status) continue;
-    if (wd[i] == wa) ha.push_back(hdrs[i]);
-    else { hb.push_back(hdrs[i]); ib.push_back((*blk_of_hdr)[i]); const uint32_t t = nrq_lds_plan(hdrs[i], wb_).total; if (t > need_b) need_b = t; }
+    if (l.on_b[i]) { hb.push_back(hdrs[i]); ib.push_back((*blk_of_hdr)[i]); }
+    else ha.push_back(hdrs[i]);
   }
   /* both lists' job records side by side in scratch arrays: the second list's few records one by one (runs of neighbours in one
    * copy), the first list's as the stretches between them -- |B| + 1 copies of 80-byte records at most.  (A kernel-side rule --
@@ -1985,9 +1642,9 @@ int pick_and_launch(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &hdrs,
     if ((rc = timing_pair(ctx, ctx->ktime_pool, ctx->ktime_used, ctx->stream, &ev1))) return rc;
     ctx->ktime_outer = true;
   }
-  rc = launch_list(ctx, hb, jb, (uint32_t)ib.size(), T, d_kc, max_out, wb_, need_b, io_aligned);
+  rc = launch_solve(ctx, hb, jb, (uint32_t)ib.size(), T, d_kc, max_out, l.wb, l.need_b, io_aligned);
   const uint32_t sb_b = ctx->stats.strip_bytes;
-  if (!rc) rc = launch_list(ctx, ha, ja, na_blocks, T, d_kc, max_out, wa, need_a, io_aligned); /* (last: the call's stats describe the wide list) */
+  if (!rc) rc = launch_solve(ctx, ha, ja, na_blocks, T, d_kc, max_out, l.wa, l.need_a, io_aligned); /* (last: the call's stats describe the wide list) */
   ctx->ktime_outer = false;
   if (rc) {
     if (ev1) ctx->ktime_used--; /* (the pair's second event will not be recorded) */
@@ -2105,38 +1762,9 @@ int nrq_ctx_set_planner(nrq_ctx *ctx, int device_planner) {
 
 int nrq_ctx_set_option(nrq_ctx *ctx, const char *name, long long value) {
   if (!ctx || !name) return -1;
-  Tuning &t = ctx->tune;
   const std::string n(name);
-  if (n == "max_wb") t.max_wb = (uint32_t)value;
-  else if (n == "no_split") t.no_split = value != 0;
-  else if (n == "no_tiny") t.no_tiny = value != 0;
-  else if (n == "no_wentry") t.no_wentry = value != 0;
-  else if (n == "wide_g") t.wide_g = (value == 2 || value == 4 || value == 8) ? (uint32_t)value : 0u;
-  else if (n == "tiny_div") t.tiny_div = (uint32_t)value;
-  else if (n == "tiny_div_dec") t.tiny_div_dec = (uint32_t)value;
-  else if (n == "no_balance") t.no_balance = value != 0;
-  else if (n == "no_lists") t.no_lists = value != 0;
-  else if (n == "no_wb12") t.no_wb12 = value != 0;
-  else if (n == "host_plan_auto") t.host_plan_auto = value != 0;
-  else if (n == "plan_pack") t.plan_pack = value != 0;
-  else if (n == "tiny_any") t.tiny_any = value != 0;
-  else if (n == "lds_max") t.lds_max = value > 0 && value <= (long long)NRQ_LDS_MAX ? (uint32_t)value : NRQ_LDS_MAX;
-  else if (n == "no_plan_stream") t.no_plan_stream = value != 0;
-  else if (n == "no_plan_split") t.no_plan_split = value != 0;
-  else if (n == "plan_split_force") t.plan_split_force = value != 0;
-  else if (n == "plan_small_state") t.plan_small_state = value != 0;
-  else if (n == "plan_big_wg") t.plan_big_wg = value != 0;
-  else if (n == "reserve_cus") t.reserve_cus = (int)value;
-  else if (n == "solve_grid") t.solve_grid = (uint64_t)value;
-  else if (n == "big_wg") t.big_wg = value != 0;
-  else if (n == "small_waves4") t.small_waves4 = value != 0;
-  else if (n == "map_spread") t.map_spread = value != 0;
-  else if (n == "encplan_dev_min_l") t.encplan_dev_min_l = (uint32_t)value;
-  else if (n == "plan_ucap") t.plan_ucap = (uint32_t)value;
-  else if (n == "plan_wrong_instance") t.plan_wrong_instance = value != 0;
-  else if (n == "plan_no_wg128") t.plan_no_wg128 = value != 0;
-  else if (n == "tx_dword") t.tx_dword = value != 0;
-  else if (n == "fail_after" && ctx->fault_inject_armed) ctx->fail_after = value > 0 ? value : 0;
+  if (ctx->tune.set(name, value)) return 0; /* (the knobs: NRQ_KNOBS, launch_shape.h) */
+  if (n == "fail_after" && ctx->fault_inject_armed) ctx->fail_after = value > 0 ? value : 0;
   else if (n == "faults_injected") return (int)ctx->faults_injected; /* (read: injected failures so far) */
   else return fail(ctx, -1, "unknown option %s", name);
   return 0;
@@ -2440,7 +2068,7 @@ struct PlanRun {
   /* the call this run was issued for: its lists point into the copies beside it */
   DecodeCall call;
   std::vector<uint32_t> lost, nlost, resi, nrep, avail;
-  PlanForm form;
+  PlanShape shape; /* the planner form this run launched */
 };
 
 static void plan_ahead_drop(nrq_ctx *ctx) {
@@ -2483,6 +2111,7 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, const DecodeCall &c) {
   const pl_work_layout wl = pl_work_plan(p.L, Mcap, npcap, ucap, kh->nnz + npcap * PL_PATCH_STRIDE);
   const uint32_t arena_cap = pl_arena_bound(p.L, Mcap, ucap, kh->nnz + npcap * PL_PATCH_STRIDE, max_nl + 8u);
   r.ucap = ucap; r.Mcap = Mcap; r.npcap = npcap; r.arena_cap = arena_cap;
+  r.shape = plan_shape(ctx->tune, ctx->ncu, p, nblk, Mcap, ucap);
   const int ab = ctx->aflip;
   ctx->aflip = (ctx->aflip + 1) % 3;
   r.ab = ab;
@@ -2543,7 +2172,7 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, const DecodeCall &c) {
     j.nrep_avail = j.nrep;
     if (sane && c.h_avail && c.h_avail[b] > j.nrep) j.nrep_avail = c.h_avail[b] < c.rep_cap ? c.h_avail[b] : c.rep_cap;
     j.arena_cap = arena_cap;
-    j.mode = plan_is_segmented(ctx, p, Mcap) ? (ctx->tune.no_wentry ? 0x100u : 0x300u) : 0u; /* bit 8: segmented run, bit 9: entry pass by nrq_wentry_kernel */
+    j.mode = r.shape.mode;
   }
   { /* (in_bytes is a multiple of 16; both buffers are 16-byte aligned allocations) */
     const uint32_t n16 = (uint32_t)(in_bytes / 16u);
@@ -2560,9 +2189,9 @@ static int plan_launch(nrq_ctx *ctx, PlanRun &r, const DecodeCall &c) {
   unsigned long long *const pprof = reinterpret_cast<unsigned long long *>(prof.p);
   hipEvent_t pe1 = nullptr;
   if (ctx->ktime_on && (rc = timing_pair(ctx, ctx->ptime_pool, ctx->ptime_used, ps, &pe1))) return rc;
-  if ((rc = launch_plan_kernel(ctx, ps, p, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ds + off_pj),
+  if ((rc = launch_plan_kernel(ctx, ps, r.shape, p, kc->dev.p, reinterpret_cast<const nrq_planjob *>(ds + off_pj),
                                reinterpret_cast<nrq_job *>(ctx->plan_jobs[ab].p), nblk, Mcap, npcap, ucap, pprof,
-                               kh->nnz + npcap * PL_PATCH_STRIDE, &r.form)))
+                               kh->nnz + npcap * PL_PATCH_STRIDE)))
     return rc;
   if (pe1) HIPCHK(ctx, hipEventRecord(pe1, ps));
   if (pprof) {
@@ -2639,9 +2268,9 @@ static int decode_device(nrq_ctx *ctx, const DecodeCall &c, std::vector<uint8_t>
   HIPCHK(ctx, hipEventSynchronize(ctx->planned[ab]));
   ctx->stats.plan_ms = now_ms() - t_begin;
   ctx->stats.plan_ahead = ahead ? 1 : 0;
-  ctx->stats.plan_wg_threads = run->form.wg_threads;
-  ctx->stats.plan_compact_state = run->form.compact;
-  ctx->stats.plan_segmented = run->form.segmented;
+  ctx->stats.plan_wg_threads = run->shape.wg_threads;
+  ctx->stats.plan_compact_state = run->shape.compact;
+  ctx->stats.plan_segmented = run->shape.segmented;
   const nrq_plan_hdr *hd = reinterpret_cast<const nrq_plan_hdr *>(hs + off_hdrs);
   std::vector<const nrq_plan_hdr *> hdrs;
   std::vector<uint32_t> hblk; /* block of every header in hdrs (pick_and_launch: the batch's two block lists) */
@@ -2748,7 +2377,7 @@ static int decode(nrq_ctx *ctx, DecodeCall &c) {
    * host planner, sequential per block, needs ~0.45 us per source symbol on the GPU box's CPU.  Measured with the reference's
    * benchmark.c (decode column, Gbit/s, device / host planner): K=100 3.5 / 9.3, K=500 8.6 / 23.8, K=1000 16.7 / 23.2, K=1500
    * 20.8 / 24.1, K=2000 22.3 / 21.8, K=2500 25.5 / 23.6, K=3000 25.7 / 23.1, K=4000 34.8 / 17.9.  So the host plans when its estimate is the shorter
-   * one (option "host_plan_auto" / NRQ_HOST_PLAN_AUTO=0: never), unless plans were issued ahead or the call solves in chunks.
+   * one (the knob host_plan_auto = 0: never), unless plans were issued ahead or the call solves in chunks.
    * (Several small blocks: decode_host plans them one after the other -- its worker threads cost more to start than such plans take.) */
   const bool host_small = ctx->planner && ctx->tune.host_plan_auto && ctx->ahead.empty() && !c.chunk_blocks &&
                           (uint64_t)38u * nblk * K < (uint64_t)20000u + (uint64_t)28u * K; /* (tools/small_calls.py: host call ~65 us + 0.3-0.4 us x K per block, planner-kernel

@@ -429,7 +429,7 @@ def test_narrow_strip_paths_at_small_sizes(G, orc, wb, split):
 @pytest.mark.parametrize("K,T", [(10000, 40), (11500, 28), (9000, 1288)])
 def test_twelve_byte_strips_where_sixteen_do_not_fit(G, orc, K, T):
     """K between ~8500 and ~12000: the 16-byte strip image exceeds the CU's LDS, the 12-byte one fits (three forward waves, a
-    dword of the strip each; nrq_device.hip widest_fit).  Chosen on its own here, checked against the oracle; with "no_wb12"
+    dword of the strip each; launch_shape.h widest_fit).  Chosen on its own here, checked against the oracle; with "no_wb12"
     the launch falls back to 8 bytes and gives the same bytes."""
     c = G.ctx()
     nblk = 2
@@ -487,7 +487,7 @@ def test_device_built_encode_plans(G, orc):
 @pytest.mark.parametrize("g", [2, 4, 8])
 def test_wide_strips(G, orc, g):
     """Wide strips (g lanes of 16 bytes per element, nrq_ctx_set_option "wide_g"): an option for small blocks that is not
-    selected automatically (nrq_device.hip launch_wb has the measurements); forced here -- intermediate, repair and
+    selected automatically (launch_shape.h solve_shape has the measurements); forced here -- intermediate, repair and
     recovered symbols byte for byte, symbol sizes that end inside a strip (T = 50, 136, 1288)."""
     c = G.ctx()
     c.set_option("wide_g", g)
@@ -849,7 +849,7 @@ def test_small_calls_take_the_host_planner(G, orc):
 @pytest.mark.parametrize("K,T,nblk", [(300, 64, 5), (1000, 32, 64), (2500, 16, 9)])
 def test_planner_workgroup_by_batch_size(G, orc, K, T, nblk):
     """A batch of at most one block per compute unit is planned by 1024-thread workgroups with the whole LDS each (nothing to
-    share a CU with; launch_plan_kernel), larger batches of small blocks by 256- or 128-thread ones that share a CU -- "plan_pack"
+    share a CU with; plan_shape), larger batches of small blocks by 256- or 128-thread ones that share a CU -- "plan_pack"
     forces the latter, as the fixture does.  Same decoded bytes both ways, one block against the oracle."""
     c = G.ctx()
     res = []

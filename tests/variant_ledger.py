@@ -39,7 +39,7 @@ SOLVE = {
     (16, 64, 3, 1, True): dict(status="default", shape=dict(K=100, T=1024, nblk=64, loss=0.2)),
     # (64 blocks of T=100 are 448 strips, not more than 2 per CU: 256/4 on an MI355X; 128 blocks are 896)
     (16, 64, 3, 1, False): dict(status="default", shape=dict(K=100, T=100, nblk=128, loss=0.2)),
-    # wide strips: never selected automatically (launch_wb: "wide_g" only)
+    # wide strips: never selected automatically (solve_shape: "wide_g" only)
     (16, 256, 4, 2, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips",
                                  why="wide strips are an experiment: only the option wide_g selects them"),
     (16, 256, 4, 4, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips",
@@ -57,10 +57,10 @@ SOLVE = {
     (4, 768, 1, 1, False): dict(status="default", shape=dict(K=27000, T=72, nblk=1, loss=0.1), backsub=32),
     # 2-byte strips
     (2, 768, 1, 1, False): dict(status="default", shape=dict(K=56403, T=16, nblk=1, loss=0.1), backsub=32),
-    (2, 768, 1, 1, True): dict(status="never", why="launch_wb allows the aligned movers only for WB >= 4"),
-    (2, 256, 4, 1, True): dict(status="never", why="launch_wb allows the aligned movers only for WB >= 4"),
-    (2, 256, 5, 1, True): dict(status="never", why="launch_wb allows the aligned movers only for WB >= 4"),
-    (2, 64, 3, 1, True): dict(status="never", why="launch_wb allows the aligned movers only for WB >= 4"),
+    (2, 768, 1, 1, True): dict(status="never", why="solve_shape allows the aligned movers only for WB >= 4"),
+    (2, 256, 4, 1, True): dict(status="never", why="solve_shape allows the aligned movers only for WB >= 4"),
+    (2, 256, 5, 1, True): dict(status="never", why="solve_shape allows the aligned movers only for WB >= 4"),
+    (2, 64, 3, 1, True): dict(status="never", why="solve_shape allows the aligned movers only for WB >= 4"),
 }
 for _wb in (8, 4, 2):
     for _nt, _wv in ((256, 4), (256, 5), (64, 3)):
