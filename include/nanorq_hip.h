@@ -274,6 +274,15 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used);
 void *nrq_rx_src(nrq_rx *rx);
 void *nrq_rx_rep(nrq_rx *rx);
 int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the rows keep their bytes */
+/* What the reception HOLDS: the symbols whose bytes lie in its rows -- per block its seen source symbols (after a decode: all K)
+ * and its repair rows in use; a symbol that got NRQ_RX_FULL is not held, and after nrq_rx_reset nothing is.  *h_n = their number,
+ * sum over the blocks of K - nlost + nrep (waits for the work enqueued before, as nrq_rx_counts).  d_tags (device, nullable) with
+ * cap >= *h_n receives their tags (nanorq_tag() form), listed on the device: block-major, within a block the source ESIs
+ * ascending, then the repair ESIs in arrival order; cap too small: -1, *h_n still filled.  Only *h_n is final on return: the
+ * writing of d_tags is enqueued on the context's stream behind the wait, so later work on that stream (an emit) sees the tags,
+ * while a read from the host or from another stream needs nrq_ctx_sync first.  It is the list a relay's NRQ_TX_HELD emit writes
+ * in full (below). */
+int nrq_rx_held(nrq_rx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n);
 
 /* ---- device-resident sender: packets (an optional FEC Payload ID and a payload, at a packet stride) written straight into
  * device memory -- for a GPU-direct NIC, or a kernel that sends from device memory -- for any list of (SBN, ESI) ----
@@ -286,6 +295,7 @@ int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the 
 typedef struct nrq_tx nrq_tx;
 #define NRQ_TX_TAG_INLINE 1u /* packet = the RFC 6330 section 3.2 FEC Payload ID (SBN 8 bits, ESI 24 bits, network byte order), then the
                               * payload at +4 (pkt_stride >= T + 4) */
+#define NRQ_TX_HELD 2u       /* tag-list emits of a relay: a block that is not ready still gives the symbols its reception holds (below) */
 #define NRQ_TX_NOT_READY (-2) /* emit result code beside 0 and -1: a block of a relay that is not ready (the packet is left untouched) */
 int nrq_tx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, const void *d_src, size_t src_stride,
                   nrq_tx **out);
@@ -294,7 +304,7 @@ void nrq_tx_destroy(nrq_tx *tx);
 int nrq_tx_encode(nrq_tx *tx);
 /* Packet k for tag d_tags[k] (nanorq_tag() form, device memory) at d_pkts + k*pkt_stride (pkt_stride >= T, + 4 inline).
  * d_results (device, nullable): 0 = written, -1 = SBN outside the transmission (the packet is left untouched); a relay also gives
- * NRQ_TX_NOT_READY. */
+ * NRQ_TX_NOT_READY (the table in the relay section).  flags: NRQ_TX_TAG_INLINE, and on a relay NRQ_TX_HELD (a sender: -1). */
 int nrq_tx_emit(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
 /* ESIs esi0 .. esi0+n-1 of EVERY block (n * nblk packets, no tag list): order 0 = block-major (packet k -> block k / n, ESI
  * esi0 + k % n), 1 = interleaved (packet k -> block k % nblk, ESI esi0 + k / nblk); d_tags_out (device, nullable) receives each
@@ -322,7 +332,24 @@ int nrq_tx_ready(nrq_tx *tx, uint32_t *h_ready);
  * gets NRQ_TX_NOT_READY in d_results (-1 keeps meaning "SBN outside the span").  nrq_tx_emit_range needs every block ready
  * (-1 and a text that names the blocks that are not).  Everything is enqueued on the context's stream, so an emit enqueued
  * after a decode sees that decode's rows and intermediate symbols; a ready block never changes again (later packets for it are
- * IGN), so its packets stay valid while the reception takes packets for other blocks. */
+ * IGN), so its packets stay valid while the reception takes packets for other blocks.
+ *
+ * Held symbols (NRQ_TX_HELD, nrq_tx_emit / nrq_otx_emit on a relay): a block that is not ready -- short of symbols, rank
+ * deficient, or decoded before the relay was attached -- still answers with the symbols the reception holds, so a relay can cut
+ * through (forward a batch as soon as it is ingested), serve a NACK from a partial block and hand all it has to a late child.
+ * The packet of (SBN, ESI), and its entry of d_results:
+ *   SBN outside the span                                         untouched   -1
+ *   block ready                                                  any ESI, as without the flag   0
+ *   block not ready, ESI < K, the source symbol is held          a copy of source row ESI       0
+ *   block not ready, ESI >= K, the repair symbol is held         a copy of its repair row       0
+ *   block not ready, the symbol is not held (or no NRQ_TX_HELD)   untouched   NRQ_TX_NOT_READY
+ * "Held" is nrq_rx_held's meaning: ADDED by nrq_rx_add (not NRQ_RX_FULL, not after a reset), or a source row a decode recovered.
+ * A held packet has the bytes that were ingested, hence those of nanorq_encode.  nrq_rx_decode reads the repair rows and their
+ * ESI list and leaves both as they are, so held repair symbols stay valid after a decode (a block decoded before the relay was
+ * attached gives all K source symbols and its received repair symbols, but no fresh ones until nrq_tx_encode); a held symbol's
+ * row does not change until a reset, and source rows change only where they were missing.  The emit is enqueue-only and sees
+ * the symbols of every nrq_rx_add enqueued before it, without a host wait.  Without the flag every call is as it was;
+ * nrq_tx_emit_range and nrq_otx_emit_all refuse it (-1: their packet maps are analytic over all blocks). */
 int nrq_rx_relay(nrq_rx *rx, nrq_tx **out);
 
 /* ---- whole objects (RFC 6330 section 4.4.1.2) on the device: an object of F bytes and its OTI, sent and received through the
@@ -380,6 +407,7 @@ void nrq_orx_destroy(nrq_orx *rx);
  * NANORQ_SYM_IGN -- the object layer's block of no symbols.) */
 int nrq_orx_add(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results);
 int nrq_orx_counts(nrq_orx *rx, uint32_t *h_nlost, uint32_t *h_nrep); /* Z entries each */
+int nrq_orx_held(nrq_orx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n); /* as nrq_rx_held, over both block classes in SBN order */
 int nrq_orx_decode(nrq_orx *rx, int *h_status, uint32_t *h_used);    /* as nrq_rx_decode, Z entries */
 /* every complete block into d_out (F bytes, device) in the object's layout; bytes past F and the bytes of incomplete blocks are
  * left untouched.  Returns the number of blocks still incomplete (>= 0), or < 0 on error.  Waits for the counts, enqueues the
@@ -389,9 +417,10 @@ int nrq_orx_write(nrq_orx *rx, void *d_out);
  * images -- class L at their start, class S behind it, each with its own K' under NANORQ_EXT_PER_BLOCK_KP; the Kt * T bytes of
  * the row images make a staged last block unnecessary, and neither nrq_orx_write nor a layout pass is on the forwarding path --
  * and whose intermediate symbols (ZL * L_L * T + ZS * L_S * T bytes) come from the context's pool.  nrq_orx_decode feeds it,
- * nrq_otx_encode makes the remaining complete blocks ready, nrq_otx_emit gives NRQ_TX_NOT_READY per packet, nrq_otx_emit_all needs
- * every block ready, nrq_otx_oti returns the object's OTI.  Packets are bit-exact with those of nrq_otx_create over the original
- * object.  Destroy it before the receiver (else it is detached). */
+ * nrq_otx_encode makes the remaining complete blocks ready, nrq_otx_emit gives NRQ_TX_NOT_READY per packet (and takes NRQ_TX_HELD,
+ * answering from the symbols either class's reception holds), nrq_otx_emit_all needs every block ready, nrq_otx_oti returns
+ * the object's OTI.  Packets are bit-exact with those of nrq_otx_create over the original object.  Destroy it before the
+ * receiver (else it is detached). */
 int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
 
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream

@@ -129,6 +129,9 @@ def lib():
         L.nrq_rx_relay.argtypes = [vp, C.POINTER(vp)]
         L.nrq_otx_ready.argtypes = [vp, u32p]
         L.nrq_orx_relay.argtypes = [vp, C.POINTER(vp)]
+    if hasattr(L, "nrq_rx_held"):  # (likewise a build from before the held symbols: held() then raises, held=True is refused)
+        L.nrq_rx_held.argtypes = [vp, vp, C.c_uint32, u32p]
+        L.nrq_orx_held.argtypes = [vp, vp, C.c_uint32, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -461,14 +464,38 @@ class Receiver(_Handle):
     def reset(self):
         self.ctx._chk(self._L.nrq_rx_reset(self._h))
 
+    def held(self):
+        """The tags (nanorq_tag() form) of every symbol the reception holds, as an [n] int32 device tensor listed on the device:
+        block-major, per block the seen source ESIs ascending, then the repair ESIs in arrival order (waits).  It is the list
+        relay().emit(tags, held=True) writes in full."""
+        return _held(self)
+
     def relay(self):
         """A Sender over this reception's own rows (nrq_rx_relay): it emits any (SBN, ESI) of every block that is ready -- decoded
         while the relay was attached, or complete and made ready by its encode().  One per reception."""
         return RelaySender(self)
 
 
+def _held(rx):
+    """<_api>_held: the count first, then the tags into a tensor of that size"""
+    import torch
+    n = C.c_uint32(0)
+    fn = getattr(rx._L, rx._api + "_held")
+    rx.ctx._chk(fn(rx._h, None, 0, C.byref(n)))
+    out = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % rx.ctx.device)
+    if n.value:
+        rx.ctx._chk(fn(rx._h, C.c_void_p(_dptr(out)), n.value, C.byref(n)))
+        rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
+    return out
+
+
 TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
+TX_HELD = 2         # NRQ_TX_HELD
 TX_NOT_READY = -2   # NRQ_TX_NOT_READY
+
+
+def _tx_flags(inline, held):
+    return (TX_TAG_INLINE if inline else 0) | (TX_HELD if held else 0)
 
 
 class _Emitter(_Handle):
@@ -489,15 +516,16 @@ class _Emitter(_Handle):
         """solve every block (the intermediate symbols stay in device memory); needed before any emit"""
         self.ctx._chk(getattr(self._L, self._api + "_encode")(self._h))
 
-    def emit(self, tags, out=None, inline=False, results=None):
+    def emit(self, tags, out=None, inline=False, results=None, held=False):
         """Packet k for tags[k] ([n] int32 / uint32 device tensor, nanorq_tag() form) in row k of out ([n, stride] uint8 device
         tensor; None: a new one).  results: optional [n] int32 device tensor (0 written, -1 SBN outside the transmission or the
         object, whose packet is left untouched; a relay: TX_NOT_READY for a block that is not ready, likewise untouched).
-        Returns out."""
+        held (relays only; a sender refuses it): a block that is not ready still gives the symbols its reception holds
+        (TX_HELD), as copies of the rows they were ingested into.  Returns out."""
         n = int(tags.shape[0])
         out, stride = self._out(n, inline, out)
         self.ctx._chk(getattr(self._L, self._api + "_emit")(self._h, C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
-                                                            TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+                                                            _tx_flags(inline, held), C.c_void_p(_dptr(results))))
         return out
 
 
@@ -522,13 +550,14 @@ class Sender(_Emitter):
         """device address of the intermediate symbols (block b's L rows at + b*L*T)"""
         return self._L.nrq_tx_inter(self._h) or 0
 
-    def emit_range(self, esi0, n, interleave=True, inline=False, out=None, tags_out=None):
+    def emit_range(self, esi0, n, interleave=True, inline=False, out=None, tags_out=None, held=False):
         """ESIs esi0 .. esi0+n-1 of every block: n * nblk packets, interleaved (packet k: block k % nblk, ESI esi0 + k // nblk) or
         block-major (block k // n, ESI esi0 + k % n).  tags_out: optional [n * nblk] int32 device tensor for each packet's tag.
+        held: refused (the range maps are analytic over all blocks; the flag is passed on so that the library says so).
         Returns out ([n * nblk, stride] uint8)."""
         out, stride = self._out(n * self.nblk, inline, out)
         self.ctx._chk(self._L.nrq_tx_emit_range(self._h, esi0, n, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
-                                                TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
+                                                _tx_flags(inline, held), C.c_void_p(_dptr(tags_out))))
         return out
 
 
@@ -617,11 +646,12 @@ class ObjectSender(_Emitter):
         p = self.params
         return p.ZL * (p.KL + nrep) + p.ZS * (p.KS + nrep)
 
-    def emit_all(self, nrep, interleave=True, inline=False, out=None, tags_out=None):
-        """ESIs 0 .. K_b + nrep - 1 of every block b, block-major or interleaved (sorted by (ESI, SBN)).  Returns out."""
+    def emit_all(self, nrep, interleave=True, inline=False, out=None, tags_out=None, held=False):
+        """ESIs 0 .. K_b + nrep - 1 of every block b, block-major or interleaved (sorted by (ESI, SBN)); held: refused, as
+        Sender.emit_range.  Returns out."""
         out, stride = self._out(self.count_all(nrep), inline, out)
         self.ctx._chk(self._L.nrq_otx_emit_all(self._h, nrep, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
-                                               TX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(tags_out))))
+                                               _tx_flags(inline, held), C.c_void_p(_dptr(tags_out))))
         return out
 
 
@@ -680,6 +710,10 @@ class ObjectReceiver(_Handle):
         used = np.zeros(self.Z, np.uint32)
         self.ctx._chk(self._L.nrq_orx_decode(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
         return st, used
+
+    def held(self):
+        """as Receiver.held, over both block classes in SBN order"""
+        return _held(self)
 
     def relay(self):
         """An ObjectSender over this receiver's row images (nrq_orx_relay): it emits any (SBN, ESI) of every block that is ready,

@@ -21,6 +21,7 @@ IEMU = os.path.join(ROOT, "tests", "emu", "libingest_emu.so")
 XEMU = os.path.join(ROOT, "tests", "emu", "libemit_emu.so")
 OEMU = os.path.join(ROOT, "tests", "emu", "libobj_emu.so")
 SEMU = os.path.join(ROOT, "tests", "emu", "libshape_emu.so")
+HEMU = os.path.join(ROOT, "tests", "emu", "libheld_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -134,6 +135,12 @@ def build_emit_emu(force=False):
     return _build_emu(XEMU, os.path.join(CSRC, "emit_emu.cpp"), ("emit_body.h", "rq_math.h"), force)
 
 
+def build_held_emu(force=False):
+    """tests/emu/libheld_emu.so: CPU emulation of the held-symbol emit and of the held listing (csrc/held_emu.cpp over emit_body.h
+    and held_body.h)."""
+    return _build_emu(HEMU, os.path.join(CSRC, "held_emu.cpp"), ("emit_body.h", "held_body.h", "ingest_body.h", "rq_math.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -151,6 +158,7 @@ if __name__ == "__main__":
     build_planner_emu(force="-f" in sys.argv)
     build_ingest_emu(force="-f" in sys.argv)
     build_emit_emu(force="-f" in sys.argv)
+    build_held_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -11,7 +11,7 @@
  * Payload of (block b, ESI e), bit-exact with nanorq_encode (nanorq_api.c):
  *   e <  K   source row e of block b (the caller's rows)
  *   e >= K   LT(C_b, e + K' - K): the XOR of the intermediate symbols rq_lt_columns names
- * nrq_device.hip instantiates these bodies in its emit kernel; emit_emu.cpp runs them sequentially on the CPU.
+ * nrq_device.hip instantiates these bodies in its emit kernels; emit_emu.cpp runs them sequentially on the CPU.
  *
  * Work order.  A packet's repair gathers hit its block's L x T bytes of intermediate symbols; the kernel walks packets BLOCK-MAJOR
  * (work item w -> packet tx_packet_of(w)) so that a block's packets run together and its rows are served from the caches, in
@@ -21,6 +21,10 @@
  * Ready mask.  A relay (a sender over a reception's rows) may hold blocks whose intermediate symbols are not written yet:
  * tx_src::ready has a bit per block of the span, and a packet of a block whose bit is clear is left untouched with the result
  * TX_NOT_READY (tx_admit).  Senders pass all ones.
+ *
+ * Held symbols.  With NRQ_TX_HELD a relay's tag-list emit carries a second table (tx_held: per segment the books and repair rows of
+ * the reception the segment reads) and admits packets through tx_admit_held: a block that is not ready still gives the symbols
+ * the reception holds, as copies of their rows.  nrq_emit_held_kernel is the kernel of that form; held_emu.cpp emulates it.
  */
 #ifndef NRQ_EMIT_BODY_H
 #define NRQ_EMIT_BODY_H
@@ -131,6 +135,76 @@ TX_HD struct tx_blk tx_pick(const struct tx_src *s, uint32_t g) {
   else if (g == 2u) t = s->seg[2];
   return t;
 }
+
+/* Held symbols (NRQ_TX_HELD, relays only).  Beside the source table lies, per segment, the index of the reception whose rows the
+ * segment reads (ing_rx's books): a packet of a block that is NOT ready is then still written when the reception holds that very
+ * symbol -- a copy of source row ESI (its seen bit is set), or of the repair row q with rep_esi[b][q] == ESI, q < nrep[b] (a
+ * repair symbol's seen bit is set when it took a row, and only then: FULL ones are not marked).  Ready blocks go the usual way. */
+struct tx_held_seg {
+  const uint32_t *seen;    /* [nblk][bm_words] */
+  const uint32_t *rep_esi; /* [nblk][rep_cap]: ESI of repair row q, arrival order */
+  const uint32_t *nrep;    /* [nblk]: repair rows used */
+  const uint8_t *rep;      /* block b's repair row q at rep + b*rep_stride + q*T */
+  uint64_t rep_stride;
+  uint32_t bm_words, rep_cap;
+};
+struct tx_held {
+  struct tx_held_seg seg[TX_SEGS];
+};
+
+#define TX_READY 0u    /* kinds of an admitted packet: built from the block's rows as ever */
+#define TX_HELD_SRC 1u /* a copy of the held source row ESI */
+#define TX_HELD_REP 2u /* a copy of the held repair row tx_held_find gives */
+
+/* the seen bit of ESI `esi` of block b (an ESI beyond the bitmap, i.e. above max_esi, is not seen: nothing is read) */
+TX_HD uint32_t tx_held_seen(const struct tx_held_seg *h, uint32_t b, uint32_t esi) {
+  if ((esi >> 5) >= h->bm_words) return 0u;
+  return (h->seen[(uint64_t)b * h->bm_words + (esi >> 5)] >> (esi & 31u)) & 1u;
+}
+
+/* held segment g, selected by value (as tx_pick) */
+TX_HD struct tx_held_seg tx_held_pick(const struct tx_held *h, uint32_t g) {
+  struct tx_held_seg t = h->seg[0];
+  if (g == 1u) t = h->seg[1];
+  else if (g == 2u) t = h->seg[2];
+  return t;
+}
+
+/* tx_admit with held symbols: the segment and *kind (TX_READY / TX_HELD_SRC / TX_HELD_REP), or TX_SEGS when the packet stays
+ * untouched.  (A TX_HELD_REP packet's row is still to be found: tx_held_find.) */
+template <bool MULTI>
+TX_HD uint32_t tx_admit_held(const struct tx_src *s, const struct tx_held *h, uint32_t tag, int32_t *code, uint32_t *kind) {
+  const uint32_t g = tx_seg<MULTI>(s, tag);
+  *kind = TX_READY;
+  if (g == TX_SEGS) { *code = TX_FOREIGN; return TX_SEGS; }
+  *code = 0;
+  if (tx_ready(s, tag)) return g;
+  const struct tx_blk t = tx_pick(s, MULTI ? g : 0u);
+  const struct tx_held_seg hs = tx_held_pick(h, MULTI ? g : 0u);
+  const uint32_t esi = tag & 0xFFFFFFu;
+  if (!tx_held_seen(&hs, tx_block(&t, tag), esi)) { *code = TX_NOT_READY; return TX_SEGS; }
+  *kind = esi < t.K ? TX_HELD_SRC : TX_HELD_REP;
+  return g;
+}
+
+/* one probe of the ESI -> repair row lookup: is repair row q of block b the one of `esi`?  (The kernel probes 64 rows per trip, a
+ * lane each, and takes a ballot; tx_held_find is the same walk one row at a time.) */
+TX_HD bool tx_held_hit(const struct tx_held_seg *h, uint32_t b, uint32_t q, uint32_t nrep, uint32_t esi) {
+  return q < nrep && h->rep_esi[(uint64_t)b * h->rep_cap + q] == esi;
+}
+TX_HD uint32_t tx_held_nrep(const struct tx_held_seg *h, uint32_t b) {
+  const uint32_t n = h->nrep[b];
+  return n < h->rep_cap ? n : h->rep_cap;
+}
+TX_HD uint32_t tx_held_find(const struct tx_held_seg *h, uint32_t b, uint32_t esi) {
+  const uint32_t nrep = tx_held_nrep(h, b);
+  for (uint32_t q = 0; q < nrep; q++)
+    if (tx_held_hit(h, b, q, nrep, esi)) return q;
+  return TX_NONE;
+}
+
+/* the rows of a TX_HELD_REP packet: the block's repair rows */
+TX_HD const uint8_t *tx_held_rep_base(const struct tx_held_seg *h, uint32_t b) { return h->rep + (uint64_t)b * h->rep_stride; }
 
 /* Range mode.  Block-major: block b's packets (nL or nS of them) one after the other.  Interleaved: round i holds ESI esi0 + i of
  * every block while i < nlo, later rounds only the first ZL blocks' (nL >= nS).  MULTI = false: a one-segment table, i.e. one

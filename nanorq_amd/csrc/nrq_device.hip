@@ -33,6 +33,7 @@
 #include "solve_body.h"
 #include "planner_body.h"
 #include "ingest_body.h"
+#include "held_body.h"
 #include "emit_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
@@ -2999,7 +3000,9 @@ struct nrq_rx {
   void *own_src, *own_rep;
   void *scratch;        /* per-call arrays */
   size_t scratch_cap;
-  void *lists;          /* nrq_ing_lists_kernel output */
+  void *lists;          /* nrq_ing_lists_kernel output, written anew by every call that reads it.  rx_held_count borrows its first
+                         * nblk + 1 words for the held offsets and total: both users run on the context's stream and neither
+                         * expects the buffer to survive from one call to the next -- keep it so */
   tx_sender *relay;     /* the relay attached to this reception (nrq_rx_relay / nrq_orx_relay), or null ... */
   uint32_t relay_seg, relay_b0; /* ... in whose table this reception is segment relay_seg, its block 0 the span's block relay_b0 */
 };
@@ -3358,6 +3361,66 @@ __global__ __launch_bounds__(256) void nrq_emit_kernel(tx_src s, tx_call c) {
   }
 }
 
+/* The emit kernel with held symbols (NRQ_TX_HELD; relays only, a tag list only): as nrq_emit_kernel, but a packet of a block that is
+ * not ready is still written when the reception holds its symbol (tx_admit_held) -- a copy of the source row, or of the repair
+ * row whose ESI it is.  That row is found by the wave that writes the packet: each lane probes one entry of the block's repair
+ * list per trip (64 consecutive ESIs, one coalesced load), a ballot gives the wave-uniform row.  A kernel of its own, so that the
+ * plain emit's instantiations are compiled from the code they always were. */
+template <int MODE, bool MULTI>
+__global__ __launch_bounds__(256) void nrq_emit_held_kernel(tx_src s, tx_held h, tx_call c) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS]; /* (MULTI only: unused LDS is not allocated) */
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
+  if (w0 + lane < c.n) {
+    const uint32_t k = tx_packet_of<MULTI>(&s, &c, (uint32_t)(w0 + lane));
+    const uint32_t tag = k < c.n ? tx_tag_of<MULTI>(&s, &c, k) : 0u;
+    int32_t code = TX_FOREIGN;
+    uint32_t kind = TX_READY;
+    const uint32_t sg = k < c.n ? tx_admit_held<MULTI>(&s, &h, tag, &code, &kind) : TX_SEGS;
+    const tx_blk sb = MULTI ? tx_pick(&s, sg) : s.seg[0];
+    uint32_t n = 0;
+    if (sg < TX_SEGS) {
+      if (kind == TX_HELD_REP) { s_cols[wv][lane][0] = 0u; n = 1u; } /* (row 0 from the base of the row found below) */
+      else n = tx_rows(&sb, tag, s_cols[wv][lane]);
+    }
+    s_n[wv][lane] = n | (kind << 8);
+    s_tag[wv][lane] = tag;
+    s_k[wv][lane] = k;
+    if (MULTI) s_seg[wv][lane] = sg;
+    if (k < c.n && c.results && kind != TX_HELD_REP) c.results[k] = code; /* (a held repair packet's: once its row is found) */
+  }
+  __syncthreads();
+  const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
+  const uint32_t T = s.seg[0].T;
+  for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][i]), n = nk & 0xFFu;
+    if (!n) continue; /* SBN outside the span, or a symbol of a block that is not ready which the reception does not hold */
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][i]);
+    const uint32_t sg = MULTI ? __builtin_amdgcn_readfirstlane(s_seg[wv][i]) : 0u;
+    const uint8_t *base;
+    if ((nk >> 8) == TX_HELD_REP) {
+      const tx_held_seg hs = sg == 0u ? h.seg[0] : sg == 1u ? h.seg[1] : h.seg[2];
+      const uint32_t b = (tag >> 24) - (sg == 0u ? s.seg[0].sbn0 : sg == 1u ? s.seg[1].sbn0 : s.seg[2].sbn0);
+      const uint32_t nrep = tx_held_nrep(&hs, b), esi = tag & 0xFFFFFFu;
+      uint32_t q = TX_NONE;
+      for (uint32_t q0 = 0; q0 < nrep && q == TX_NONE; q0 += 64u) {
+        const uint64_t m = __ballot(tx_held_hit(&hs, b, q0 + lane, nrep, esi));
+        if (m) q = q0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+      }
+      if (c.results && lane == 0) c.results[s_k[wv][i]] = q == TX_NONE ? TX_NOT_READY : 0;
+      if (q == TX_NONE) continue; /* (the books say otherwise: a marked repair ESI has its row) */
+      base = tx_held_rep_base(&hs, b) + (uint64_t)q * T;
+    } else if constexpr (MULTI) {
+      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
+    } else {
+      base = tx_base(&s.seg[0], tag);
+    }
+    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
+  }
+}
+
 /* tag-list bucketing over the span of nblk blocks from sbn0: packets per bucket (tx_bin), a histogram in LDS per tile of
  * TX_BIN_TILE packets, added to cnt[] */
 __global__ __launch_bounds__(256) void nrq_tx_hist_kernel(uint32_t sbn0, uint32_t nblk, const uint32_t *tags, uint32_t n, uint32_t *cnt) {
@@ -3512,21 +3575,43 @@ static int tx_encode(tx_sender *tx) {
   return 0;
 }
 
-/* checks shared by every emit call */
-static int tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags) {
+/* checks shared by every emit call; list: the tag-list form, which alone takes NRQ_TX_HELD, and only on a relay */
+static int tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t flags, bool list = false) {
   nrq_ctx *ctx = tx->ctx;
   if (tx->detached) return fail(ctx, -1, "%s: the relay's reception was destroyed", who);
   if (!tx->encoded) return fail(ctx, -1, "%s: %s", who, tx->unencoded);
-  if (flags & ~(uint32_t)NRQ_TX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_HELD)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if ((flags & NRQ_TX_HELD) && !list) return fail(ctx, -1, "%s: NRQ_TX_HELD goes with a tag list (the range forms map packets to every block)", who);
+  if ((flags & NRQ_TX_HELD) && !tx->relay) return fail(ctx, -1, "%s: NRQ_TX_HELD needs a relay (a sender holds no reception)", who);
   if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
   const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0;
   if (pkt_stride < (size_t)tx->s.seg[0].T + (inl ? 4u : 0u)) return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
   return 0;
 }
 
-/* the emit kernel at the widest path the addresses allow, in its one-segment form for a one-segment table */
-static int tx_launch(tx_sender *tx, const tx_call &c) {
+/* the table beside a relay's source table: per segment the books of the reception it reads (tx_held, emit_body.h) */
+static tx_held tx_held_table(const tx_sender *tx) {
+  tx_held h{};
+  for (uint32_t g = 0; g < tx->s.nseg; g++) {
+    const ing_rx &r = tx->from[g]->r;
+    tx_held_seg &t = h.seg[g];
+    t.seen = r.seen; t.bm_words = r.bm_words;
+    t.rep_esi = r.rep_esi; t.nrep = r.nrep; t.rep_cap = r.rep_cap;
+    t.rep = r.rep; t.rep_stride = r.rep_stride;
+  }
+  return h;
+}
+
+/* the emit kernel at the widest path the addresses allow, in its one-segment form for a one-segment table; held: the kernel that
+ * also answers from the symbols the relay's receptions hold */
+static int tx_launch(tx_sender *tx, const tx_call &c, bool held = false) {
   using emit_fn = void (*)(tx_src, tx_call);
+  using held_fn = void (*)(tx_src, tx_held, tx_call);
+  static const held_fn hkern[2][4] = { /* [multi-segment][mode] */
+      {nrq_emit_held_kernel<TX_V16, false>, nrq_emit_held_kernel<TX_V16_SHIFT, false>, nrq_emit_held_kernel<TX_DWORD, false>,
+       nrq_emit_held_kernel<TX_BYTE, false>},
+      {nrq_emit_held_kernel<TX_V16, true>, nrq_emit_held_kernel<TX_V16_SHIFT, true>, nrq_emit_held_kernel<TX_DWORD, true>,
+       nrq_emit_held_kernel<TX_BYTE, true>}};
   static const emit_fn kern[2][4] = { /* [multi-segment][mode] */
       {nrq_emit_kernel<TX_V16, false>, nrq_emit_kernel<TX_V16_SHIFT, false>, nrq_emit_kernel<TX_DWORD, false>,
        nrq_emit_kernel<TX_BYTE, false>},
@@ -3537,9 +3622,15 @@ static int tx_launch(tx_sender *tx, const tx_call &c) {
   uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | s.seg[0].T;
   for (uint32_t g = 0; g < s.nseg; g++)
     al |= reinterpret_cast<uintptr_t>(s.seg[g].src) | s.seg[g].src_stride | reinterpret_cast<uintptr_t>(s.seg[g].inter) | s.seg[g].inter_stride;
+  tx_held h{};
+  if (held) {
+    h = tx_held_table(tx);
+    for (uint32_t g = 0; g < s.nseg; g++) al |= reinterpret_cast<uintptr_t>(h.seg[g].rep) | h.seg[g].rep_stride; /* (held repair rows are copied too) */
+  }
   const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (c.inl ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
   const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
-  hipLaunchKernelGGL(kern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, c);
+  if (held) hipLaunchKernelGGL(hkern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, h, c);
+  else hipLaunchKernelGGL(kern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, c);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
@@ -3549,7 +3640,7 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
                         int32_t *d_results) {
   if (!tx) return -1;
   nrq_ctx *ctx = tx->ctx;
-  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags);
+  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags, true);
   if (rc) return rc;
   if (n == 0) return 0;
   if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u)", who, n);
@@ -3582,7 +3673,7 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
   c.tags = d_tags;
   c.order = order;
   c.results = d_results;
-  return tx_launch(tx, c);
+  return tx_launch(tx, c, (flags & NRQ_TX_HELD) != 0);
 }
 
 /* range mode (the caller has checked its arguments): ESIs esi0 .. esi0+nL-1 of each of the span's first ZL blocks, esi0 ..
@@ -4045,6 +4136,102 @@ int nrq_orx_write(nrq_orx *rx, void *d_out) {
   }
   if (incomplete < (int)Z && (rc = obj_layout_launch(ctx, l))) return rc;
   return incomplete;
+}
+
+} /* extern "C" */
+
+/* ================================================ what a reception holds (nrq_rx_held / nrq_orx_held, held_body.h) ==== */
+/* one workgroup per block: seen source ESIs plus repair rows used -> cnt[b] */
+__global__ __launch_bounds__(256) void nrq_held_count_kernel(ing_rx r, uint32_t *cnt) {
+  __shared__ uint32_t ps[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = hl_words(&r);
+  uint32_t n = 0;
+  for (uint32_t w = t; w < nw; w += 256u) n += hl_popc(hl_have(&r, b, w));
+  ps[t] = n;
+  __syncthreads();
+  for (uint32_t s = 128; s; s >>= 1) {
+    if (t < s) ps[t] += ps[t + s];
+    __syncthreads();
+  }
+  if (t == 0) cnt[b] = ps[0] + hl_nrep(&r, b);
+}
+
+/* one workgroup per block: its tags to out + off[b] -- the seen source ESIs ascending (256 words per round: a scan over their
+ * counts places each word's tags), then the repair ESIs in arrival order */
+__global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint32_t *off, uint32_t *out) {
+  __shared__ uint32_t ps[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = hl_words(&r);
+  uint32_t o = off[b];
+  for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
+    const uint32_t w = w0 + t;
+    const uint32_t have = w < nw ? hl_have(&r, b, w) : 0u, cnt = hl_popc(have);
+    ps[t] = cnt;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+      const uint32_t v = t >= d ? ps[t - d] : 0u;
+      __syncthreads();
+      ps[t] += v;
+      __syncthreads();
+    }
+    hl_put(&r, b, w, have, out + o + ps[t] - cnt);
+    o += ps[255];
+    __syncthreads();
+  }
+  const uint32_t nrep = hl_nrep(&r, b);
+  for (uint32_t q = t; q < nrep; q += 256u) out[o + q] = hl_rep_tag(&r, b, q);
+}
+
+/* count and scan, enqueued: the blocks' exclusive offsets and, behind them, the total, in the reception's list buffer.
+ * That buffer is the output of nrq_ing_lists_kernel (nrq_rx.lists), of whose 2 * nblk + ... words this takes the first nblk + 1:
+ * rx_fetch_lists launches its kernel again before it reads, the fill kernel reads the offsets on the same stream before anything
+ * later can overwrite them, so the two uses cannot meet.  A caller that kept the lists on the device across calls would break this. */
+static int rx_held_count(nrq_rx *rx) {
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  uint32_t *cnt = (uint32_t *)rx->lists;
+  HIPCHK(ctx, hipMemsetAsync(cnt + r.nblk, 0, 4u, ctx->stream));
+  hipLaunchKernelGGL(nrq_held_count_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, r.nblk + 1u, cnt);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* the held tags of up to two receptions, one behind the other */
+static int held_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
+  *h_n = 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t n[2] = {0, 0};
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    const int rc = rx_held_count(rxs[i]);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&n[i], (uint32_t *)rxs[i]->lists + rxs[i]->r.nblk, 4u, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *h_n = n[0] + n[1];
+  if (!d_tags) return 0;
+  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are held, d_tags has room for %u", who, *h_n, cap);
+  uint32_t at = 0;
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    if (n[i]) hipLaunchKernelGGL(nrq_held_fill_kernel, dim3(rxs[i]->r.nblk), dim3(256), 0, ctx->stream, rxs[i]->r, (const uint32_t *)rxs[i]->lists, d_tags + at);
+    at += n[i];
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rx_held(nrq_rx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!rx) return -1;
+  return held_list(rx->ctx, "nrq_rx_held", &rx, 1, d_tags, cap, h_n);
+}
+
+int nrq_orx_held(nrq_orx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!rx) return -1;
+  return held_list(rx->ctx, "nrq_orx_held", rx->rx, 2, d_tags, cap, h_n); /* (class L, then class S: SBN order) */
 }
 
 } /* extern "C" */
