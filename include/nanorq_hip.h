@@ -283,6 +283,32 @@ int nrq_rx_reset(nrq_rx *rx); /* forget everything received (enqueue only); the 
  * while a read from the host or from another stream needs nrq_ctx_sync first.  It is the list a relay's NRQ_TX_HELD emit writes
  * in full (below). */
 int nrq_rx_held(nrq_rx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n);
+/* What the reception WANTS: the tags (nanorq_tag() form) it asks upstream for to top its blocks up, listed on the device -- the
+ * NACK of a node in a distribution tree, in the form nrq_tx_emit / nrq_otx_emit take (with or without NRQ_TX_HELD), so the loop
+ * want -> emit -> add -> decode runs without a host-built list.  Per block b, with g = its missing source symbols (nlost of
+ * nrq_rx_counts) and r = its repair rows in use, min(nrep, rep_cap):
+ *   g == 0 (complete: nothing was missing, or a decode recovered it): nothing, in either mode.
+ *   flags == NRQ_WANT_SOURCE: the g source ESIs < K whose seen bit is clear, ascending -- the symbols a parent relay that is not
+ *     ready can still give under NRQ_TX_HELD where it holds them, and a sender gives as plain row copies.  extra and esi_from
+ *     must be 0 (-1).
+ *   flags == 0 (repair symbols): need = max(g + extra - r, 0), capped at the free repair rows rep_cap - r (a symbol beyond them
+ *     would only come back NRQ_RX_FULL); the list is the `need` lowest ESIs e with max(K, esi_from) <= e <= max_esi whose seen bit
+ *     is clear, ascending -- shorter if the range holds fewer, empty if esi_from > max_esi.  A repair ESI's seen bit is set only
+ *     when the symbol was ADDED: one that got NRQ_RX_FULL is asked for again, which is intended.  extra > 2^24: -1.
+ *   any other flag bit: -1.
+ * Tags are ((sbn0 + b) << 24) | e, block-major in SBN order.  The list depends on the reception's books alone: the same books
+ * give the same list.
+ * extra is the overhead wanted beyond g received symbols (0, 1 or 2 in practice).  RANK DEFICIENCY: a block that nrq_rx_decode
+ * left at status 0 although r >= g has enough symbols but not enough independent ones; the reception keeps no decode verdicts, so
+ * such a block wants nothing until the caller raises extra above its surplus r - g (ask again with extra = r - g + 1 or more).
+ * The price on the other blocks is at most extra symbols each.  esi_from keeps the requests of a node with several parents, or
+ * to a parent that already runs a carousel, in disjoint ESI ranges.
+ * The calling contract is nrq_rx_held's: the call waits for the work enqueued before it and *h_n, the total, is final on return;
+ * d_tags NULL counts only; cap < *h_n: -1, *h_n still filled, nothing written; else the writing of d_tags is enqueued on the
+ * context's stream, so an emit enqueued behind it sees the tags without a host wait (a read from the host or from another stream
+ * needs nrq_ctx_sync first).  The call only reads the reception's books; after nrq_rx_reset every block wants all of itself. */
+#define NRQ_WANT_SOURCE 1u
+int nrq_rx_want(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n);
 
 /* ---- device-resident sender: packets (an optional FEC Payload ID and a payload, at a packet stride) written straight into
  * device memory -- for a GPU-direct NIC, or a kernel that sends from device memory -- for any list of (SBN, ESI) ----
@@ -408,6 +434,8 @@ void nrq_orx_destroy(nrq_orx *rx);
 int nrq_orx_add(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t flags, int32_t *d_results);
 int nrq_orx_counts(nrq_orx *rx, uint32_t *h_nlost, uint32_t *h_nrep); /* Z entries each */
 int nrq_orx_held(nrq_orx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n); /* as nrq_rx_held, over both block classes in SBN order */
+/* as nrq_rx_want, over both block classes in SBN order: each class with its own K, esi_from applies to both */
+int nrq_orx_want(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n);
 int nrq_orx_decode(nrq_orx *rx, int *h_status, uint32_t *h_used);    /* as nrq_rx_decode, Z entries */
 /* every complete block into d_out (F bytes, device) in the object's layout; bytes past F and the bytes of incomplete blocks are
  * left untouched.  Returns the number of blocks still incomplete (>= 0), or < 0 on error.  Waits for the counts, enqueues the

@@ -132,6 +132,9 @@ def lib():
     if hasattr(L, "nrq_rx_held"):  # (likewise a build from before the held symbols: held() then raises, held=True is refused)
         L.nrq_rx_held.argtypes = [vp, vp, C.c_uint32, u32p]
         L.nrq_orx_held.argtypes = [vp, vp, C.c_uint32, u32p]
+    if hasattr(L, "nrq_rx_want"):  # (likewise a build from before the want listing: want() then raises)
+        L.nrq_rx_want.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, u32p]
+        L.nrq_orx_want.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -470,6 +473,15 @@ class Receiver(_Handle):
         relay().emit(tags, held=True) writes in full."""
         return _held(self)
 
+    def want(self, extra=0, source=False, esi_from=0):
+        """The tags (nanorq_tag() form) the reception asks upstream for, as an [n] int32 device tensor listed on the device,
+        block-major and ascending within a block (waits).  Default: per incomplete block the lowest unseen repair ESIs from
+        max(K, esi_from), as many as it lacks plus `extra`, less the repair rows it has, at most its free repair rows.
+        source=True (WANT_SOURCE): its missing source ESIs -- what parent.emit(tags, held=True) of a relay that is not ready can
+        still answer.  A complete block wants nothing.  A block a decode left at status 0 with enough symbols (rank deficient)
+        wants nothing until extra exceeds its surplus."""
+        return _want(self, extra, source, esi_from)
+
     def relay(self):
         """A Sender over this reception's own rows (nrq_rx_relay): it emits any (SBN, ESI) of every block that is ready -- decoded
         while the relay was attached, or complete and made ready by its encode().  One per reception."""
@@ -485,6 +497,23 @@ def _held(rx):
     out = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % rx.ctx.device)
     if n.value:
         rx.ctx._chk(fn(rx._h, C.c_void_p(_dptr(out)), n.value, C.byref(n)))
+        rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
+    return out
+
+
+WANT_SOURCE = 1     # NRQ_WANT_SOURCE
+
+
+def _want(rx, extra, source, esi_from):
+    """<_api>_want: the count first, then the tags into a tensor of that size"""
+    import torch
+    n = C.c_uint32(0)
+    fn = getattr(rx._L, rx._api + "_want")
+    args = (WANT_SOURCE if source else 0, extra, esi_from)
+    rx.ctx._chk(fn(rx._h, *args, None, 0, C.byref(n)))
+    out = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % rx.ctx.device)
+    if n.value:
+        rx.ctx._chk(fn(rx._h, *args, C.c_void_p(_dptr(out)), n.value, C.byref(n)))
         rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
     return out
 
@@ -714,6 +743,10 @@ class ObjectReceiver(_Handle):
     def held(self):
         """as Receiver.held, over both block classes in SBN order"""
         return _held(self)
+
+    def want(self, extra=0, source=False, esi_from=0):
+        """as Receiver.want, over both block classes in SBN order (each class with its own K)"""
+        return _want(self, extra, source, esi_from)
 
     def relay(self):
         """An ObjectSender over this receiver's row images (nrq_orx_relay): it emits any (SBN, ESI) of every block that is ready,

@@ -34,6 +34,7 @@
 #include "planner_body.h"
 #include "ingest_body.h"
 #include "held_body.h"
+#include "want_body.h"
 #include "emit_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
@@ -3000,9 +3001,9 @@ struct nrq_rx {
   void *own_src, *own_rep;
   void *scratch;        /* per-call arrays */
   size_t scratch_cap;
-  void *lists;          /* nrq_ing_lists_kernel output, written anew by every call that reads it.  rx_held_count borrows its first
-                         * nblk + 1 words for the held offsets and total: both users run on the context's stream and neither
-                         * expects the buffer to survive from one call to the next -- keep it so */
+  void *lists;          /* nrq_ing_lists_kernel output, written anew by every call that reads it.  rx_held_count and rx_want_count
+                         * each borrow its first nblk + 1 words for their offsets and total: all users run on the context's stream
+                         * and none expects the buffer to survive from one call to the next -- keep it so */
   tx_sender *relay;     /* the relay attached to this reception (nrq_rx_relay / nrq_orx_relay), or null ... */
   uint32_t relay_seg, relay_b0; /* ... in whose table this reception is segment relay_seg, its block 0 the span's block relay_b0 */
 };
@@ -4182,9 +4183,11 @@ __global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint
 }
 
 /* count and scan, enqueued: the blocks' exclusive offsets and, behind them, the total, in the reception's list buffer.
- * That buffer is the output of nrq_ing_lists_kernel (nrq_rx.lists), of whose 2 * nblk + ... words this takes the first nblk + 1:
- * rx_fetch_lists launches its kernel again before it reads, the fill kernel reads the offsets on the same stream before anything
- * later can overwrite them, so the two uses cannot meet.  A caller that kept the lists on the device across calls would break this. */
+ * That buffer is the output of nrq_ing_lists_kernel (nrq_rx.lists), of whose 2 * nblk + ... words this takes the first nblk + 1,
+ * and so does rx_want_count below.  The rule for every user: write the words anew in the call that reads them, read them on the
+ * context's stream within that call, expect nothing of them afterwards.  rx_fetch_lists launches its kernel again before it
+ * reads, the fill kernels read the offsets on the same stream before anything later can overwrite them, so the uses cannot meet.
+ * A caller that kept the lists on the device across calls would break this. */
 static int rx_held_count(nrq_rx *rx) {
   nrq_ctx *ctx = rx->ctx;
   const ing_rx &r = rx->r;
@@ -4232,6 +4235,112 @@ int nrq_rx_held(nrq_rx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
 int nrq_orx_held(nrq_orx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
   if (!rx) return -1;
   return held_list(rx->ctx, "nrq_orx_held", rx->rx, 2, d_tags, cap, h_n); /* (class L, then class S: SBN order) */
+}
+
+} /* extern "C" */
+
+/* ================================================ what a reception wants (nrq_rx_want / nrq_orx_want, want_body.h) ==== */
+/* one workgroup per block: the tags it lists -> cnt[b].  Rounds of 256 seen words from the word of ESI lo, until `need` wanted
+ * ESIs are found or the range ends: in repair mode that is one round unless thousands of symbols are asked for, whatever max_esi */
+__global__ __launch_bounds__(256) void nrq_want_count_kernel(ing_rx r, wn_q q, uint32_t *cnt) {
+  __shared__ uint32_t ps[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x, w_end = wn_end(&q), need = wn_need(&r, &q, b);
+  uint32_t found = 0;
+  for (uint32_t w0 = wn_first(&q); w0 < w_end && found < need; w0 += WN_ROUND) { /* (found and need are the same in every thread) */
+    const uint32_t w = w0 + t;
+    ps[t] = w < w_end ? hl_popc(wn_bits(&r, &q, b, w)) : 0u;
+    __syncthreads();
+    for (uint32_t s = 128; s; s >>= 1) {
+      if (t < s) ps[t] += ps[t + s];
+      __syncthreads();
+    }
+    found += ps[0];
+    __syncthreads();
+  }
+  if (t == 0) cnt[b] = min(found, need);
+}
+
+/* one workgroup per block: its tags to out + off[b], ascending -- per round a scan over the 256 words' counts gives each word the
+ * rank of its first wanted ESI in the block, and the word writes those of rank below `need` */
+__global__ __launch_bounds__(256) void nrq_want_fill_kernel(ing_rx r, wn_q q, const uint32_t *off, uint32_t *out) {
+  __shared__ uint32_t ps[256];
+  const uint32_t b = blockIdx.x, t = threadIdx.x, w_end = wn_end(&q), need = wn_need(&r, &q, b);
+  uint32_t *dst = out + off[b];
+  uint32_t placed = 0;
+  for (uint32_t w0 = wn_first(&q); w0 < w_end && placed < need; w0 += WN_ROUND) {
+    const uint32_t w = w0 + t;
+    const uint32_t bits = w < w_end ? wn_bits(&r, &q, b, w) : 0u, c = hl_popc(bits);
+    ps[t] = c;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+      const uint32_t v = t >= d ? ps[t - d] : 0u;
+      __syncthreads();
+      ps[t] += v;
+      __syncthreads();
+    }
+    wn_put(&r, b, w, bits, placed + ps[t] - c, need, dst);
+    placed += ps[255];
+    __syncthreads();
+  }
+}
+
+/* count and scan, enqueued, into the first nblk + 1 words of the reception's list buffer (the rule: rx_held_count) */
+static int rx_want_count(nrq_rx *rx, const wn_q &q) {
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  uint32_t *cnt = (uint32_t *)rx->lists;
+  HIPCHK(ctx, hipMemsetAsync(cnt + r.nblk, 0, 4u, ctx->stream));
+  hipLaunchKernelGGL(nrq_want_count_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, q, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, r.nblk + 1u, cnt);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* the wanted tags of up to two receptions, one behind the other */
+static int want_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t flags, uint32_t extra, uint32_t esi_from,
+                     uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
+  *h_n = 0;
+  switch (wn_check(flags, extra, esi_from)) {
+    case 1: return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+    case 2: return fail(ctx, -1, "%s: NRQ_WANT_SOURCE takes neither extra nor esi_from (%u, %u)", who, extra, esi_from);
+    case 3: return fail(ctx, -1, "%s: extra %u is above 2^24", who, extra);
+    default: break;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t n[2] = {0, 0};
+  wn_q q[2] = {};
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    q[i] = wn_query(&rxs[i]->r, flags, extra, esi_from);
+    const int rc = rx_want_count(rxs[i], q[i]);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&n[i], (uint32_t *)rxs[i]->lists + rxs[i]->r.nblk, 4u, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *h_n = n[0] + n[1];
+  if (!d_tags) return 0;
+  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are wanted, d_tags has room for %u", who, *h_n, cap);
+  uint32_t at = 0;
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    if (n[i]) hipLaunchKernelGGL(nrq_want_fill_kernel, dim3(rxs[i]->r.nblk), dim3(256), 0, ctx->stream, rxs[i]->r, q[i], (const uint32_t *)rxs[i]->lists, d_tags + at);
+    at += n[i];
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rx_want(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!rx) return -1;
+  return want_list(rx->ctx, "nrq_rx_want", &rx, 1, flags, extra, esi_from, d_tags, cap, h_n);
+}
+
+int nrq_orx_want(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!rx) return -1;
+  return want_list(rx->ctx, "nrq_orx_want", rx->rx, 2, flags, extra, esi_from, d_tags, cap, h_n); /* (class L, then class S: SBN order) */
 }
 
 } /* extern "C" */
