@@ -451,6 +451,41 @@ int nrq_orx_write(nrq_orx *rx, void *d_out);
  * receiver (else it is detached). */
 int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
 
+/* ---- reception sets: the packets of MANY receptions in one buffer, ingested in one pass ----
+ * A set is a table of member receptions of one context and one T, each under a 32-bit KEY the caller chooses (a TOI, a flow
+ * number): a tag names (SBN, ESI) and nothing more, the key names the reception or object the SBN belongs to.  nrq_rxset_add
+ * runs the passes of nrq_rx_add once over all packets with the table in device memory, where today R receptions fed from one
+ * buffer cost R scans (and an object of two block classes two and a half).  Members stay ordinary receptions: nrq_rx_add /
+ * nrq_orx_add on a member between two set calls, counts, lists, decode, reset, held, want and relays work on the same books.
+ * The caps follow from the kernels: one LDS counter per block in the histogram pass and four in the classify pass (4 KB + 16 KB at
+ * 1024 blocks), 4 B x blocks x tiles of scratch, a linear search over the members per packet. */
+typedef struct nrq_rxset nrq_rxset;
+#define NRQ_RXSET_MAX_MEMBERS 64u   /* receptions (an object with two classes counts twice) */
+#define NRQ_RXSET_MAX_BLOCKS  1024u /* blocks over all members */
+#define NRQ_RX_KEY_INLINE 2u        /* with NRQ_RX_TAG_INLINE: packet = key (32 bits, network byte order), FEC Payload ID, payload at +8 */
+int nrq_rxset_create(nrq_ctx *ctx, uint32_t T, nrq_rxset **out);
+void nrq_rxset_destroy(nrq_rxset *set); /* members live on, detached */
+/* Attach a reception, or an object receiver (both block classes, and the SBN >= Z rule of nrq_orx_add), under `key`.  Refused
+ * (-1, nrq_ctx_error): another context; a T that is not the set's; a reception that is in a set already; a (key, SBN span) that
+ * overlaps a member's (the same span under another key is fine, so is another span under the same key); for an object, any other
+ * member under its key, and any further member under an object's key -- an object owns its key; a cap exceeded.  Attach and
+ * detach wait for the context's stream (the table lives in device memory).  Destroying a member that is still attached detaches
+ * it first. */
+int nrq_rxset_attach(nrq_rxset *set, uint32_t key, nrq_rx *rx);
+int nrq_rxset_attach_obj(nrq_rxset *set, uint32_t key, nrq_orx *orx);
+int nrq_rxset_detach(nrq_rxset *set, uint32_t key); /* every member under key; unknown key: -1 */
+/* Ingest n packets (enqueue only, on the context's stream).  Packets and tags as in nrq_rx_add; packet k's key is d_keys[k]
+ * (device), or lies in the packet in front of the FEC Payload ID with NRQ_RX_KEY_INLINE | NRQ_RX_TAG_INLINE (d_keys and d_tags
+ * NULL; pkt_stride >= T + 8), or is 0 for every packet (d_keys NULL without the flag).  Every member ends with what nrq_rx_add on
+ * it alone gives for exactly the packets that carry its key, in packet order: the same codes in the same entries of d_results
+ * (device, nullable), the same rows, the same repair list in arrival order, the same counts and seen bits.  A packet with an
+ * attached object's key and SBN >= Z gets what nrq_orx_add gives it (ERR above max_esi, else IGN).  A packet that belongs to no
+ * member -- an unknown key, or a known key that is no object's with an SBN outside its members -- keeps its d_results entry
+ * untouched, and nothing of it is copied.  n == 0 and an empty set: 0.  Errors (-1): those of nrq_rx_add, NRQ_RX_KEY_INLINE
+ * without NRQ_RX_TAG_INLINE, NRQ_RX_KEY_INLINE with d_keys. */
+int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
+                  uint32_t flags, int32_t *d_results);
+
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()
  * synchronises, returns the durations of the launches since the last read/enable in launch order. */

@@ -135,6 +135,14 @@ def lib():
     if hasattr(L, "nrq_rx_want"):  # (likewise a build from before the want listing: want() then raises)
         L.nrq_rx_want.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, u32p]
         L.nrq_orx_want.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, u32p]
+    if hasattr(L, "nrq_rxset_create"):  # (likewise a build from before the reception sets: ReceiverSet then raises)
+        L.nrq_rxset_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+        L.nrq_rxset_destroy.argtypes = [vp]
+        L.nrq_rxset_destroy.restype = None
+        L.nrq_rxset_attach.argtypes = [vp, C.c_uint32, vp]
+        L.nrq_rxset_attach_obj.argtypes = [vp, C.c_uint32, vp]
+        L.nrq_rxset_detach.argtypes = [vp, C.c_uint32]
+        L.nrq_rxset_add.argtypes = [vp, vp, sz, vp, vp, C.c_uint32, C.c_uint32, vp]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -360,6 +368,9 @@ class Context:
 
 RX_TAG_INLINE = 1   # NRQ_RX_TAG_INLINE
 RX_FULL = 3         # NRQ_RX_FULL
+RX_KEY_INLINE = 2   # NRQ_RX_KEY_INLINE
+RXSET_MAX_MEMBERS = 64   # NRQ_RXSET_MAX_MEMBERS
+RXSET_MAX_BLOCKS = 1024  # NRQ_RXSET_MAX_BLOCKS
 
 
 def _dptr(x):
@@ -765,6 +776,53 @@ class ObjectReceiver(_Handle):
         rc = self._L.nrq_orx_write(self._h, C.c_void_p(_dptr(out)))
         self.ctx._chk(min(rc, 0))
         return out, rc
+
+
+class ReceiverSet(_Handle):
+    """A set of device-resident receptions of one T (nrq_rxset, include/nanorq_hip.h): Receivers and ObjectReceivers attached
+    under 32-bit keys, fed from ONE packet buffer in one pass.  Members stay ordinary receptions; closing one detaches it, closing
+    the set leaves its members usable."""
+    _api = "nrq_rxset"
+
+    def __init__(self, ctx, T):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.T = T
+        self._members = {}  # key -> the attached receivers (kept alive as long as they are attached)
+        if not hasattr(self._L, "nrq_rxset_create"):
+            raise NrqError("this library build has no reception sets")
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_rxset_create(ctx._h, T, C.byref(h)))
+        self._h = h
+
+    def attach(self, key, rx):
+        """rx: a Receiver, or an ObjectReceiver (both block classes; it owns its key).  May wait for the context's stream."""
+        fn = self._L.nrq_rxset_attach_obj if isinstance(rx, ObjectReceiver) else self._L.nrq_rxset_attach
+        self.ctx._chk(fn(self._h, key, rx._h))
+        self._members.setdefault(key, []).append(rx)
+
+    def detach(self, key):
+        """every member under key (an unknown key raises).  May wait for the context's stream."""
+        self.ctx._chk(self._L.nrq_rxset_detach(self._h, key))
+        self._members.pop(key, None)
+
+    def add(self, payload, keys=None, tags=None, inline=False, key_inline=False, results=None, n=None, stride=None):
+        """Ingest the packets of all members (enqueue only).  payload, tags, inline, results, n, stride as in Receiver.add; keys:
+        [n] int32 / uint32 device tensor of each packet's key, or key_inline=True (with inline=True) when each packet starts with
+        its key in front of the FEC Payload ID, or neither: every packet has key 0.  Packets that belong to no member keep their
+        results entry."""
+        if hasattr(payload, "data_ptr"):
+            n = payload.shape[0] if n is None else n
+            stride = payload.stride(0) * payload.element_size() if stride is None else stride
+        if n is None or stride is None:
+            raise ValueError("a raw payload address needs n and stride")
+        if inline == (tags is not None):
+            raise ValueError("give either tags or inline=True")
+        if key_inline and (not inline or keys is not None):
+            raise ValueError("key_inline=True goes with inline=True and without keys")
+        flags = (RX_TAG_INLINE if inline else 0) | (RX_KEY_INLINE if key_inline else 0)
+        self.ctx._chk(self._L.nrq_rxset_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)),
+                                            n, flags, C.c_void_p(_dptr(results))))
 
 
 def plan_ops(plan, header=None):

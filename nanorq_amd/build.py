@@ -23,6 +23,7 @@ OEMU = os.path.join(ROOT, "tests", "emu", "libobj_emu.so")
 SEMU = os.path.join(ROOT, "tests", "emu", "libshape_emu.so")
 HEMU = os.path.join(ROOT, "tests", "emu", "libheld_emu.so")
 WEMU = os.path.join(ROOT, "tests", "emu", "libwant_emu.so")
+REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -147,6 +148,11 @@ def build_want_emu(force=False):
     return _build_emu(WEMU, os.path.join(CSRC, "want_emu.cpp"), ("want_body.h", "held_body.h", "ingest_body.h"), force)
 
 
+def build_rxset_emu(force=False):
+    """tests/emu/librxset_emu.so: CPU emulation of a reception set's ingest (csrc/rxset_emu.cpp over ingest_set_body.h)."""
+    return _build_emu(REMU, os.path.join(CSRC, "rxset_emu.cpp"), ("ingest_set_body.h", "ingest_body.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -166,6 +172,7 @@ if __name__ == "__main__":
     build_emit_emu(force="-f" in sys.argv)
     build_held_emu(force="-f" in sys.argv)
     build_want_emu(force="-f" in sys.argv)
+    build_rxset_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

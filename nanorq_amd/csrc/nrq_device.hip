@@ -33,6 +33,7 @@
 #include "solve_body.h"
 #include "planner_body.h"
 #include "ingest_body.h"
+#include "ingest_set_body.h"
 #include "held_body.h"
 #include "want_body.h"
 #include "emit_body.h"
@@ -2933,6 +2934,7 @@ __global__ __launch_bounds__(256) void nrq_ing_fold_kernel(ing_rx r, ing_call c)
 
 struct ing_mask { uint32_t w[8]; }; /* a bit per block of the reception (nblk <= 256) */
 struct tx_sender;
+struct nrq_rxset;
 
 /* blocks a decode recovered: every source ESI counts as seen from now on (what nanorq_repair_block does to the bitmap) */
 __global__ __launch_bounds__(256) void nrq_ing_mark_kernel(ing_rx r, ing_mask m) {
@@ -3006,12 +3008,14 @@ struct nrq_rx {
                          * and none expects the buffer to survive from one call to the next -- keep it so */
   tx_sender *relay;     /* the relay attached to this reception (nrq_rx_relay / nrq_orx_relay), or null ... */
   uint32_t relay_seg, relay_b0; /* ... in whose table this reception is segment relay_seg, its block 0 the span's block relay_b0 */
+  nrq_rxset *set;       /* the reception set this reception is a member of (nrq_rxset_attach), or null */
 };
 
 /* the relay's side of a reception (defined with the senders below) */
 static uint64_t relay_inter(const tx_sender *tx, uint32_t seg, uint32_t b); /* where block b of segment seg has its intermediate symbols */
 static void relay_set(tx_sender *tx, uint32_t b0, uint32_t nblk, bool valid); /* blocks b0 .. b0+nblk-1 of the span: intermediate symbols (not) written */
 static void relay_detach(tx_sender *tx);                                    /* a reception of the relay goes away */
+static void rxset_drop(nrq_rx *rx);                                         /* a member of a reception set goes away (defined with the sets below) */
 
 static size_t rx_al(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
@@ -3085,6 +3089,7 @@ void nrq_rx_destroy(nrq_rx *rx) {
   if (!rx) return;
   nrq_ctx *ctx = rx->ctx;
   if (rx->relay) relay_detach(rx->relay); /* (its later calls fail with an error text; it frees what it owns itself) */
+  if (rx->set) rxset_drop(rx);            /* (the set's table is rewritten without it, behind the work enqueued so far) */
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
   for (void *p : {rx->own_src, rx->own_rep, rx->state, rx->scratch, rx->lists})
     if (p) nrq_dev_free(ctx, p);
@@ -4341,6 +4346,351 @@ int nrq_rx_want(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, u
 int nrq_orx_want(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
   if (!rx) return -1;
   return want_list(rx->ctx, "nrq_orx_want", rx->rx, 2, flags, extra, esi_from, d_tags, cap, h_n); /* (class L, then class S: SBN order) */
+}
+
+} /* extern "C" */
+
+/* ================================================ reception sets (nrq_rxset_*, ingest_set_body.h) ==== */
+/* The seven passes of the ingest above over a member table in device memory: one chain of kernels for the packets of all
+ * members.  Per-block passes run one workgroup per GLOBAL block and find its member from the block offsets; per-tile passes count
+ * per global block in LDS sized by the set's block total (dynamic: a set of 256 blocks pays what a reception of 256 blocks pays). */
+__global__ __launch_bounds__(256) void nrq_ings_first_kernel(const ings_tab *__restrict__ t, ings_call s) {
+  __shared__ uint32_t skey[INGS_MAX_MEMBERS], ssbn0[INGS_MAX_MEMBERS], scnt[INGS_MAX_MEMBERS], sobjZ[INGS_MAX_MEMBERS];
+  const uint32_t nmem = t->nmem, i = threadIdx.x;
+  if (i < nmem) { skey[i] = t->key[i]; ssbn0[i] = t->sbn0[i]; scnt[i] = t->cnt[i]; sobjZ[i] = t->objZ[i]; }
+  __syncthreads();
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= s.c.n) return;
+  uint32_t key, tag;
+  ings_decode(&s, k, &key, &tag);
+  ings_first(t, &s, k, tag, ings_find(skey, ssbn0, scnt, sobjZ, nmem, key, tag >> 24));
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_done_kernel(const ings_tab *__restrict__ t) {
+  __shared__ uint32_t smx[256], scnt[256];
+  const uint32_t g = blockIdx.x, i = threadIdx.x;
+  const uint32_t m = ings_member_of_block(t->blk0, t->nmem, g), b = g - t->blk0[m];
+  const ing_rx *r = &t->r[m];
+  const uint32_t K = r->K;
+  uint32_t mx = 0, cnt = 0;
+  if (r->gaps[b])
+    for (uint32_t e = i; e < K; e += 256u) ing_done_part(r, b, e, &mx, &cnt);
+  smx[i] = mx;
+  scnt[i] = cnt;
+  __syncthreads();
+  for (uint32_t d = 128; d; d >>= 1) {
+    if (i < d) { smx[i] = max(smx[i], smx[i + d]); scnt[i] += scnt[i + d]; }
+    __syncthreads();
+  }
+  if (i == 0) ing_done_finish(r, b, smx[0], scnt[0]);
+}
+
+/* dynamic LDS: t->nblk counters */
+__global__ __launch_bounds__(256) void nrq_ings_hist_kernel(const ings_tab *__restrict__ t, ings_call s) {
+  extern __shared__ uint32_t ings_h[];
+  const uint32_t i = threadIdx.x, k = blockIdx.x * ING_TILE + i, nb = t->nblk;
+  for (uint32_t g = i; g < nb; g += 256u) ings_h[g] = 0;
+  __syncthreads();
+  if (k < s.c.n) {
+    const uint32_t g = ings_cand(t, &s, k);
+    if (g != ING_NONE) atomicAdd(&ings_h[g], 1u);
+  }
+  __syncthreads();
+  for (uint32_t g = i; g < nb; g += 256u) s.c.base[(size_t)g * s.c.ntiles + blockIdx.x] = ings_h[g];
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_scan_kernel(const ings_tab *__restrict__ t, ings_call s) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x, i = threadIdx.x, nt = s.c.ntiles;
+  const uint32_t m = ings_member_of_block(t->blk0, t->nmem, g), b = g - t->blk0[m];
+  const ing_rx *r = &t->r[m];
+  const uint32_t per = (nt + 255u) / 256u, t0 = min(nt, i * per), t1 = min(nt, t0 + per);
+  uint32_t *base = s.c.base + (size_t)g * nt;
+  uint32_t sum = 0;
+  for (uint32_t j = t0; j < t1; j++) sum += base[j];
+  ps[i] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+    const uint32_t v = i >= d ? ps[i - d] : 0u;
+    __syncthreads();
+    ps[i] += v;
+    __syncthreads();
+  }
+  const uint32_t nrep0 = r->nrep[b], total = ps[255];
+  uint32_t run = nrep0 + ps[i] - sum;
+  for (uint32_t j = t0; j < t1; j++) { const uint32_t v = base[j]; base[j] = run; run += v; }
+  __syncthreads(); /* (every thread has read nrep[b]) */
+  if (i == 0) r->nrep[b] = min(nrep0 + total, r->rep_cap);
+}
+
+/* dynamic LDS: 4 * t->nblk counters (per wave, per global block).  The ballot loop is the one of nrq_ing_classify_kernel with the
+ * global block in place of the local one: a wave may hold candidates of several members. */
+__global__ __launch_bounds__(256) void nrq_ings_classify_kernel(const ings_tab *__restrict__ t, ings_call s) {
+  extern __shared__ uint32_t ings_wc[];
+  const uint32_t i = threadIdx.x, lane = i & 63u, w = i >> 6, k = blockIdx.x * ING_TILE + i, nb = t->nblk;
+  for (uint32_t j = i; j < 4u * nb; j += 256u) ings_wc[j] = 0;
+  __syncthreads();
+  const uint32_t g = k < s.c.n ? ings_cand(t, &s, k) : ING_NONE;
+  const bool cand = g != ING_NONE;
+  uint64_t todo = __ballot(cand);
+  uint32_t rank = 0;
+  while (todo) { /* (wave-uniform) */
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t lg = __shfl(g, leader);
+    const bool mine = cand && g == lg;
+    const uint64_t mk = __ballot(mine);
+    if (mine) rank = (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
+    if ((int)lane == leader) ings_wc[w * nb + lg] = (uint32_t)__popcll(mk);
+    todo &= ~mk;
+  }
+  __syncthreads();
+  uint32_t row = ING_NONE;
+  if (cand) {
+    row = s.c.base[(size_t)g * s.c.ntiles + blockIdx.x] + rank;
+    for (uint32_t w2 = 0; w2 < w; w2++) row += ings_wc[w2 * nb + g];
+  }
+  if (k < s.c.n) ings_classify(t, &s, k, row);
+}
+
+/* nrq_ing_copy_kernel with the payload's offset in the packet (0, 4 or 8) as an argument */
+__global__ __launch_bounds__(256) void nrq_ings_copy_kernel(const uint8_t *__restrict__ pkts, uint64_t pkt_stride, const uint64_t *__restrict__ dst,
+                                                            uint32_t n, uint32_t T, uint32_t poff) {
+  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (k >= n) return;
+  uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(dst[k]);
+  if (!d) return;
+  const uint8_t *__restrict__ sp = pkts + (size_t)k * pkt_stride + poff;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(sp) | reinterpret_cast<uintptr_t>(d) | T;
+  if ((al & 15u) == 0) {
+    for (uint32_t off = lane * 16u; off < T; off += 2u * 1024u) {
+      const uint4 v0 = *reinterpret_cast<const uint4 *>(sp + off);
+      const bool two = off + 1024u < T;
+      uint4 v1;
+      if (two) v1 = *reinterpret_cast<const uint4 *>(sp + off + 1024u);
+      *reinterpret_cast<uint4 *>(d + off) = v0;
+      if (two) *reinterpret_cast<uint4 *>(d + off + 1024u) = v1;
+    }
+  } else if ((al & 3u) == 0) {
+    for (uint32_t off = lane * 4u; off < T; off += 2u * 256u) {
+      const uint32_t v0 = *reinterpret_cast<const uint32_t *>(sp + off);
+      const bool two = off + 256u < T;
+      uint32_t v1 = 0;
+      if (two) v1 = *reinterpret_cast<const uint32_t *>(sp + off + 256u);
+      *reinterpret_cast<uint32_t *>(d + off) = v0;
+      if (two) *reinterpret_cast<uint32_t *>(d + off + 256u) = v1;
+    }
+  } else {
+    for (uint32_t off = lane; off < T; off += 64u) d[off] = sp[off];
+  }
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_fold_kernel(const ings_tab *__restrict__ t, ings_call s) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k < s.c.n) ings_fold(t, &s, k);
+}
+
+static_assert(NRQ_RXSET_MAX_MEMBERS == INGS_MAX_MEMBERS && NRQ_RXSET_MAX_BLOCKS == INGS_MAX_BLOCKS, "the header's caps are the kernels'");
+
+struct rxset_member {
+  uint32_t key;
+  nrq_rx *rx;
+  uint32_t objZ; /* a block class of an attached object of Z blocks; 0: a plain reception */
+};
+
+struct nrq_rxset {
+  nrq_ctx *ctx;
+  uint32_t T;
+  std::vector<rxset_member> mem; /* sorted by (key, sbn0): the order of the device table */
+  uint32_t nblk;                 /* blocks over all members */
+  void *tab;                     /* struct ings_tab in device memory */
+  void *scratch;                 /* per-call arrays */
+  size_t scratch_cap;
+};
+
+/* the member table as `mem` has it, into device memory.  Waits for the stream first: an ingest enqueued before still reads the
+ * old table. */
+static int rxset_upload(nrq_rxset *set, const std::vector<rxset_member> &mem) {
+  nrq_ctx *ctx = set->ctx;
+  std::vector<ings_tab> hv(1);
+  ings_tab &h = hv[0];
+  memset(&h, 0, sizeof(h));
+  h.nmem = (uint32_t)mem.size();
+  for (uint32_t i = 0; i < h.nmem; i++) {
+    const ing_rx &r = mem[i].rx->r;
+    h.key[i] = mem[i].key; h.sbn0[i] = r.sbn0; h.cnt[i] = r.nblk; h.objZ[i] = mem[i].objZ;
+    h.blk0[i] = h.nblk;
+    h.nblk += r.nblk;
+    h.r[i] = r;
+  }
+  h.blk0[h.nmem] = h.nblk;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy(set->tab, &h, sizeof(h), hipMemcpyHostToDevice));
+  return 0;
+}
+
+/* take `mem` as the set's members (sorted here); on failure the set keeps the ones it had */
+static int rxset_commit(nrq_rxset *set, std::vector<rxset_member> &mem) {
+  std::sort(mem.begin(), mem.end(), [](const rxset_member &a, const rxset_member &b) {
+    return a.key != b.key ? a.key < b.key : a.rx->r.sbn0 < b.rx->r.sbn0;
+  });
+  const int rc = rxset_upload(set, mem);
+  if (rc) return rc;
+  for (const rxset_member &m : set->mem) m.rx->set = nullptr;
+  set->mem.swap(mem);
+  set->nblk = 0;
+  for (const rxset_member &m : set->mem) { m.rx->set = set; set->nblk += m.rx->r.nblk; }
+  return 0;
+}
+
+/* a reception goes away (nrq_rx_destroy): it leaves its set first */
+static void rxset_drop(nrq_rx *rx) {
+  nrq_rxset *set = rx->set;
+  std::vector<rxset_member> mem;
+  for (const rxset_member &m : set->mem)
+    if (m.rx != rx) mem.push_back(m);
+  if (rxset_commit(set, mem) != 0) { /* (the table could not be written: an empty host list keeps every later ingest off the stale one) */
+    for (const rxset_member &m : set->mem) m.rx->set = nullptr;
+    set->mem.clear();
+    set->nblk = 0;
+  }
+}
+
+static int rxset_attach(nrq_rxset *set, const char *who, uint32_t key, nrq_rx *const *rxs, int nrx, uint32_t objZ) {
+  nrq_ctx *ctx = set->ctx;
+  std::vector<rxset_member> mem = set->mem;
+  uint32_t nblk = set->nblk;
+  for (int i = 0; i < nrx; i++) {
+    nrq_rx *rx = rxs[i];
+    if (!rx) continue;
+    const ing_rx &r = rx->r;
+    if (rx->ctx != ctx) return fail(ctx, -1, "%s: the reception belongs to another context", who);
+    if (r.T != set->T) return fail(ctx, -1, "%s: the reception's T %u is not the set's %u", who, r.T, set->T);
+    if (rx->set) return fail(ctx, -1, "%s: the reception is in a set already", who);
+    for (const rxset_member &m : set->mem) {
+      if (m.key != key) continue;
+      if (objZ || m.objZ) return fail(ctx, -1, "%s: key %u has members already, and an object owns its key", who, key);
+      const ing_rx &o = m.rx->r;
+      if (r.sbn0 < o.sbn0 + o.nblk && o.sbn0 < r.sbn0 + r.nblk)
+        return fail(ctx, -1, "%s: SBNs %u..%u under key %u overlap a member's %u..%u", who, r.sbn0, r.sbn0 + r.nblk - 1u, key, o.sbn0,
+                    o.sbn0 + o.nblk - 1u);
+    }
+    if (mem.size() >= NRQ_RXSET_MAX_MEMBERS) return fail(ctx, -1, "%s: a set holds at most %u receptions", who, NRQ_RXSET_MAX_MEMBERS);
+    if (nblk + r.nblk > NRQ_RXSET_MAX_BLOCKS) return fail(ctx, -1, "%s: a set holds at most %u blocks", who, NRQ_RXSET_MAX_BLOCKS);
+    nblk += r.nblk;
+    mem.push_back(rxset_member{key, rx, objZ});
+  }
+  if (mem.size() == set->mem.size()) return fail(ctx, -1, "%s: nothing to attach", who);
+  return rxset_commit(set, mem);
+}
+
+extern "C" {
+
+int nrq_rxset_create(nrq_ctx *ctx, uint32_t T, nrq_rxset **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_rxset_create: out is NULL");
+  *out = nullptr;
+  if (T == 0) return fail(ctx, -1, "nrq_rxset_create: T is 0");
+  nrq_rxset *set = new (std::nothrow) nrq_rxset();
+  if (!set) return fail(ctx, -1, "nrq_rxset_create: out of host memory");
+  set->ctx = ctx;
+  set->T = T;
+  const int rc = nrq_dev_alloc(ctx, sizeof(ings_tab), &set->tab);
+  if (rc) {
+    delete set;
+    return rc;
+  }
+  *out = set;
+  return 0;
+}
+
+void nrq_rxset_destroy(nrq_rxset *set) {
+  if (!set) return;
+  nrq_ctx *ctx = set->ctx;
+  for (const rxset_member &m : set->mem) m.rx->set = nullptr;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {set->tab, set->scratch})
+    if (p) nrq_dev_free(ctx, p);
+  delete set;
+}
+
+int nrq_rxset_attach(nrq_rxset *set, uint32_t key, nrq_rx *rx) {
+  if (!set) return -1;
+  if (!rx) return fail(set->ctx, -1, "nrq_rxset_attach: the reception is NULL");
+  return rxset_attach(set, "nrq_rxset_attach", key, &rx, 1, 0);
+}
+
+int nrq_rxset_attach_obj(nrq_rxset *set, uint32_t key, nrq_orx *orx) {
+  if (!set) return -1;
+  if (!orx) return fail(set->ctx, -1, "nrq_rxset_attach_obj: the object receiver is NULL");
+  return rxset_attach(set, "nrq_rxset_attach_obj", key, orx->rx, 2, orx->prm.Z);
+}
+
+int nrq_rxset_detach(nrq_rxset *set, uint32_t key) {
+  if (!set) return -1;
+  std::vector<rxset_member> mem;
+  for (const rxset_member &m : set->mem)
+    if (m.key != key) mem.push_back(m);
+  if (mem.size() == set->mem.size()) return fail(set->ctx, -1, "nrq_rxset_detach: no member under key %u", key);
+  return rxset_commit(set, mem);
+}
+
+int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
+                  uint32_t flags, int32_t *d_results) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const bool inl = (flags & NRQ_RX_TAG_INLINE) != 0, kinl = (flags & NRQ_RX_KEY_INLINE) != 0;
+  if (flags & ~(uint32_t)(NRQ_RX_TAG_INLINE | NRQ_RX_KEY_INLINE)) return fail(ctx, -1, "nrq_rxset_add: unknown flags 0x%x", flags);
+  if (kinl && !inl) return fail(ctx, -1, "nrq_rxset_add: NRQ_RX_KEY_INLINE needs NRQ_RX_TAG_INLINE");
+  if (kinl && d_keys) return fail(ctx, -1, "nrq_rxset_add: give either d_keys or NRQ_RX_KEY_INLINE");
+  if (n == 0 || set->mem.empty()) return 0;
+  if (!d_pkts || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_rxset_add: bad packets (n=%u)", n);
+  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "nrq_rxset_add: give either d_tags or NRQ_RX_TAG_INLINE");
+  const uint32_t poff = kinl ? 8u : inl ? 4u : 0u;
+  if (pkt_stride < (size_t)set->T + poff) return fail(ctx, -1, "nrq_rxset_add: pkt_stride %zu shorter than a packet", pkt_stride);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ings_call s{};
+  ing_call &c = s.c;
+  c.pkts = (const uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.tags = d_tags;
+  c.n = n;
+  c.ntiles = (n + ING_TILE - 1u) / ING_TILE;
+  s.keys = d_keys;
+  s.key_inline = kinl ? 1u : 0u;
+  const size_t a4 = rx_al((size_t)n * 4u), o_mem = a4, o_codes = o_mem + a4, o_fidx = o_codes + a4, o_dst = o_fidx + a4,
+               o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)set->nblk * c.ntiles * 4u);
+  if (set->scratch_cap < need) {
+    if (set->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, set->scratch);
+      set->scratch = nullptr;
+      set->scratch_cap = 0;
+    }
+    int rc = nrq_dev_alloc(ctx, need, &set->scratch);
+    if (rc) return rc;
+    set->scratch_cap = need;
+  }
+  uint8_t *p = (uint8_t *)set->scratch;
+  c.tagv = (uint32_t *)p;
+  s.mem = (uint32_t *)(p + o_mem);
+  c.codes = d_results ? d_results : (int32_t *)(p + o_codes);
+  c.fidx = (uint32_t *)(p + o_fidx);
+  c.dst = (uint64_t *)(p + o_dst);
+  c.base = (uint32_t *)(p + o_base);
+  const ings_tab *t = (const ings_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  const uint32_t g = (n + 255u) / 256u, nb = set->nblk;
+  hipLaunchKernelGGL(nrq_ings_first_kernel, dim3(g), dim3(256), 0, st, t, s);
+  hipLaunchKernelGGL(nrq_ings_done_kernel, dim3(nb), dim3(256), 0, st, t);
+  hipLaunchKernelGGL(nrq_ings_hist_kernel, dim3(c.ntiles), dim3(256), nb * 4u, st, t, s);
+  hipLaunchKernelGGL(nrq_ings_scan_kernel, dim3(nb), dim3(256), 0, st, t, s);
+  hipLaunchKernelGGL(nrq_ings_classify_kernel, dim3(c.ntiles), dim3(256), nb * 16u, st, t, s);
+  hipLaunchKernelGGL(nrq_ings_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c.pkts, (uint64_t)pkt_stride, (const uint64_t *)c.dst, n, set->T,
+                     poff);
+  hipLaunchKernelGGL(nrq_ings_fold_kernel, dim3(g), dim3(256), 0, st, t, s);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
 }
 
 } /* extern "C" */
