@@ -485,6 +485,37 @@ int nrq_rxset_detach(nrq_rxset *set, uint32_t key); /* every member under key; u
  * without NRQ_RX_TAG_INLINE, NRQ_RX_KEY_INLINE with d_keys. */
 int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
                   uint32_t flags, int32_t *d_results);
+/* ---- counts, lists and decode of ALL members in one call ----
+ * The block order of a set: members sorted by (key, first SBN), a member's blocks in SBN order -- an attached object is its Z
+ * blocks in SBN order under its key.  The order depends on the membership alone, not on the order of the attach calls, and
+ * changes only with attach, detach and a member's destruction.  Every per-block array below is in this order.
+ *
+ * nrq_rxset_blocks: entry j = (key, SBN) of block j.  *h_n = the number of blocks; h_keys / h_sbn nullable (both NULL: the
+ * number only); cap < *h_n with an array given: -1, *h_n still filled.  Host state only: no wait, no launch. */
+int nrq_rxset_blocks(nrq_rxset *set, uint32_t *h_keys, uint32_t *h_sbn, uint32_t cap, uint32_t *h_n);
+/* nrq_rx_counts over all members: one gather kernel over the member table, one download, one wait. */
+int nrq_rxset_counts(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep);
+/* nrq_rx_lists over all members, compact: h_nlost / h_nrep per block (nullable), and in h_lists (nullable, room for cap words)
+ * block by block its repair ESIs in arrival order, then its missing source ESIs ascending -- word for word what nrq_rx_lists
+ * gives for that member's block.  *h_total (nullable) = the words of all lists; cap < *h_total with h_lists given: -1, *h_total
+ * and the counts still filled.  One listing pass on the device (a count per block, one scan, a fill per block), two downloads. */
+int nrq_rxset_lists(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep, uint32_t *h_lists, size_t cap, size_t *h_total);
+/* nrq_rx_decode over all members: h_status[j] / h_used[j] (h_used nullable) per block, with nrq_rx_decode's meaning.  One listing
+ * pass and one fetch for the whole set; the blocks nrq_rx_decode's rule selects -- gaps ng != 0, repair rows nr >= ng, nr - ng <=
+ * max_esi - K; min(nr, ng + 2) repair symbols up front, the rest on demand -- grouped by (K, K', relay attached or not) across
+ * the members, every group in calls of at most 256 blocks (the decode path's tested batch; a set holds 1024); ONE marking
+ * launch.  A block without gaps has status 1 without work.
+ * Afterwards every member is in the state its own nrq_rx_decode (nrq_orx_decode) would have left it in: the same verdict and
+ * `used` per block, the same recovered source rows, the seen bits below K set and the gaps 0 of a recovered block (later packets
+ * for it are IGN), repair rows and their ESI list untouched.  A member with a relay attached gets its recovered blocks'
+ * intermediate symbols written into the relay's buffer, and those blocks are ready when the call returns, as documented for
+ * nrq_rx_decode; members without one pass no intermediate address (the needed-pivot back-substitution stays).
+ * An empty set, or nothing selectable: 0 and no decode launch (the listing pass still runs on a set with blocks).  h_status
+ * NULL: -1 and an error text.  h_status is final on return; the solves and the marking are enqueued on the context's stream.
+ * Errors: when a decode call fails, the blocks of the calls that succeeded before it are still marked -- their books say what
+ * their rows hold -- the blocks of the failed and of the later calls have status 0 and their books as before, and the failing
+ * call's code and text are returned.  A second nrq_rxset_decode finishes the job. */
+int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used);
 
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()

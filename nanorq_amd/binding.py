@@ -143,6 +143,11 @@ def lib():
         L.nrq_rxset_attach_obj.argtypes = [vp, C.c_uint32, vp]
         L.nrq_rxset_detach.argtypes = [vp, C.c_uint32]
         L.nrq_rxset_add.argtypes = [vp, vp, sz, vp, vp, C.c_uint32, C.c_uint32, vp]
+    if hasattr(L, "nrq_rxset_decode"):  # (likewise a build from before the set-wide counts, lists and decode: those methods then raise)
+        L.nrq_rxset_blocks.argtypes = [vp, u32p, u32p, C.c_uint32, u32p]
+        L.nrq_rxset_counts.argtypes = [vp, u32p, u32p]
+        L.nrq_rxset_lists.argtypes = [vp, u32p, u32p, u32p, sz, C.POINTER(sz)]
+        L.nrq_rxset_decode.argtypes = [vp, ip, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -823,6 +828,52 @@ class ReceiverSet(_Handle):
         flags = (RX_TAG_INLINE if inline else 0) | (RX_KEY_INLINE if key_inline else 0)
         self.ctx._chk(self._L.nrq_rxset_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)),
                                             n, flags, C.c_void_p(_dptr(results))))
+
+    def _fn(self, name):
+        if not hasattr(self._L, name):
+            raise NrqError("this library build has no %s" % name)
+        return getattr(self._L, name)
+
+    def blocks(self):
+        """(keys, sbns) of the set's blocks as uint32 arrays, in the set's block order: members sorted by (key, first SBN), a
+        member's blocks in SBN order.  Every per-block array of counts(), lists() and decode() is in this order (host state only)."""
+        fn = self._fn("nrq_rxset_blocks")
+        n = C.c_uint32(0)
+        self.ctx._chk(fn(self._h, None, None, 0, C.byref(n)))
+        keys, sbns = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            self.ctx._chk(fn(self._h, _u32(keys), _u32(sbns), n.value, C.byref(n)))
+        return keys, sbns
+
+    def counts(self):
+        """(missing source symbols, repair rows used) per block of all members, in block order (one kernel, one download; waits)."""
+        n = len(self.blocks()[0])
+        nl, nr = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self.ctx._chk(self._fn("nrq_rxset_counts")(self._h, _u32(nl), _u32(nr)))
+        return nl, nr
+
+    def lists(self):
+        """(nlost, nrep, lists): the counts per block and, in one uint32 array, block by block its repair ESIs in arrival order
+        followed by its missing source ESIs ascending (block j's words start at sum(nlost[:j] + nrep[:j]); waits)."""
+        fn = self._fn("nrq_rxset_lists")
+        n = len(self.blocks()[0])
+        nl, nr = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        total = C.c_size_t(0)
+        self.ctx._chk(fn(self._h, _u32(nl), _u32(nr), None, 0, C.byref(total)))
+        lists = np.zeros(total.value, np.uint32)
+        if total.value:
+            self.ctx._chk(fn(self._h, _u32(nl), _u32(nr), _u32(lists), total.value, C.byref(total)))
+        return nl, nr, lists
+
+    def decode(self):
+        """Decode every member in place with one listing pass, the decodable blocks of all members grouped by code parameters
+        into as few decode calls as possible, and one marking launch; returns (status, used) per block in block order, with
+        Receiver.decode's meaning.  Every member is left as its own decode() would have left it."""
+        fn = self._fn("nrq_rxset_decode")
+        n = len(self.blocks()[0])
+        st, used = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        self.ctx._chk(fn(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
+        return st, used
 
 
 def plan_ops(plan, header=None):

@@ -24,6 +24,7 @@ SEMU = os.path.join(ROOT, "tests", "emu", "libshape_emu.so")
 HEMU = os.path.join(ROOT, "tests", "emu", "libheld_emu.so")
 WEMU = os.path.join(ROOT, "tests", "emu", "libwant_emu.so")
 REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
+LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -153,6 +154,13 @@ def build_rxset_emu(force=False):
     return _build_emu(REMU, os.path.join(CSRC, "rxset_emu.cpp"), ("ingest_set_body.h", "ingest_body.h"), force)
 
 
+def build_rxset_lists_emu(force=False):
+    """tests/emu/librxset_lists_emu.so: CPU emulation of a reception set's listing passes and the grouping of its decode
+    (csrc/rxset_lists_emu.cpp over lists_set_body.h and rxset_plan.h)."""
+    return _build_emu(LEMU, os.path.join(CSRC, "rxset_lists_emu.cpp"),
+                      ("lists_set_body.h", "rxset_plan.h", "ingest_set_body.h", "ingest_body.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -173,6 +181,7 @@ if __name__ == "__main__":
     build_held_emu(force="-f" in sys.argv)
     build_want_emu(force="-f" in sys.argv)
     build_rxset_emu(force="-f" in sys.argv)
+    build_rxset_lists_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -34,6 +34,8 @@
 #include "planner_body.h"
 #include "ingest_body.h"
 #include "ingest_set_body.h"
+#include "lists_set_body.h"
+#include "rxset_plan.h"
 #include "held_body.h"
 #include "want_body.h"
 #include "emit_body.h"
@@ -4505,6 +4507,10 @@ struct nrq_rxset {
   void *tab;                     /* struct ings_tab in device memory */
   void *scratch;                 /* per-call arrays */
   size_t scratch_cap;
+  void *lists;                   /* the listing passes' output (lists_set_body.h), sized for the worst case of the members.  The rule of
+                                  * rx_held_count holds: written anew by every call that reads it, read on the context's stream
+                                  * within that call, nothing expected of it afterwards */
+  size_t lists_cap;
 };
 
 /* the member table as `mem` has it, into device memory.  Waits for the stream first: an ingest enqueued before still reads the
@@ -4534,8 +4540,22 @@ static int rxset_commit(nrq_rxset *set, std::vector<rxset_member> &mem) {
   std::sort(mem.begin(), mem.end(), [](const rxset_member &a, const rxset_member &b) {
     return a.key != b.key ? a.key < b.key : a.rx->r.sbn0 < b.rx->r.sbn0;
   });
-  const int rc = rxset_upload(set, mem);
+  /* the list buffer: every block's K + rep_cap list words at most, gaps and offsets of all blocks, the total */
+  size_t words = 1;
+  for (const rxset_member &m : mem) words += (size_t)m.rx->r.nblk * ((size_t)m.rx->r.K + m.rx->r.rep_cap + 2u);
+  void *lists = nullptr;
+  int rc = words * 4u > set->lists_cap ? nrq_dev_alloc(set->ctx, words * 4u, &lists) : 0;
   if (rc) return rc;
+  rc = rxset_upload(set, mem);
+  if (rc) {
+    if (lists) nrq_dev_free(set->ctx, lists);
+    return rc;
+  }
+  if (lists) { /* (the upload has waited for the stream: nothing reads the old buffer any more) */
+    if (set->lists) nrq_dev_free(set->ctx, set->lists);
+    set->lists = lists;
+    set->lists_cap = words * 4u;
+  }
   for (const rxset_member &m : set->mem) m.rx->set = nullptr;
   set->mem.swap(mem);
   set->nblk = 0;
@@ -4609,7 +4629,7 @@ void nrq_rxset_destroy(nrq_rxset *set) {
   nrq_ctx *ctx = set->ctx;
   for (const rxset_member &m : set->mem) m.rx->set = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {set->tab, set->scratch})
+  for (void *p : {set->tab, set->scratch, set->lists})
     if (p) nrq_dev_free(ctx, p);
   delete set;
 }
@@ -4691,6 +4711,247 @@ int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const u
   hipLaunchKernelGGL(nrq_ings_fold_kernel, dim3(g), dim3(256), 0, st, t, s);
   HIPCHK(ctx, hipGetLastError());
   return 0;
+}
+
+} /* extern "C" */
+
+/* ================================================ a set's counts, lists and decode (lists_set_body.h, rxset_plan.h) ==== */
+/* nrq_rx_counts, nrq_rx_lists and nrq_rx_decode over all members of a set at once, in the order of the table's global block
+ * numbers.  The lists are made as the held / want listings are -- count, one scan, fill -- because the single form's serial sum
+ * over all earlier blocks, in one lane of every workgroup, is 1024 dependent loads through the table at a full set. */
+__global__ __launch_bounds__(256) void nrq_ings_counts_kernel(const ings_tab *__restrict__ t, uint32_t *__restrict__ out) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x, nb = t->nblk;
+  if (g >= nb) return;
+  uint32_t ng, nr;
+  lss_counts(t, g, &ng, &nr);
+  out[g] = ng;
+  out[nb + g] = nr;
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_lists_count_kernel(const ings_tab *__restrict__ t, uint32_t *__restrict__ buf) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g < t->nblk) lss_list_count(t, g, buf);
+}
+
+/* counts -> exclusive offsets, in place, n <= 1025 entries (nrq_tx_scan_kernel is one lane over at most 257): one workgroup, a
+ * run of entries per thread, a scan over the threads' sums */
+__global__ __launch_bounds__(256) void nrq_ings_lists_scan_kernel(uint32_t n, uint32_t *cnt) {
+  __shared__ uint32_t ps[256];
+  const uint32_t i = threadIdx.x;
+  const uint32_t per = (n + 255u) / 256u, j0 = min(n, i * per), j1 = min(n, j0 + per);
+  uint32_t sum = 0;
+  for (uint32_t j = j0; j < j1; j++) sum += cnt[j];
+  ps[i] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+    const uint32_t v = i >= d ? ps[i - d] : 0u;
+    __syncthreads();
+    ps[i] += v;
+    __syncthreads();
+  }
+  uint32_t run = ps[i] - sum;
+  for (uint32_t j = j0; j < j1; j++) { const uint32_t v = cnt[j]; cnt[j] = run; run += v; }
+}
+
+/* one workgroup per global block: its repair ESIs in arrival order, then its missing source ESIs ascending (256 words per round:
+ * a scan over their counts places each word's ESIs), to the block's offset behind the 2 * nblk + 1 words of gaps and offsets */
+__global__ __launch_bounds__(256) void nrq_ings_lists_fill_kernel(const ings_tab *__restrict__ t, uint32_t *buf) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x, i = threadIdx.x, nb = t->nblk;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  uint32_t *out = buf + 2u * nb + 1u + buf[nb + g];
+  const uint32_t nrep = r->nrep[b], nw = lss_words(r);
+  for (uint32_t q = i; q < nrep; q += 256u) out[q] = r->rep_esi[(size_t)b * r->rep_cap + q];
+  uint32_t o = nrep;
+  for (uint32_t w0 = 0; w0 < nw; w0 += LSS_ROUND) {
+    const uint32_t w = w0 + i, miss = lss_miss(r, b, w), cnt = lss_popc(miss);
+    ps[i] = cnt;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
+      const uint32_t v = i >= d ? ps[i - d] : 0u;
+      __syncthreads();
+      ps[i] += v;
+      __syncthreads();
+    }
+    lss_put(w, miss, out + o + ps[i] - cnt);
+    o += ps[255];
+    __syncthreads();
+  }
+}
+
+struct ings_mask { uint32_t w[INGS_MAX_BLOCKS / 32u]; }; /* a bit per global block of the set */
+
+/* nrq_ing_mark_kernel over the table: one workgroup per global block, at work where the block's bit is set */
+__global__ __launch_bounds__(256) void nrq_ings_mark_kernel(const ings_tab *__restrict__ t, ings_mask m) {
+  const uint32_t g = blockIdx.x;
+  if (!((m.w[g >> 5] >> (g & 31u)) & 1u)) return;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  const uint32_t K = r->K;
+  uint32_t *seen = r->seen + (size_t)b * r->bm_words;
+  for (uint32_t w = threadIdx.x; w * 32u < K; w += 256u) {
+    const uint32_t nb = min(32u, K - w * 32u);
+    seen[w] |= nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+  }
+  if (threadIdx.x == 0) r->gaps[b] = 0;
+}
+
+/* the lists of all members: head = gaps[nb], offsets[nb + 1] (the last one the total), lists = exactly the list words.  One
+ * listing pass; the head comes down first, then the list bytes, as in rx_fetch_lists. */
+static int rxset_fetch_lists(nrq_rxset *set, std::vector<uint32_t> &head, std::vector<uint32_t> &lists) {
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk;
+  const ings_tab *t = (const ings_tab *)set->tab;
+  uint32_t *buf = (uint32_t *)set->lists;
+  hipLaunchKernelGGL(nrq_ings_lists_count_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, ctx->stream, t, buf);
+  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, nb + 1u, buf + nb);
+  hipLaunchKernelGGL(nrq_ings_lists_fill_kernel, dim3(nb), dim3(256), 0, ctx->stream, t, buf);
+  HIPCHK(ctx, hipGetLastError());
+  head.assign(2u * (size_t)nb + 1u, 0);
+  HIPCHK(ctx, hipMemcpyAsync(head.data(), buf, head.size() * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t total = head[2u * (size_t)nb];
+  lists.assign(total ? total : 1, 0);
+  if (total) {
+    HIPCHK(ctx, hipMemcpyAsync(lists.data(), buf + 2u * (size_t)nb + 1u, total * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rxset_blocks(nrq_rxset *set, uint32_t *h_keys, uint32_t *h_sbn, uint32_t cap, uint32_t *h_n) {
+  if (!set) return -1;
+  if (!h_n) return fail(set->ctx, -1, "nrq_rxset_blocks: h_n is NULL");
+  *h_n = set->nblk;
+  if (!h_keys && !h_sbn) return 0;
+  if (cap < set->nblk) return fail(set->ctx, -1, "nrq_rxset_blocks: the set has %u blocks, the arrays have room for %u", set->nblk, cap);
+  uint32_t j = 0;
+  for (const rxset_member &m : set->mem)
+    for (uint32_t b = 0; b < m.rx->r.nblk; b++, j++) {
+      if (h_keys) h_keys[j] = m.key;
+      if (h_sbn) h_sbn[j] = m.rx->r.sbn0 + b;
+    }
+  return 0;
+}
+
+int nrq_rxset_counts(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(nrq_ings_counts_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, ctx->stream, (const ings_tab *)set->tab, (uint32_t *)set->lists);
+  HIPCHK(ctx, hipGetLastError());
+  std::vector<uint32_t> cnt(2u * (size_t)nb);
+  HIPCHK(ctx, hipMemcpyAsync(cnt.data(), set->lists, cnt.size() * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (h_nlost) memcpy(h_nlost, cnt.data(), (size_t)nb * 4u);
+  if (h_nrep) memcpy(h_nrep, cnt.data() + nb, (size_t)nb * 4u);
+  return 0;
+}
+
+int nrq_rxset_lists(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep, uint32_t *h_lists, size_t cap, size_t *h_total) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk;
+  if (h_total) *h_total = 0;
+  if (nb == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> head, lists;
+  const int rc = rxset_fetch_lists(set, head, lists);
+  if (rc) return rc;
+  const size_t total = head[2u * (size_t)nb];
+  if (h_total) *h_total = total;
+  for (uint32_t j = 0; j < nb; j++) {
+    if (h_nlost) h_nlost[j] = head[j];
+    if (h_nrep) h_nrep[j] = head[nb + j + 1u] - head[nb + j] - head[j];
+  }
+  if (!h_lists) return 0;
+  if (cap < total) return fail(ctx, -1, "nrq_rxset_lists: the lists have %zu words, h_lists has room for %zu", total, cap);
+  memcpy(h_lists, lists.data(), total * 4u);
+  return 0;
+}
+
+int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  if (!h_status) return fail(ctx, -1, "nrq_rxset_decode: h_status is NULL");
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> head, lists;
+  int rc = rxset_fetch_lists(set, head, lists);
+  if (rc) return rc;
+  /* per global block: its member, its block in the member, its counts */
+  std::vector<rxset_plan_member> pm(set->mem.size());
+  std::vector<uint32_t> member(nb), blk(nb), ng(nb), nr(nb);
+  uint32_t j = 0;
+  for (size_t m = 0; m < set->mem.size(); m++) {
+    const nrq_rx *rx = set->mem[m].rx;
+    pm[m] = rxset_plan_member{rx->r.K, rx->Kp, rx->r.max_esi, rx->relay ? 1u : 0u};
+    for (uint32_t b = 0; b < rx->r.nblk; b++, j++) {
+      member[j] = (uint32_t)m;
+      blk[j] = b;
+      ng[j] = head[j];
+      nr[j] = head[nb + j + 1u] - head[nb + j] - head[j];
+      h_status[j] = ng[j] == 0 ? 1 : 0;
+      if (h_used) h_used[j] = 0;
+    }
+  }
+  const std::vector<rxset_chunk> chunks = rxset_plan(pm.data(), member.data(), ng.data(), nr.data(), nb);
+  ings_mask mask{};
+  bool any = false;
+  std::string err;
+  std::vector<uint32_t> lost, resi, nlost, nuse, navail, used;
+  std::vector<uint64_t> sv, rv, iv;
+  std::vector<int> st;
+  for (const rxset_chunk &c : chunks) {
+    const size_t ns = c.blocks.size();
+    uint32_t lost_cap = 1, rep_cap = 1;
+    for (uint32_t g : c.blocks) { lost_cap = std::max(lost_cap, ng[g]); rep_cap = std::max(rep_cap, nr[g]); }
+    lost.assign(ns * lost_cap, 0); resi.assign(ns * rep_cap, 0);
+    nlost.resize(ns); nuse.resize(ns); navail.resize(ns); used.assign(ns, 0); sv.resize(ns); rv.resize(ns); st.assign(ns, 0);
+    iv.resize(c.has_relay ? ns : 0);
+    for (size_t i = 0; i < ns; i++) {
+      const uint32_t g = c.blocks[i], b = blk[g];
+      const nrq_rx *rx = set->mem[member[g]].rx;
+      const ing_rx &r = rx->r;
+      const uint32_t *l = lists.data() + head[nb + g];
+      memcpy(resi.data() + i * rep_cap, l, (size_t)nr[g] * 4u);
+      memcpy(lost.data() + i * lost_cap, l + nr[g], (size_t)ng[g] * 4u);
+      nlost[i] = ng[g];
+      nuse[i] = rxset_nuse(ng[g], nr[g]);
+      navail[i] = nr[g];
+      sv[i] = (uint64_t)(uintptr_t)(r.src + b * r.src_stride);
+      rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
+      if (c.has_relay) iv[i] = relay_inter(rx->relay, rx->relay_seg, b);
+    }
+    rc = nrq_decode_blocks_vi(ctx, c.K, c.Kp, set->T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
+                              navail.data(), rep_cap, rv.data(), c.has_relay ? iv.data() : nullptr, st.data(), used.data());
+    if (rc) { /* this chunk's and the later chunks' blocks keep status 0 and their books; the chunks before it are marked below */
+      err = ctx->err;
+      break;
+    }
+    for (size_t i = 0; i < ns; i++) {
+      const uint32_t g = c.blocks[i];
+      nrq_rx *rx = set->mem[member[g]].rx;
+      h_status[g] = st[i];
+      if (h_used) h_used[g] = used[i];
+      if (!st[i]) continue;
+      mask.w[g >> 5] |= 1u << (g & 31u);
+      any = true;
+      if (rx->relay) relay_set(rx->relay, rx->relay_b0 + blk[g], 1, true);
+    }
+  }
+  if (any) {
+    hipLaunchKernelGGL(nrq_ings_mark_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const ings_tab *)set->tab, mask);
+    if (!rc) HIPCHK(ctx, hipGetLastError());
+  }
+  if (rc) ctx->err = err;
+  return rc;
 }
 
 } /* extern "C" */
