@@ -517,6 +517,45 @@ int nrq_rxset_lists(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep, uint32_
  * call's code and text are returned.  A second nrq_rxset_decode finishes the job. */
 int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used);
 
+/* ---- sender sets: the packets of MANY transmissions and objects written into one buffer in one pass ----
+ * The send-side counterpart of a reception set: a table of member transmissions (nrq_tx: senders and relays) and objects (nrq_otx:
+ * object senders and objects' relays) of one context and one T, each under a 32-bit key.  nrq_txset_emit answers a request that
+ * spans members -- packet k for (d_keys[k], d_tags[k]) -- with one chain of kernels, and with NRQ_TX_KEY_INLINE writes the packet
+ * form nrq_rxset_add reads with NRQ_RX_KEY_INLINE, where today R members cost R emits into R buffers and a repack.  Members stay
+ * ordinary transmissions: their own emit calls work between set calls.  The caps follow from the kernels: a linear search over
+ * the table's segments per packet, one LDS counter and one ready bit per block. */
+typedef struct nrq_txset nrq_txset;
+#define NRQ_TXSET_MAX_SEGS   64u    /* table segments: a transmission is one, an object up to three */
+#define NRQ_TXSET_MAX_BLOCKS 1024u  /* blocks over all members */
+#define NRQ_TX_KEY_INLINE 4u        /* with NRQ_TX_TAG_INLINE: packet = key (32 bits, network byte order), FEC Payload ID, payload at +8 */
+int nrq_txset_create(nrq_ctx *ctx, uint32_t T, nrq_txset **out);
+void nrq_txset_destroy(nrq_txset *set); /* members live on, detached */
+/* Attach a transmission, or an object (it owns its key), under `key`.  Refused (-1, nrq_ctx_error) by the rules of
+ * nrq_rxset_attach: another context; a T that is not the set's; a transmission that is in a set already; a (key, SBN span) that
+ * overlaps a member's; for an object, any other member under its key, and any further member under an object's key; a cap
+ * exceeded.  Attach and detach wait for the context's stream (the table lives in device memory).  Destroying a member that is
+ * still attached detaches it first. */
+int nrq_txset_attach(nrq_txset *set, uint32_t key, nrq_tx *tx);
+int nrq_txset_attach_obj(nrq_txset *set, uint32_t key, nrq_otx *tx);
+int nrq_txset_detach(nrq_txset *set, uint32_t key); /* every member under key; unknown key: -1 */
+/* The set's blocks in its block order -- members sorted by (key, first SBN), a member's blocks in SBN order -- as
+ * nrq_rxset_blocks gives a reception set's.  Host state only. */
+int nrq_txset_blocks(nrq_txset *set, uint32_t *h_keys, uint32_t *h_sbn, uint32_t cap, uint32_t *h_n);
+/* Emit n packets (enqueue only, on the context's stream; no host wait): packet k at d_pkts + k*pkt_stride for key d_keys[k]
+ * (device; NULL: every key is 0) and tag d_tags[k].  flags: NRQ_TX_TAG_INLINE, NRQ_TX_HELD, and with NRQ_TX_TAG_INLINE
+ * NRQ_TX_KEY_INLINE (the key in front of the FEC Payload ID); pkt_stride >= T, + 4 with the tag inline, + 8 with key and tag.
+ * A packet whose (key, SBN) names a member gets, byte for byte, the FEC Payload ID, the payload and the d_results entry (device,
+ * nullable) that member's own nrq_tx_emit / nrq_otx_emit gives for that tag under the same NRQ_TX_TAG_INLINE and NRQ_TX_HELD
+ * bits -- 0, or NRQ_TX_NOT_READY for a relay's block that is not ready, with the held-symbol table above under NRQ_TX_HELD.  The
+ * members' ready state is taken as it is at this call.  NRQ_TX_HELD is accepted on any set: a member that is a plain sender has no
+ * reception and answers as without the flag.  A packet that belongs to no member -- an unknown key, a key that is no object's
+ * with an SBN outside its members, SBN >= Z of an object -- is left wholly untouched and gets -1.  n == 0 and an empty set: 0.
+ * Refused (-1 and a text, nothing enqueued): NRQ_TX_KEY_INLINE without NRQ_TX_TAG_INLINE, an unknown flag, a stride too small,
+ * NULL packets or tags, a member that is a sender and not encoded, a relay member whose reception was destroyed (the text names
+ * the key). */
+int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride,
+                   uint32_t flags, int32_t *d_results);
+
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()
  * synchronises, returns the durations of the launches since the last read/enable in launch order. */

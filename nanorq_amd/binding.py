@@ -148,6 +148,15 @@ def lib():
         L.nrq_rxset_counts.argtypes = [vp, u32p, u32p]
         L.nrq_rxset_lists.argtypes = [vp, u32p, u32p, u32p, sz, C.POINTER(sz)]
         L.nrq_rxset_decode.argtypes = [vp, ip, u32p]
+    if hasattr(L, "nrq_txset_create"):  # (likewise a build from before the sender sets: SenderSet then raises)
+        L.nrq_txset_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+        L.nrq_txset_destroy.argtypes = [vp]
+        L.nrq_txset_destroy.restype = None
+        L.nrq_txset_attach.argtypes = [vp, C.c_uint32, vp]
+        L.nrq_txset_attach_obj.argtypes = [vp, C.c_uint32, vp]
+        L.nrq_txset_detach.argtypes = [vp, C.c_uint32]
+        L.nrq_txset_blocks.argtypes = [vp, u32p, u32p, C.c_uint32, u32p]
+        L.nrq_txset_emit.argtypes = [vp, vp, vp, C.c_uint32, vp, sz, C.c_uint32, vp]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -376,6 +385,9 @@ RX_FULL = 3         # NRQ_RX_FULL
 RX_KEY_INLINE = 2   # NRQ_RX_KEY_INLINE
 RXSET_MAX_MEMBERS = 64   # NRQ_RXSET_MAX_MEMBERS
 RXSET_MAX_BLOCKS = 1024  # NRQ_RXSET_MAX_BLOCKS
+TX_KEY_INLINE = 4        # NRQ_TX_KEY_INLINE
+TXSET_MAX_SEGS = 64      # NRQ_TXSET_MAX_SEGS
+TXSET_MAX_BLOCKS = 1024  # NRQ_TXSET_MAX_BLOCKS
 
 
 def _dptr(x):
@@ -874,6 +886,68 @@ class ReceiverSet(_Handle):
         st, used = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         self.ctx._chk(fn(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
         return st, used
+
+
+class SenderSet(_Handle):
+    """A set of device-resident transmissions of one T (nrq_txset, include/nanorq_hip.h): Senders, RelaySenders, ObjectSenders and
+    RelayObjectSenders attached under 32-bit keys, whose packets ONE emit writes into one buffer.  Members stay ordinary
+    transmissions; closing one detaches it, closing the set leaves its members usable."""
+    _api = "nrq_txset"
+
+    def __init__(self, ctx, T):
+        self.ctx = ctx
+        self._L = ctx._L
+        self.T = T
+        self._members = {}  # key -> the attached senders (kept alive as long as they are attached)
+        if not hasattr(self._L, "nrq_txset_create"):
+            raise NrqError("this library build has no sender sets")
+        h = C.c_void_p()
+        ctx._chk(self._L.nrq_txset_create(ctx._h, T, C.byref(h)))
+        self._h = h
+
+    def attach(self, key, tx):
+        """tx: a Sender or RelaySender, or an ObjectSender or RelayObjectSender (it owns its key).  May wait for the context's
+        stream."""
+        fn = self._L.nrq_txset_attach_obj if isinstance(tx, ObjectSender) else self._L.nrq_txset_attach
+        self.ctx._chk(fn(self._h, key, tx._h))
+        self._members.setdefault(key, []).append(tx)
+
+    def detach(self, key):
+        """every member under key (an unknown key raises).  May wait for the context's stream."""
+        self.ctx._chk(self._L.nrq_txset_detach(self._h, key))
+        self._members.pop(key, None)
+
+    def blocks(self):
+        """(keys, sbns) of the set's blocks as uint32 arrays, in the set's block order, as ReceiverSet.blocks()"""
+        n = C.c_uint32(0)
+        self.ctx._chk(self._L.nrq_txset_blocks(self._h, None, None, 0, C.byref(n)))
+        keys, sbns = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            self.ctx._chk(self._L.nrq_txset_blocks(self._h, _u32(keys), _u32(sbns), n.value, C.byref(n)))
+        return keys, sbns
+
+    def stride(self, inline=False, key_inline=False):
+        """the packet stride of out=None: T, or T + 4 (inline) or T + 8 (key_inline) rounded up to 16"""
+        hdr = 8 if key_inline else 4 if inline else 0
+        return (self.T + hdr + 15) // 16 * 16 if hdr else self.T
+
+    def emit(self, keys, tags, out=None, inline=False, key_inline=False, results=None, held=False):
+        """Packet k for (keys[k], tags[k]) ([n] int32 / uint32 device tensors; keys None: every key 0) in row k of out
+        ([n, stride] uint8 device tensor; None: a new one).  inline: the FEC Payload ID in front of the payload; key_inline (with
+        inline): the key in front of that, the form ReceiverSet.add(key_inline=True) reads.  results: optional [n] int32 device
+        tensor, with _Emitter.emit's codes; a packet of no member is left untouched with -1.  held: as _Emitter.emit, on the relay
+        members (plain senders answer as without it).  Enqueue only.  Returns out."""
+        n = int(tags.shape[0])
+        if out is None:
+            import torch
+            out = torch.empty((n, self.stride(inline, key_inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            stride = out.shape[1]
+        else:
+            stride = out.stride(0) * out.element_size()
+        flags = _tx_flags(inline, held) | (TX_KEY_INLINE if key_inline else 0)
+        self.ctx._chk(self._L.nrq_txset_emit(self._h, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
+                                             flags, C.c_void_p(_dptr(results))))
+        return out
 
 
 def plan_ops(plan, header=None):

@@ -25,6 +25,7 @@ HEMU = os.path.join(ROOT, "tests", "emu", "libheld_emu.so")
 WEMU = os.path.join(ROOT, "tests", "emu", "libwant_emu.so")
 REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
+TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -161,6 +162,11 @@ def build_rxset_lists_emu(force=False):
                       ("lists_set_body.h", "rxset_plan.h", "ingest_set_body.h", "ingest_body.h"), force)
 
 
+def build_txset_emu(force=False):
+    """tests/emu/libtxset_emu.so: CPU emulation of a sender set's emit (csrc/txset_emu.cpp over emit_set_body.h)."""
+    return _build_emu(TEMU, os.path.join(CSRC, "txset_emu.cpp"), ("emit_set_body.h", "emit_body.h", "rq_math.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -182,6 +188,7 @@ if __name__ == "__main__":
     build_want_emu(force="-f" in sys.argv)
     build_rxset_emu(force="-f" in sys.argv)
     build_rxset_lists_emu(force="-f" in sys.argv)
+    build_txset_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -39,6 +39,7 @@
 #include "held_body.h"
 #include "want_body.h"
 #include "emit_body.h"
+#include "emit_set_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
@@ -3487,7 +3488,9 @@ struct tx_sender {
    * the relay's encode for a block that is complete (only complete blocks ever get the bit: ready = complete and written). */
   bool relay, detached;  /* detached: a reception was destroyed first; every later call fails */
   nrq_rx *from[2];
+  struct nrq_txset *set; /* the sender set this transmission is a member of (nrq_txset_attach), or null */
 };
+static void txset_drop(tx_sender *tx); /* a member of a sender set goes away (defined with the sets below) */
 
 struct nrq_tx : tx_sender {};
 
@@ -3518,6 +3521,7 @@ template <class S>
 static void tx_destroy(S *tx) {
   if (!tx) return;
   nrq_ctx *ctx = tx->ctx;
+  if (tx->set) txset_drop(tx); /* (the set's table is rewritten without it, behind the work enqueued so far) */
   for (nrq_rx *r : tx->from)
     if (r) r->relay = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
@@ -4952,6 +4956,434 @@ int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used) {
   }
   if (rc) ctx->err = err;
   return rc;
+}
+
+} /* extern "C" */
+
+/* ================================================ sender sets (nrq_txset_*, emit_set_body.h) ==== */
+/* The tag-list emit over a segment table in device memory: one chain of kernels writes the packets of all members into one
+ * buffer.  Three bucketing passes make the block-major work order over the set's global blocks -- the histogram pass also finds
+ * each packet's segment (a linear search over the compact arrays staged in LDS; every lane reads the same entry) and leaves it
+ * in c.seg[] for the passes behind it -- then nrq_emit_set_kernel writes the packets.  Kernels of their own: every nrq_emit_kernel
+ * and nrq_emit_held_kernel instantiation is compiled from the code it always was. */
+enum : int { TXS_V16_KEY = 4 }; /* beside TX_V16 .. TX_BYTE: 16-byte loads and stores under the 8-byte header (key, FEC Payload ID) */
+
+__global__ __launch_bounds__(256) void nrq_txs_hist_kernel(const txs_tab *__restrict__ t, txs_call c, uint32_t *__restrict__ cnt) {
+  __shared__ uint32_t skey[TXS_MAX_SEGS], ssbn0[TXS_MAX_SEGS], scnt[TXS_MAX_SEGS], sblk0[TXS_MAX_SEGS];
+  __shared__ uint32_t h[TXS_MAX_BLOCKS + 1u];
+  const uint32_t nseg = min(t->nseg, TXS_MAX_SEGS), nb = min(t->nblk, TXS_MAX_BLOCKS), i = threadIdx.x;
+  if (i < nseg) { skey[i] = t->key[i]; ssbn0[i] = t->sbn0[i]; scnt[i] = t->cnt[i]; sblk0[i] = t->blk0[i]; }
+  for (uint32_t g = i; g <= nb; g += 256u) h[g] = 0;
+  __syncthreads();
+  const uint32_t k0 = blockIdx.x * TX_BIN_TILE, k1 = min(c.n, k0 + TX_BIN_TILE);
+  for (uint32_t k = k0 + i; k < k1; k += 256u) {
+    const uint32_t tag = c.tags[k], sg = txs_find(skey, ssbn0, scnt, nseg, txs_key_of(&c, k), tag >> 24);
+    c.seg[k] = sg;
+    atomicAdd(&h[txs_bin(ssbn0, sblk0, nb, sg, tag)], 1u);
+  }
+  __syncthreads();
+  for (uint32_t g = i; g <= nb; g += 256u)
+    if (h[g]) atomicAdd(&cnt[g], h[g]);
+}
+
+/* each tile reserves its packets' places in every bucket (one atomic per bucket and tile), then writes order[] */
+__global__ __launch_bounds__(256) void nrq_txs_place_kernel(const txs_tab *__restrict__ t, txs_call c, uint32_t *__restrict__ cursor) {
+  __shared__ uint32_t ssbn0[TXS_MAX_SEGS], sblk0[TXS_MAX_SEGS];
+  __shared__ uint32_t h[TXS_MAX_BLOCKS + 1u], base[TXS_MAX_BLOCKS + 1u];
+  constexpr uint32_t PER = TX_BIN_TILE / 256u;
+  const uint32_t nseg = min(t->nseg, TXS_MAX_SEGS), nb = min(t->nblk, TXS_MAX_BLOCKS), i = threadIdx.x;
+  if (i < nseg) { ssbn0[i] = t->sbn0[i]; sblk0[i] = t->blk0[i]; }
+  for (uint32_t g = i; g <= nb; g += 256u) h[g] = 0;
+  __syncthreads();
+  const uint32_t k0 = blockIdx.x * TX_BIN_TILE;
+  uint32_t bin[PER], rank[PER];
+#pragma unroll
+  for (uint32_t r = 0; r < PER; r++) {
+    const uint32_t k = k0 + r * 256u + i;
+    bin[r] = TX_NONE;
+    if (k < c.n) {
+      const uint32_t sg = c.seg[k];
+      bin[r] = sg < nseg ? txs_bin(ssbn0, sblk0, nb, sg, c.tags[k]) : nb;
+    }
+    rank[r] = bin[r] != TX_NONE ? atomicAdd(&h[bin[r]], 1u) : 0u;
+  }
+  __syncthreads();
+  for (uint32_t g = i; g <= nb; g += 256u) base[g] = h[g] ? atomicAdd(&cursor[g], h[g]) : 0u;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < PER; r++)
+    if (bin[r] != TX_NONE) c.order[base[bin[r]] + rank[r]] = k0 + r * 256u + i;
+}
+
+/* the packet of (key, tag) at P in the call's header form (hdr = 0 / 4 / 8): tx_payload under the key word, or the 16-byte form
+ * of the 8-byte header */
+template <int MODE>
+__device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t *cols, uint32_t n, uint32_t key,
+                                            uint32_t tag, uint8_t *__restrict__ P, uint32_t hdr, uint32_t lane) {
+  if constexpr (MODE == TXS_V16_KEY) {
+    /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-2 .. 4j+1: the previous lane's .z .w (the key word and the header
+     * for j = 0, the wave's last lane of the previous round for its first lane), then this chunk's .x .y; the last .z .w go to +T */
+    const uint32_t nch = T >> 4;
+    uint32_t cz = txs_key_word(key), cw = tx_header_word(tag);
+    for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
+      const uint32_t j = j0 + lane;
+      const bool act = j < nch;
+      tx_u128 v{0u, 0u, 0u, 0u};
+      if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
+      uint32_t pz = __shfl_up(v.z, 1u), pw = __shfl_up(v.w, 1u);
+      if (lane == 0) { pz = cz; pw = cw; }
+      if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{pz, pw, v.x, v.y};
+      if (j == nch - 1u) *reinterpret_cast<uint2 *>(P + T) = make_uint2(v.z, v.w);
+      cz = __shfl(v.z, 63);
+      cw = __shfl(v.w, 63);
+    }
+  } else if constexpr (MODE == TX_DWORD) {
+    if (hdr == 8u) {
+      if (lane == 0) *reinterpret_cast<uint32_t *>(P) = txs_key_word(key);
+      P += 4;
+    }
+    tx_payload<TX_DWORD>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane);
+  } else if constexpr (MODE == TX_BYTE) {
+    if (hdr == 8u) {
+      if (lane < 4u) P[lane] = (uint8_t)(txs_key_word(key) >> (8u * lane));
+      P += 4;
+    }
+    tx_payload<TX_BYTE>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane);
+  } else {
+    tx_payload<MODE>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane); /* (TX_V16: hdr = 0; TX_V16_SHIFT: hdr = 4) */
+  }
+}
+
+/* The wave shape of nrq_emit_kernel over the table: one wave per TX_WAVE_PKTS work items in block-major order.  Each lane admits
+ * one item and builds its column list into LDS from its segment's parameters, read from the table (lanes of one block read the
+ * same entry); then the wave writes the items' packets one after the other, the segment index made wave-uniform so that its
+ * fields come through the uniform table pointer.  HELD: a packet of a block that is not ready is still written when the segment's
+ * reception holds its symbol, the repair row found by the 64-entry ballot lookup of nrq_emit_held_kernel. */
+template <int MODE, bool HELD>
+__global__ __launch_bounds__(256) void nrq_emit_set_kernel(const txs_tab *__restrict__ t, txs_ready rdy, txs_call c) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS], s_key[TX_WAVES][TX_WAVE_PKTS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * TX_WAVE_PKTS;
+  if (w0 + lane < c.n) {
+    const uint32_t k = c.order[w0 + lane];
+    uint32_t n = 0, kind = TX_READY, tag = 0, sg = TXS_NONE, key = 0;
+    if (k < c.n) { /* (always: the work order is a permutation) */
+      tag = c.tags[k];
+      key = txs_key_of(&c, k);
+      sg = c.seg[k];
+      int32_t code = TX_FOREIGN;
+      if (sg < TXS_MAX_SEGS) {
+        const txs_seg *S = &t->seg[sg];
+        if (txs_admit(S, &rdy, HELD, tag, &code, &kind)) {
+          if (kind == TX_HELD_REP) { s_cols[wv][lane][0] = 0u; n = 1u; } /* (row 0 from the base of the row found below) */
+          else n = tx_rows(&S->b, tag, s_cols[wv][lane]);
+        }
+      }
+      if (c.results && kind != TX_HELD_REP) c.results[k] = code; /* (a held repair packet's: once its row is found) */
+    }
+    s_n[wv][lane] = n | (kind << 8);
+    s_tag[wv][lane] = tag;
+    s_k[wv][lane] = k;
+    s_seg[wv][lane] = sg;
+    s_key[wv][lane] = key;
+  }
+  __syncthreads();
+  const uint32_t cnt = w0 >= c.n ? 0u : (uint32_t)min((uint64_t)TX_WAVE_PKTS, c.n - w0);
+  const uint32_t T = c.T;
+  for (uint32_t i = 0; i < cnt; i++) { /* (wave-uniform) */
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][i]), n = nk & 0xFFu;
+    if (!n) continue; /* no member, or a symbol of a block that is not ready which is not held */
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][i]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(s_k[wv][i]);
+    const uint32_t key = __builtin_amdgcn_readfirstlane(s_key[wv][i]);
+    const txs_seg *S = &t->seg[__builtin_amdgcn_readfirstlane(s_seg[wv][i])];
+    const uint8_t *base;
+    if (HELD && (nk >> 8) == TX_HELD_REP) {
+      const tx_held_seg *hs = &S->h;
+      const uint32_t b = (tag >> 24) - S->b.sbn0;
+      const uint32_t nrep = tx_held_nrep(hs, b), esi = tag & 0xFFFFFFu;
+      uint32_t q = TX_NONE;
+      for (uint32_t q0 = 0; q0 < nrep && q == TX_NONE; q0 += 64u) {
+        const uint64_t m = __ballot(tx_held_hit(hs, b, q0 + lane, nrep, esi));
+        if (m) q = q0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+      }
+      if (c.results && lane == 0) c.results[k] = q == TX_NONE ? TX_NOT_READY : 0;
+      if (q == TX_NONE) continue; /* (the books say otherwise: a marked repair ESI has its row) */
+      base = tx_held_rep_base(hs, b) + (uint64_t)q * T;
+    } else {
+      base = tx_base(&S->b, tag);
+    }
+    txs_payload<MODE>(base, T, s_cols[wv][i], n, key, tag, c.pkts + (uint64_t)k * c.pkt_stride, c.hdr, lane);
+  }
+}
+
+struct txset_member {
+  uint32_t key;
+  tx_sender *tx;
+  bool obj; /* an object: it owns its key */
+};
+struct txset_seg { /* one row of the device table, as the host remembers it */
+  tx_sender *tx;
+  uint32_t g;      /* segment of tx->s */
+};
+
+struct nrq_txset {
+  nrq_ctx *ctx;
+  uint32_t T;
+  std::vector<txset_member> mem; /* sorted by (key, first SBN) */
+  std::vector<txset_seg> segs;   /* sorted by (key, sbn0): the order of the device table */
+  uint32_t nblk;                 /* blocks over all members */
+  void *tab;                     /* struct txs_tab in device memory */
+  void *scratch;                 /* per-call arrays: bucket counts, the packets' segments, the work order */
+  size_t scratch_cap;
+};
+
+static uint32_t txset_key_of(const nrq_txset *set, const tx_sender *tx) {
+  for (const txset_member &m : set->mem)
+    if (m.tx == tx) return m.key;
+  return 0;
+}
+
+/* the table rows of `mem` (sorted), in table order */
+static std::vector<txset_seg> txset_rows(const std::vector<txset_member> &mem) {
+  std::vector<txset_seg> rows;
+  for (const txset_member &m : mem) {
+    std::vector<txset_seg> own;
+    for (uint32_t g = 0; g < m.tx->s.nseg; g++) own.push_back(txset_seg{m.tx, g});
+    std::sort(own.begin(), own.end(), [](const txset_seg &a, const txset_seg &b) { return a.tx->s.seg[a.g].sbn0 < b.tx->s.seg[b.g].sbn0; });
+    rows.insert(rows.end(), own.begin(), own.end());
+  }
+  return rows;
+}
+
+/* the segment table of `rows` into device memory.  Waits for the stream first: an emit enqueued before still reads the old
+ * table. */
+static int txset_upload(nrq_txset *set, const std::vector<txset_member> &mem, const std::vector<txset_seg> &rows) {
+  nrq_ctx *ctx = set->ctx;
+  std::vector<txs_tab> hv(1);
+  txs_tab &h = hv[0];
+  memset(&h, 0, sizeof(h));
+  h.nseg = (uint32_t)rows.size();
+  for (uint32_t i = 0; i < h.nseg; i++) {
+    const tx_sender *tx = rows[i].tx;
+    const uint32_t g = rows[i].g;
+    txs_seg &S = h.seg[i];
+    S.b = tx->s.seg[g];
+    if (tx->relay && !tx->detached && tx->from[g]) S.h = tx_held_table(tx).seg[g];
+    for (const txset_member &m : mem)
+      if (m.tx == tx) S.key = m.key;
+    S.blk0 = h.nblk;
+    h.key[i] = S.key; h.sbn0[i] = S.b.sbn0; h.cnt[i] = S.b.nblk; h.blk0[i] = S.blk0;
+    h.nblk += S.b.nblk;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy(set->tab, &h, sizeof(h), hipMemcpyHostToDevice));
+  return 0;
+}
+
+/* take `mem` as the set's members (sorted here); on failure the set keeps the ones it had */
+static int txset_commit(nrq_txset *set, std::vector<txset_member> &mem) {
+  std::sort(mem.begin(), mem.end(), [](const txset_member &a, const txset_member &b) {
+    return a.key != b.key ? a.key < b.key : a.tx->s.sbn0 < b.tx->s.sbn0;
+  });
+  std::vector<txset_seg> rows = txset_rows(mem);
+  const int rc = txset_upload(set, mem, rows);
+  if (rc) return rc;
+  for (const txset_member &m : set->mem) m.tx->set = nullptr;
+  set->mem.swap(mem);
+  set->segs.swap(rows);
+  set->nblk = 0;
+  for (const txset_member &m : set->mem) { m.tx->set = set; set->nblk += m.tx->s.Z; }
+  return 0;
+}
+
+/* a transmission goes away (nrq_tx_destroy / nrq_otx_destroy): it leaves its set first */
+static void txset_drop(tx_sender *tx) {
+  nrq_txset *set = tx->set;
+  std::vector<txset_member> mem;
+  for (const txset_member &m : set->mem)
+    if (m.tx != tx) mem.push_back(m);
+  if (txset_commit(set, mem) != 0) { /* (the table could not be written: an empty host list keeps every later emit off the stale one) */
+    for (const txset_member &m : set->mem) m.tx->set = nullptr;
+    set->mem.clear();
+    set->segs.clear();
+    set->nblk = 0;
+  }
+}
+
+static int txset_attach(nrq_txset *set, const char *who, uint32_t key, tx_sender *tx, bool obj) {
+  nrq_ctx *ctx = set->ctx;
+  const tx_src &s = tx->s;
+  if (tx->ctx != ctx) return fail(ctx, -1, "%s: the transmission belongs to another context", who);
+  if (s.seg[0].T != set->T) return fail(ctx, -1, "%s: the transmission's T %u is not the set's %u", who, s.seg[0].T, set->T);
+  if (tx->set) return fail(ctx, -1, "%s: the transmission is in a set already", who);
+  for (const txset_member &m : set->mem) {
+    if (m.key != key) continue;
+    if (obj || m.obj) return fail(ctx, -1, "%s: key %u has members already, and an object owns its key", who, key);
+    const tx_src &o = m.tx->s;
+    if (s.sbn0 < o.sbn0 + o.Z && o.sbn0 < s.sbn0 + s.Z)
+      return fail(ctx, -1, "%s: SBNs %u..%u under key %u overlap a member's %u..%u", who, s.sbn0, s.sbn0 + s.Z - 1u, key, o.sbn0,
+                  o.sbn0 + o.Z - 1u);
+  }
+  if (set->segs.size() + s.nseg > NRQ_TXSET_MAX_SEGS) return fail(ctx, -1, "%s: a set holds at most %u table segments", who, NRQ_TXSET_MAX_SEGS);
+  if (set->nblk + s.Z > NRQ_TXSET_MAX_BLOCKS) return fail(ctx, -1, "%s: a set holds at most %u blocks", who, NRQ_TXSET_MAX_BLOCKS);
+  std::vector<txset_member> mem = set->mem;
+  mem.push_back(txset_member{key, tx, obj});
+  return txset_commit(set, mem);
+}
+
+static_assert(NRQ_TXSET_MAX_SEGS == TXS_MAX_SEGS && NRQ_TXSET_MAX_BLOCKS == TXS_MAX_BLOCKS, "the header's caps are the table's");
+
+extern "C" {
+
+int nrq_txset_create(nrq_ctx *ctx, uint32_t T, nrq_txset **out) {
+  if (!ctx) return -1;
+  if (!out) return fail(ctx, -1, "nrq_txset_create: out is NULL");
+  *out = nullptr;
+  if (T == 0) return fail(ctx, -1, "nrq_txset_create: T is 0");
+  nrq_txset *set = new (std::nothrow) nrq_txset();
+  if (!set) return fail(ctx, -1, "nrq_txset_create: out of host memory");
+  set->ctx = ctx;
+  set->T = T;
+  const int rc = nrq_dev_alloc(ctx, sizeof(txs_tab), &set->tab);
+  if (rc) {
+    delete set;
+    return rc;
+  }
+  *out = set;
+  return 0;
+}
+
+void nrq_txset_destroy(nrq_txset *set) {
+  if (!set) return;
+  nrq_ctx *ctx = set->ctx;
+  for (const txset_member &m : set->mem) m.tx->set = nullptr;
+  (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
+  for (void *p : {set->tab, set->scratch})
+    if (p) nrq_dev_free(ctx, p);
+  delete set;
+}
+
+int nrq_txset_attach(nrq_txset *set, uint32_t key, nrq_tx *tx) {
+  if (!set) return -1;
+  if (!tx) return fail(set->ctx, -1, "nrq_txset_attach: the transmission is NULL");
+  return txset_attach(set, "nrq_txset_attach", key, tx, false);
+}
+
+int nrq_txset_attach_obj(nrq_txset *set, uint32_t key, nrq_otx *tx) {
+  if (!set) return -1;
+  if (!tx) return fail(set->ctx, -1, "nrq_txset_attach_obj: the object sender is NULL");
+  return txset_attach(set, "nrq_txset_attach_obj", key, tx, true);
+}
+
+int nrq_txset_detach(nrq_txset *set, uint32_t key) {
+  if (!set) return -1;
+  std::vector<txset_member> mem;
+  for (const txset_member &m : set->mem)
+    if (m.key != key) mem.push_back(m);
+  if (mem.size() == set->mem.size()) return fail(set->ctx, -1, "nrq_txset_detach: no member under key %u", key);
+  return txset_commit(set, mem);
+}
+
+int nrq_txset_blocks(nrq_txset *set, uint32_t *h_keys, uint32_t *h_sbn, uint32_t cap, uint32_t *h_n) {
+  if (!set) return -1;
+  if (!h_n) return fail(set->ctx, -1, "nrq_txset_blocks: h_n is NULL");
+  *h_n = set->nblk;
+  if (!h_keys && !h_sbn) return 0;
+  if (cap < set->nblk) return fail(set->ctx, -1, "nrq_txset_blocks: the set has %u blocks, the arrays have room for %u", set->nblk, cap);
+  uint32_t j = 0;
+  for (const txset_seg &r : set->segs) {
+    const tx_blk &t = r.tx->s.seg[r.g];
+    const uint32_t key = txset_key_of(set, r.tx);
+    for (uint32_t b = 0; b < t.nblk; b++, j++) {
+      if (h_keys) h_keys[j] = key;
+      if (h_sbn) h_sbn[j] = t.sbn0 + b;
+    }
+  }
+  return 0;
+}
+
+int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                   int32_t *d_results) {
+  using set_fn = void (*)(const txs_tab *, txs_ready, txs_call);
+  static const set_fn kern[2][5] = { /* [held][mode] */
+      {nrq_emit_set_kernel<TX_V16, false>, nrq_emit_set_kernel<TX_V16_SHIFT, false>, nrq_emit_set_kernel<TX_DWORD, false>,
+       nrq_emit_set_kernel<TX_BYTE, false>, nrq_emit_set_kernel<TXS_V16_KEY, false>},
+      {nrq_emit_set_kernel<TX_V16, true>, nrq_emit_set_kernel<TX_V16_SHIFT, true>, nrq_emit_set_kernel<TX_DWORD, true>,
+       nrq_emit_set_kernel<TX_BYTE, true>, nrq_emit_set_kernel<TXS_V16_KEY, true>}};
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0, kinl = (flags & NRQ_TX_KEY_INLINE) != 0, held = (flags & NRQ_TX_HELD) != 0;
+  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_HELD | NRQ_TX_KEY_INLINE)) return fail(ctx, -1, "nrq_txset_emit: unknown flags 0x%x", flags);
+  if (kinl && !inl) return fail(ctx, -1, "nrq_txset_emit: NRQ_TX_KEY_INLINE needs NRQ_TX_TAG_INLINE");
+  if (n == 0 || set->mem.empty()) return 0;
+  if (!d_pkts) return fail(ctx, -1, "nrq_txset_emit: d_pkts is NULL");
+  if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_txset_emit: bad tags (n=%u)", n);
+  const uint32_t hdr = kinl ? 8u : inl ? 4u : 0u;
+  if (pkt_stride < (size_t)set->T + hdr) return fail(ctx, -1, "nrq_txset_emit: pkt_stride %zu shorter than a packet", pkt_stride);
+  for (const txset_member &m : set->mem) {
+    if (m.tx->detached) return fail(ctx, -1, "nrq_txset_emit: the reception of the relay under key %u was destroyed", m.key);
+    if (!m.tx->encoded) return fail(ctx, -1, "nrq_txset_emit: the member under key %u is not encoded (%s)", m.key, m.tx->unencoded);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t nb = set->nblk, nbins = nb + 1u;
+  const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
+  if (set->scratch_cap < need) {
+    if (set->scratch) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+      nrq_dev_free(ctx, set->scratch);
+      set->scratch = nullptr;
+      set->scratch_cap = 0;
+    }
+    const int rc = nrq_dev_alloc(ctx, need, &set->scratch);
+    if (rc) return rc;
+    set->scratch_cap = need;
+  }
+  /* the ready bits of the global blocks as the members have them NOW, by value into this call's kernel arguments: a relay's mask
+   * changes in decodes, encodes and resets without any call on the set, and an emit still queued keeps the bits it was given */
+  txs_ready rdy{};
+  uintptr_t al = reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | set->T;
+  uint32_t g0 = 0;
+  for (const txset_seg &r : set->segs) {
+    const tx_sender *tx = r.tx;
+    const tx_blk &t = tx->s.seg[r.g];
+    for (uint32_t b = 0; b < t.nblk; b++)
+      if (!tx->relay || tx_is_ready(tx, t.sbn0 + b - tx->s.sbn0)) rdy.w[(g0 + b) >> 5] |= 1u << ((g0 + b) & 31u);
+    g0 += t.nblk;
+    al |= reinterpret_cast<uintptr_t>(t.src) | t.src_stride | reinterpret_cast<uintptr_t>(t.inter) | t.inter_stride;
+    if (held && tx->relay) { /* (held repair rows are copied too) */
+      const ing_rx &rr = tx->from[r.g]->r;
+      al |= reinterpret_cast<uintptr_t>(rr.rep) | rr.rep_stride;
+    }
+  }
+  const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (hdr == 8u ? TXS_V16_KEY : hdr ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
+  uint8_t *p = (uint8_t *)set->scratch;
+  uint32_t *cnt = (uint32_t *)p;
+  txs_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.hdr = hdr;
+  c.T = set->T;
+  c.keys = d_keys;
+  c.tags = d_tags;
+  c.seg = (uint32_t *)(p + o_seg);
+  c.order = (uint32_t *)(p + o_order);
+  c.results = d_results;
+  const txs_tab *t = (const txs_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_txs_hist_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
+  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_txs_place_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
+  const dim3 grid((n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
+  hipLaunchKernelGGL(kern[held][mode], grid, wg, 0, st, t, rdy, c);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
 }
 
 } /* extern "C" */
