@@ -14,21 +14,9 @@
 
 #include "ingest_body.h"
 
-/* 32-bit words of a block's seen bitmap that cover its source ESIs */
-ING_HD uint32_t hl_words(const struct ing_rx *r) { return (r->K + 31u) / 32u; }
-
-/* the seen source ESIs of word w of block b (bits at or above K masked off) */
+/* the seen source ESIs of word w (below ing_src_words) of block b */
 ING_HD uint32_t hl_have(const struct ing_rx *r, uint32_t b, uint32_t w) {
-  const uint32_t nb = r->K - w * 32u < 32u ? r->K - w * 32u : 32u;
-  return r->seen[(uint64_t)b * r->bm_words + w] & (nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u));
-}
-
-ING_HD uint32_t hl_popc(uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (uint32_t)__popc(v);
-#else
-  return (uint32_t)__builtin_popcount(v);
-#endif
+  return r->seen[(uint64_t)b * r->bm_words + w] & ing_src_mask(r, w);
 }
 
 /* repair rows of block b in use */
@@ -38,12 +26,7 @@ ING_HD uint32_t hl_nrep(const struct ing_rx *r, uint32_t b) { return r->nrep[b] 
 ING_HD uint32_t hl_put(const struct ing_rx *r, uint32_t b, uint32_t w, uint32_t have, uint32_t *out) {
   uint32_t n = 0;
   while (have) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t i = (uint32_t)__ffs(have) - 1u;
-#else
-    const uint32_t i = (uint32_t)__builtin_ctz(have);
-#endif
-    out[n++] = ((r->sbn0 + b) << 24) | (w * 32u + i);
+    out[n++] = ((r->sbn0 + b) << 24) | (w * 32u + ing_lowbit(have));
     have &= have - 1u;
   }
   return n;

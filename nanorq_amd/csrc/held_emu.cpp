@@ -105,7 +105,7 @@ int emu_rx_held(const uint32_t *prm, const uint32_t *seen, const uint32_t *nrep,
   std::vector<uint32_t> off(r.nblk + 1u, 0);
   for (uint32_t b = 0; b < r.nblk; b++) { /* count */
     uint32_t c = hl_nrep(&r, b);
-    for (uint32_t w = 0; w < hl_words(&r); w++) c += hl_popc(hl_have(&r, b, w));
+    for (uint32_t w = 0; w < ing_src_words(&r); w++) c += ing_popc(hl_have(&r, b, w));
     off[b] = c;
   }
   uint32_t run_ = 0; /* scan */
@@ -115,7 +115,7 @@ int emu_rx_held(const uint32_t *prm, const uint32_t *seen, const uint32_t *nrep,
   if (cap < *n) return -1;
   for (uint32_t b = 0; b < r.nblk; b++) { /* fill */
     uint32_t o = off[b];
-    for (uint32_t w = 0; w < hl_words(&r); w++) o += hl_put(&r, b, w, hl_have(&r, b, w), out + o);
+    for (uint32_t w = 0; w < ing_src_words(&r); w++) o += hl_put(&r, b, w, hl_have(&r, b, w), out + o);
     for (uint32_t q = 0; q < hl_nrep(&r, b); q++) out[o + q] = hl_rep_tag(&r, b, q);
   }
   return 0;

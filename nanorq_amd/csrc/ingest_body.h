@@ -81,6 +81,32 @@ ING_HD bool ing_seen(const struct ing_rx *r, uint32_t b, uint32_t esi) {
   return (r->seen[(uint64_t)b * r->bm_words + (esi >> 5)] >> (esi & 31u)) & 1u;
 }
 
+/* 32-bit words of a block's seen bitmap that cover its source ESIs */
+ING_HD uint32_t ing_src_words(const struct ing_rx *r) { return (r->K + 31u) / 32u; }
+
+/* the bits of word w (below ing_src_words) that are source ESIs: the last word is masked at K.  A decode that recovers a block
+ * sets exactly these in every word (nanorq_repair_block); the listings read no others as source symbols. */
+ING_HD uint32_t ing_src_mask(const struct ing_rx *r, uint32_t w) {
+  const uint32_t nb = r->K - w * 32u < 32u ? r->K - w * 32u : 32u;
+  return nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+}
+
+/* set bits of v; the number of its lowest set bit (v != 0) */
+ING_HD uint32_t ing_popc(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__popc(v);
+#else
+  return (uint32_t)__builtin_popcount(v);
+#endif
+}
+ING_HD uint32_t ing_lowbit(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__ffs(v) - 1u;
+#else
+  return (uint32_t)__builtin_ctz(v);
+#endif
+}
+
 /* pass 1 */
 ING_HD void ing_first(const struct ing_rx *r, const struct ing_call *c, uint32_t k) {
   uint32_t tag;

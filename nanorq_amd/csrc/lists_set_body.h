@@ -45,33 +45,16 @@ ING_HD void lss_list_count(const struct ings_tab *t, uint32_t g, uint32_t *buf) 
   if (g == 0) buf[2u * t->nblk] = 0;
 }
 
-/* 32-bit words of a block's seen bitmap that cover its source ESIs */
-ING_HD uint32_t lss_words(const struct ing_rx *r) { return (r->K + 31u) / 32u; }
-
-/* the missing source ESIs of word w of block b (the last word masked at K; w beyond the words: none) */
+/* the missing source ESIs of word w of block b (w beyond the words of the source ESIs: none) */
 ING_HD uint32_t lss_miss(const struct ing_rx *r, uint32_t b, uint32_t w) {
-  if (w >= lss_words(r)) return 0u;
-  const uint32_t nb = r->K - w * 32u < 32u ? r->K - w * 32u : 32u;
-  return ~r->seen[(uint64_t)b * r->bm_words + w] & (nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u));
-}
-
-ING_HD uint32_t lss_popc(uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (uint32_t)__popc(v);
-#else
-  return (uint32_t)__builtin_popcount(v);
-#endif
+  if (w >= ing_src_words(r)) return 0u;
+  return ~r->seen[(uint64_t)b * r->bm_words + w] & ing_src_mask(r, w);
 }
 
 /* the ESIs of word w's missing bits, ascending, to out[0 ..] */
 ING_HD void lss_put(uint32_t w, uint32_t miss, uint32_t *out) {
   while (miss) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t i = (uint32_t)__ffs(miss) - 1u;
-#else
-    const uint32_t i = (uint32_t)__builtin_ctz(miss);
-#endif
-    *out++ = w * 32u + i;
+    *out++ = w * 32u + ing_lowbit(miss);
     miss &= miss - 1u;
   }
 }

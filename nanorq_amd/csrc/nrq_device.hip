@@ -2804,7 +2804,113 @@ int nrq_timer_stop_ms(nrq_ctx *ctx, float *ms) {
 
 } /* extern "C" */
 
+/* the per-call device arrays of a reception, a sender or a set: kept from call to call, grown when a call needs more */
+struct DevScratch {
+  void *p;
+  size_t cap;
+  int ensure(nrq_ctx *ctx, size_t need) {
+    if (cap >= need) return 0;
+    if (p) HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
+    release(ctx);
+    const int rc = nrq_dev_alloc(ctx, need, &p);
+    if (!rc) cap = need;
+    return rc;
+  }
+  void release(nrq_ctx *ctx) { /* (the owner has waited for the stream: the pool hands freed blocks out again at once) */
+    if (p) nrq_dev_free(ctx, p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+/* ================================================ a 256-thread workgroup's scans and sums ==== */
+/* ps = 256 words of LDS, t = threadIdx.x; every thread of the workgroup calls, each ends with a barrier behind its last write.
+ * A caller that goes round again puts a barrier of its own behind its last read of ps. */
+
+/* inclusive scan (Hillis-Steele) of the threads' v: returns v of threads 0 .. t summed, ps[255] is the total */
+__device__ __forceinline__ uint32_t wg_scan(uint32_t *ps, uint32_t t, uint32_t v) {
+  ps[t] = v;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) {
+    const uint32_t u = t >= d ? ps[t - d] : 0u;
+    __syncthreads();
+    ps[t] += u;
+    __syncthreads();
+  }
+  return ps[t];
+}
+
+/* tree sum of the threads' v, returned to every thread */
+__device__ __forceinline__ uint32_t wg_sum(uint32_t *ps, uint32_t t, uint32_t v) {
+  ps[t] = v;
+  __syncthreads();
+  for (uint32_t s = 128; s; s >>= 1) {
+    if (t < s) ps[t] += ps[t + s];
+    __syncthreads();
+  }
+  return ps[0];
+}
+
+/* a[0 .. n) -> start + its exclusive prefix sums, in place: a run of entries per thread, a scan over the threads' sums.  Returns
+ * the sum of the entries. */
+__device__ __forceinline__ uint32_t wg_scan_runs(uint32_t *ps, uint32_t t, uint32_t *a, uint32_t n, uint32_t start) {
+  const uint32_t per = (n + 255u) / 256u, j0 = min(n, t * per), j1 = min(n, j0 + per);
+  uint32_t s = 0;
+  for (uint32_t j = j0; j < j1; j++) s += a[j];
+  uint32_t run = start + wg_scan(ps, t, s) - s;
+  for (uint32_t j = j0; j < j1; j++) { const uint32_t v = a[j]; a[j] = run; run += v; }
+  return ps[255];
+}
+
 /* ================================================ device-resident receiver (nrq_rx_*, ingest_body.h) ==== */
+/* The per-block passes as workgroup bodies of (reception, block): nrq_ing_*_kernel runs them on its by-value reception and
+ * blockIdx.x, nrq_ings_*_kernel on the member and block it finds in the set's table (lss_block). */
+
+/* done: the max and the count of ing_done_part over the block's K source ESIs */
+__device__ __forceinline__ void ing_done_wg(const ing_rx *r, uint32_t b, uint32_t *smx, uint32_t *scnt) {
+  const uint32_t t = threadIdx.x, K = r->K;
+  uint32_t mx = 0, cnt = 0;
+  if (r->gaps[b])
+    for (uint32_t e = t; e < K; e += 256u) ing_done_part(r, b, e, &mx, &cnt);
+  smx[t] = mx;
+  scnt[t] = cnt;
+  __syncthreads();
+  for (uint32_t s = 128; s; s >>= 1) {
+    if (t < s) { smx[t] = max(smx[t], smx[t + s]); scnt[t] += scnt[t + s]; }
+    __syncthreads();
+  }
+  if (t == 0) ing_done_finish(r, b, smx[0], scnt[0]);
+}
+
+/* scan: the block's nt tile counts -> the row of each tile's first candidate, starting at the rows already used */
+__device__ __forceinline__ void ing_scan_wg(const ing_rx *r, uint32_t b, uint32_t *base, uint32_t nt, uint32_t *ps) {
+  const uint32_t nrep0 = r->nrep[b]; /* (read by every thread before the scan's barriers, written behind them) */
+  const uint32_t total = wg_scan_runs(ps, threadIdx.x, base, nt, nrep0);
+  if (threadIdx.x == 0) r->nrep[b] = min(nrep0 + total, r->rep_cap);
+}
+
+/* mark: a block a decode recovered: every source ESI counts as seen from now on (what nanorq_repair_block does to the bitmap) */
+__device__ __forceinline__ void ing_mark_wg(const ing_rx *r, uint32_t b) {
+  const uint32_t nw = ing_src_words(r);
+  uint32_t *seen = r->seen + (size_t)b * r->bm_words;
+  for (uint32_t w = threadIdx.x; w < nw; w += 256u) seen[w] |= ing_src_mask(r, w);
+  if (threadIdx.x == 0) r->gaps[b] = 0;
+}
+
+/* list fill: the block's repair ESIs in arrival order, then its missing source ESIs ascending (LSS_ROUND words per round: a scan
+ * over their counts places each word's ESIs), to out[0 ..] */
+__device__ __forceinline__ void ing_lists_fill_wg(const ing_rx *r, uint32_t b, uint32_t *out, uint32_t *ps) {
+  const uint32_t t = threadIdx.x, nrep = r->nrep[b], nw = ing_src_words(r);
+  for (uint32_t q = t; q < nrep; q += 256u) out[q] = r->rep_esi[(size_t)b * r->rep_cap + q];
+  uint32_t o = nrep;
+  for (uint32_t w0 = 0; w0 < nw; w0 += LSS_ROUND) {
+    const uint32_t w = w0 + t, miss = lss_miss(r, b, w), cnt = ing_popc(miss);
+    lss_put(w, miss, out + o + wg_scan(ps, t, cnt) - cnt);
+    o += ps[255];
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(256) void nrq_ing_init_kernel(ing_rx r) {
   const uint32_t b = blockIdx.x * 256u + threadIdx.x;
   if (b < r.nblk) { r.gaps[b] = r.K; r.nrep[b] = 0; }
@@ -2815,21 +2921,10 @@ __global__ __launch_bounds__(256) void nrq_ing_first_kernel(ing_rx r, ing_call c
   if (k < c.n) ing_first(&r, &c, k);
 }
 
-/* one workgroup per block: the max and the count of ing_done_part over the block's K source ESIs */
+/* one workgroup per block */
 __global__ __launch_bounds__(256) void nrq_ing_done_kernel(ing_rx r) {
   __shared__ uint32_t smx[256], scnt[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x;
-  uint32_t mx = 0, cnt = 0;
-  if (r.gaps[b])
-    for (uint32_t e = t; e < r.K; e += 256u) ing_done_part(&r, b, e, &mx, &cnt);
-  smx[t] = mx;
-  scnt[t] = cnt;
-  __syncthreads();
-  for (uint32_t s = 128; s; s >>= 1) {
-    if (t < s) { smx[t] = max(smx[t], smx[t + s]); scnt[t] += scnt[t + s]; }
-    __syncthreads();
-  }
-  if (t == 0) ing_done_finish(&r, b, smx[0], scnt[0]);
+  ing_done_wg(&r, blockIdx.x, smx, scnt);
 }
 
 /* one workgroup per tile of ING_TILE packets: repair candidates per block */
@@ -2849,24 +2944,7 @@ __global__ __launch_bounds__(256) void nrq_ing_hist_kernel(ing_rx r, ing_call c)
 /* one workgroup per block: exclusive scan of the block's tile counts, starting at the rows already used */
 __global__ __launch_bounds__(256) void nrq_ing_scan_kernel(ing_rx r, ing_call c) {
   __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, nt = c.ntiles;
-  const uint32_t per = (nt + 255u) / 256u, t0 = min(nt, t * per), t1 = min(nt, t0 + per);
-  uint32_t *base = c.base + (size_t)b * nt;
-  uint32_t s = 0;
-  for (uint32_t i = t0; i < t1; i++) s += base[i];
-  ps[t] = s;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-    const uint32_t v = t >= d ? ps[t - d] : 0u;
-    __syncthreads();
-    ps[t] += v;
-    __syncthreads();
-  }
-  const uint32_t nrep0 = r.nrep[b], total = ps[255];
-  uint32_t run = nrep0 + ps[t] - s;
-  for (uint32_t i = t0; i < t1; i++) { const uint32_t v = base[i]; base[i] = run; run += v; }
-  __syncthreads(); /* (every thread has read nrep[b]) */
-  if (t == 0) r.nrep[b] = min(nrep0 + total, r.rep_cap);
+  ing_scan_wg(&r, blockIdx.x, c.base + (size_t)blockIdx.x * c.ntiles, c.ntiles, ps);
 }
 
 /* one workgroup per tile: a candidate's rank among its block's candidates in the tile, in packet order (wave by wave: a ballot
@@ -2898,14 +2976,16 @@ __global__ __launch_bounds__(256) void nrq_ing_classify_kernel(ing_rx r, ing_cal
   if (k < c.n) ing_classify(&r, &c, k, row);
 }
 
-/* one wave per packet: the payload to its row, 16-byte accesses when both ends and T allow (tag mode with a 16-byte stride),
- * else 4-byte (an inline header leaves the payload at +4), else bytes; two accesses in flight per lane */
-__global__ __launch_bounds__(256) void nrq_ing_copy_kernel(ing_call c, uint32_t T) {
+/* one wave per packet: the payload (at payload_off in the packet: 0, or behind an inline header of 4 or 8 bytes) to its row,
+ * 16-byte accesses when both ends and T allow (tag mode with a 16-byte stride), else 4-byte (a 4-byte header), else bytes; two
+ * accesses in flight per lane */
+__global__ __launch_bounds__(256) void nrq_ing_copy_kernel(const uint8_t *__restrict__ pkts, uint64_t pkt_stride, const uint64_t *__restrict__ dst,
+                                                           uint32_t n, uint32_t T, uint32_t payload_off) {
   const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (k >= c.n) return;
-  uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(c.dst[k]);
+  if (k >= n) return;
+  uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(dst[k]);
   if (!d) return;
-  const uint8_t *__restrict__ s = c.pkts + (size_t)k * c.pkt_stride + ing_payload_off(&c);
+  const uint8_t *__restrict__ s = pkts + (size_t)k * pkt_stride + payload_off;
   const uintptr_t al = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) | T;
   if ((al & 15u) == 0) {
     for (uint32_t off = lane * 16u; off < T; off += 2u * 1024u) {
@@ -2939,20 +3019,14 @@ struct ing_mask { uint32_t w[8]; }; /* a bit per block of the reception (nblk <=
 struct tx_sender;
 struct nrq_rxset;
 
-/* blocks a decode recovered: every source ESI counts as seen from now on (what nanorq_repair_block does to the bitmap) */
+/* the blocks a decode recovered: one workgroup per block, at work where the block's bit is set */
 __global__ __launch_bounds__(256) void nrq_ing_mark_kernel(ing_rx r, ing_mask m) {
   const uint32_t b = blockIdx.x;
-  if (!((m.w[b >> 5] >> (b & 31u)) & 1u)) return;
-  uint32_t *seen = r.seen + (size_t)b * r.bm_words;
-  for (uint32_t w = threadIdx.x; w * 32u < r.K; w += 256u) {
-    const uint32_t nb = min(32u, r.K - w * 32u);
-    seen[w] |= nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
-  }
-  if (threadIdx.x == 0) r.gaps[b] = 0;
+  if ((m.w[b >> 5] >> (b & 31u)) & 1u) ing_mark_wg(&r, b);
 }
 
 /* one workgroup per block: the compact lists.  out = gaps[nblk], nrep[nblk], then block by block its repair ESIs (arrival
- * order) and its missing source ESIs (ascending) */
+ * order) and its missing source ESIs (ascending).  One launch: lane 0 sums the counts of the blocks before its own */
 __global__ __launch_bounds__(256) void nrq_ing_lists_kernel(ing_rx r, uint32_t *out) {
   __shared__ uint32_t ps[256];
   __shared__ uint32_t s_off;
@@ -2965,37 +3039,7 @@ __global__ __launch_bounds__(256) void nrq_ing_lists_kernel(ing_rx r, uint32_t *
     out[r.nblk + b] = r.nrep[b];
   }
   __syncthreads();
-  const uint32_t nrep = r.nrep[b];
-  uint32_t off = s_off;
-  for (uint32_t q = t; q < nrep; q += 256u) out[off + q] = r.rep_esi[(size_t)b * r.rep_cap + q];
-  off += nrep;
-  const uint32_t *seen = r.seen + (size_t)b * r.bm_words;
-  const uint32_t nw = (r.K + 31u) / 32u;
-  for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
-    const uint32_t w = w0 + t;
-    uint32_t miss = 0;
-    if (w < nw) {
-      const uint32_t nb = min(32u, r.K - w * 32u);
-      miss = ~seen[w] & (nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u));
-    }
-    const uint32_t cnt = (uint32_t)__popc(miss);
-    ps[t] = cnt;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-      const uint32_t v = t >= d ? ps[t - d] : 0u;
-      __syncthreads();
-      ps[t] += v;
-      __syncthreads();
-    }
-    uint32_t o = off + ps[t] - cnt;
-    while (miss) {
-      const uint32_t i = (uint32_t)__ffs(miss) - 1u;
-      out[o++] = w * 32u + i;
-      miss &= miss - 1u;
-    }
-    off += ps[255];
-    __syncthreads();
-  }
+  ing_lists_fill_wg(&r, b, out + s_off, ps);
 }
 
 struct nrq_rx {
@@ -3004,11 +3048,10 @@ struct nrq_rx {
   uint32_t Kp;
   void *state;          /* first | seen | gaps | nrep | live | rep_esi */
   void *own_src, *own_rep;
-  void *scratch;        /* per-call arrays */
-  size_t scratch_cap;
-  void *lists;          /* nrq_ing_lists_kernel output, written anew by every call that reads it.  rx_held_count and rx_want_count
-                         * each borrow its first nblk + 1 words for their offsets and total: all users run on the context's stream
-                         * and none expects the buffer to survive from one call to the next -- keep it so */
+  DevScratch scratch;   /* per-call arrays */
+  void *lists;          /* nrq_ing_lists_kernel output, written anew by every call that reads it.  rx_list_count borrows its first
+                         * nblk + 1 words for the offsets and total of a held or want listing: all users run on the context's
+                         * stream and none expects the buffer to survive from one call to the next -- keep it so */
   tx_sender *relay;     /* the relay attached to this reception (nrq_rx_relay / nrq_orx_relay), or null ... */
   uint32_t relay_seg, relay_b0; /* ... in whose table this reception is segment relay_seg, its block 0 the span's block relay_b0 */
   nrq_rxset *set;       /* the reception set this reception is a member of (nrq_rxset_attach), or null */
@@ -3094,8 +3137,9 @@ void nrq_rx_destroy(nrq_rx *rx) {
   if (rx->relay) relay_detach(rx->relay); /* (its later calls fail with an error text; it frees what it owns itself) */
   if (rx->set) rxset_drop(rx);            /* (the set's table is rewritten without it, behind the work enqueued so far) */
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {rx->own_src, rx->own_rep, rx->state, rx->scratch, rx->lists})
+  for (void *p : {rx->own_src, rx->own_rep, rx->state, rx->lists})
     if (p) nrq_dev_free(ctx, p);
+  rx->scratch.release(ctx);
   delete rx;
 }
 
@@ -3128,18 +3172,9 @@ int nrq_rx_add(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t
   c.ntiles = (n + ING_TILE - 1u) / ING_TILE;
   const size_t o_codes = rx_al((size_t)n * 4u), o_fidx = o_codes + rx_al((size_t)n * 4u), o_dst = o_fidx + rx_al((size_t)n * 4u),
                o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)r.nblk * c.ntiles * 4u);
-  if (rx->scratch_cap < need) {
-    if (rx->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, rx->scratch);
-      rx->scratch = nullptr;
-      rx->scratch_cap = 0;
-    }
-    int rc = nrq_dev_alloc(ctx, need, &rx->scratch);
-    if (rc) return rc;
-    rx->scratch_cap = need;
-  }
-  uint8_t *s = (uint8_t *)rx->scratch;
+  const int rc = rx->scratch.ensure(ctx, need);
+  if (rc) return rc;
+  uint8_t *s = (uint8_t *)rx->scratch.p;
   c.tagv = (uint32_t *)s;
   c.codes = d_results ? d_results : (int32_t *)(s + o_codes);
   c.fidx = (uint32_t *)(s + o_fidx);
@@ -3152,7 +3187,8 @@ int nrq_rx_add(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t
   hipLaunchKernelGGL(nrq_ing_hist_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c);
   hipLaunchKernelGGL(nrq_ing_scan_kernel, dim3(r.nblk), dim3(256), 0, st, r, c);
   hipLaunchKernelGGL(nrq_ing_classify_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c);
-  hipLaunchKernelGGL(nrq_ing_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c, r.T);
+  hipLaunchKernelGGL(nrq_ing_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, r.T,
+                     ing_payload_off(&c));
   hipLaunchKernelGGL(nrq_ing_fold_kernel, dim3(g), dim3(256), 0, st, r, c);
   HIPCHK(ctx, hipGetLastError());
   return 0;
@@ -3208,67 +3244,98 @@ int nrq_rx_lists(nrq_rx *rx, uint32_t *h_nlost, uint32_t *h_nrep, uint32_t *h_lo
   return 0;
 }
 
+/* The downloaded lists of some receptions' blocks in the host form both decodes read.  Listed block j is block blk[j] of rx[j],
+ * which is member[j] of the caller's rxset_plan_member array; it has ng[j] missing source ESIs and nr[j] repair ESIs, and
+ * words[off[j] ..] holds the repair ESIs in arrival order, then the missing source ESIs ascending. */
+struct rx_listing {
+  std::vector<nrq_rx *> rx;
+  std::vector<uint32_t> member, blk, ng, nr;
+  std::vector<size_t> off;
+  std::vector<uint32_t> words;
+  void add(nrq_rx *x, uint32_t m, uint32_t b, uint32_t g, uint32_t r, size_t o) {
+    rx.push_back(x); member.push_back(m); blk.push_back(b); ng.push_back(g); nr.push_back(r); off.push_back(o);
+  }
+};
+
+/* The decode of listed blocks, one nrq_decode_blocks_vi per chunk of their rxset_plan.  h_status / h_used of every listed block:
+ * status 1 for a block without gaps, 0 and 0 symbols used for one that is not decoded now, else what its decode call says.  With
+ * a relay attached to a block's reception the decode also writes the block's intermediate symbols into the relay's buffer (and
+ * so back-substitutes all pivots) and the relay learns of every recovered block; without one it asks for none, as
+ * nrq_decode_blocks_v.  `recovered`: the listed blocks whose decode succeeded, for the caller's mark launch.  A failing decode
+ * call ends it with that call's code and error text: its chunk's and the later chunks' blocks keep status 0 and their books, the
+ * chunks before it are in `recovered`. */
+static int rx_decode_listed(nrq_ctx *ctx, const rx_listing &L, const std::vector<rxset_chunk> &chunks, int *h_status, uint32_t *h_used,
+                            std::vector<uint32_t> &recovered) {
+  for (size_t j = 0; j < L.rx.size(); j++) {
+    h_status[j] = L.ng[j] == 0 ? 1 : 0;
+    if (h_used) h_used[j] = 0;
+  }
+  std::vector<uint32_t> lost, resi, nlost, nuse, navail, used;
+  std::vector<uint64_t> sv, rv, iv;
+  std::vector<int> st;
+  for (const rxset_chunk &c : chunks) {
+    const size_t ns = c.blocks.size();
+    uint32_t lost_cap = 1, rep_cap = 1;
+    for (uint32_t j : c.blocks) { lost_cap = std::max(lost_cap, L.ng[j]); rep_cap = std::max(rep_cap, L.nr[j]); }
+    lost.assign(ns * lost_cap, 0); resi.assign(ns * rep_cap, 0);
+    nlost.resize(ns); nuse.resize(ns); navail.resize(ns); used.assign(ns, 0); sv.resize(ns); rv.resize(ns); st.assign(ns, 0);
+    iv.resize(c.has_relay ? ns : 0);
+    for (size_t i = 0; i < ns; i++) {
+      const uint32_t j = c.blocks[i], b = L.blk[j], ng = L.ng[j], nr = L.nr[j];
+      const nrq_rx *rx = L.rx[j];
+      const ing_rx &r = rx->r;
+      const uint32_t *l = L.words.data() + L.off[j];
+      memcpy(resi.data() + i * rep_cap, l, (size_t)nr * 4u);
+      memcpy(lost.data() + i * lost_cap, l + nr, (size_t)ng * 4u);
+      nlost[i] = ng;
+      nuse[i] = rxset_nuse(ng, nr);
+      navail[i] = nr;
+      sv[i] = (uint64_t)(uintptr_t)(r.src + b * r.src_stride);
+      rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
+      if (c.has_relay) iv[i] = relay_inter(rx->relay, rx->relay_seg, b);
+    }
+    const int rc = nrq_decode_blocks_vi(ctx, c.K, c.Kp, L.rx[c.blocks[0]]->r.T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap,
+                                        resi.data(), nuse.data(), navail.data(), rep_cap, rv.data(), c.has_relay ? iv.data() : nullptr,
+                                        st.data(), used.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < ns; i++) {
+      const uint32_t j = c.blocks[i];
+      const nrq_rx *rx = L.rx[j];
+      h_status[j] = st[i];
+      if (h_used) h_used[j] = used[i];
+      if (!st[i]) continue;
+      recovered.push_back(j);
+      if (rx->relay) relay_set(rx->relay, rx->relay_b0 + L.blk[j], 1, true);
+    }
+  }
+  return 0;
+}
+
+/* a reception decodes as a set of one member: at most 256 blocks, so its selected blocks are one chunk, one decode call */
+static_assert(RXSET_CHUNK_BLOCKS >= 256u, "nrq_rx_decode is one decode call over a reception's up to 256 blocks");
+
 int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
   if (!rx) return -1;
   nrq_ctx *ctx = rx->ctx;
   if (!h_status) return fail(ctx, -1, "nrq_rx_decode: h_status is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const ing_rx &r = rx->r;
-  std::vector<uint32_t> cnt, lists;
-  int rc = rx_fetch_lists(rx, cnt, lists);
+  std::vector<uint32_t> cnt;
+  rx_listing L;
+  int rc = rx_fetch_lists(rx, cnt, L.words);
   if (rc) return rc;
-  /* the blocks that can be decoded now, by the rules of nanorq_repair_block: gaps, at least as many repair symbols as gaps,
-   * and no more extra symbols than the rows beyond L (max_esi - K) */
-  std::vector<uint32_t> sel, lost, resi, nlost, nuse, navail, used;
-  std::vector<uint64_t> sv, rv;
-  std::vector<size_t> offs(r.nblk);
-  uint32_t lost_cap = 1, rep_cap = 1;
   size_t off = 0;
-  for (uint32_t b = 0; b < r.nblk; b++) {
-    offs[b] = off;
-    const uint32_t ng = cnt[b], nr = cnt[r.nblk + b];
-    off += (size_t)ng + nr;
-    h_status[b] = ng == 0 ? 1 : 0;
-    if (h_used) h_used[b] = 0;
-    if (ng == 0 || nr < ng || nr - ng > r.max_esi - r.K) continue;
-    sel.push_back(b);
-    lost_cap = std::max(lost_cap, ng);
-    rep_cap = std::max(rep_cap, nr);
+  for (uint32_t b = 0; b < r.nblk; b++) { /* (the device format has no offsets: the lists lie one behind the other) */
+    L.add(rx, 0, b, cnt[b], cnt[r.nblk + b], off);
+    off += (size_t)cnt[b] + cnt[r.nblk + b];
   }
-  if (sel.empty()) return 0;
-  const size_t ns = sel.size();
-  lost.assign(ns * lost_cap, 0); resi.assign(ns * rep_cap, 0);
-  nlost.resize(ns); nuse.resize(ns); navail.resize(ns); used.assign(ns, 0); sv.resize(ns); rv.resize(ns);
-  for (size_t i = 0; i < ns; i++) {
-    const uint32_t b = sel[i], ng = cnt[b], nr = cnt[r.nblk + b];
-    memcpy(resi.data() + i * rep_cap, lists.data() + offs[b], (size_t)nr * 4u);
-    memcpy(lost.data() + i * lost_cap, lists.data() + offs[b] + nr, (size_t)ng * 4u);
-    nlost[i] = ng;
-    nuse[i] = nr - ng > 2u ? ng + 2u : nr; /* as the object layer: two extra symbols up front, the rest on demand */
-    navail[i] = nr;
-    sv[i] = (uint64_t)(uintptr_t)(r.src + b * r.src_stride);
-    rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
-  }
-  std::vector<int> st(ns, 0);
-  /* with a relay attached the decode also writes the intermediate symbols of every block it recovers, into the relay's buffer
-   * (and so back-substitutes all pivots); without one it asks for none, as nrq_decode_blocks_v */
-  std::vector<uint64_t> iv;
-  if (rx->relay) {
-    iv.resize(ns);
-    for (size_t i = 0; i < ns; i++) iv[i] = relay_inter(rx->relay, rx->relay_seg, sel[i]);
-  }
-  rc = nrq_decode_blocks_vi(ctx, r.K, rx->Kp, r.T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
-                            navail.data(), rep_cap, rv.data(), rx->relay ? iv.data() : nullptr, st.data(), used.data());
-  if (rc) return rc;
-  ing_mask m{};
-  bool any = false;
-  for (size_t i = 0; i < ns; i++) {
-    h_status[sel[i]] = st[i];
-    if (h_used) h_used[sel[i]] = used[i];
-    if (st[i]) { m.w[sel[i] >> 5] |= 1u << (sel[i] & 31u); any = true; }
-    if (st[i] && rx->relay) relay_set(rx->relay, rx->relay_b0 + sel[i], 1, true);
-  }
-  if (any) {
+  const rxset_plan_member pm{r.K, rx->Kp, r.max_esi, rx->relay ? 1u : 0u};
+  std::vector<uint32_t> recovered;
+  rc = rx_decode_listed(ctx, L, rxset_plan(&pm, L.member.data(), L.ng.data(), L.nr.data(), r.nblk), h_status, h_used, recovered);
+  if (rc) return rc; /* (of the one chunk: no block is marked) */
+  if (!recovered.empty()) {
+    ing_mask m{};
+    for (uint32_t b : recovered) m.w[b >> 5] |= 1u << (b & 31u);
     hipLaunchKernelGGL(nrq_ing_mark_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, m);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -3481,8 +3548,7 @@ struct tx_sender {
   void *own[2];          /* device buffers it owns: the intermediate symbols; an object's row images or staged last block */
   bool encoded;
   const char *unencoded; /* the emit calls' refusal before the encode */
-  void *scratch;         /* list mode: bucket counts, then the work order */
-  size_t scratch_cap;
+  DevScratch scratch;    /* list mode: bucket counts, then the work order */
   /* A relay (nrq_rx_relay / nrq_orx_relay): segment g's source rows are those of the reception from[g], and s.ready has the bit
    * of every block whose intermediate symbols are written -- by a decode of the reception while the relay was attached, or by
    * the relay's encode for a block that is complete (only complete blocks ever get the bit: ready = complete and written). */
@@ -3525,8 +3591,9 @@ static void tx_destroy(S *tx) {
   for (nrq_rx *r : tx->from)
     if (r) r->relay = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {tx->own[0], tx->own[1], tx->scratch})
+  for (void *p : {tx->own[0], tx->own[1]})
     if (p) nrq_dev_free(ctx, p);
+  tx->scratch.release(ctx);
   delete tx;
 }
 
@@ -3659,17 +3726,8 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
   const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if (tx->scratch_cap < need) {
-    if (tx->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, tx->scratch);
-      tx->scratch = nullptr;
-      tx->scratch_cap = 0;
-    }
-    if ((rc = nrq_dev_alloc(ctx, need, &tx->scratch))) return rc;
-    tx->scratch_cap = need;
-  }
-  uint32_t *cnt = (uint32_t *)tx->scratch, *order = (uint32_t *)((uint8_t *)tx->scratch + o_order);
+  if ((rc = tx->scratch.ensure(ctx, need))) return rc;
+  uint32_t *cnt = (uint32_t *)tx->scratch.p, *order = (uint32_t *)((uint8_t *)tx->scratch.p + o_order);
   hipStream_t st = ctx->stream;
   const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
   HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
@@ -4156,36 +4214,23 @@ int nrq_orx_write(nrq_orx *rx, void *d_out) {
 /* one workgroup per block: seen source ESIs plus repair rows used -> cnt[b] */
 __global__ __launch_bounds__(256) void nrq_held_count_kernel(ing_rx r, uint32_t *cnt) {
   __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = hl_words(&r);
+  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = ing_src_words(&r);
   uint32_t n = 0;
-  for (uint32_t w = t; w < nw; w += 256u) n += hl_popc(hl_have(&r, b, w));
-  ps[t] = n;
-  __syncthreads();
-  for (uint32_t s = 128; s; s >>= 1) {
-    if (t < s) ps[t] += ps[t + s];
-    __syncthreads();
-  }
-  if (t == 0) cnt[b] = ps[0] + hl_nrep(&r, b);
+  for (uint32_t w = t; w < nw; w += 256u) n += ing_popc(hl_have(&r, b, w));
+  n = wg_sum(ps, t, n);
+  if (t == 0) cnt[b] = n + hl_nrep(&r, b);
 }
 
 /* one workgroup per block: its tags to out + off[b] -- the seen source ESIs ascending (256 words per round: a scan over their
  * counts places each word's tags), then the repair ESIs in arrival order */
 __global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint32_t *off, uint32_t *out) {
   __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = hl_words(&r);
+  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = ing_src_words(&r);
   uint32_t o = off[b];
   for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
     const uint32_t w = w0 + t;
-    const uint32_t have = w < nw ? hl_have(&r, b, w) : 0u, cnt = hl_popc(have);
-    ps[t] = cnt;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-      const uint32_t v = t >= d ? ps[t - d] : 0u;
-      __syncthreads();
-      ps[t] += v;
-      __syncthreads();
-    }
-    hl_put(&r, b, w, have, out + o + ps[t] - cnt);
+    const uint32_t have = w < nw ? hl_have(&r, b, w) : 0u, cnt = ing_popc(have);
+    hl_put(&r, b, w, have, out + o + wg_scan(ps, t, cnt) - cnt);
     o += ps[255];
     __syncthreads();
   }
@@ -4194,46 +4239,62 @@ __global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint
 }
 
 /* count and scan, enqueued: the blocks' exclusive offsets and, behind them, the total, in the reception's list buffer.
+ * `count(rx, cnt)` launches the kernel that writes a count per block.
  * That buffer is the output of nrq_ing_lists_kernel (nrq_rx.lists), of whose 2 * nblk + ... words this takes the first nblk + 1,
- * and so does rx_want_count below.  The rule for every user: write the words anew in the call that reads them, read them on the
- * context's stream within that call, expect nothing of them afterwards.  rx_fetch_lists launches its kernel again before it
+ * for a held and for a want listing alike.  The rule for every user: write the words anew in the call that reads them, read them
+ * on the context's stream within that call, expect nothing of them afterwards.  rx_fetch_lists launches its kernel again before it
  * reads, the fill kernels read the offsets on the same stream before anything later can overwrite them, so the uses cannot meet.
  * A caller that kept the lists on the device across calls would break this. */
-static int rx_held_count(nrq_rx *rx) {
+template <class Count>
+static int rx_list_count(nrq_rx *rx, Count count) {
   nrq_ctx *ctx = rx->ctx;
   const ing_rx &r = rx->r;
   uint32_t *cnt = (uint32_t *)rx->lists;
   HIPCHK(ctx, hipMemsetAsync(cnt + r.nblk, 0, 4u, ctx->stream));
-  hipLaunchKernelGGL(nrq_held_count_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, cnt);
+  count(rx, cnt);
   hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, r.nblk + 1u, cnt);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
 
-/* the held tags of up to two receptions, one behind the other */
-static int held_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
-  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
-  *h_n = 0;
+/* a listing (`what`: "held", "wanted") of up to two receptions, one behind the other: count per reception, the totals downloaded,
+ * then `fill(i, rx, off, out)` launches the kernel that writes reception i's tags to out[off[b] ..] */
+template <class Count, class Fill>
+static int rx_list(nrq_ctx *ctx, const char *who, const char *what, nrq_rx *const *rxs, int nrx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n,
+                   Count count, Fill fill) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   uint32_t n[2] = {0, 0};
   for (int i = 0; i < nrx; i++) {
     if (!rxs[i]) continue;
-    const int rc = rx_held_count(rxs[i]);
+    const int rc = rx_list_count(rxs[i], [&](nrq_rx *rx, uint32_t *cnt) { count(i, rx, cnt); });
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(&n[i], (uint32_t *)rxs[i]->lists + rxs[i]->r.nblk, 4u, hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   *h_n = n[0] + n[1];
   if (!d_tags) return 0;
-  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are held, d_tags has room for %u", who, *h_n, cap);
+  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are %s, d_tags has room for %u", who, *h_n, what, cap);
   uint32_t at = 0;
   for (int i = 0; i < nrx; i++) {
     if (!rxs[i]) continue;
-    if (n[i]) hipLaunchKernelGGL(nrq_held_fill_kernel, dim3(rxs[i]->r.nblk), dim3(256), 0, ctx->stream, rxs[i]->r, (const uint32_t *)rxs[i]->lists, d_tags + at);
+    if (n[i]) fill(i, rxs[i], (const uint32_t *)rxs[i]->lists, d_tags + at);
     at += n[i];
   }
   HIPCHK(ctx, hipGetLastError());
   return 0;
+}
+
+/* the held tags of up to two receptions */
+static int held_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
+  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
+  *h_n = 0;
+  hipStream_t st = ctx->stream;
+  return rx_list(
+      ctx, who, "held", rxs, nrx, d_tags, cap, h_n,
+      [&](int, nrq_rx *rx, uint32_t *cnt) { hipLaunchKernelGGL(nrq_held_count_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, cnt); },
+      [&](int, nrq_rx *rx, const uint32_t *off, uint32_t *out) {
+        hipLaunchKernelGGL(nrq_held_fill_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, off, out);
+      });
 }
 
 extern "C" {
@@ -4259,13 +4320,7 @@ __global__ __launch_bounds__(256) void nrq_want_count_kernel(ing_rx r, wn_q q, u
   uint32_t found = 0;
   for (uint32_t w0 = wn_first(&q); w0 < w_end && found < need; w0 += WN_ROUND) { /* (found and need are the same in every thread) */
     const uint32_t w = w0 + t;
-    ps[t] = w < w_end ? hl_popc(wn_bits(&r, &q, b, w)) : 0u;
-    __syncthreads();
-    for (uint32_t s = 128; s; s >>= 1) {
-      if (t < s) ps[t] += ps[t + s];
-      __syncthreads();
-    }
-    found += ps[0];
+    found += wg_sum(ps, t, w < w_end ? ing_popc(wn_bits(&r, &q, b, w)) : 0u);
     __syncthreads();
   }
   if (t == 0) cnt[b] = min(found, need);
@@ -4280,34 +4335,14 @@ __global__ __launch_bounds__(256) void nrq_want_fill_kernel(ing_rx r, wn_q q, co
   uint32_t placed = 0;
   for (uint32_t w0 = wn_first(&q); w0 < w_end && placed < need; w0 += WN_ROUND) {
     const uint32_t w = w0 + t;
-    const uint32_t bits = w < w_end ? wn_bits(&r, &q, b, w) : 0u, c = hl_popc(bits);
-    ps[t] = c;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-      const uint32_t v = t >= d ? ps[t - d] : 0u;
-      __syncthreads();
-      ps[t] += v;
-      __syncthreads();
-    }
-    wn_put(&r, b, w, bits, placed + ps[t] - c, need, dst);
+    const uint32_t bits = w < w_end ? wn_bits(&r, &q, b, w) : 0u, c = ing_popc(bits);
+    wn_put(&r, b, w, bits, placed + wg_scan(ps, t, c) - c, need, dst);
     placed += ps[255];
     __syncthreads();
   }
 }
 
-/* count and scan, enqueued, into the first nblk + 1 words of the reception's list buffer (the rule: rx_held_count) */
-static int rx_want_count(nrq_rx *rx, const wn_q &q) {
-  nrq_ctx *ctx = rx->ctx;
-  const ing_rx &r = rx->r;
-  uint32_t *cnt = (uint32_t *)rx->lists;
-  HIPCHK(ctx, hipMemsetAsync(cnt + r.nblk, 0, 4u, ctx->stream));
-  hipLaunchKernelGGL(nrq_want_count_kernel, dim3(r.nblk), dim3(256), 0, ctx->stream, r, q, cnt);
-  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, r.nblk + 1u, cnt);
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
-}
-
-/* the wanted tags of up to two receptions, one behind the other */
+/* the wanted tags of up to two receptions */
 static int want_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t flags, uint32_t extra, uint32_t esi_from,
                      uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
   if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
@@ -4318,28 +4353,16 @@ static int want_list(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx,
     case 3: return fail(ctx, -1, "%s: extra %u is above 2^24", who, extra);
     default: break;
   }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  uint32_t n[2] = {0, 0};
   wn_q q[2] = {};
-  for (int i = 0; i < nrx; i++) {
-    if (!rxs[i]) continue;
-    q[i] = wn_query(&rxs[i]->r, flags, extra, esi_from);
-    const int rc = rx_want_count(rxs[i], q[i]);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(&n[i], (uint32_t *)rxs[i]->lists + rxs[i]->r.nblk, 4u, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  *h_n = n[0] + n[1];
-  if (!d_tags) return 0;
-  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are wanted, d_tags has room for %u", who, *h_n, cap);
-  uint32_t at = 0;
-  for (int i = 0; i < nrx; i++) {
-    if (!rxs[i]) continue;
-    if (n[i]) hipLaunchKernelGGL(nrq_want_fill_kernel, dim3(rxs[i]->r.nblk), dim3(256), 0, ctx->stream, rxs[i]->r, q[i], (const uint32_t *)rxs[i]->lists, d_tags + at);
-    at += n[i];
-  }
-  HIPCHK(ctx, hipGetLastError());
-  return 0;
+  for (int i = 0; i < nrx; i++)
+    if (rxs[i]) q[i] = wn_query(&rxs[i]->r, flags, extra, esi_from);
+  hipStream_t st = ctx->stream;
+  return rx_list(
+      ctx, who, "wanted", rxs, nrx, d_tags, cap, h_n,
+      [&](int i, nrq_rx *rx, uint32_t *cnt) { hipLaunchKernelGGL(nrq_want_count_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, q[i], cnt); },
+      [&](int i, nrq_rx *rx, const uint32_t *off, uint32_t *out) {
+        hipLaunchKernelGGL(nrq_want_fill_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, q[i], off, out);
+      });
 }
 
 extern "C" {
@@ -4358,8 +4381,10 @@ int nrq_orx_want(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from,
 
 /* ================================================ reception sets (nrq_rxset_*, ingest_set_body.h) ==== */
 /* The seven passes of the ingest above over a member table in device memory: one chain of kernels for the packets of all
- * members.  Per-block passes run one workgroup per GLOBAL block and find its member from the block offsets; per-tile passes count
- * per global block in LDS sized by the set's block total (dynamic: a set of 256 blocks pays what a reception of 256 blocks pays). */
+ * members.  Per-block passes run one workgroup per GLOBAL block, find its member from the block offsets and run the single
+ * form's workgroup body on it; the copy pass is the single form's kernel; per-packet and per-tile passes are kernels of their own
+ * (they read the table and count per global block in LDS sized by the set's block total: dynamic, a set of 256 blocks pays what
+ * a reception of 256 blocks pays). */
 __global__ __launch_bounds__(256) void nrq_ings_first_kernel(const ings_tab *__restrict__ t, ings_call s) {
   __shared__ uint32_t skey[INGS_MAX_MEMBERS], ssbn0[INGS_MAX_MEMBERS], scnt[INGS_MAX_MEMBERS], sobjZ[INGS_MAX_MEMBERS];
   const uint32_t nmem = t->nmem, i = threadIdx.x;
@@ -4374,21 +4399,9 @@ __global__ __launch_bounds__(256) void nrq_ings_first_kernel(const ings_tab *__r
 
 __global__ __launch_bounds__(256) void nrq_ings_done_kernel(const ings_tab *__restrict__ t) {
   __shared__ uint32_t smx[256], scnt[256];
-  const uint32_t g = blockIdx.x, i = threadIdx.x;
-  const uint32_t m = ings_member_of_block(t->blk0, t->nmem, g), b = g - t->blk0[m];
-  const ing_rx *r = &t->r[m];
-  const uint32_t K = r->K;
-  uint32_t mx = 0, cnt = 0;
-  if (r->gaps[b])
-    for (uint32_t e = i; e < K; e += 256u) ing_done_part(r, b, e, &mx, &cnt);
-  smx[i] = mx;
-  scnt[i] = cnt;
-  __syncthreads();
-  for (uint32_t d = 128; d; d >>= 1) {
-    if (i < d) { smx[i] = max(smx[i], smx[i + d]); scnt[i] += scnt[i + d]; }
-    __syncthreads();
-  }
-  if (i == 0) ing_done_finish(r, b, smx[0], scnt[0]);
+  uint32_t b;
+  const ing_rx *r = lss_block(t, blockIdx.x, &b);
+  ing_done_wg(r, b, smx, scnt);
 }
 
 /* dynamic LDS: t->nblk counters */
@@ -4407,26 +4420,9 @@ __global__ __launch_bounds__(256) void nrq_ings_hist_kernel(const ings_tab *__re
 
 __global__ __launch_bounds__(256) void nrq_ings_scan_kernel(const ings_tab *__restrict__ t, ings_call s) {
   __shared__ uint32_t ps[256];
-  const uint32_t g = blockIdx.x, i = threadIdx.x, nt = s.c.ntiles;
-  const uint32_t m = ings_member_of_block(t->blk0, t->nmem, g), b = g - t->blk0[m];
-  const ing_rx *r = &t->r[m];
-  const uint32_t per = (nt + 255u) / 256u, t0 = min(nt, i * per), t1 = min(nt, t0 + per);
-  uint32_t *base = s.c.base + (size_t)g * nt;
-  uint32_t sum = 0;
-  for (uint32_t j = t0; j < t1; j++) sum += base[j];
-  ps[i] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-    const uint32_t v = i >= d ? ps[i - d] : 0u;
-    __syncthreads();
-    ps[i] += v;
-    __syncthreads();
-  }
-  const uint32_t nrep0 = r->nrep[b], total = ps[255];
-  uint32_t run = nrep0 + ps[i] - sum;
-  for (uint32_t j = t0; j < t1; j++) { const uint32_t v = base[j]; base[j] = run; run += v; }
-  __syncthreads(); /* (every thread has read nrep[b]) */
-  if (i == 0) r->nrep[b] = min(nrep0 + total, r->rep_cap);
+  uint32_t b;
+  const ing_rx *r = lss_block(t, blockIdx.x, &b);
+  ing_scan_wg(r, b, s.c.base + (size_t)blockIdx.x * s.c.ntiles, s.c.ntiles, ps);
 }
 
 /* dynamic LDS: 4 * t->nblk counters (per wave, per global block).  The ballot loop is the one of nrq_ing_classify_kernel with the
@@ -4458,38 +4454,6 @@ __global__ __launch_bounds__(256) void nrq_ings_classify_kernel(const ings_tab *
   if (k < s.c.n) ings_classify(t, &s, k, row);
 }
 
-/* nrq_ing_copy_kernel with the payload's offset in the packet (0, 4 or 8) as an argument */
-__global__ __launch_bounds__(256) void nrq_ings_copy_kernel(const uint8_t *__restrict__ pkts, uint64_t pkt_stride, const uint64_t *__restrict__ dst,
-                                                            uint32_t n, uint32_t T, uint32_t poff) {
-  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (k >= n) return;
-  uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(dst[k]);
-  if (!d) return;
-  const uint8_t *__restrict__ sp = pkts + (size_t)k * pkt_stride + poff;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(sp) | reinterpret_cast<uintptr_t>(d) | T;
-  if ((al & 15u) == 0) {
-    for (uint32_t off = lane * 16u; off < T; off += 2u * 1024u) {
-      const uint4 v0 = *reinterpret_cast<const uint4 *>(sp + off);
-      const bool two = off + 1024u < T;
-      uint4 v1;
-      if (two) v1 = *reinterpret_cast<const uint4 *>(sp + off + 1024u);
-      *reinterpret_cast<uint4 *>(d + off) = v0;
-      if (two) *reinterpret_cast<uint4 *>(d + off + 1024u) = v1;
-    }
-  } else if ((al & 3u) == 0) {
-    for (uint32_t off = lane * 4u; off < T; off += 2u * 256u) {
-      const uint32_t v0 = *reinterpret_cast<const uint32_t *>(sp + off);
-      const bool two = off + 256u < T;
-      uint32_t v1 = 0;
-      if (two) v1 = *reinterpret_cast<const uint32_t *>(sp + off + 256u);
-      *reinterpret_cast<uint32_t *>(d + off) = v0;
-      if (two) *reinterpret_cast<uint32_t *>(d + off + 256u) = v1;
-    }
-  } else {
-    for (uint32_t off = lane; off < T; off += 64u) d[off] = sp[off];
-  }
-}
-
 __global__ __launch_bounds__(256) void nrq_ings_fold_kernel(const ings_tab *__restrict__ t, ings_call s) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k < s.c.n) ings_fold(t, &s, k);
@@ -4509,10 +4473,9 @@ struct nrq_rxset {
   std::vector<rxset_member> mem; /* sorted by (key, sbn0): the order of the device table */
   uint32_t nblk;                 /* blocks over all members */
   void *tab;                     /* struct ings_tab in device memory */
-  void *scratch;                 /* per-call arrays */
-  size_t scratch_cap;
+  DevScratch scratch;            /* per-call arrays */
   void *lists;                   /* the listing passes' output (lists_set_body.h), sized for the worst case of the members.  The rule of
-                                  * rx_held_count holds: written anew by every call that reads it, read on the context's stream
+                                  * rx_list_count holds: written anew by every call that reads it, read on the context's stream
                                   * within that call, nothing expected of it afterwards */
   size_t lists_cap;
 };
@@ -4633,8 +4596,9 @@ void nrq_rxset_destroy(nrq_rxset *set) {
   nrq_ctx *ctx = set->ctx;
   for (const rxset_member &m : set->mem) m.rx->set = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {set->tab, set->scratch, set->lists})
+  for (void *p : {set->tab, set->lists})
     if (p) nrq_dev_free(ctx, p);
+  set->scratch.release(ctx);
   delete set;
 }
 
@@ -4684,18 +4648,9 @@ int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const u
   s.key_inline = kinl ? 1u : 0u;
   const size_t a4 = rx_al((size_t)n * 4u), o_mem = a4, o_codes = o_mem + a4, o_fidx = o_codes + a4, o_dst = o_fidx + a4,
                o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)set->nblk * c.ntiles * 4u);
-  if (set->scratch_cap < need) {
-    if (set->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, set->scratch);
-      set->scratch = nullptr;
-      set->scratch_cap = 0;
-    }
-    int rc = nrq_dev_alloc(ctx, need, &set->scratch);
-    if (rc) return rc;
-    set->scratch_cap = need;
-  }
-  uint8_t *p = (uint8_t *)set->scratch;
+  const int rc = set->scratch.ensure(ctx, need);
+  if (rc) return rc;
+  uint8_t *p = (uint8_t *)set->scratch.p;
   c.tagv = (uint32_t *)p;
   s.mem = (uint32_t *)(p + o_mem);
   c.codes = d_results ? d_results : (int32_t *)(p + o_codes);
@@ -4710,8 +4665,7 @@ int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const u
   hipLaunchKernelGGL(nrq_ings_hist_kernel, dim3(c.ntiles), dim3(256), nb * 4u, st, t, s);
   hipLaunchKernelGGL(nrq_ings_scan_kernel, dim3(nb), dim3(256), 0, st, t, s);
   hipLaunchKernelGGL(nrq_ings_classify_kernel, dim3(c.ntiles), dim3(256), nb * 16u, st, t, s);
-  hipLaunchKernelGGL(nrq_ings_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c.pkts, (uint64_t)pkt_stride, (const uint64_t *)c.dst, n, set->T,
-                     poff);
+  hipLaunchKernelGGL(nrq_ing_copy_kernel, dim3((n + 3u) / 4u), dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, set->T, poff);
   hipLaunchKernelGGL(nrq_ings_fold_kernel, dim3(g), dim3(256), 0, st, t, s);
   HIPCHK(ctx, hipGetLastError());
   return 0;
@@ -4737,51 +4691,19 @@ __global__ __launch_bounds__(256) void nrq_ings_lists_count_kernel(const ings_ta
   if (g < t->nblk) lss_list_count(t, g, buf);
 }
 
-/* counts -> exclusive offsets, in place, n <= 1025 entries (nrq_tx_scan_kernel is one lane over at most 257): one workgroup, a
- * run of entries per thread, a scan over the threads' sums */
+/* counts -> exclusive offsets, in place, n <= 1025 entries (nrq_tx_scan_kernel is one lane over at most 257): one workgroup */
 __global__ __launch_bounds__(256) void nrq_ings_lists_scan_kernel(uint32_t n, uint32_t *cnt) {
   __shared__ uint32_t ps[256];
-  const uint32_t i = threadIdx.x;
-  const uint32_t per = (n + 255u) / 256u, j0 = min(n, i * per), j1 = min(n, j0 + per);
-  uint32_t sum = 0;
-  for (uint32_t j = j0; j < j1; j++) sum += cnt[j];
-  ps[i] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-    const uint32_t v = i >= d ? ps[i - d] : 0u;
-    __syncthreads();
-    ps[i] += v;
-    __syncthreads();
-  }
-  uint32_t run = ps[i] - sum;
-  for (uint32_t j = j0; j < j1; j++) { const uint32_t v = cnt[j]; cnt[j] = run; run += v; }
+  (void)wg_scan_runs(ps, threadIdx.x, cnt, n, 0u);
 }
 
-/* one workgroup per global block: its repair ESIs in arrival order, then its missing source ESIs ascending (256 words per round:
- * a scan over their counts places each word's ESIs), to the block's offset behind the 2 * nblk + 1 words of gaps and offsets */
+/* one workgroup per global block: its list to the block's offset behind the 2 * nblk + 1 words of gaps and offsets */
 __global__ __launch_bounds__(256) void nrq_ings_lists_fill_kernel(const ings_tab *__restrict__ t, uint32_t *buf) {
   __shared__ uint32_t ps[256];
-  const uint32_t g = blockIdx.x, i = threadIdx.x, nb = t->nblk;
+  const uint32_t g = blockIdx.x, nb = t->nblk;
   uint32_t b;
   const ing_rx *r = lss_block(t, g, &b);
-  uint32_t *out = buf + 2u * nb + 1u + buf[nb + g];
-  const uint32_t nrep = r->nrep[b], nw = lss_words(r);
-  for (uint32_t q = i; q < nrep; q += 256u) out[q] = r->rep_esi[(size_t)b * r->rep_cap + q];
-  uint32_t o = nrep;
-  for (uint32_t w0 = 0; w0 < nw; w0 += LSS_ROUND) {
-    const uint32_t w = w0 + i, miss = lss_miss(r, b, w), cnt = lss_popc(miss);
-    ps[i] = cnt;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) { /* inclusive scan (Hillis-Steele) */
-      const uint32_t v = i >= d ? ps[i - d] : 0u;
-      __syncthreads();
-      ps[i] += v;
-      __syncthreads();
-    }
-    lss_put(w, miss, out + o + ps[i] - cnt);
-    o += ps[255];
-    __syncthreads();
-  }
+  ing_lists_fill_wg(r, b, buf + 2u * nb + 1u + buf[nb + g], ps);
 }
 
 struct ings_mask { uint32_t w[INGS_MAX_BLOCKS / 32u]; }; /* a bit per global block of the set */
@@ -4792,13 +4714,7 @@ __global__ __launch_bounds__(256) void nrq_ings_mark_kernel(const ings_tab *__re
   if (!((m.w[g >> 5] >> (g & 31u)) & 1u)) return;
   uint32_t b;
   const ing_rx *r = lss_block(t, g, &b);
-  const uint32_t K = r->K;
-  uint32_t *seen = r->seen + (size_t)b * r->bm_words;
-  for (uint32_t w = threadIdx.x; w * 32u < K; w += 256u) {
-    const uint32_t nb = min(32u, K - w * 32u);
-    seen[w] |= nb == 32u ? 0xFFFFFFFFu : ((1u << nb) - 1u);
-  }
-  if (threadIdx.x == 0) r->gaps[b] = 0;
+  ing_mark_wg(r, b);
 }
 
 /* the lists of all members: head = gaps[nb], offsets[nb + 1] (the last one the total), lists = exactly the list words.  One
@@ -4886,75 +4802,25 @@ int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used) {
   const uint32_t nb = set->nblk;
   if (nb == 0) return 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<uint32_t> head, lists;
-  int rc = rxset_fetch_lists(set, head, lists);
+  std::vector<uint32_t> head;
+  rx_listing L;
+  int rc = rxset_fetch_lists(set, head, L.words);
   if (rc) return rc;
-  /* per global block: its member, its block in the member, its counts */
   std::vector<rxset_plan_member> pm(set->mem.size());
-  std::vector<uint32_t> member(nb), blk(nb), ng(nb), nr(nb);
   uint32_t j = 0;
   for (size_t m = 0; m < set->mem.size(); m++) {
-    const nrq_rx *rx = set->mem[m].rx;
+    nrq_rx *rx = set->mem[m].rx;
     pm[m] = rxset_plan_member{rx->r.K, rx->Kp, rx->r.max_esi, rx->relay ? 1u : 0u};
-    for (uint32_t b = 0; b < rx->r.nblk; b++, j++) {
-      member[j] = (uint32_t)m;
-      blk[j] = b;
-      ng[j] = head[j];
-      nr[j] = head[nb + j + 1u] - head[nb + j] - head[j];
-      h_status[j] = ng[j] == 0 ? 1 : 0;
-      if (h_used) h_used[j] = 0;
-    }
+    for (uint32_t b = 0; b < rx->r.nblk; b++, j++) L.add(rx, (uint32_t)m, b, head[j], head[nb + j + 1u] - head[nb + j] - head[j], head[nb + j]);
   }
-  const std::vector<rxset_chunk> chunks = rxset_plan(pm.data(), member.data(), ng.data(), nr.data(), nb);
-  ings_mask mask{};
-  bool any = false;
-  std::string err;
-  std::vector<uint32_t> lost, resi, nlost, nuse, navail, used;
-  std::vector<uint64_t> sv, rv, iv;
-  std::vector<int> st;
-  for (const rxset_chunk &c : chunks) {
-    const size_t ns = c.blocks.size();
-    uint32_t lost_cap = 1, rep_cap = 1;
-    for (uint32_t g : c.blocks) { lost_cap = std::max(lost_cap, ng[g]); rep_cap = std::max(rep_cap, nr[g]); }
-    lost.assign(ns * lost_cap, 0); resi.assign(ns * rep_cap, 0);
-    nlost.resize(ns); nuse.resize(ns); navail.resize(ns); used.assign(ns, 0); sv.resize(ns); rv.resize(ns); st.assign(ns, 0);
-    iv.resize(c.has_relay ? ns : 0);
-    for (size_t i = 0; i < ns; i++) {
-      const uint32_t g = c.blocks[i], b = blk[g];
-      const nrq_rx *rx = set->mem[member[g]].rx;
-      const ing_rx &r = rx->r;
-      const uint32_t *l = lists.data() + head[nb + g];
-      memcpy(resi.data() + i * rep_cap, l, (size_t)nr[g] * 4u);
-      memcpy(lost.data() + i * lost_cap, l + nr[g], (size_t)ng[g] * 4u);
-      nlost[i] = ng[g];
-      nuse[i] = rxset_nuse(ng[g], nr[g]);
-      navail[i] = nr[g];
-      sv[i] = (uint64_t)(uintptr_t)(r.src + b * r.src_stride);
-      rv[i] = (uint64_t)(uintptr_t)(r.rep + b * r.rep_stride);
-      if (c.has_relay) iv[i] = relay_inter(rx->relay, rx->relay_seg, b);
-    }
-    rc = nrq_decode_blocks_vi(ctx, c.K, c.Kp, set->T, (uint32_t)ns, sv.data(), lost.data(), nlost.data(), lost_cap, resi.data(), nuse.data(),
-                              navail.data(), rep_cap, rv.data(), c.has_relay ? iv.data() : nullptr, st.data(), used.data());
-    if (rc) { /* this chunk's and the later chunks' blocks keep status 0 and their books; the chunks before it are marked below */
-      err = ctx->err;
-      break;
-    }
-    for (size_t i = 0; i < ns; i++) {
-      const uint32_t g = c.blocks[i];
-      nrq_rx *rx = set->mem[member[g]].rx;
-      h_status[g] = st[i];
-      if (h_used) h_used[g] = used[i];
-      if (!st[i]) continue;
-      mask.w[g >> 5] |= 1u << (g & 31u);
-      any = true;
-      if (rx->relay) relay_set(rx->relay, rx->relay_b0 + blk[g], 1, true);
-    }
-  }
-  if (any) {
+  std::vector<uint32_t> recovered;
+  rc = rx_decode_listed(ctx, L, rxset_plan(pm.data(), L.member.data(), L.ng.data(), L.nr.data(), nb), h_status, h_used, recovered);
+  if (!recovered.empty()) { /* (also behind a failed chunk: the chunks before it stay marked, the error text is that chunk's) */
+    ings_mask mask{};
+    for (uint32_t g : recovered) mask.w[g >> 5] |= 1u << (g & 31u);
     hipLaunchKernelGGL(nrq_ings_mark_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const ings_tab *)set->tab, mask);
     if (!rc) HIPCHK(ctx, hipGetLastError());
   }
-  if (rc) ctx->err = err;
   return rc;
 }
 
@@ -5136,8 +5002,7 @@ struct nrq_txset {
   std::vector<txset_seg> segs;   /* sorted by (key, sbn0): the order of the device table */
   uint32_t nblk;                 /* blocks over all members */
   void *tab;                     /* struct txs_tab in device memory */
-  void *scratch;                 /* per-call arrays: bucket counts, the packets' segments, the work order */
-  size_t scratch_cap;
+  DevScratch scratch;            /* per-call arrays: bucket counts, the packets' segments, the work order */
 };
 
 static uint32_t txset_key_of(const nrq_txset *set, const tx_sender *tx) {
@@ -5262,8 +5127,8 @@ void nrq_txset_destroy(nrq_txset *set) {
   nrq_ctx *ctx = set->ctx;
   for (const txset_member &m : set->mem) m.tx->set = nullptr;
   (void)hipStreamSynchronize(ctx->stream); /* (the pool hands freed blocks out again at once) */
-  for (void *p : {set->tab, set->scratch})
-    if (p) nrq_dev_free(ctx, p);
+  if (set->tab) nrq_dev_free(ctx, set->tab);
+  set->scratch.release(ctx);
   delete set;
 }
 
@@ -5331,17 +5196,8 @@ int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tag
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint32_t nb = set->nblk, nbins = nb + 1u;
   const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if (set->scratch_cap < need) {
-    if (set->scratch) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); /* (the previous call's kernels may still read it) */
-      nrq_dev_free(ctx, set->scratch);
-      set->scratch = nullptr;
-      set->scratch_cap = 0;
-    }
-    const int rc = nrq_dev_alloc(ctx, need, &set->scratch);
-    if (rc) return rc;
-    set->scratch_cap = need;
-  }
+  const int rc = set->scratch.ensure(ctx, need);
+  if (rc) return rc;
   /* the ready bits of the global blocks as the members have them NOW, by value into this call's kernel arguments: a relay's mask
    * changes in decodes, encodes and resets without any call on the set, and an emit still queued keeps the bits it was given */
   txs_ready rdy{};
@@ -5360,7 +5216,7 @@ int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tag
     }
   }
   const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (hdr == 8u ? TXS_V16_KEY : hdr ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
-  uint8_t *p = (uint8_t *)set->scratch;
+  uint8_t *p = (uint8_t *)set->scratch.p;
   uint32_t *cnt = (uint32_t *)p;
   txs_call c{};
   c.pkts = (uint8_t *)d_pkts;

@@ -95,13 +95,13 @@ int emu_rxset_lists(uint32_t nmem, const uint32_t *prm, const uint64_t *ptr, uin
       uint32_t b;
       const ing_rx *r = lss_block(&t, g, &b);
       uint32_t *out = w + 2u * nb + 1u + w[nb + g];
-      const uint32_t nrep = r->nrep[b], nw = lss_words(r);
+      const uint32_t nrep = r->nrep[b], nw = ing_src_words(r);
       for (uint32_t q = 0; q < nrep; q++) out[q] = r->rep_esi[(uint64_t)b * r->rep_cap + q];
       uint32_t o = nrep;
       for (uint32_t w0 = 0; w0 < nw; w0 += LSS_ROUND) {
         uint32_t ps = 0; /* (the inclusive scan over the round's threads) */
         for (uint32_t i = 0; i < LSS_ROUND; i++) {
-          const uint32_t miss = lss_miss(r, b, w0 + i), cnt = lss_popc(miss);
+          const uint32_t miss = lss_miss(r, b, w0 + i), cnt = ing_popc(miss);
           ps += cnt;
           lss_put(w0 + i, miss, out + o + ps - cnt);
         }

@@ -1,7 +1,7 @@
 /*
- * rxset_plan.h -- which blocks of a reception set one nrq_rxset_decode decodes, and in which decode calls.
+ * rxset_plan.h -- which blocks one nrq_rxset_decode or nrq_rx_decode (a set of one member) decodes, and in which decode calls.
  *
- *   rxset_selected()   the rule of nrq_rx_decode for one block
+ *   rxset_selected()   whether a block is decoded now
  *   rxset_nuse()       the repair symbols such a block hands the decode up front
  *   rxset_plan()       the selected blocks of a set as chunks of one (K, K', has_relay) each
  *
@@ -16,7 +16,9 @@
 #include <vector>
 
 /* blocks of one decode call at most: the largest batch the decode path has been put through (the tests, bench.py).  A set holds
- * up to 1024 blocks; a group beyond this is cut, the decode path's envelope is not widened here. */
+ * up to 1024 blocks; a group beyond this is cut, the decode path's envelope is not widened here.  Not below 256: a reception has
+ * up to 256 blocks, and nrq_rx_decode counts on them being ONE chunk, in block order (one decode call whose failure leaves no
+ * block marked; nrq_device.hip asserts it). */
 #define RXSET_CHUNK_BLOCKS 256u
 
 struct rxset_plan_member {

@@ -18,7 +18,7 @@
 
 #include <stdint.h>
 
-#include "held_body.h" /* hl_popc, hl_nrep */
+#include "held_body.h" /* hl_nrep */
 #include "ingest_body.h"
 
 #define WN_SOURCE 1u            /* NRQ_WANT_SOURCE */
@@ -72,12 +72,7 @@ ING_HD uint32_t wn_bits(const struct ing_rx *r, const struct wn_q *q, uint32_t b
  * word, `out` = the block's place in the list -- as far as their rank stays below need */
 ING_HD void wn_put(const struct ing_rx *r, uint32_t b, uint32_t w, uint32_t bits, uint32_t rank, uint32_t need, uint32_t *out) {
   while (bits && rank < need) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t i = (uint32_t)__ffs(bits) - 1u;
-#else
-    const uint32_t i = (uint32_t)__builtin_ctz(bits);
-#endif
-    out[rank++] = ((r->sbn0 + b) << 24) | (w * 32u + i);
+    out[rank++] = ((r->sbn0 + b) << 24) | (w * 32u + ing_lowbit(bits));
     bits &= bits - 1u;
   }
 }

@@ -31,7 +31,7 @@ int emu_rx_want(const uint32_t *prm, const uint32_t *seen, const uint32_t *gaps,
     uint32_t found = 0;
     for (uint32_t w0 = w_first; w0 < w_end && found < need; w0 += WN_ROUND)
       for (uint32_t t = 0; t < WN_ROUND; t++)
-        if (w0 + t < w_end) found += hl_popc(wn_bits(&r, &q, b, w0 + t));
+        if (w0 + t < w_end) found += ing_popc(wn_bits(&r, &q, b, w0 + t));
     off[b] = found < need ? found : need;
   }
   uint32_t run_ = 0; /* scan */
@@ -46,10 +46,10 @@ int emu_rx_want(const uint32_t *prm, const uint32_t *seen, const uint32_t *gaps,
       uint32_t run = 0;
       for (uint32_t t = 0; t < WN_ROUND; t++) {
         bits[t] = w0 + t < w_end ? wn_bits(&r, &q, b, w0 + t) : 0u;
-        run += hl_popc(bits[t]);
+        run += ing_popc(bits[t]);
         ps[t] = run;
       }
-      for (uint32_t t = 0; t < WN_ROUND; t++) wn_put(&r, b, w0 + t, bits[t], placed + ps[t] - hl_popc(bits[t]), need, out + off[b]);
+      for (uint32_t t = 0; t < WN_ROUND; t++) wn_put(&r, b, w0 + t, bits[t], placed + ps[t] - ing_popc(bits[t]), need, out + off[b]);
       placed += ps[WN_ROUND - 1u];
     }
   }

@@ -13,7 +13,7 @@ import pytest
 import nanorq_amd
 from nanorq_amd import EXT_PER_BLOCK_KP, EXT_SUBBLOCKS, TX_NOT_READY, NrqError
 from held_support import host_held
-from rx_support import ADDED, DUP, FULL
+from rx_support import ADDED, DUP, FULL, ModelRx, payloads_for
 from tx_support import FILL, range_tags, tag
 from util import payload
 
@@ -322,6 +322,27 @@ def test_listing_and_full_dump(ctx, torch, orc, K, T):
             assert np.array_equal(rx2.held().cpu().numpy().view(np.uint32), h)
             assert rx2.decode()[0].all()
             assert np.array_equal(_host(ctx, rx2.source), src)
+
+
+def test_listing_past_256_seen_words(ctx, torch):
+    """K = 8200: 257 seen words per block, so the fill goes a second round with one live lane and the offset of the first"""
+    K, T, nblk, sbn0, rep_cap = 8200, 16, 2, 3, 8
+    rng = np.random.default_rng(8200)
+    mod = ModelRx(K, T, nblk, rep_cap, sbn0=sbn0, Kp=nanorq_amd.params(K)["Kp"])
+    tags = []
+    for b in range(nblk):
+        have = rng.random(K) < 0.5
+        have[[b, 8192 + b, K - 1]] = True  # (seen symbols in the first word and in word 256)
+        tags += [tag(sbn0 + b, e) for e in np.flatnonzero(have)] + [tag(sbn0 + b, K + 7 * q + b) for q in range(5)]
+    tags = np.array(tags, np.uint32)[rng.permutation(len(tags))]
+    pay = payloads_for(tags, T)
+    with nanorq_amd.Receiver(ctx, K, T, nblk, rep_cap=rep_cap, sbn0=sbn0) as rx:
+        for part in np.array_split(np.arange(len(tags)), 2):
+            assert np.array_equal(_add(ctx, torch, rx, _dev(torch, pay[part]), tags=tags[part]), mod.add(pay[part], tags[part]))
+        seen = [~np.isin(np.arange(K), mod.lost(b)) for b in range(nblk)]
+        want = host_held(sbn0, K, seen, mod.reps)
+        assert len(want) == len(tags)
+        assert np.array_equal(rx.held().cpu().numpy().view(np.uint32), want)
 
 
 def test_merge_two_partial_receptions(ctx, torch, orc):

@@ -43,6 +43,7 @@ def _state(rx, torch, K, T, nblk, rep_cap, src_t, rep_t):
     (100, 36, 5, 0, 30, 3000),            # 4-byte copies
     (1000, 13, 4, 2, 500, 9000),          # byte copies
     (1000, 64, 2, 0, 20, 70000),          # many tiles, rep_cap overflow, heavy duplication
+    (8200, 16, 2, 0, 40, 20000),          # 257 seen words per block: the list fill's second round (one live lane, the offset carried over)
 ])
 def test_device_ingest_matches_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, n, inline):
     Kp = nanorq_amd.params(K)["Kp"]
@@ -63,6 +64,8 @@ def test_device_ingest_matches_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, 
             tg_d = None if inline else _dev(torch, tags.view(np.int32))
             rx.add(pk_d, tags=tg_d, inline=inline, results=res_d)
             r_emu = emu.add(pk, None if inline else tags)
+            if K > 8192:  # (the second round has ESIs to place, behind those of the first)
+                assert all(emu.lost(b).min() < 32 and emu.lost(b).max() >= 8192 for b in range(nblk))
             r_dev = res_d.cpu().numpy()
             assert np.array_equal(r_dev, r_emu), np.flatnonzero(r_dev != r_emu)[:10]
             lost, reps, s, r = _state(rx, torch, K, T, nblk, rep_cap, src_t, rep_t)

@@ -63,8 +63,12 @@ def _concat_lists(rxs):
 
 
 # ------------------------------------------------------------------------------------- blocks, counts, lists ----
+# MIX4 and a member of one block of 257 seen words: the list fill's second round (one live lane, the offset carried over)
+MIX4_K8200 = MIX4 + [(7, 8200, 1, 0)]
+
+
 @pytest.mark.parametrize("small_cap", [True, False])
-@pytest.mark.parametrize("mix", [MIX4, MIX360], ids=["mix4", "mix360"])
+@pytest.mark.parametrize("mix", [MIX4, MIX360, MIX4_K8200], ids=["mix4", "mix360", "mix4_k8200"])
 def test_blocks_counts_lists_against_the_members(ctx, torch, mix, small_cap):
     rng = np.random.default_rng(len(mix) * 10 + small_cap)
     kps = [nanorq_amd.params(m[1])["Kp"] for m in mix]
@@ -92,6 +96,10 @@ def test_blocks_counts_lists_against_the_members(ctx, torch, mix, small_cap):
             assert nr.any() and len(words) == int(nl.sum()) + int(nr.sum())
             return nl
         assert check(rxs).any()
+        for _, rx in rxs:
+            if rx.K > 8192:  # (the second round has ESIs to place, behind those of the first)
+                lost = rx.lists()[0][0]
+                assert lost.min() < 32 and lost.max() >= 8192
         gone = mix[0][0]
         st.detach(gone)
         check([m for m in rxs if m[0] != gone])

@@ -135,6 +135,29 @@ def test_listing_equals_the_model(ctx, torch, name):
             assert np.array_equal(_u32(ctx, rx.want(extra=extra, source=source, esi_from=esi_from)), want)
 
 
+def test_source_listing_past_256_seen_words(ctx, torch):
+    """K = 8200, two blocks: 257 seen words per block, so the source listing goes a second round with one live lane and the offset
+    of the first"""
+    K, T, nblk, sbn0, rep_cap = 8200, 16, 2, 3, 8
+    rng = np.random.default_rng(8200)
+    mod = ModelRx(K, T, nblk, rep_cap, sbn0=sbn0, Kp=nanorq_amd.params(K)["Kp"])
+    tags = []
+    for b in range(nblk):
+        have = rng.random(K) < 0.5
+        have[[b, 8192 + b, K - 1]] = False  # (missing symbols in the first word and in word 256)
+        tags += [(sbn0 + b) << 24 | int(e) for e in np.flatnonzero(have)] + [(sbn0 + b) << 24 | (K + 7 * q + b) for q in range(5)]
+    tags = np.array(tags, np.uint32)[rng.permutation(len(tags))]
+    pay = payloads_for(tags, T)
+    with nanorq_amd.Receiver(ctx, K, T, nblk, rep_cap=rep_cap, sbn0=sbn0) as rx:
+        for part in np.array_split(np.arange(len(tags)), 2):
+            assert np.array_equal(_add(ctx, torch, rx, _dev(torch, pay[part]), tags=tags[part]), mod.add(pay[part], tags[part]))
+        want = model_want(mod, source=True)
+        assert len(want) == sum(len(mod.lost(b)) for b in range(nblk)) and all(mod.lost(b).max() == K - 1 for b in range(nblk))
+        rc, n, buf = _want_raw(ctx, torch, rx, WANT_SOURCE, 0, 0)
+        assert rc == 0 and n == len(want) and np.array_equal(buf[:n], want) and (buf[n:] == GUARD).all()
+        assert np.array_equal(_u32(ctx, rx.want(source=True)), want)
+
+
 def test_contract(ctx, torch):
     case = case_of("boundary_K33")
     T = 16
