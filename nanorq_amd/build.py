@@ -121,7 +121,7 @@ def _build_emu(target, src, headers, force):
 
 
 def build_emu(force=False):
-    return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"), ("solve_body.h", "plan.h"), force)
+    return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"), ("solve_body.h", "split_body.h", "plan.h", "rq_math.h"), force)
 
 
 def build_planner_emu(force=False):

@@ -121,7 +121,10 @@ enum KnobKind { KNOB_FLAG, KNOB_NFLAG, KNOB_NUM, KNOB_BOOLNUM, KNOB_WIDEG, KNOB_
   K(bool, plan_wrong_instance, false, 0, "plan_wrong_instance", KNOB_FLAG)                                                                              \
   /* inactive-column capacity of the device planner (0 = P + 768, at most 1280); tests lower it to send blocks through the                              \
    * capacity fallback (host re-plan) */                                                                                                                \
-  K(uint32_t, plan_ucap, 0, 0, "plan_ucap", KNOB_NUM)
+  K(uint32_t, plan_ucap, 0, 0, "plan_ucap", KNOB_NUM)                                                                                                   \
+  /* (tests) strip bytes of the split solve's back-substitution: 0 = by the W words per row (solve_shape), 16 = 16-byte strips                          \
+   * whatever they are.  (Nothing forces 32: beyond 20 words its tables do not fit beside a second workgroup.) */                                      \
+  K(uint32_t, backsub_sb, 0, 0, "backsub_sb", KNOB_NUM)
 
 static inline long long knob_norm(KnobKind kind, long long v) {
   switch (kind) {
@@ -427,7 +430,7 @@ static inline SolveShape solve_shape(const Tuning &t, int ncu, uint32_t ahead_hi
   if (split) {
     s.ybuf_stride = ((size_t)(max_slots + in.max_u) * T + 255u) & ~(size_t)255u;
     /* 32-byte strips while the tables (4 KiB per W word) leave room for two workgroups per CU, 16-byte strips beyond */
-    const uint32_t sb = in.max_wpr <= 20u ? 32u : 16u, nsb = (T + sb - 1u) / sb;
+    const uint32_t sb = in.max_wpr <= 20u && t.backsub_sb != 16u ? 32u : 16u, nsb = (T + sb - 1u) / sb;
     s.backsub_strip = sb; s.backsub_nsb = nsb; s.backsub_tbl = in.max_wpr * 8u * 16u * sb;
     if (s.backsub_tbl > NRQ_LDS_MAX) { s.err = SHAPE_BACKSUB_TABLES; return s; } /* (reported behind the solve kernel's launch, as ever) */
     uint32_t nchunks = (2048u + nsb * nblk - 1u) / (nsb * nblk);

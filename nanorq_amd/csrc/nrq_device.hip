@@ -31,6 +31,7 @@
 #include "planner_host.h"
 #include "rq_math.h"
 #include "solve_body.h"
+#include "split_body.h"
 #include "planner_body.h"
 #include "ingest_body.h"
 #include "ingest_set_body.h"
@@ -751,124 +752,16 @@ __global__ __launch_bounds__(256) void nrq_backsub_kernel(const nrq_job *__restr
                                                           size_t ybuf_stride, uint32_t nchunks) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t tid = threadIdx.x, chunk = blockIdx.y, blk = blockIdx.z;
-  /* Workgroup i runs on XCD i % 8 (round-robin dispatch).  The strips that share a 128-byte line of every row -- 128 / SB
-   * neighbours -- are given to workgroups i, i + 8, i + 16 ... : same XCD, dispatched together, walking the pivots in step, so
-   * a line fetched for one of them is in that XCD's L2 for the others (with strip = i the neighbours sat on different XCDs and
-   * every one of them fetched the line from HBM: the kernel is bound by its scattered 32-byte row accesses). */
-  uint32_t strip = blockIdx.x;
-  {
-    constexpr uint32_t NB_ = 128u / SB, PER = 8u * NB_;
-    const uint32_t i = blockIdx.x, full = (gridDim.x / PER) * PER;
-    if (i < full) {
-      const uint32_t r = i % PER, g = (i / PER) * 8u + (r & 7u), j = r >> 3;
-      strip = g * NB_ + j;
-    }
-  }
-  const uint8_t *plan = reinterpret_cast<const uint8_t *>(jobs[blk].plan);
-  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
-  if (h->status) return;
-  const uint32_t M = h->M, u = h->u, wpr = h->wpr, npiv = h->npiv, stride = h->npiv_pad;
-  const NRQ_GAS uint16_t *pivslot = gptr<uint16_t>(plan + h->off_pivslot);
-  const NRQ_GAS uint16_t *uslot = gptr<uint16_t>(plan + h->off_uslot);
-  const NRQ_GAS uint32_t *wt = gptr<uint32_t>(plan + h->off_wt);
-  NRQ_GAS uint8_t *Y = gptr_w<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride));
-  const NRQ_GAS uint8_t *Cu = Y + (size_t)M * T;
-  const uint32_t col0 = strip * SB, rem = T - col0, valid = rem < (uint32_t)SB ? rem : (uint32_t)SB;
-  constexpr int NQ = SB / 16;
-  auto load = [&](const NRQ_GAS uint8_t *p, SV<16> (&v)[NQ]) {
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const uint32_t o = (uint32_t)q * 16u;
-      v[q] = o < valid ? g_get<16>(p + o, valid - o < 16u ? valid - o : 16u) : sv_zero<16>();
-    }
-  };
-  auto store = [&](NRQ_GAS uint8_t *p, const SV<16> (&v)[NQ]) {
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const uint32_t o = (uint32_t)q * 16u;
-      if (o < valid) g_put<16>(p + o, valid - o < 16u ? valid - o : 16u, v[q]);
-    }
-  };
-  /* tables: entry (grp, nib) = XOR of C_u[4 grp + b] over the bits b of nib */
-  const uint32_t ngroups = wpr * 8u;
-  for (uint32_t e = tid; e < ngroups * 16u; e += 256u) {
-    const uint32_t grp = e >> 4, nib = e & 15u;
-    SV<16> acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) acc[q] = sv_zero<16>();
-#pragma unroll
-    for (uint32_t b = 0; b < 4; b++) {
-      const uint32_t x = grp * 4u + b;
-      if (((nib >> b) & 1u) && x < u) {
-        SV<16> t[NQ];
-        load(Cu + (size_t)x * T + col0, t);
-#pragma unroll
-        for (int q = 0; q < NQ; q++) sv_xor<16>(acc[q], t[q]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; q++) lds_put<16>(smem, e * NQ + q, acc[q]);
-  }
+  SplitCtx<SB> c;
+  if (!sp_ctx<SB>(c, reinterpret_cast<const uint8_t *>(jobs[blk].plan), gptr_w<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride)), T,
+                  sp_strip_of<SB>(blockIdx.x, gridDim.x)))
+    return;
+  sp_tables<SB>(c, smem, tid);
   __syncthreads();
-  if (chunk == 0) /* park the inactive columns in the slots the plan reserved for them (rows that are no pivots) */
-    for (uint32_t x = tid; x < u; x += 256u) {
-      SV<16> t[NQ];
-      load(Cu + (size_t)x * T + col0, t);
-      store(Y + (size_t)uslot[x] * T + col0, t);
-    }
-  const uint32_t k0 = (uint32_t)(((uint64_t)npiv * chunk) / nchunks), k1 = (uint32_t)(((uint64_t)npiv * (chunk + 1u)) / nchunks);
-  /* A pivot per thread and trip: Y(slot) ^= W_k * C_u through the tables.  Everything a pivot needs from memory -- its slot, its
-   * row, its first WCH words of W -- is asked for while the pivot BEFORE it does its lookups (all loads unconditional: a word
-   * beyond wpr re-reads the last one and is not used): before, a pivot was a chain of seven trips (slot, row, five groups of four
-   * W words: 12 us per pivot at K'=56403, 1.8 ms per launch, 3.3 ms at K=27000 T=65504). */
-  constexpr uint32_t WCH = 20u;
-  auto words = [&](uint32_t k, uint32_t w0, uint32_t (&b)[WCH]) {
-#pragma unroll
-    for (uint32_t j = 0; j < WCH; j++) b[j] = wt[(size_t)(w0 + j < wpr ? w0 + j : wpr - 1u) * stride + k];
-  };
-  uint32_t k = k0 + tid;
-  if (k >= k1) return;
-  uint32_t bits_n[WCH];
-  SV<16> acc_n[NQ];
-  NRQ_GAS uint8_t *row_n = Y + (size_t)pivslot[k] * T + col0;
-  load(row_n, acc_n);
-  words(k, 0u, bits_n);
-  for (; k < k1; k += 256u) {
-    SV<16> acc[NQ];
-    uint32_t bits[WCH];
-    NRQ_GAS uint8_t *row = row_n;
-#pragma unroll
-    for (int z = 0; z < NQ; z++) acc[z] = acc_n[z];
-#pragma unroll
-    for (uint32_t j = 0; j < WCH; j++) bits[j] = bits_n[j];
-    const uint32_t kn = k + 256u;
-    if (kn < k1) {
-      row_n = Y + (size_t)pivslot[kn] * T + col0;
-      load(row_n, acc_n);
-      words(kn, 0u, bits_n);
-    }
-    for (uint32_t w0 = 0;;) {
-#pragma unroll
-      for (uint32_t j = 0; j < WCH; j++) {
-        if (w0 + j >= wpr) break;
-#pragma unroll
-        for (uint32_t q = 0; q < 8; q++) {
-          const uint32_t e = ((w0 + j) * 8u + q) * 16u + ((bits[j] >> (4u * q)) & 15u);
-#pragma unroll
-          for (int z = 0; z < NQ; z++) sv_xor<16>(acc[z], lds_get<16>(smem, e * NQ + z));
-        }
-      }
-      w0 += WCH;
-      if (w0 >= wpr) break;
-      words(k, w0, bits); /* (more than WCH words: u > 640) */
-    }
-    store(row, acc);
-  }
+  sp_backsub<SB>(c, smem, chunk, nchunks, tid);
 }
 
-/* Results of the split solve, from the final slot image in the work buffer: workgroup (e, blk) writes one row --
- * intermediate symbol e = row colslot[e] (if the job wants them), or generated symbol q = XOR of the rows its list
- * names (plan slots of its LT neighbours), to the row of `out` the job assigns. */
+/* Results of the split solve, from the final slot image in the work buffer: workgroup (e, blk) writes one row (split_body.h) */
 __global__ __launch_bounds__(256) void nrq_collect_kernel(const nrq_job *__restrict__ jobs, uint32_t T, const uint8_t *__restrict__ ybuf,
                                                           size_t ybuf_stride) {
   const uint32_t e = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x;
@@ -876,40 +769,12 @@ __global__ __launch_bounds__(256) void nrq_collect_kernel(const nrq_job *__restr
   const uint8_t *plan = reinterpret_cast<const uint8_t *>(j->plan);
   const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
   if (h->status) return;
-  const uint32_t ni = j->inter ? h->L : 0u;
-  if (e >= ni + j->nout) return;
-  const NRQ_GAS uint8_t *F = gptr<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride));
+  if (e >= sc_elems(j, h)) return;
   __shared__ uint32_t rows[RQ_MAX_LT_COLS + 1];
   __shared__ uint32_t nrows;
-  NRQ_GAS uint8_t *dst;
-  if (e < ni) {
-    if (tid == 0) { rows[0] = gptr<uint16_t>(plan + h->off_colslot)[e]; nrows = 1u; }
-    dst = gptr_w<uint8_t>(j->inter) + (size_t)e * T;
-  } else {
-    const uint32_t q = e - ni;
-    const NRQ_GAS uint32_t *cptr = gptr<uint32_t>(j->out_cptr);
-    const NRQ_GAS uint16_t *osl = gptr<uint16_t>(j->out_slots);
-    const uint32_t a = cptr[q], n = cptr[q + 1] - a;
-    if (tid < n && tid <= RQ_MAX_LT_COLS) rows[tid] = osl[a + tid];
-    if (tid == 0) nrows = n <= RQ_MAX_LT_COLS ? n : RQ_MAX_LT_COLS;
-    dst = gptr_w<uint8_t>(j->out) + (size_t)gptr<uint32_t>(j->out_row)[q] * T;
-  }
+  NRQ_GAS uint8_t *dst = sc_fetch(j, plan, e, T, tid, rows, &nrows);
   __syncthreads();
-  const uint32_t n = nrows;
-  const bool vec = (T & 15u) == 0 && ((reinterpret_cast<uintptr_t>(F) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
-  if (vec) {
-    for (uint32_t off = tid * 16u; off < T; off += 256u * 16u) {
-      SV<16> acc = sv_zero<16>();
-      for (uint32_t k = 0; k < n; k++) sv_xor<16>(acc, g_get_stream<16>(F + (size_t)rows[k] * T + off, 16u));
-      g_put<16>(dst + off, 16u, acc);
-    }
-  } else {
-    for (uint32_t off = tid; off < T; off += 256u) {
-      uint8_t acc = 0;
-      for (uint32_t k = 0; k < n; k++) acc ^= F[(size_t)rows[k] * T + off];
-      dst[off] = acc;
-    }
-  }
+  sc_sum(gptr<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride)), dst, T, rows, nrows, tid);
 }
 
 /* Symbol ingestion on the device (nrq_scatter_symbols): symbol k of a contiguous packet buffer goes to the row its

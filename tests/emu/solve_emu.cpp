@@ -7,6 +7,11 @@
  * exercise strip indexing, the packed GF(256) arithmetic, the HDPC Horner evaluation and the
  * chunk/sync schedule against the oracle.  It is not part of the product and is never shipped in
  * libnanorq_hip.so.
+ *
+ * The split solve of narrow strips (emu_solve_split): the strips stop after the dense stage and hand Y and C_u to a work
+ * buffer (ph_store_raw + the scatter), then split_body.h -- the bodies of nrq_backsub_kernel<SB> and nrq_collect_kernel --
+ * runs for every workgroup of the grids the launch would use.  emu_backsub / emu_collect run those bodies on arrays of the
+ * caller's.
  */
 #include <cstdint>
 #include <cstdlib>
@@ -16,6 +21,7 @@
 static uint32_t g_dense_shared_min_nt = 512; /* workgroup size from which the dense fold shares the multiples (kernel: 512) */
 #define NRQ_DENSE_SHARED_MIN_NT g_dense_shared_min_nt
 #include "../../nanorq_amd/csrc/solve_body.h"
+#include "../../nanorq_amd/csrc/split_body.h"
 extern "C" void emu_set_dense_shared_min_nt(uint32_t v) { g_dense_shared_min_nt = v; }
 static int g_hdpc_regs = 0; /* 1: the HDPC phase in the form of the big workgroup (register accumulators) */
 extern "C" void emu_set_hdpc_regs(int v) { g_hdpc_regs = v; }
@@ -41,7 +47,9 @@ template <int WB> static bool emu_forward(const StripCtx<WB> &c) {
   return true;
 }
 
-template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t strip, const uint8_t *kc, std::vector<uint8_t> &ostage) {
+/* ybuf: the block's work buffer of a split solve ((M + u) rows of T bytes); nullptr: the whole solve in the strip */
+template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t strip, const uint8_t *kc, std::vector<uint8_t> &ostage,
+                                       uint8_t *ybuf = nullptr) {
   const uint32_t NT = 256;
   StripCtx<WB> c;
   c.job = &job;
@@ -83,6 +91,22 @@ template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t 
   if (dense_fold_shared(NT)) PHASE(ph_hdpc_reduce);
   for (uint32_t t = 0; t < NT; t++) ph_dense_free<WB, 1, true>(c, t, NT);
   for (uint32_t t = 0; t < NT; t++) ph_dense_cu<WB, 1, true>(c, t, NT);
+  if (ybuf) { /* the split solve: slot image and C_u staged per strip, scattered to full-width rows of the work buffer */
+    constexpr uint32_t SPL = nrq_group_strips(WB);
+    const uint32_t nstrips = (T + WB - 1) / WB, ne = c.h->M + c.h->u;
+    const size_t ostride = ((size_t)ne * WB + 255u) & ~(size_t)255u;
+    if (strip % SPL == 0) ostage.assign(ostride * SPL + 64, 0x3C);
+    for (uint32_t t = 0; t < NT; t++) ph_store_raw<WB>(c, ostage.data() + (size_t)(strip % SPL) * ostride, t, NT);
+    if (strip % SPL == SPL - 1 || strip + 1 == nstrips) {
+      GroupDst<WB> g; /* (nrq_solve_kernel group_dst with a work buffer) */
+      g.inter = ybuf; g.out = gptr_w<uint8_t>(c.job->out); g.orow = gptr<uint32_t>(c.job->out_row);
+      g.ni = ne; g.nout = 0u; g.T = T; g.strip0 = (strip / SPL) * SPL; g.nstrips = nstrips; g.lsub = __builtin_ctz(SPL);
+      const uint32_t np = NT - NRQ_ROW, units = ne * SPL, cut = units / 3;
+      for (uint32_t p = 0; p < np; p++) pf_scatter<WB>(g, ostage.data(), ostride, 0, cut, p, np);
+      for (uint32_t p = 0; p < np; p++) pf_scatter<WB, 1, true>(g, ostage.data(), ostride, cut, units, p, np);
+    }
+    return 1;
+  }
   PHASE(ph_tables);
   PHASE(ph_backsub);
   PHASE(ph_park);
@@ -125,4 +149,76 @@ extern "C" int emu_solve(const nrq_job *job, uint32_t T, uint32_t wb, const uint
     }
   }
   return r;
+}
+
+/* ---- the second half of a split solve (split_body.h) ---- */
+
+/* nrq_backsub_kernel<SB> on grid (gridx, nchunks) for one block: Y = its work buffer.  Workgroups run one after the other,
+ * the last first (they share nothing but the rows they read: any order gives the same buffer), each with tables of its own in
+ * garbage-filled "LDS".  -2: a workgroup was given a strip the row does not have. */
+template <int SB> static int run_backsub(const uint8_t *plan, uint8_t *Y, uint32_t T, uint32_t gridx, uint32_t nchunks) {
+  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
+  std::vector<uint8_t> lds((size_t)h->wpr * 8u * 16u * SB + 64, 0xA5);
+  uint8_t *tbl = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(lds.data()) + 15) & ~(uintptr_t)15);
+  for (uint32_t chunk = nchunks; chunk-- > 0;)
+    for (uint32_t wg = gridx; wg-- > 0;) {
+      SplitCtx<SB> c;
+      const uint32_t strip = sp_strip_of<SB>(wg, gridx);
+      if (!sp_ctx<SB>(c, plan, Y, T, strip)) return 0;
+      if ((uint64_t)strip * SB >= T) return -2;
+      memset(tbl, 0xA5, (size_t)h->wpr * 8u * 16u * SB);
+      for (uint32_t t = 0; t < SP_NT; t++) sp_tables<SB>(c, tbl, t);
+      for (uint32_t t = 0; t < SP_NT; t++) sp_backsub<SB>(c, tbl, chunk, nchunks, t);
+    }
+  return 1;
+}
+
+/* nrq_collect_kernel on grid x = grid_e for one block: F = the final slot image */
+static int run_collect(const nrq_job *job, uint32_t T, const uint8_t *F, uint32_t grid_e) {
+  const uint8_t *plan = reinterpret_cast<const uint8_t *>(job->plan);
+  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
+  if (h->status) return 0;
+  for (uint32_t e = 0; e < grid_e; e++) {
+    if (e >= sc_elems(job, h)) continue;
+    uint32_t rows[RQ_MAX_LT_COLS + 1], nrows = 0xA5A5A5A5u;
+    for (uint32_t k = 0; k <= RQ_MAX_LT_COLS; k++) rows[k] = 0xA5A5A5A5u;
+    uint8_t *dst[SP_NT];
+    for (uint32_t t = 0; t < SP_NT; t++) dst[t] = sc_fetch(job, plan, e, T, t, rows, &nrows);
+    for (uint32_t t = 0; t < SP_NT; t++) sc_sum(F, dst[t], T, rows, nrows, t);
+  }
+  return 1;
+}
+
+extern "C" uint32_t emu_backsub_strip_of(uint32_t sb, uint32_t wg, uint32_t gridx) {
+  return sb == 32 ? sp_strip_of<32>(wg, gridx) : sp_strip_of<16>(wg, gridx);
+}
+extern "C" void emu_backsub_chunk(uint32_t npiv, uint32_t chunk, uint32_t nchunks, uint32_t *k01) {
+  sp_chunk_bounds(npiv, chunk, nchunks, &k01[0], &k01[1]);
+}
+/* the back-substitution of one block on the caller's plan and work buffer, strips of sb bytes, grid ((T + sb - 1) / sb, nchunks) */
+extern "C" int emu_backsub(const uint8_t *plan, uint8_t *Y, uint32_t T, uint32_t sb, uint32_t nchunks) {
+  if (sb != 32 && sb != 16) return -1;
+  const uint32_t gridx = (T + sb - 1) / sb;
+  return sb == 32 ? run_backsub<32>(plan, Y, T, gridx, nchunks) : run_backsub<16>(plan, Y, T, gridx, nchunks);
+}
+/* the results of one block from the caller's slot image */
+extern "C" int emu_collect(const nrq_job *job, uint32_t T, const uint8_t *F, uint32_t grid_e) { return run_collect(job, T, F, grid_e); }
+
+/* the split solve of one block at strip width wb (4 or 2): every pointer in `job` is a host pointer */
+extern "C" int emu_solve_split(const nrq_job *job, uint32_t T, uint32_t wb, const uint8_t *kc, uint32_t sb, uint32_t nchunks) {
+  const uint8_t *plan = reinterpret_cast<const uint8_t *>(job->plan);
+  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
+  if (h->status) return 0;
+  if ((wb != 4 && wb != 2) || (sb != 32 && sb != 16) || nchunks < 1) return -1;
+  std::vector<uint8_t> ybuf((size_t)(h->M + h->u) * T + 64, 0x77); /* (device memory nobody cleared) */
+  uint8_t *Y = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(ybuf.data()) + 15) & ~(uintptr_t)15);
+  const uint32_t nstrips = (T + wb - 1) / wb;
+  std::vector<uint8_t> ostage;
+  int r = 1;
+  for (uint32_t s = 0; s < nstrips && r == 1; s++)
+    r = wb == 4 ? run_strip<4>(*job, T, s, kc, ostage, Y) : run_strip<2>(*job, T, s, kc, ostage, Y);
+  if (r != 1) return r;
+  r = emu_backsub(plan, Y, T, sb, nchunks);
+  if (r != 1) return r;
+  return run_collect(job, T, Y, sc_elems(job, h) + 3u);
 }

@@ -19,7 +19,7 @@ PLAN_OUT = ("err", "wg_threads", "compact", "segmented", "mode", "nparts", "part
 # every knob setting a test reaches through an option, one at a time (and the defaults)
 SOLVE_KNOBS = [{}, {"tiny_any": 1}, {"no_tiny": 1}, {"small_waves4": 0}, {"big_wg": 1}, {"wide_g": 2}, {"wide_g": 4}, {"wide_g": 8},
                {"no_split": 1}, {"solve_grid": 64}, {"solve_grid": 1000}, {"reserve_cus": 0}, {"reserve_cus": 40},
-               {"wide_g": 4, "big_wg": 1}, {"tiny_any": 1, "small_waves4": 0}]
+               {"wide_g": 4, "big_wg": 1}, {"tiny_any": 1, "small_waves4": 0}, {"backsub_sb": 16}]
 LIST_KNOBS = [{}, {"max_wb": 8}, {"max_wb": 12}, {"max_wb": 2}, {"no_wb12": 1}, {"lds_max": 60000}, {"lds_max": 20000}, {"no_lists": 1},
               {"lds_max": 100000, "no_wb12": 1}]
 PLAN_KNOBS = [{}, {"plan_pack": 1}, {"plan_big_wg": 1}, {"plan_split_force": 1}, {"plan_wrong_instance": 1},
@@ -77,7 +77,8 @@ def header_for(emu, wb, need, u):
 def test_knob_names(emu):
     """an option name the table does not hold is refused; fault injection is not a knob"""
     with Tuning(emu, {}) as t:
-        for name in (b"no_lists", b"no_wb12", b"max_wb", b"no_split", b"wide_g", b"lds_max", b"plan_ucap", b"tx_dword", b"host_plan_auto"):
+        for name in (b"no_lists", b"no_wb12", b"max_wb", b"no_split", b"wide_g", b"lds_max", b"plan_ucap", b"tx_dword", b"host_plan_auto",
+                     b"backsub_sb"):
             assert emu.emu_tuning_set(t.p, name, 1) == 0, name
         for name in (b"fail_after", b"faults_injected", b"nonsense", b"NRQ_NO_LISTS", b""):
             assert emu.emu_tuning_set(t.p, name, 1) == -1, name
@@ -153,6 +154,9 @@ def test_solve_shape_holds_for_any_tuning(emu):
                     assert s["res_elems"] == max_out, what
                     assert s["backsub_strip"] in (16, 32) and 1 <= s["nchunks"] <= 16, what
                     assert emu.emu_lds_alloc(s["backsub_tbl"]) * (2 if s["backsub_strip"] == 32 else 1) <= LDS, what
+                    # 16-byte strips beyond 20 W words, or when the test knob asks for them; the tables are those of that strip
+                    assert s["backsub_strip"] == (16 if (u + 31) // 32 > 20 or knobs.get("backsub_sb") == 16 else 32), what
+                    assert s["backsub_tbl"] == (u + 31) // 32 * 128 * s["backsub_strip"], what
                 else:
                     assert s["backsub_strip"] == 0, what
     assert cases > 20000

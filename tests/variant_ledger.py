@@ -74,7 +74,12 @@ BACKSUB = {
     # shape: the device planner's inactivation count depends on which wave claims a column first, and one reception (10 % loss,
     # overhead 2, loss pattern seed 3) gave u = 631 in one run and 671 in another on an MI355X.  racy: the test runs the shape and
     # compares with the oracle whichever strip it took; seeing 16 is not required.
-    16: dict(status="default", racy=True, shape=dict(K=56403, T=16, nblk=1, loss=0.1, oh=2, seed=3)),
+    # pinned: the test that reaches the instance in EVERY run -- one block of K'=56403 whose plan comes from the HOST planner
+    # (set_planner(False): the same plan each time, u = 655, 21 W words per row), so 2-byte strips, nrq_backsub_kernel<16> with its
+    # loop over a second batch of W words, and the collect, at T = 16 and 40, with and without intermediate symbols, against the
+    # oracle.  It does not cover the default launch path (device planner, no option set): that stays with the racy shape.
+    16: dict(status="default", racy=True, shape=dict(K=56403, T=16, nblk=1, loss=0.1, oh=2, seed=3),
+             pinned="tests/test_gpu_split.py::test_backsub16_second_word_batch"),
 }
 
 # nrq_plan_kernel<NT, compact>: the decode planner; stats plan_wg_threads, plan_compact_state (and plan_segmented)
