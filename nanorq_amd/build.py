@@ -26,6 +26,7 @@ WEMU = os.path.join(ROOT, "tests", "emu", "libwant_emu.so")
 REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
+NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -121,7 +122,16 @@ def _build_emu(target, src, headers, force):
 
 
 def build_emu(force=False):
-    return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"), ("solve_body.h", "split_body.h", "plan.h", "rq_math.h"), force)
+    return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"),
+                      ("solve_body.h", "split_body.h", "plan.h", "rq_math.h", os.path.join(ROOT, "tests", "emu", "strip_emu.h")), force)
+
+
+def build_launch_emu(force=False):
+    """tests/emu/liblaunch_emu.so: a whole solve launch on the CPU -- the shape launch_shape.h decides, every workgroup's work slots,
+    movers and staging sets as nrq_solve_kernel runs them -- on arrays between pages nobody may touch (tests/emu/launch_emu.cpp)."""
+    return _build_emu(NEMU, os.path.join(ROOT, "tests", "emu", "launch_emu.cpp"),
+                      ("launch_shape.h", "planner_body.h", "solve_body.h", "split_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h",
+                       os.path.join(ROOT, "tests", "emu", "strip_emu.h"), os.path.join(ROOT, "tests", "emu", "wave_emu.h")), force)
 
 
 def build_planner_emu(force=False):
@@ -191,4 +201,5 @@ if __name__ == "__main__":
     build_txset_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
+    build_launch_emu(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

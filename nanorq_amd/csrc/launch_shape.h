@@ -47,7 +47,7 @@ static inline uint32_t lds_alloc(uint32_t bytes) { return (bytes + NRQ_LDS_GRANU
 #define NRQ_SMALL_WV 4   /* the 256-thread variant: workgroups per compute unit = waves per SIMD it is built for */
 #endif
 
-/* with many blocks in the launch all line groups of a block go to workgroups of one XCD (nrq_map_group in nrq_device.hip) */
+/* with many blocks in the launch all line groups of a block go to workgroups of one XCD (nrq_map_group in solve_body.h) */
 static inline bool nrq_map_by_block(uint32_t nblk) { return nblk >= 64u || (nblk >= 8u && (nblk & 7u) == 0u); }
 
 /* ============================================================================================

@@ -53,34 +53,8 @@ static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's colu
  * Kernels
  * ========================================================================================== */
 
-/* Work: "line groups" -- the 128/WB strips of one block that share a 128-byte line of every symbol row.  Slot q
- * of the work list -> (block, group); workgroup g takes the slots g, g + gridDim.x, ...  With many blocks in the
- * launch (by_block) all groups of a block go to workgroups of one XCD (workgroup g runs on XCD g % 8, observed;
- * speed only), so that the block's plan -- every strip walks the whole op stream -- is served by one L2
- * (nrq_map_by_block, launch_shape.h). */
-__device__ __forceinline__ bool nrq_map_group(uint32_t q, uint32_t nblk, uint32_t gpb, bool by_block, uint32_t *blk, uint32_t *grp) {
-  if (by_block) {
-    const uint32_t m = q >> 3;
-    *blk = (m / gpb) * 8u + (q & 7u);
-    *grp = m % gpb;
-  } else {
-    *blk = q / gpb;
-    *grp = q % gpb;
-  }
-  return *blk < nblk;
-}
-
-/* first slot >= q (stepping by gridDim.x) that holds a group of a solvable block; >= nslots if none */
-__device__ __forceinline__ uint32_t nrq_next_group(uint32_t q, uint32_t nslots, const nrq_job *__restrict__ jobs, uint32_t nblk,
-                                                   uint32_t gpb, bool by_block) {
-  for (; q < nslots; q += gridDim.x) {
-    uint32_t blk, grp;
-    if (!nrq_map_group(q, nblk, gpb, by_block, &blk, &grp)) continue;
-    const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(jobs[blk].plan);
-    if (h->status == 0) return q; /* rank deficient blocks: nothing is written for them */
-  }
-  return nslots;
-}
+/* (nrq_map_group / nrq_next_group, which deal the work slots to the workgroups, are in solve_body.h: the launch emulation of
+ * tests/emu runs the same two functions) */
 
 /* The data stage: persistent workgroups, one line group at a time, its strips one after the other (solve_body.h:
  * load -> forward passes -> HDPC -> dense stage -> back-substitution -> store).  While wave 0 runs the forward
@@ -224,7 +198,7 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
     g.ni = nrq_uniform(g.ni); g.nout = nrq_uniform(g.nout);
     return g.ni + g.nout;
   };
-  uint32_t q = nrq_next_group(blockIdx.x, nslots, jobs, nblk, gpb, by_block != 0u);
+  uint32_t q = nrq_next_group(blockIdx.x, gridDim.x, nslots, jobs, nblk, gpb, by_block != 0u);
   if (q >= nslots) return;
   uint32_t buf = 0, done = 0, qp = nslots; /* qp: the group whose results wait in the other output set */
   {
@@ -235,7 +209,7 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
     __syncthreads();
   }
   while (q < nslots) {
-    const uint32_t qn = nrq_next_group(q + gridDim.x, nslots, jobs, nblk, gpb, by_block != 0u);
+    const uint32_t qn = nrq_next_group(q + gridDim.x, gridDim.x, nslots, jobs, nblk, gpb, by_block != 0u);
     GroupSrc<WB> gn;
     GroupDst<WB> gp;
     uint32_t blk, blkn = 0, units_n = 0, units_p = 0;

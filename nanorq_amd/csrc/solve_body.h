@@ -65,10 +65,12 @@ typedef struct nrq_job {
   uint32_t pad;
 } nrq_job;
 
-/* true in every lane of the wave if the condition holds in one (the CPU emulation runs a thread at a time: the thread's own) */
+/* true in every lane of the wave if the condition holds in one (a CPU emulation runs a thread at a time: the thread's own word --
+ * unless it brings a NRQ_WAVE_ANY of its own that knows the wave's, tests/emu/wave_emu.h) */
 #if defined(__HIP_DEVICE_COMPILE__)
+#undef NRQ_WAVE_ANY
 #define NRQ_WAVE_ANY(x) (__ballot(x) != 0ull)
-#else
+#elif !defined(NRQ_WAVE_ANY)
 #define NRQ_WAVE_ANY(x) (x)
 #endif
 /* A value that is the same in every lane of the wave, said so: it then lives in a scalar register (the descriptors of the
@@ -1677,6 +1679,12 @@ template <int WB, int G = 1> SB_HD void ph_park(const StripCtx<WB, G> &c, uint32
 #define NRQ_STORE_SLACK (16u + NRQ_STORE_TRIP * 4u)
 #define NRQ_LT_LIST_MAX 33u /* (= RQ_LT_COLS_MAX_REAL of rq_math.h; nrq_device.hip checks the two against each other) */
 static_assert(NRQ_LT_LIST_MAX <= 2u * NRQ_STORE_TRIP, "ph_store reads at most two trips of a list; out_slots[] slack is sized for that");
+/* What the slack must hold.  A wave goes on for as many trips as its longest list needs, and EVERY lane reads every trip from its own
+ * list's start on: a list of n >= 1 entries that is the array's last is read n' = trips * NRQ_STORE_TRIP entries far, n' - n past the
+ * array's end.  Worst: a list of one entry in a wave with a list of NRQ_LT_LIST_MAX (for that list itself, when it is the last: fewer). */
+#define NRQ_STORE_TRIPS_MAX ((NRQ_LT_LIST_MAX + NRQ_STORE_TRIP - 1u) / NRQ_STORE_TRIP)
+static_assert(NRQ_STORE_SLACK >= 2u * (NRQ_STORE_TRIPS_MAX * NRQ_STORE_TRIP - 1u),
+              "the bytes behind out_slots[] do not cover ph_store's reads past a last list of one entry in a wave with a list of NRQ_LT_LIST_MAX");
 template <int WB, int G = 1> SB_HD uint32_t out_elems(const nrq_job *job, const nrq_plan_hdr *h) { return (job->inter ? h->L : 0u) + job->nout; }
 /* FAST: the form for the big workgroup (168 registers per thread); the 256- and 64-thread variants, built for 96-128 registers,
  * keep the lean loop (measured at K=1000: store phase 20 k -> 31 k clocks with the fast form there) */
@@ -1695,9 +1703,14 @@ SB_HD void store_trip(const NRQ_GAS uint16_t *osl, uint32_t e, uint32_t end, uin
     const u4 w = *reinterpret_cast<const NRQ_GAS u4a *>(osl + e + 8u * k);
     raw[4u * k] = w.x; raw[4u * k + 1u] = w.y; raw[4u * k + 2u] = w.z; raw[4u * k + 3u] = w.w;
   }
+#elif defined(NRQ_STORE_TRIP_UNBOUNDED)
+  /* the device's reads on the host: the same 16-byte pieces, past the list's end and the array's alike -- for the emulation that
+   * gives out_slots[] exactly the bytes the host sites allocate, with a page nobody may touch behind them (tests/emu/launch_emu.cpp) */
+#pragma unroll
+  for (uint32_t k = 0; k < NRQ_STORE_TRIP / 8u; k++) memcpy(&raw[4u * k], osl + e + 8u * k, 16);
 #else
 #pragma unroll
-  for (uint32_t k = 0; k < NRQ_STORE_TRIP / 2u; k++) /* (the emulator's arrays have no slack: stay inside the list) */
+  for (uint32_t k = 0; k < NRQ_STORE_TRIP / 2u; k++) /* (solve_emu.cpp's arrays have no slack: stay inside the list) */
     raw[k] = (e + 2u * k < end ? (uint32_t)osl[e + 2u * k] : 0u) | (e + 2u * k + 1u < end ? (uint32_t)osl[e + 2u * k + 1u] : 0u) << 16;
 #endif
 }
@@ -1918,6 +1931,35 @@ template <int WB, int G = 1, bool PIPELINED = false> SB_HD void pf_scatter(const
   }
 #endif
   pf_scatter_impl<WB, G, PIPELINED, false>(g, ostage, stage_stride, u0, u1, p, np, sub);
+}
+
+/* Work: "line groups" -- the 128/WB strips of one block that share a 128-byte line of every symbol row.  Slot q
+ * of the work list -> (block, group); workgroup g takes the slots g, g + grid, ...  With many blocks in the
+ * launch (by_block) all groups of a block go to workgroups of one XCD (workgroup g runs on XCD g % 8, observed;
+ * speed only), so that the block's plan -- every strip walks the whole op stream -- is served by one L2
+ * (nrq_map_by_block, launch_shape.h). */
+SB_HD bool nrq_map_group(uint32_t q, uint32_t nblk, uint32_t gpb, bool by_block, uint32_t *blk, uint32_t *grp) {
+  if (by_block) {
+    const uint32_t m = q >> 3;
+    *blk = (m / gpb) * 8u + (q & 7u);
+    *grp = m % gpb;
+  } else {
+    *blk = q / gpb;
+    *grp = q % gpb;
+  }
+  return *blk < nblk;
+}
+
+/* first slot >= q (stepping by `grid`, the workgroups of the launch: gridDim.x) that holds a group of a solvable block; >= nslots if none */
+SB_HD uint32_t nrq_next_group(uint32_t q, uint32_t grid, uint32_t nslots, const nrq_job *__restrict__ jobs, uint32_t nblk,
+                                 uint32_t gpb, bool by_block) {
+  for (; q < nslots; q += grid) {
+    uint32_t blk, grp;
+    if (!nrq_map_group(q, nblk, gpb, by_block, &blk, &grp)) continue;
+    const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(jobs[blk].plan);
+    if (h->status == 0) return q; /* rank deficient blocks: nothing is written for them */
+  }
+  return nslots;
 }
 
 #endif /* NRQ_SOLVE_BODY_H */

@@ -27,6 +27,10 @@ uint32_t emu_lds_max(void) { return NRQ_LDS_MAX; }
 uint32_t emu_lds_alloc(uint32_t bytes) { return lds_alloc(bytes); }
 uint32_t emu_lds_need(const uint32_t *f, uint32_t w) { return nrq_lds_plan(&make_hdrs(f, 1)[0], w).total; }
 uint32_t emu_map_by_block(uint32_t nblk) { return nrq_map_by_block(nblk) ? 1u : 0u; }
+/* nrq_map_group (solve_body.h): bg = {block, group} of work slot q; the verdict: 1 = a block of the launch */
+int emu_map_group(uint32_t q, uint32_t nblk, uint32_t gpb, int by_block, uint32_t *bg) {
+  return nrq_map_group(q, nblk, gpb, by_block != 0, &bg[0], &bg[1]) ? 1 : 0;
+}
 int emu_solve_key_compiled(int wb, int nt, int wv, int g, int al) { return solve_key_index(SolveKey{wb, nt, wv, g, al != 0}) >= 0; }
 int emu_plan_key_compiled(uint32_t nt, uint32_t compact) { return plan_key_index(nt, compact) >= 0; }
 uint32_t emu_widest_fit(const void *t, const uint32_t *f, uint32_t *need) {
@@ -43,7 +47,7 @@ void emu_solve_lists(const void *t, const uint32_t *f, uint32_t n, int can_split
 }
 
 /* in = {wb, nblk, T, lds_bytes, max_out, io_aligned, ncu, ahead_hint}; the maxima over the headers are taken here as the launch
- * takes them.  out: 24 words, see tests/test_launch_shape_emu.py */
+ * takes them.  out: 26 words (the last two: stage_bytes(), low and high half), see tests/test_launch_shape_emu.py */
 void emu_solve_shape(const void *t, const uint32_t *in, const uint32_t *f, uint32_t n, uint32_t *out) {
   const std::vector<nrq_plan_hdr> h = make_hdrs(f, n);
   const std::vector<const nrq_plan_hdr *> hp = ptrs(h);
@@ -57,9 +61,10 @@ void emu_solve_shape(const void *t, const uint32_t *in, const uint32_t *f, uint3
     if (x.wpr > si.max_wpr) si.max_wpr = x.wpr;
   }
   const SolveShape s = solve_shape(*static_cast<const Tuning *>(t), (int)in[6], in[7], si);
-  const uint32_t o[24] = {(uint32_t)s.err, (uint32_t)s.key.WB, (uint32_t)s.key.NT, (uint32_t)s.key.WV, (uint32_t)s.key.G, s.key.AL, s.lds_bytes,
+  const uint64_t sb = s.stage_bytes();
+  const uint32_t o[26] = {(uint32_t)s.err, (uint32_t)s.key.WB, (uint32_t)s.key.NT, (uint32_t)s.key.WV, (uint32_t)s.key.G, s.key.AL, s.lds_bytes,
                           s.wg_threads, s.wg_waves, s.split, s.by_block, s.nstrips, s.spl, s.occ, s.grid, s.lsub, s.nslots, s.stage_stride,
-                          s.ostage_stride, (uint32_t)s.ybuf_stride, s.res_elems, s.backsub_strip, s.backsub_tbl, s.nchunks};
+                          s.ostage_stride, (uint32_t)s.ybuf_stride, s.res_elems, s.backsub_strip, s.backsub_tbl, s.nchunks, (uint32_t)sb, (uint32_t)(sb >> 32)};
   memcpy(out, o, sizeof(o));
 }
 

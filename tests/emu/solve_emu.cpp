@@ -22,30 +22,10 @@ static uint32_t g_dense_shared_min_nt = 512; /* workgroup size from which the de
 #define NRQ_DENSE_SHARED_MIN_NT g_dense_shared_min_nt
 #include "../../nanorq_amd/csrc/solve_body.h"
 #include "../../nanorq_amd/csrc/split_body.h"
+#include "strip_emu.h" /* the phases of one strip, the split tail: shared with launch_emu.cpp */
 extern "C" void emu_set_dense_shared_min_nt(uint32_t v) { g_dense_shared_min_nt = v; }
 static int g_hdpc_regs = 0; /* 1: the HDPC phase in the form of the big workgroup (register accumulators) */
 extern "C" void emu_set_hdpc_regs(int v) { g_hdpc_regs = v; }
-
-/* The forward passes in the order the kernel's wave 0 issues them (plan.h): step q applies row q-NRQ_PIPE,
- * then reads the sources of row q -- so a plan that puts dependent rows closer than NRQ_PIPE rows apart
- * produces wrong symbols here, exactly as it would on the GPU. */
-template <int WB> static bool emu_forward(const StripCtx<WB> &c) {
-  const uint32_t *ops = c.template arr<uint32_t>(c.h->off_ops);
-  const uint32_t nrows = c.h->nrows, P = NRQ_PIPE;
-  if (c.h->pipe != NRQ_PIPE) return false;
-  std::vector<SV<WB>> v((size_t)(P + 1) * NRQ_ROW);
-  for (uint32_t q = 0; q < nrows + P; q++) {
-    if (q >= P) {
-      const SV<WB> *vr = &v[(size_t)((q - P) % (P + 1)) * NRQ_ROW];
-      for (uint32_t l = 0; l < NRQ_ROW; l++) ph_row_apply<WB>(c, ops[NRQ_OP_INDEX(q - P, l)], vr[l]);
-    }
-    if (q < nrows) {
-      SV<WB> *vr = &v[(size_t)(q % (P + 1)) * NRQ_ROW];
-      for (uint32_t l = 0; l < NRQ_ROW; l++) vr[l] = ph_row_read<WB>(c, ops[NRQ_OP_INDEX(q, l)]);
-    }
-  }
-  return true;
-}
 
 /* ybuf: the block's work buffer of a split solve ((M + u) rows of T bytes); nullptr: the whole solve in the strip */
 template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t strip, const uint8_t *kc, std::vector<uint8_t> &ostage,
@@ -64,39 +44,26 @@ template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t 
   c.strip = strip;
   uint32_t rem = T - strip * WB;
   c.valid = rem < (uint32_t)WB ? rem : (uint32_t)WB;
-#define PHASE(fn) for (uint32_t t = 0; t < NT; t++) fn<WB>(c, t, NT)
+  constexpr uint32_t SPL = nrq_group_strips(WB);
+  const size_t stride = ((size_t)c.h->M * WB + 255u) & ~(size_t)255u;
+  std::vector<uint8_t> stage(stride * SPL + 64, 0x5A);
   { /* the way the persistent kernel fills the image: the gathering threads bring the whole line group of this
-     * strip into the per-strip staging buffers, then all threads copy this strip's buffer into the image */
-    constexpr uint32_t SPL = nrq_group_strips(WB);
-    const size_t stride = ((size_t)c.h->M * WB + 255u) & ~(size_t)255u;
-    std::vector<uint8_t> stage(stride * SPL + 64, 0x5A);
+     * strip into the per-strip staging buffers, then all threads copy this strip's buffer into the image (strip_phases) */
     GroupSrc<WB> g;
     g.rowsrc = gptr<uint32_t>(c.job->rowsrc); g.src = gptr<uint8_t>(c.job->src); g.rep = gptr<uint8_t>(c.job->rep);
     g.M = c.h->M; g.T = T; g.strip0 = (strip / SPL) * SPL; g.nstrips = (T + WB - 1) / WB; g.lsub = __builtin_ctz(SPL);
     const uint32_t np = NT - NRQ_ROW, units = g.M * SPL, half = units / 2;
     for (uint32_t p = 0; p < np; p++) pf_gather<WB>(g, stage.data(), stride, 0, half, p, np);   /* in two portions, */
     for (uint32_t p = 0; p < np; p++) pf_gather<WB, 1, true>(g, stage.data(), stride, half, units, p, np); /* as the kernel does */
-    for (uint32_t t = 0; t < NT; t++) pf_commit<WB>(c, stage.data() + (size_t)(strip % SPL) * stride, 0u, t, NT);
-    PHASE(ph_clear);
   }
-  if (!emu_forward<WB>(c)) return -7;
-  if (g_hdpc_regs) { for (uint32_t t = 0; t < NT; t++) ph_hdpc<WB, 1, true>(c, t, NT); } else PHASE(ph_hdpc);
-  PHASE(ph_hdpc_reduce);
-  for (uint32_t w0 = 0; w0 < c.h->lpr; w0 += low_table_words<WB>(c)) {
-    for (uint32_t t = 0; t < NT; t++) ph_low_tables<WB>(c, w0, t, NT);
-    for (uint32_t t = 0; t < NT; t++) { uint32_t cb[NRQ_COMBINE_WU]; ph_combine_fetch<WB>(c, w0, t, NT, cb); ph_combine<WB>(c, w0, t, NT, cb); }
-  }
-  if (c.h->lpr) PHASE(ph_clear_x);
-  for (uint32_t t = 0; t < NT; t++) ph_dense_fold<WB, 1, 8>(c, t, NT); /* (the form of the 256-thread workgroup) */
-  if (dense_fold_shared(NT)) PHASE(ph_hdpc_reduce);
-  for (uint32_t t = 0; t < NT; t++) ph_dense_free<WB, 1, true>(c, t, NT);
-  for (uint32_t t = 0; t < NT; t++) ph_dense_cu<WB, 1, true>(c, t, NT);
-  if (ybuf) { /* the split solve: slot image and C_u staged per strip, scattered to full-width rows of the work buffer */
-    constexpr uint32_t SPL = nrq_group_strips(WB);
-    const uint32_t nstrips = (T + WB - 1) / WB, ne = c.h->M + c.h->u;
-    const size_t ostride = ((size_t)ne * WB + 255u) & ~(size_t)255u;
-    if (strip % SPL == 0) ostage.assign(ostride * SPL + 64, 0x3C);
-    for (uint32_t t = 0; t < NT; t++) ph_store_raw<WB>(c, ostage.data() + (size_t)(strip % SPL) * ostride, t, NT);
+  const uint32_t nstrips = (T + WB - 1) / WB, ne = ybuf ? c.h->M + c.h->u : out_elems<WB>(c.job, c.h);
+  const size_t ostride = ((size_t)ne * WB + 255u) & ~(size_t)255u;
+  if (strip % SPL == 0) ostage.assign(ostride * SPL + 64, 0x3C);
+  StripForm f; /* (the forms this emulation has always run: the dense fold of the 256-thread workgroup, the batched dense phases) */
+  f.hnt = NT; f.hdpc_regs = g_hdpc_regs != 0;
+  const int r = strip_phases<WB, 1>(&c, NT, f, stage.data() + (size_t)(strip % SPL) * stride, ostage.data() + (size_t)(strip % SPL) * ostride, ybuf != nullptr);
+  if (r != 1) return r;
+  if (ybuf) { /* the split solve: slot image and C_u, staged per strip, scattered to full-width rows of the work buffer */
     if (strip % SPL == SPL - 1 || strip + 1 == nstrips) {
       GroupDst<WB> g; /* (nrq_solve_kernel group_dst with a work buffer) */
       g.inter = ybuf; g.out = gptr_w<uint8_t>(c.job->out); g.orow = gptr<uint32_t>(c.job->out_row);
@@ -107,25 +74,15 @@ template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t 
     }
     return 1;
   }
-  PHASE(ph_tables);
-  PHASE(ph_backsub);
-  PHASE(ph_park);
-  { /* results: staged per strip, then scattered to the symbol rows a line group at a time */
-    constexpr uint32_t SPL = nrq_group_strips(WB);
-    const uint32_t nstrips = (T + WB - 1) / WB, ne = out_elems<WB>(c.job, c.h);
-    const size_t ostride = ((size_t)ne * WB + 255u) & ~(size_t)255u;
-    if (strip % SPL == 0) ostage.assign(ostride * SPL + 64, 0x3C);
-    for (uint32_t t = 0; t < NT; t++) ph_store<WB>(c, ostage.data() + (size_t)(strip % SPL) * ostride, t, NT);
-    if (strip % SPL == SPL - 1 || strip + 1 == nstrips) {
-      GroupDst<WB> g;
-      g.inter = gptr_w<uint8_t>(c.job->inter); g.out = gptr_w<uint8_t>(c.job->out); g.orow = gptr<uint32_t>(c.job->out_row);
-      g.ni = c.job->inter ? c.h->L : 0u; g.nout = c.job->nout; g.T = T; g.strip0 = (strip / SPL) * SPL; g.nstrips = nstrips; g.lsub = __builtin_ctz(SPL);
-      const uint32_t np = NT - NRQ_ROW, units = ne * SPL, cut = units / 3;
-      for (uint32_t p = 0; p < np; p++) pf_scatter<WB>(g, ostage.data(), ostride, 0, cut, p, np);
-      for (uint32_t p = 0; p < np; p++) pf_scatter<WB, 1, true>(g, ostage.data(), ostride, cut, units, p, np);
-    }
+  /* results: staged per strip, then scattered to the symbol rows a line group at a time */
+  if (strip % SPL == SPL - 1 || strip + 1 == nstrips) {
+    GroupDst<WB> g;
+    g.inter = gptr_w<uint8_t>(c.job->inter); g.out = gptr_w<uint8_t>(c.job->out); g.orow = gptr<uint32_t>(c.job->out_row);
+    g.ni = c.job->inter ? c.h->L : 0u; g.nout = c.job->nout; g.T = T; g.strip0 = (strip / SPL) * SPL; g.nstrips = nstrips; g.lsub = __builtin_ctz(SPL);
+    const uint32_t np = NT - NRQ_ROW, units = ne * SPL, cut = units / 3;
+    for (uint32_t p = 0; p < np; p++) pf_scatter<WB>(g, ostage.data(), ostride, 0, cut, p, np);
+    for (uint32_t p = 0; p < np; p++) pf_scatter<WB, 1, true>(g, ostage.data(), ostride, cut, units, p, np);
   }
-#undef PHASE
   return 1;
 }
 
@@ -151,43 +108,7 @@ extern "C" int emu_solve(const nrq_job *job, uint32_t T, uint32_t wb, const uint
   return r;
 }
 
-/* ---- the second half of a split solve (split_body.h) ---- */
-
-/* nrq_backsub_kernel<SB> on grid (gridx, nchunks) for one block: Y = its work buffer.  Workgroups run one after the other,
- * the last first (they share nothing but the rows they read: any order gives the same buffer), each with tables of its own in
- * garbage-filled "LDS".  -2: a workgroup was given a strip the row does not have. */
-template <int SB> static int run_backsub(const uint8_t *plan, uint8_t *Y, uint32_t T, uint32_t gridx, uint32_t nchunks) {
-  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
-  std::vector<uint8_t> lds((size_t)h->wpr * 8u * 16u * SB + 64, 0xA5);
-  uint8_t *tbl = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(lds.data()) + 15) & ~(uintptr_t)15);
-  for (uint32_t chunk = nchunks; chunk-- > 0;)
-    for (uint32_t wg = gridx; wg-- > 0;) {
-      SplitCtx<SB> c;
-      const uint32_t strip = sp_strip_of<SB>(wg, gridx);
-      if (!sp_ctx<SB>(c, plan, Y, T, strip)) return 0;
-      if ((uint64_t)strip * SB >= T) return -2;
-      memset(tbl, 0xA5, (size_t)h->wpr * 8u * 16u * SB);
-      for (uint32_t t = 0; t < SP_NT; t++) sp_tables<SB>(c, tbl, t);
-      for (uint32_t t = 0; t < SP_NT; t++) sp_backsub<SB>(c, tbl, chunk, nchunks, t);
-    }
-  return 1;
-}
-
-/* nrq_collect_kernel on grid x = grid_e for one block: F = the final slot image */
-static int run_collect(const nrq_job *job, uint32_t T, const uint8_t *F, uint32_t grid_e) {
-  const uint8_t *plan = reinterpret_cast<const uint8_t *>(job->plan);
-  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
-  if (h->status) return 0;
-  for (uint32_t e = 0; e < grid_e; e++) {
-    if (e >= sc_elems(job, h)) continue;
-    uint32_t rows[RQ_MAX_LT_COLS + 1], nrows = 0xA5A5A5A5u;
-    for (uint32_t k = 0; k <= RQ_MAX_LT_COLS; k++) rows[k] = 0xA5A5A5A5u;
-    uint8_t *dst[SP_NT];
-    for (uint32_t t = 0; t < SP_NT; t++) dst[t] = sc_fetch(job, plan, e, T, t, rows, &nrows);
-    for (uint32_t t = 0; t < SP_NT; t++) sc_sum(F, dst[t], T, rows, nrows, t);
-  }
-  return 1;
-}
+/* ---- the second half of a split solve (split_body.h; run_backsub / run_collect: strip_emu.h) ---- */
 
 extern "C" uint32_t emu_backsub_strip_of(uint32_t sb, uint32_t wg, uint32_t gridx) {
   return sb == 32 ? sp_strip_of<32>(wg, gridx) : sp_strip_of<16>(wg, gridx);

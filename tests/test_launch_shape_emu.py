@@ -12,7 +12,8 @@ from nanorq_amd import build as nbuild
 U32 = C.c_uint32
 WIDTHS = (16, 12, 8, 4, 2)
 SOLVE_OUT = ("err", "WB", "NT", "WV", "G", "AL", "lds", "wg_threads", "wg_waves", "split", "by_block", "nstrips", "spl", "occ", "grid",
-             "lsub", "nslots", "stage_stride", "ostage_stride", "ybuf_stride", "res_elems", "backsub_strip", "backsub_tbl", "nchunks")
+             "lsub", "nslots", "stage_stride", "ostage_stride", "ybuf_stride", "res_elems", "backsub_strip", "backsub_tbl", "nchunks", "stage_bytes_lo",
+             "stage_bytes_hi")
 PLAN_OUT = ("err", "wg_threads", "compact", "segmented", "mode", "nparts", "part0", "part1", "part2", "qcap", "lowcap", "sh_bytes",
             "dyn_bytes", "wentry_wgs", "wpass_wgs", "wpass_lds", "mh_wgs", "mh_dyn")
 
@@ -37,6 +38,7 @@ def emu():
     L.emu_solve_lists.argtypes = [C.c_void_p, C.c_void_p, U32, C.c_int, C.c_void_p, C.c_void_p]
     L.emu_solve_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, U32, C.c_void_p]
     L.emu_plan_shape.argtypes = [C.c_void_p, C.c_int, U32, U32, U32, U32, C.c_void_p]
+    L.emu_map_group.argtypes = [U32, U32, U32, C.c_int, C.c_void_p]
     for f in (L.emu_lds_max, L.emu_lds_alloc, L.emu_lds_need, L.emu_map_by_block, L.emu_widest_fit):
         f.restype = U32
     return L
@@ -98,10 +100,10 @@ def test_compiled_instances(emu):
 def test_solve_shape_holds_for_any_tuning(emu):
     LDS = emu.emu_lds_max()
     needs = (300, 2000, 9000, 13000, 23000, 32000, 40000, 81000, 82500, 120000, LDS)
-    nblks = (1, 2, 7, 8, 16, 63, 64, 256, 1000, 4000)
+    nblks = (1, 2, 7, 8, 16, 63, 64, 65, 256, 1000, 4000)  # (65: mapped by block octets, the last octet of one block)
     Ts = (16, 40, 64, 72, 100, 1024, 1280, 1288)
     out = (U32 * len(SOLVE_OUT))()
-    cases = 0
+    cases = refused = 0
     for knobs in SOLVE_KNOBS:
         with Tuning(emu, knobs) as t:
             for wb, need, nblk, T, many, ncu, io in itertools.product(WIDTHS, needs, nblks, Ts, (False, True), (256, 64), (0, 1)):
@@ -140,15 +142,28 @@ def test_solve_shape_holds_for_any_tuning(emu):
                 assert s["nstrips"] == -(-T // wbe), what
                 assert s["by_block"] == emu.emu_map_by_block(nblk), what
                 sub = 1 << s["lsub"]
-                assert sub < 2 * s["spl"], what
+                assert sub <= s["spl"], what  # (a slot's strips each have a staging buffer of their own: there are spl per set)
                 assert s["nslots"] == ((nblk + 7) // 8 * 8 if s["by_block"] else nblk) * -(-s["nstrips"] // sub), what
                 assert 1 <= s["grid"] <= s["nslots"], what
                 assert s["grid"] >= 8 or s["grid"] == s["nslots"], what
                 assert not s["by_block"] or s["grid"] % 8 == 0, what
+                # the slots as nrq_map_group deals them: each of the last eight (the last block octet) is a group of a block of the launch
+                # or is refused (a partial octet), and the last group of the last block has a slot
+                gpb, bg = -(-s["nstrips"] // sub), (U32 * 2)()
+                for q in range(max(0, s["nslots"] - 8), s["nslots"]):
+                    if emu.emu_map_group(q, nblk, gpb, s["by_block"], bg):
+                        assert bg[0] < nblk and bg[1] < gpb, what
+                    else:
+                        assert s["by_block"] and nblk % 8 and bg[0] >= nblk, what
+                        refused += 1
+                q_last = (((nblk - 1) // 8 * gpb + gpb - 1) * 8 + (nblk - 1) % 8) if s["by_block"] else (nblk - 1) * gpb + gpb - 1
+                assert q_last < s["nslots"] and emu.emu_map_group(q_last, nblk, gpb, s["by_block"], bg) and tuple(bg) == (nblk - 1, gpb - 1), what
                 # staging holds the rows of a strip, in whole 256-byte pieces
                 rows_out = h[0] + u if s["split"] else max_out
                 assert s["stage_stride"] % 256 == 0 and s["stage_stride"] >= h[0] * wbe, what
                 assert s["ostage_stride"] % 256 == 0 and s["ostage_stride"] >= rows_out * wbe, what
+                # ... two sets of spl input and spl output buffers per workgroup: what the kernel strides through
+                assert s["stage_bytes_lo"] | s["stage_bytes_hi"] << 32 == s["grid"] * 2 * s["spl"] * (s["stage_stride"] + s["ostage_stride"]), what
                 if s["split"]:
                     assert s["ybuf_stride"] % 256 == 0 and s["ybuf_stride"] >= (h[0] + u) * T, what
                     assert s["res_elems"] == max_out, what
@@ -159,7 +174,7 @@ def test_solve_shape_holds_for_any_tuning(emu):
                     assert s["backsub_tbl"] == (u + 31) // 32 * 128 * s["backsub_strip"], what
                 else:
                     assert s["backsub_strip"] == 0, what
-    assert cases > 20000
+    assert cases > 20000 and refused > 500
 
 
 def test_plan_shape_holds_for_any_tuning(emu):

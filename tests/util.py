@@ -38,3 +38,27 @@ def received_set(K, lost, overhead):
     keep = np.setdiff1d(np.arange(K, dtype=np.uint32), lost)
     rep = np.arange(K, K + len(lost) + overhead, dtype=np.uint32)
     return np.concatenate([keep, rep])
+
+
+_UNDEC = {}
+
+
+def undecodable(orc, K, block):
+    """A reception of block `block` with no overhead whose system is rank deficient: the first of loss_pattern(K, 0.6, 90000 + s, block),
+    repair ESIs from K, that the host planner refuses.  (~1 % of receptions without overhead are; kept per (K, block).)"""
+    import nanorq_amd
+    if (K, block) not in _UNDEC:
+        p = orc.params(K)
+        kc = nanorq_amd.host_kconst(K)
+        for s in range(4000):
+            lost = loss_pattern(K, 0.6, seed=90000 + s, block=block)
+            if not len(lost):
+                continue
+            isis = np.arange(p["Kp"], dtype=np.uint32)
+            isis[lost] = np.arange(K, K + len(lost), dtype=np.uint32) + (p["Kp"] - K)  # (the ISI of repair ESI e is e + K' - K)
+            if nanorq_amd.plan_header(nanorq_amd.host_plan(K, isis, kc))["status"] != 0:
+                _UNDEC[(K, block)] = lost
+                break
+        else:
+            raise AssertionError("no rank deficient reception found")
+    return _UNDEC[(K, block)]
