@@ -202,6 +202,9 @@ int nrq_dev_copy(nrq_ctx *ctx, void *d_dst, const void *d_src, size_t bytes); /*
 /* nrq_dev_alloc / nrq_dev_free come out of a caching pool of the context (no hipMalloc / hipFree per call, no
  * synchronisation on free); nrq_dev_trim hands the cached blocks back to the driver. */
 int nrq_dev_trim(nrq_ctx *ctx);
+/* nrq_dev_free refuses (-1) an address that is no block of the context and a block that is already cached (a second free).
+ * The pool's books, for tests: out[0] blocks the pool owns (handed out or cached), out[1] blocks cached, out[2] bytes cached. */
+int nrq_dev_pool_books(nrq_ctx *ctx, size_t out[3]);
 
 /* ---- what the object layer's streaming path is made of (reference: transfer_esi / load_symbol_matrix,
  * lib/nanorq.c:148-182, and the seek+read/write loops of lib/io.c behind them) ----

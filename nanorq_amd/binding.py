@@ -76,6 +76,9 @@ def lib():
     L.nrq_gen_symbols.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, sz, C.c_uint32, u32p, vp, sz]
     L.nrq_dev_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     L.nrq_dev_free.argtypes = [vp, vp]
+    if hasattr(L, "nrq_dev_pool_books"):  # (NANORQ_HIP_LIB may name a build from before the pool's books were readable)
+        L.nrq_dev_pool_books.argtypes = [vp, C.POINTER(sz)]
+    L.nrq_dev_trim.argtypes = [vp]
     L.nrq_dev_upload.argtypes = [vp, vp, vp, sz]
     L.nrq_dev_download.argtypes = [vp, vp, vp, sz]
     L.nrq_dev_memset.argtypes = [vp, vp, C.c_int, sz]

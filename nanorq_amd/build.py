@@ -3,6 +3,7 @@
   libnanorq_hip.so   product: gfx950 kernels + C ABI (include/nanorq_hip.h) + drop-in nanorq.h/io.h
                      layer, compiled with hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
   tests/emu/lib*_emu.so       test support: the kernels' phase code and the launch decisions, built by g++ for the CPU tier
+  tests/emu/libnanorq_model.so  test support: the library's HOST layer, from the same sources, over a model of the HIP runtime
 
 The .so files are git-ignored but travel to the GPU box with the working tree.
 """
@@ -27,6 +28,7 @@ REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
+MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -188,6 +190,74 @@ def build_shape_emu(force=False):
                       ("launch_shape.h", "planner_body.h", "solve_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h"), force)
 
 
+def build_model_lib(force=False, out=None, sanitize=False):
+    """tests/emu/libnanorq_model.so: the host layer of the library -- the host-only object of nrq_device.hip, with every launch
+    turned into a call of the model by the force-included tests/emu/hip_model.h, planner_host.cpp, nanorq_api.c, io.c -- linked
+    with the model runtime tests/emu/hip_model.cpp (and the effects of the library's own kernels, tests/emu/model_effects.cpp)
+    instead of the HIP runtime.  Kernels do not run in it.  `out` + `sanitize`: another file, every source compiled by the
+    clang that hipcc drives with -fsanitize=address,undefined (host code only: there is no device code in this library)."""
+    emu = os.path.join(ROOT, "tests", "emu")
+    hook, model, effects = os.path.join(emu, "hip_model.h"), os.path.join(emu, "hip_model.cpp"), os.path.join(emu, "model_effects.cpp")
+    target = out or MODEL
+    if not force and not _newer(target, _deps() + [hook, model, effects]):
+        return target
+    hipcc = _hipcc()
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    objdir = os.path.join(HERE, "build_model" if out is None else "build_" + os.path.basename(out))
+    os.makedirs(objdir, exist_ok=True)
+    common = ["-O2", "-g1", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + emu]
+    cc, cxx, san, hip_san = "gcc", "g++", [], []
+    if sanitize:
+        llvm = os.path.join(rocm, "lib", "llvm", "bin")
+        cc, cxx = os.path.join(llvm, "clang"), os.path.join(llvm, "clang++")
+        san = ["-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+        hip_san = [x for f in san for x in ("-Xarch_host", f)]
+    objs = []
+
+    def obj(cmd, src, name):
+        o = os.path.join(objdir, name + ".o")
+        subprocess.run([*cmd, *common, "-c", src, "-o", o], check=True)
+        objs.append(o)
+        return o
+
+    dev = obj([hipcc, "--offload-host-only", "-std=c++17", "-Wno-pass-failed", "-DNRQ_HIP_MODEL_HOOK", "-include", hook, *hip_san],
+              os.path.join(CSRC, HIP_SOURCES[0]), HIP_SOURCES[0])
+    for s in CXX_SOURCES:
+        obj([cxx, "-std=c++17", "-Wall", *san], os.path.join(CSRC, s), s)
+    for s in C_SOURCES:
+        obj([cc, "-std=gnu11", "-Wall", "-D_FILE_OFFSET_BITS=64", *san], os.path.join(CSRC, s), s)
+    # (plain C++ over the runtime's own prototypes: the headers that ship next to the compiler)
+    obj([cxx, "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), *san], model, "hip_model.cpp")
+    # the library's own kernels' effects.  (UBSan only in a sanitizer build: with AddressSanitizer's global instrumentation the
+    # runtime refuses this object's string literals at load time as "not properly aligned", before main runs; the file is test
+    # support on top of the model, not host-layer code)
+    obj([cxx, "-std=c++17", "-Wall", "-Wno-unknown-pragmas", *[f for f in san if f != "-fsanitize=address,undefined"],
+         *(["-fsanitize=undefined"] if sanitize else [])], effects, "model_effects.cpp")
+    # the host-only object still names the device code's image; nobody reads it here: the symbol gets a value at link time
+    undefined = subprocess.run(["nm", "-u", dev], check=True, stdout=subprocess.PIPE).stdout.decode().split()
+    defs = ["-Wl,--defsym=%s=0" % n for n in undefined if n.startswith("__hip_fatbin")]
+    subprocess.run([cxx, "-shared", "-fPIC", *san, "-o", target, *objs, *defs, "-lpthread", "-ldl"], check=True)
+    return target
+
+
+def build_model_exercise(force=False, sanitize=True):
+    """tests/emu/model_exercise(_asan): tests/emu/model_exercise.cpp, a program of its own over the model library -- with
+    `sanitize` over tests/emu/libnanorq_model_asan.so, host layer, model and program under AddressSanitizer / UBSan.  Run it
+    directly: a sanitizer report or a failed check makes its exit status non-zero."""
+    emu = os.path.join(ROOT, "tests", "emu")
+    src = os.path.join(emu, "model_exercise.cpp")
+    exe = os.path.join(emu, "model_exercise_asan" if sanitize else "model_exercise")
+    lib = build_model_lib(force=force, out=os.path.join(emu, "libnanorq_model_asan.so") if sanitize else None, sanitize=sanitize)
+    if force or _newer(exe, [src, lib]):
+        cxx, san = "g++", []
+        if sanitize:
+            cxx = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(_hipcc()))), "lib", "llvm", "bin", "clang++")
+            san = ["-O1", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+        subprocess.run([cxx, "-std=c++17", "-Wall", "-g1", *san, "-I" + os.path.join(ROOT, "include"), "-I" + emu, src, "-o", exe,
+                        "-L" + emu, "-l:" + os.path.basename(lib), "-Wl,-rpath,$ORIGIN", "-lpthread"], check=True)
+    return exe
+
+
 if __name__ == "__main__":
     build_lib(force="-f" in sys.argv, verbose=True)
     build_emu(force="-f" in sys.argv)
@@ -202,4 +272,5 @@ if __name__ == "__main__":
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)
+    build_model_lib(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

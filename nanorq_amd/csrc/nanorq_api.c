@@ -475,6 +475,11 @@ bool nanorq_set_max_esi(nanorq *rq, uint32_t max_esi) { /* nanorq.c:471-476 */
   return true;
 }
 
+/* A wait in front of a release -- a pool block, page-locked memory, or the return to a caller who may free the packet buffer
+ * the copies read: it is tried twice, so that one failed attempt (the first may report an error without having waited) does
+ * not let the release run under copies in flight.  true = the stream has been waited for. */
+static bool stream_settled(nrq_ctx *c, int which) { return nrq_stream_sync(c, which) == 0 || nrq_stream_sync(c, which) == 0; }
+
 /* deferred ingestion: wait for device di's upload pieces and release what they used */
 static void settle_uploads(nanorq *rq, int di) {
   struct upstate *u = &rq->up[di];
@@ -482,8 +487,8 @@ static void settle_uploads(nanorq *rq, int di) {
   nrq_ctx *c = dctx(di);
   if (c) {
     gpu_lock(di);
-    nrq_stream_sync(c, 1);
-    nrq_stream_sync(c, 3);
+    (void)stream_settled(c, 1);
+    (void)stream_settled(c, 3);
     for (unsigned i = 0; i < u->nblob; i++) nrq_dev_free(c, u->blob[i]);
     gpu_unlock(di);
   }
@@ -1522,8 +1527,8 @@ static void *add_all_worker(void *arg) {
       host_free(dst, dst_pinned);
     }
     if (!ok || nold) { /* (replaced repair rows are freed below: nothing may still be copying out of them) */
-      nrq_stream_sync(c, 1);
-      nrq_stream_sync(c, 3);
+      (void)stream_settled(c, 1);
+      (void)stream_settled(c, 3);
       settle_uploads(rq, di);
     }
     for (unsigned i = 0; i < nold; i++) nrq_dev_free(c, olds[i]);
@@ -1566,7 +1571,7 @@ static void *add_all_worker(void *arg) {
         }
       }
       if (fill && ok) ok = nrq_scatter_symbols(c, 1, d_blob, fill, (uint32_t)T, cdst) == 0;
-      ok = nrq_stream_sync(c, 1) == 0 && ok;
+      ok = stream_settled(c, 1) && ok;
       if (d_blob) nrq_dev_free(c, d_blob);
       free(cdst);
       if (j->deferred) settle_uploads(rq, di);
@@ -1615,14 +1620,14 @@ static void *add_all_worker(void *arg) {
       u->pin_cached[u->npin] = false;
       u->pin[u->npin++] = h_dst;
     } else {
-      ok = nrq_stream_sync(c, 1) == 0 && ok;
+      ok = stream_settled(c, 1) && ok;
       if (d_blob) nrq_dev_free(c, d_blob);
       if (d_dst) nrq_dev_free(c, d_dst);
       if (h_dst) nrq_host_free_pinned(h_dst);
       if (j->deferred) settle_uploads(rq, di);
     }
   } else if (!j->deferred) {
-    ok = nrq_stream_sync(c, 1) == 0 && ok;
+    ok = stream_settled(c, 1) && ok;
   }
   for (unsigned i = 0; i < nold; i++) nrq_dev_free(c, olds[i]);
   gpu_unlock(di);

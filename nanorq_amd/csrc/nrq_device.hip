@@ -2380,9 +2380,19 @@ int nrq_dev_free(nrq_ctx *ctx, void *p) {
   if (!p) return 0;
   auto it = ctx->pool_size.find(p);
   if (it == ctx->pool_size.end()) return fail(ctx, -1, "nrq_dev_free: not a block of this context");
+  /* a block that is already cached is refused: a second entry would hand it to two owners and nrq_dev_trim would release it twice */
+  for (auto r = ctx->pool_free.equal_range(it->second); r.first != r.second; ++r.first)
+    if (r.first->second == p) return fail(ctx, -1, "nrq_dev_free: the block was freed already");
   ctx->pool_free.emplace(it->second, p);
   ctx->pool_cached += it->second;
   if (ctx->pool_cached > ((size_t)24 << 30)) nrq_dev_trim(ctx); /* keep the cache bounded */
+  return 0;
+}
+int nrq_dev_pool_books(nrq_ctx *ctx, size_t out[3]) {
+  if (!ctx || !out) return -1;
+  out[0] = ctx->pool_size.size();
+  out[1] = ctx->pool_free.size();
+  out[2] = ctx->pool_cached;
   return 0;
 }
 int nrq_dev_trim(nrq_ctx *ctx) {

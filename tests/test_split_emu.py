@@ -397,7 +397,7 @@ def test_gpu_split_shapes_get_the_grids_they_name():
     L.emu_tuning_free.argtypes = [C.c_void_p]
     L.emu_tuning_set.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.emu_solve_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    out = (C.c_uint32 * 24)()
+    out = (C.c_uint32 * 26)()   # (emu_solve_shape writes 26 words: tests/emu/shape_emu.cpp)
     #        T, nblk, backsub_sb, wpr -> strip, nchunks
     for T, nblk, knob, wpr, strip, nchunks in [(1040, 9, 0, 2, 32, 7), (1040, 32, 16, 1, 16, 1), (1043, 3, 0, 2, 32, 16),
                                                (1043, 3, 16, 2, 16, 11), (48, 2, 0, 5, 32, 16), (16, 1, 0, 21, 16, 16),
