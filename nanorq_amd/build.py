@@ -4,6 +4,7 @@
                      layer, compiled with hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
   tests/emu/lib*_emu.so       test support: the kernels' phase code and the launch decisions, built by g++ for the CPU tier
   tests/emu/libnanorq_model.so  test support: the library's HOST layer, from the same sources, over a model of the HIP runtime
+  tests/gpu/librows_probe.so  test support: the row pipelines of solve_body.h behind kernels of their own (gfx950, needs a GPU to run)
 
 The .so files are git-ignored but travel to the GPU box with the working tree.
 """
@@ -29,6 +30,7 @@ LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
+ROWS = os.path.join(ROOT, "tests", "gpu", "librows_probe.so")
 
 HIP_SOURCES = ["nrq_device.hip"]
 CXX_SOURCES = ["planner_host.cpp"]
@@ -240,6 +242,16 @@ def build_model_lib(force=False, out=None, sanitize=False):
     return target
 
 
+def build_rows_probe(force=False):
+    """tests/gpu/librows_probe.so: tests/gpu/rows_probe.hip, the device-only row pipelines of solve_body.h (fwd_rows and its half /
+    third forms, rev_rows, fwd_rows_wide) and its address helpers in kernels that run them on images of the caller's.  A library
+    of its own, so that libnanorq_hip.so holds no kernel it does not ship; cross-compiles without a GPU."""
+    src = os.path.join(ROOT, "tests", "gpu", "rows_probe.hip")
+    if force or _newer(ROWS, [src, os.path.join(CSRC, "solve_body.h"), os.path.join(CSRC, "plan.h")]):
+        subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + CSRC, "-shared", "-fPIC", src, "-o", ROWS], check=True)
+    return ROWS
+
+
 def build_model_exercise(force=False, sanitize=True):
     """tests/emu/model_exercise(_asan): tests/emu/model_exercise.cpp, a program of its own over the model library -- with
     `sanitize` over tests/emu/libnanorq_model_asan.so, host layer, model and program under AddressSanitizer / UBSan.  Run it
@@ -273,4 +285,5 @@ if __name__ == "__main__":
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)
     build_model_lib(force="-f" in sys.argv)
+    build_rows_probe(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -63,6 +63,8 @@ def test_ledger_rows_are_well_formed(inst):
             assert _test_exists(row["test"]), what
         else:
             assert "shape" in row or "via" in row, what
+        if "rows" in row:  # the variant's row pipeline on its own (tests/test_gpu_rows.py)
+            assert _test_exists(row["rows"]), what
         if "pinned" in row:  # a racy default row names the test that reaches the variant in every run
             assert row.get("racy") and _test_exists(row["pinned"]), what
     for name, row in V.FEATURES.items():

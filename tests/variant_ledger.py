@@ -20,6 +20,10 @@ _NARROW_SMALL = ("a narrower width is taken only when the next wider image excee
                  "LDS: the full-size workgroup")
 _NARROW_TEST = "tests/test_gpu_parity.py::test_narrow_strip_paths_at_small_sizes"
 
+# rows: the variant's row pipeline (fwd_rows_wide<G>) also runs on its own, against a plain replay of its op stream, whatever the
+# launch options: the test's case [fwd_rows_wide-G]
+_ROWS_TEST = "tests/test_gpu_rows.py::test_rows"
+
 SOLVE = {
     # 16-byte strips, full-size workgroup
     (16, 768, 1, 1, True): dict(status="default", shape=dict(K=1500, T=1280, nblk=1, loss=0.2),
@@ -40,11 +44,11 @@ SOLVE = {
     # (64 blocks of T=100 are 448 strips, not more than 2 per CU: 256/4 on an MI355X; 128 blocks are 896)
     (16, 64, 3, 1, False): dict(status="default", shape=dict(K=100, T=100, nblk=128, loss=0.2)),
     # wide strips: never selected automatically (solve_shape: "wide_g" only)
-    (16, 256, 4, 2, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips",
+    (16, 256, 4, 2, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips", rows=_ROWS_TEST,
                                  why="wide strips are an experiment: only the option wide_g selects them"),
-    (16, 256, 4, 4, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips",
+    (16, 256, 4, 4, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips", rows=_ROWS_TEST,
                                  why="wide strips are an experiment: only the option wide_g selects them"),
-    (16, 256, 4, 8, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips",
+    (16, 256, 4, 8, False): dict(status="forced", test="tests/test_gpu_parity.py::test_wide_strips", rows=_ROWS_TEST,
                                  why="wide strips are an experiment: only the option wide_g selects them"),
     # 12-byte strips (compiled for the full-size workgroup only)
     (12, 768, 1, 1, True): dict(status="default", shape=dict(K=10000, T=1280, nblk=2, loss=0.1)),
