@@ -519,6 +519,27 @@ int nrq_rxset_lists(nrq_rxset *set, uint32_t *h_nlost, uint32_t *h_nrep, uint32_
  * their rows hold -- the blocks of the failed and of the later calls have status 0 and their books as before, and the failing
  * call's code and text are returned.  A second nrq_rxset_decode finishes the job. */
 int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used);
+/* ---- what ALL members want or hold, with keys: the request of a whole set in one call ----
+ * nrq_rxset_want / nrq_rxset_held: the list is the concatenation, in the set's block order (above), of what each member's own
+ * nrq_rx_want / nrq_rx_held gives for the same arguments, word for word; d_keys[i] is the key of the member d_tags[i] belongs
+ * to.  An attached object contributes what nrq_orx_want / nrq_orx_held gives (class L, then class S) under its one key.  Per block
+ * the rules are the ones written at nrq_rx_want -- a complete block lists nothing, NRQ_WANT_SOURCE lists the clear source bits,
+ * repair mode lists min(max(g + extra - r, 0), rep_cap - r) ESIs, the lowest unseen ones in [max(K, esi_from), max_esi] -- with
+ * each MEMBER's own K, max_esi and rep_cap; the rank-deficiency note there applies as it stands.  Held lists a block's seen
+ * source ESIs ascending, then its repair ESIs in arrival order, as nrq_rx_held.  (keys, tags) is the form nrq_txset_emit takes:
+ * want -> emit -> nrq_rxset_add -> nrq_rxset_decode runs for all members without a per-member call or a host-built list.
+ * The calling contract is nrq_rx_want's: the call waits for the work enqueued before it; *h_n, the total number of tags, is
+ * final on return, and so is h_cnt (nullable): one entry per block in block order, as nrq_rxset_blocks reports them, the number
+ * of tags that block lists, from the same download as the total.  d_tags NULL counts only; cap < *h_n: -1 with *h_n and h_cnt
+ * still filled and nothing written; else the writing of d_tags and d_keys is enqueued on the context's stream, so an
+ * nrq_txset_emit enqueued behind it sees both without a host wait (a read from the host or from another stream needs
+ * nrq_ctx_sync first).  d_keys is nullable when d_tags is given (a set whose keys the caller does not need); d_keys without
+ * d_tags: -1.  Argument errors are nrq_rx_want's; h_n NULL: -1.  An empty set: 0 with *h_n = 0 and no launch.  Three launches
+ * (a count per block, one scan, a fill per block), one download and one wait for the whole set.  The call only reads the
+ * members' books. */
+int nrq_rxset_want(nrq_rxset *set, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_keys, uint32_t *d_tags, uint32_t cap,
+                   uint32_t *h_cnt, uint32_t *h_n);
+int nrq_rxset_held(nrq_rxset *set, uint32_t *d_keys, uint32_t *d_tags, uint32_t cap, uint32_t *h_cnt, uint32_t *h_n);
 
 /* ---- sender sets: the packets of MANY transmissions and objects written into one buffer in one pass ----
  * The send-side counterpart of a reception set: a table of member transmissions (nrq_tx: senders and relays) and objects (nrq_otx:

@@ -151,6 +151,9 @@ def lib():
         L.nrq_rxset_counts.argtypes = [vp, u32p, u32p]
         L.nrq_rxset_lists.argtypes = [vp, u32p, u32p, u32p, sz, C.POINTER(sz)]
         L.nrq_rxset_decode.argtypes = [vp, ip, u32p]
+    if hasattr(L, "nrq_rxset_want"):  # (likewise a build from before the set-wide want and held listings: those methods then raise)
+        L.nrq_rxset_want.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, u32p, u32p]
+        L.nrq_rxset_held.argtypes = [vp, vp, vp, C.c_uint32, u32p, u32p]
     if hasattr(L, "nrq_txset_create"):  # (likewise a build from before the sender sets: SenderSet then raises)
         L.nrq_txset_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
         L.nrq_txset_destroy.argtypes = [vp]
@@ -889,6 +892,31 @@ class ReceiverSet(_Handle):
         st, used = np.zeros(n, np.int32), np.zeros(n, np.uint32)
         self.ctx._chk(fn(self._h, st.ctypes.data_as(C.POINTER(C.c_int)), _u32(used)))
         return st, used
+
+    def _listing(self, fn, args, per_block):
+        """a set-wide listing with keys, as _want / _held: the count call, two tensors of that size, the fill call"""
+        import torch
+        n = C.c_uint32(0)
+        cnt = np.zeros(len(self.blocks()[0]), np.uint32)
+        self.ctx._chk(fn(self._h, *args, None, None, 0, _u32(cnt) if per_block else None, C.byref(n)))
+        keys = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        tags = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        if n.value:
+            self.ctx._chk(fn(self._h, *args, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n.value, None, C.byref(n)))
+            self.ctx.sync()  # (torch's stream and the library's are not ordered: the lists are complete on return)
+        return (keys, tags, cnt) if per_block else (keys, tags)
+
+    def want(self, extra=0, source=False, esi_from=0, per_block=False):
+        """(keys, tags): what every member's own want(extra, source, esi_from) lists, one behind the other in block order, and
+        beside each tag the key of its member -- [n] int32 device tensors listed on the device in one pass (three launches, one
+        wait for the whole set), the form SenderSet.emit(keys, tags, ...) takes.  Each member is asked with its own K, max_esi
+        and repair rows.  per_block=True: also the number of tags per block, a uint32 array in blocks() order."""
+        return self._listing(self._fn("nrq_rxset_want"), (WANT_SOURCE if source else 0, extra, esi_from), per_block)
+
+    def held(self, per_block=False):
+        """(keys, tags): what every member's own held() lists, one behind the other in block order, with each tag's key, as
+        want() -- the list SenderSet.emit(keys, tags, held=True) over the members' relays writes in full."""
+        return self._listing(self._fn("nrq_rxset_held"), (), per_block)
 
 
 class SenderSet(_Handle):

@@ -27,6 +27,7 @@ HEMU = os.path.join(ROOT, "tests", "emu", "libheld_emu.so")
 WEMU = os.path.join(ROOT, "tests", "emu", "libwant_emu.so")
 REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
+QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
@@ -176,6 +177,13 @@ def build_rxset_lists_emu(force=False):
                       ("lists_set_body.h", "rxset_plan.h", "ingest_set_body.h", "ingest_body.h"), force)
 
 
+def build_rxset_want_emu(force=False):
+    """tests/emu/librxset_want_emu.so: CPU emulation of a reception set's want and held listings with keys
+    (csrc/rxset_want_emu.cpp over want_set_body.h)."""
+    return _build_emu(QEMU, os.path.join(CSRC, "rxset_want_emu.cpp"),
+                      ("want_set_body.h", "lists_set_body.h", "want_body.h", "held_body.h", "ingest_set_body.h", "ingest_body.h"), force)
+
+
 def build_txset_emu(force=False):
     """tests/emu/libtxset_emu.so: CPU emulation of a sender set's emit (csrc/txset_emu.cpp over emit_set_body.h)."""
     return _build_emu(TEMU, os.path.join(CSRC, "txset_emu.cpp"), ("emit_set_body.h", "emit_body.h", "rq_math.h"), force)
@@ -280,6 +288,7 @@ if __name__ == "__main__":
     build_want_emu(force="-f" in sys.argv)
     build_rxset_emu(force="-f" in sys.argv)
     build_rxset_lists_emu(force="-f" in sys.argv)
+    build_rxset_want_emu(force="-f" in sys.argv)
     build_txset_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)

@@ -39,6 +39,7 @@
 #include "rxset_plan.h"
 #include "held_body.h"
 #include "want_body.h"
+#include "want_set_body.h"
 #include "emit_body.h"
 #include "emit_set_body.h"
 #include "obj_body.h"
@@ -4060,31 +4061,42 @@ int nrq_orx_write(nrq_orx *rx, void *d_out) {
 } /* extern "C" */
 
 /* ================================================ what a reception holds (nrq_rx_held / nrq_orx_held, held_body.h) ==== */
-/* one workgroup per block: seen source ESIs plus repair rows used -> cnt[b] */
-__global__ __launch_bounds__(256) void nrq_held_count_kernel(ing_rx r, uint32_t *cnt) {
-  __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = ing_src_words(&r);
+/* The listing passes as workgroup bodies of (reception, block): nrq_held_*_kernel runs them on its by-value reception and
+ * blockIdx.x, nrq_ings_held_*_kernel on the member and block it finds in a set's table (ps: 256 words of LDS). */
+/* count: seen source ESIs plus repair rows used -> cnt[g] */
+__device__ __forceinline__ void hl_count_wg(const ing_rx *r, uint32_t b, uint32_t *cnt, uint32_t g, uint32_t *ps) {
+  const uint32_t t = threadIdx.x, nw = ing_src_words(r);
   uint32_t n = 0;
-  for (uint32_t w = t; w < nw; w += 256u) n += ing_popc(hl_have(&r, b, w));
+  for (uint32_t w = t; w < nw; w += 256u) n += ing_popc(hl_have(r, b, w));
   n = wg_sum(ps, t, n);
-  if (t == 0) cnt[b] = n + hl_nrep(&r, b);
+  if (t == 0) cnt[g] = n + hl_nrep(r, b);
 }
 
-/* one workgroup per block: its tags to out + off[b] -- the seen source ESIs ascending (256 words per round: a scan over their
- * counts places each word's tags), then the repair ESIs in arrival order */
-__global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint32_t *off, uint32_t *out) {
-  __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, nw = ing_src_words(&r);
-  uint32_t o = off[b];
+/* fill: the block's tags to out[o ..] -- the seen source ESIs ascending (256 words per round: a scan over their counts places
+ * each word's tags), then the repair ESIs in arrival order */
+__device__ __forceinline__ void hl_fill_wg(const ing_rx *r, uint32_t b, uint32_t *out, uint32_t o, uint32_t *ps) {
+  const uint32_t t = threadIdx.x, nw = ing_src_words(r);
   for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
     const uint32_t w = w0 + t;
-    const uint32_t have = w < nw ? hl_have(&r, b, w) : 0u, cnt = ing_popc(have);
-    hl_put(&r, b, w, have, out + o + wg_scan(ps, t, cnt) - cnt);
+    const uint32_t have = w < nw ? hl_have(r, b, w) : 0u, cnt = ing_popc(have);
+    hl_put(r, b, w, have, out + o + wg_scan(ps, t, cnt) - cnt);
     o += ps[255];
     __syncthreads();
   }
-  const uint32_t nrep = hl_nrep(&r, b);
-  for (uint32_t q = t; q < nrep; q += 256u) out[o + q] = hl_rep_tag(&r, b, q);
+  const uint32_t nrep = hl_nrep(r, b);
+  for (uint32_t q = t; q < nrep; q += 256u) out[o + q] = hl_rep_tag(r, b, q);
+}
+
+/* one workgroup per block: seen source ESIs plus repair rows used -> cnt[b] */
+__global__ __launch_bounds__(256) void nrq_held_count_kernel(ing_rx r, uint32_t *cnt) {
+  __shared__ uint32_t ps[256];
+  hl_count_wg(&r, blockIdx.x, cnt, blockIdx.x, ps);
+}
+
+/* one workgroup per block: its tags to out + off[b] */
+__global__ __launch_bounds__(256) void nrq_held_fill_kernel(ing_rx r, const uint32_t *off, uint32_t *out) {
+  __shared__ uint32_t ps[256];
+  hl_fill_wg(&r, blockIdx.x, out, off[blockIdx.x], ps);
 }
 
 /* count and scan, enqueued: the blocks' exclusive offsets and, behind them, the total, in the reception's list buffer.
@@ -4161,34 +4173,45 @@ int nrq_orx_held(nrq_orx *rx, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
 } /* extern "C" */
 
 /* ================================================ what a reception wants (nrq_rx_want / nrq_orx_want, want_body.h) ==== */
-/* one workgroup per block: the tags it lists -> cnt[b].  Rounds of 256 seen words from the word of ESI lo, until `need` wanted
- * ESIs are found or the range ends: in repair mode that is one round unless thousands of symbols are asked for, whatever max_esi */
-__global__ __launch_bounds__(256) void nrq_want_count_kernel(ing_rx r, wn_q q, uint32_t *cnt) {
-  __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, w_end = wn_end(&q), need = wn_need(&r, &q, b);
+/* The listing passes as workgroup bodies of (reception, query, block), as hl_count_wg / hl_fill_wg above. */
+/* count: the tags the block lists -> cnt[g].  Rounds of 256 seen words from the word of ESI lo, until `need` wanted ESIs are found
+ * or the range ends: in repair mode that is one round unless thousands of symbols are asked for, whatever max_esi */
+__device__ __forceinline__ void wn_count_wg(const ing_rx *r, const wn_q *q, uint32_t b, uint32_t *cnt, uint32_t g, uint32_t *ps) {
+  const uint32_t t = threadIdx.x, w_end = wn_end(q), need = wn_need(r, q, b);
   uint32_t found = 0;
-  for (uint32_t w0 = wn_first(&q); w0 < w_end && found < need; w0 += WN_ROUND) { /* (found and need are the same in every thread) */
+  for (uint32_t w0 = wn_first(q); w0 < w_end && found < need; w0 += WN_ROUND) { /* (found and need are the same in every thread) */
     const uint32_t w = w0 + t;
-    found += wg_sum(ps, t, w < w_end ? ing_popc(wn_bits(&r, &q, b, w)) : 0u);
+    found += wg_sum(ps, t, w < w_end ? ing_popc(wn_bits(r, q, b, w)) : 0u);
     __syncthreads();
   }
-  if (t == 0) cnt[b] = min(found, need);
+  if (t == 0) cnt[g] = min(found, need);
 }
 
-/* one workgroup per block: its tags to out + off[b], ascending -- per round a scan over the 256 words' counts gives each word the
- * rank of its first wanted ESI in the block, and the word writes those of rank below `need` */
-__global__ __launch_bounds__(256) void nrq_want_fill_kernel(ing_rx r, wn_q q, const uint32_t *off, uint32_t *out) {
-  __shared__ uint32_t ps[256];
-  const uint32_t b = blockIdx.x, t = threadIdx.x, w_end = wn_end(&q), need = wn_need(&r, &q, b);
-  uint32_t *dst = out + off[b];
+/* fill: the block's tags to out[*off ..], ascending -- per round a scan over the 256 words' counts gives each word the rank of its
+ * first wanted ESI in the block, and the word writes those of rank below `need` */
+__device__ __forceinline__ void wn_fill_wg(const ing_rx *r, const wn_q *q, uint32_t b, uint32_t *out, const uint32_t *off, uint32_t *ps) {
+  const uint32_t t = threadIdx.x, w_end = wn_end(q), need = wn_need(r, q, b);
+  uint32_t *dst = out + *off;
   uint32_t placed = 0;
-  for (uint32_t w0 = wn_first(&q); w0 < w_end && placed < need; w0 += WN_ROUND) {
+  for (uint32_t w0 = wn_first(q); w0 < w_end && placed < need; w0 += WN_ROUND) {
     const uint32_t w = w0 + t;
-    const uint32_t bits = w < w_end ? wn_bits(&r, &q, b, w) : 0u, c = ing_popc(bits);
-    wn_put(&r, b, w, bits, placed + wg_scan(ps, t, c) - c, need, dst);
+    const uint32_t bits = w < w_end ? wn_bits(r, q, b, w) : 0u, c = ing_popc(bits);
+    wn_put(r, b, w, bits, placed + wg_scan(ps, t, c) - c, need, dst);
     placed += ps[255];
     __syncthreads();
   }
+}
+
+/* one workgroup per block: the tags it lists -> cnt[b] */
+__global__ __launch_bounds__(256) void nrq_want_count_kernel(ing_rx r, wn_q q, uint32_t *cnt) {
+  __shared__ uint32_t ps[256];
+  wn_count_wg(&r, &q, blockIdx.x, cnt, blockIdx.x, ps);
+}
+
+/* one workgroup per block: its tags to out + off[b] */
+__global__ __launch_bounds__(256) void nrq_want_fill_kernel(ing_rx r, wn_q q, const uint32_t *off, uint32_t *out) {
+  __shared__ uint32_t ps[256];
+  wn_fill_wg(&r, &q, blockIdx.x, out, off + blockIdx.x, ps);
 }
 
 /* the wanted tags of up to two receptions */
@@ -4671,6 +4694,130 @@ int nrq_rxset_decode(nrq_rxset *set, int *h_status, uint32_t *h_used) {
     if (!rc) HIPCHK(ctx, hipGetLastError());
   }
   return rc;
+}
+
+} /* extern "C" */
+
+/* ================================================ what a set's members want and hold (nrq_rxset_want / _held, want_set_body.h) ==== */
+/* nrq_rx_want and nrq_rx_held over all members of a set at once, with the member's key beside every tag: three launches and one
+ * download for the whole set where the members' own calls make three launches, a download and a wait EACH.  One workgroup per
+ * GLOBAL block finds its member (lss_block: wave-uniform, the table is read through the uniform pointer) and runs the single
+ * form's workgroup body on it -- a want call forms that member's wn_q from the call's three words, since K, max_esi and rep_cap
+ * are the member's own.  The counts and offsets are the first nb + 1 words of the set's list buffer, under rx_list_count's rule. */
+__global__ __launch_bounds__(256) void nrq_ings_want_count_kernel(const ings_tab *__restrict__ t, wns_call c, uint32_t *__restrict__ cnt) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  const wn_q q = wns_query(r, &c);
+  wn_count_wg(r, &q, b, cnt, g, ps);
+  if (threadIdx.x == 0) wns_count_end(t, g, cnt);
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_held_count_kernel(const ings_tab *__restrict__ t, uint32_t *__restrict__ cnt) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  hl_count_wg(r, b, cnt, g, ps);
+  if (threadIdx.x == 0) wns_count_end(t, g, cnt);
+}
+
+/* one workgroup per global block: its tags to tags[off[g] .. off[g + 1]), then its key to the same entries of keys (nullable) --
+ * all 256 threads stride over them, so the key stores are coalesced instead of one beside every scattered tag store.  A block
+ * that lists nothing (complete, or nothing held) is left at once. */
+__global__ __launch_bounds__(256) void nrq_ings_want_fill_kernel(const ings_tab *__restrict__ t, wns_call c, const uint32_t *__restrict__ off,
+                                                                 uint32_t *__restrict__ tags, uint32_t *__restrict__ keys) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x, lo = off[g], hi = off[g + 1u];
+  if (lo == hi) return; /* (the same in every thread) */
+  uint32_t b, key;
+  const ing_rx *r = wns_block(t, g, &b, &key);
+  const wn_q q = wns_query(r, &c);
+  wn_fill_wg(r, &q, b, tags, off + g, ps);
+  if (keys) wns_put_keys(keys, lo, hi, key, threadIdx.x, 256u);
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_held_fill_kernel(const ings_tab *__restrict__ t, const uint32_t *__restrict__ off,
+                                                                 uint32_t *__restrict__ tags, uint32_t *__restrict__ keys) {
+  __shared__ uint32_t ps[256];
+  const uint32_t g = blockIdx.x, lo = off[g], hi = off[g + 1u];
+  if (lo == hi) return;
+  uint32_t b, key;
+  const ing_rx *r = wns_block(t, g, &b, &key);
+  hl_fill_wg(r, b, tags, lo, ps);
+  if (keys) wns_put_keys(keys, lo, hi, key, threadIdx.x, 256u);
+}
+
+/* a listing (`what`: "held", "wanted") of all members with keys, shaped like rx_list: `count(cnt)` launches the kernel that
+ * writes a count per global block and 0 behind them, ONE scan, ONE download (the nb + 1 offsets when the per-block counts are
+ * asked for, else the total alone) and wait, then `fill(off)` launches the kernel that writes tags and keys */
+template <class Count, class Fill>
+static int rxset_list(nrq_rxset *set, const char *who, const char *what, uint32_t *d_tags, uint32_t cap, uint32_t *h_cnt, uint32_t *h_n,
+                      Count count, Fill fill) {
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t *off = (uint32_t *)set->lists;
+  count(off);
+  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, nb + 1u, off);
+  HIPCHK(ctx, hipGetLastError());
+  std::vector<uint32_t> h(h_cnt ? (size_t)nb + 1u : 1u, 0);
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), h_cnt ? off : off + nb, h.size() * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *h_n = h.back();
+  if (h_cnt)
+    for (uint32_t g = 0; g < nb; g++) h_cnt[g] = h[g + 1u] - h[g];
+  if (!d_tags) return 0;
+  if (cap < *h_n) return fail(ctx, -1, "%s: %u symbols are %s, d_tags has room for %u", who, *h_n, what, cap);
+  if (*h_n == 0) return 0;
+  fill((const uint32_t *)off);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rxset_want(nrq_rxset *set, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_keys, uint32_t *d_tags, uint32_t cap,
+                   uint32_t *h_cnt, uint32_t *h_n) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_rxset_want";
+  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
+  *h_n = 0;
+  switch (wn_check(flags, extra, esi_from)) {
+    case 1: return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+    case 2: return fail(ctx, -1, "%s: NRQ_WANT_SOURCE takes neither extra nor esi_from (%u, %u)", who, extra, esi_from);
+    case 3: return fail(ctx, -1, "%s: extra %u is above 2^24", who, extra);
+    default: break;
+  }
+  if (d_keys && !d_tags) return fail(ctx, -1, "%s: d_keys without d_tags", who);
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  const ings_tab *t = (const ings_tab *)set->tab;
+  const wns_call c{flags, extra, esi_from};
+  hipStream_t st = ctx->stream;
+  return rxset_list(
+      set, who, "wanted", d_tags, cap, h_cnt, h_n,
+      [&](uint32_t *cnt) { hipLaunchKernelGGL(nrq_ings_want_count_kernel, dim3(nb), dim3(256), 0, st, t, c, cnt); },
+      [&](const uint32_t *off) { hipLaunchKernelGGL(nrq_ings_want_fill_kernel, dim3(nb), dim3(256), 0, st, t, c, off, d_tags, d_keys); });
+}
+
+int nrq_rxset_held(nrq_rxset *set, uint32_t *d_keys, uint32_t *d_tags, uint32_t cap, uint32_t *h_cnt, uint32_t *h_n) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_rxset_held";
+  if (!h_n) return fail(ctx, -1, "%s: h_n is NULL", who);
+  *h_n = 0;
+  if (d_keys && !d_tags) return fail(ctx, -1, "%s: d_keys without d_tags", who);
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  const ings_tab *t = (const ings_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  return rxset_list(
+      set, who, "held", d_tags, cap, h_cnt, h_n,
+      [&](uint32_t *cnt) { hipLaunchKernelGGL(nrq_ings_held_count_kernel, dim3(nb), dim3(256), 0, st, t, cnt); },
+      [&](const uint32_t *off) { hipLaunchKernelGGL(nrq_ings_held_fill_kernel, dim3(nb), dim3(256), 0, st, t, off, d_tags, d_keys); });
 }
 
 } /* extern "C" */
