@@ -30,6 +30,8 @@ def _stride(kind, T, inline):
     (100, 16, 2, 1, 1000),       # an object's larger K' (block 0's row coded into a short block)
     (1000, 20, 2, 254, None),    # SBNs up to 255, T a multiple of 4 but not of 16
     (300, 48, 3, 0, None),
+    (100, 1040, 2, 0, None),     # the sizes at which the device's 16-byte and 4-byte lane forms go into a second round of the wave
+    (100, 260, 2, 0, None),
 ])
 @pytest.mark.parametrize("inline", [False, True])
 @pytest.mark.parametrize("stride_kind", ["tight", "pad4", "r16", "odd"])

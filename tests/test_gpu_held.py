@@ -12,9 +12,9 @@ import pytest
 
 import nanorq_amd
 from nanorq_amd import EXT_PER_BLOCK_KP, EXT_SUBBLOCKS, TX_NOT_READY, NrqError
-from held_support import host_held
-from rx_support import ADDED, DUP, FULL, ModelRx, payloads_for
-from tx_support import FILL, range_tags, tag
+from held_support import emu_emit_held, host_held
+from rx_support import ADDED, DUP, FULL, EmuRx, ModelRx, payloads_for
+from tx_support import FILL, emit_mode, params_L, range_tags, tag
 from util import payload
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +139,54 @@ def test_partial_blocks(ctx, torch, orc, K, nblk, inline):
                     if inl:
                         hd = pk2[_dev(torch, got[some])][:, :4].cpu().numpy()
                         assert np.array_equal(hd, tags[some][got[some]].astype(">u4").view(np.uint8).reshape(-1, 4))
+
+
+def test_second_round_of_the_shifted_form_matches_emulation(ctx, torch):
+    """nrq_emit_held_kernel<TX_V16_SHIFT, false> at T = 1040 (65 chunks of 16 bytes: a second round of the wave with one live lane,
+    whose left neighbour is the carry of lane 63) against the emulated held emit, whole buffer and guard rows: a reception and
+    its emulation fed the same lossy stream, block 0 complete and made ready by the relay's encode, so ready packets (gathers
+    over the intermediate symbols), held source and repair rows (copies), symbols not held and foreign SBNs are all asked for"""
+    K, T, nblk, sbn0, cap = 30, 1040, 3, 2, 8
+    Kp = nanorq_amd.params(K)["Kp"]
+    L = params_L(Kp)
+    rng = np.random.default_rng(1040)
+    emu = EmuRx(K, T, nblk, cap, sbn0=sbn0, Kp=Kp)
+    sent = np.array([tag(sbn0 + b, e) for b in range(nblk) for e in range(K + K // 4 + 4)], np.uint32)
+    keep = (rng.random(len(sent)) >= 0.25) | ((sent >> 24) == sbn0)  # (block 0 loses nothing)
+    deliv = sent[keep]
+    rng.shuffle(deliv)
+    with nanorq_amd.Receiver(ctx, K, T, nblk, cap, sbn0=sbn0) as rx, rx.relay() as relay:
+        for part in np.array_split(deliv, 2):
+            pl = payloads_for(part, T, 3)
+            _add(ctx, torch, rx, _dev(torch, pl), tags=part)
+            emu.add(pl, tags=part)
+        relay.encode()
+        ctx.sync()
+        ready = relay.ready()
+        assert ready[0] and not ready[1:].any()
+        inter = ctx.download(relay.inter_ptr, nblk * L * T).reshape(nblk, L, T)
+        extra = [tag(s, e) for s in range(sbn0 - 1, sbn0 + nblk + 1) for e in (emu.max_esi, emu.max_esi + 1, (1 << 24) - 1, K + 60)]
+        ask = np.concatenate([sent, np.array(extra, np.uint32)])
+        rng.shuffle(ask)
+        n, stride = len(ask), T + 16
+        buf = torch.full((n + 2, stride), FILL, dtype=torch.uint8, device="cuda")
+        out = buf[1:n + 1]
+        rows = [(rx.src_ptr, K * T), (relay.inter_ptr, L * T), (rx.rep_ptr, cap * T)]
+        assert emit_mode(out.data_ptr(), stride, T, 4, rows) == "TX_V16_SHIFT"
+        res = torch.full((n,), 77, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        relay.emit(_tags_dev(torch, ask), out=out, inline=True, results=res, held=True)
+        ctx.sync()
+        epk, eres = emu_emit_held([emu], [Kp], [inter], (sbn0, nblk, nblk), ready, ask, True, stride)
+        res = res.cpu().numpy()
+        assert np.array_equal(res, eres), np.flatnonzero(res != eres)[:10]
+        got = buf.cpu().numpy()
+        assert (got[0] == FILL).all() and (got[-1] == FILL).all(), "guard rows"
+        assert np.array_equal(got[1:-1], epk), np.flatnonzero((got[1:-1] != epk).any(axis=1))[:10]
+        blk, esi = (ask >> 24).astype(int) - sbn0, ask & 0xFFFFFF
+        cold = (blk >= 1) & (blk < nblk)
+        assert (res[(blk == 0) & (esi >= K)] == 0).any() and (res[cold & (esi < K)] == 0).any() and (res[cold & (esi >= K)] == 0).any()
+        assert (res[cold] == TX_NOT_READY).any() and (res == -1).any()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. codes ----
@@ -414,6 +462,46 @@ OBJ_CASES = [
     (213, 64, 5, 1, 8, EXT_PER_BLOCK_KP),
     (213, 100, 5, 1, 4, 0),   # dword rows
 ]
+
+
+@pytest.mark.parametrize("inline,slack,mode", [(False, 0, "TX_V16"), (True, 12, "TX_V16_SHIFT"), (True, 0, "TX_DWORD"), (False, 3, "TX_BYTE")])
+def test_object_held_emit_modes(ctx, torch, inline, slack, mode):
+    """nrq_emit_held_kernel<MODE, true> (an object relay's table of several segments: two block classes) in each of its four
+    modes, picked by the packet stride and the header, against the object's own packets: what the reception holds comes back
+    byte for byte, what it does not hold stays untouched.  The row images are the library's own allocations, so the mode
+    assertion covers what the test hands over: the buffer, its stride and T."""
+    Kt, T, Z, nrep = 213, 64, 5, 8
+    data = payload(Kt * T - 37, seed=Kt + int(inline) + slack)
+    rng = np.random.default_rng(slack + int(inline))
+    with nanorq_amd.ObjectSender(ctx, _dev(torch, data), T, Z=Z) as tx:
+        assert tx.params.ZL and tx.params.ZS
+        tx.encode()
+        n = tx.count_all(nrep)
+        t_o = torch.zeros(n, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        sent = tx.emit_all(nrep, inline=True, tags_out=t_o)
+        ctx.sync()
+        tags = t_o.cpu().numpy().view(np.uint32)
+        oti = tx.oti
+    got = rng.random(n) >= 0.3
+    got[(tags & 0xFFFFFF) == 0] = False  # (no block is complete)
+    with nanorq_amd.ObjectReceiver(ctx, *oti, rep_cap=nrep) as rx, rx.relay() as relay:
+        assert (_add(ctx, torch, rx, sent[_dev(torch, np.flatnonzero(got))].contiguous(), inline=True) == ADDED).all()
+        assert not relay.ready().any()
+        ask = np.concatenate([tags, [tag(Z, 0), tag(255, 3)]]).astype(np.uint32)
+        off = 4 if inline else 0
+        stride = T + off + slack
+        pk, res = _emit(ctx, torch, relay, ask, T, inline=inline, slack=slack)
+        assert emit_mode(pk.data_ptr(), stride, T, off) == mode
+        assert list(res[n:]) == [-1, -1] and bool((pk[n:] == FILL).all())
+        pk, res = pk[:n].cpu().numpy(), res[:n]
+        assert np.array_equal(res == 0, got) and (res[~got] == TX_NOT_READY).all()
+        sent_h = sent.cpu().numpy()
+        assert ((tags[got] & 0xFFFFFF) >= 43).any()  # (held repair rows among them: K is 43 and 42)
+        assert np.array_equal(pk[got, off:off + T], sent_h[got, 4:4 + T]), "a held packet differs from the origin's"
+        if inline:
+            assert np.array_equal(pk[got, :4], sent_h[got, :4])
+        assert (pk[got, off + T:] == FILL).all() and (pk[~got] == FILL).all()
 
 
 @pytest.mark.parametrize("case", OBJ_CASES)

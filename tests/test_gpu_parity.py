@@ -916,3 +916,93 @@ def test_rows_by_address_pair(G):
         for d in (d_rows, d_pairs, d_back):
             c.free(d)
         L.nanorq_pinned_free(C.c_void_p(hp))
+
+
+# ------------------------------------------------------------------------------------------------- the three small movers ----
+MOVER_FILL = 0xA5
+
+
+def _filled(c, nbytes):
+    d = c.alloc(nbytes)
+    c.memset(d, MOVER_FILL, nbytes)
+    return d
+
+
+# (T, byte offset of the output): nrq_gen_kernel has 256 lanes of 16 bytes -- T = 4096 is exactly one trip of its loop, 4112 a second
+# trip of one lane; the byte path is taken for T = 20 and 257 (T) and for an output 4 bytes off a 16-byte boundary (alignment)
+@pytest.mark.parametrize("T,off,vec", [(4096, 0, True), (4112, 0, True), (20, 0, False), (257, 0, False), (48, 4, False)])
+def test_gen_symbols_trips_and_byte_path(G, orc, T, off, vec):
+    """nrq_gen_symbols at K = 10 into a prefilled buffer, the whole buffer compared: source rows (ISI < K) and the oracle's repair
+    symbols where rows were asked for, the fill byte in the guard rows before and after them"""
+    K, nblk = 10, 2
+    p = orc.params(K)
+    L, Kp = p["L"], p["Kp"]
+    src = np.stack([payload(K * T, seed=T, block=b).reshape(K, T) for b in range(nblk)])
+    c = G.ctx()
+    isis = np.array([0, 5, K - 1, Kp, Kp + 7, Kp + 100000], np.uint32)
+    n = len(isis)
+    total = T + off + nblk * n * T + T
+    d_src, d_int, d_buf = c.alloc(nblk * K * T), c.alloc(nblk * L * T), _filled(c, total)
+    d_out = d_buf + T + off
+    assert vec == ((T | d_int | (L * T) | d_out | (n * T)) % 16 == 0)  # (the kernel's own rule: the path this case is listed for)
+    c.upload(d_src, src)
+    c.encode_blocks(K, T, nblk, d_src, K * T, 0, 0, [], d_int, L * T)
+    c.gen_symbols(K, T, nblk, d_int, L * T, isis, d_out, n * T)
+    c.sync()
+    got = c.download(d_buf, total)
+    want = np.full(total, MOVER_FILL, np.uint8)
+    rows = want[T + off:T + off + nblk * n * T].reshape(nblk, n, T)
+    for b in range(nblk):
+        rows[b, :3] = src[b, [0, 5, K - 1]]  # systematic
+        rows[b, 3:] = orc.encode_block(src[b], K, T, isis[3:] - (Kp - K))[0]
+    bad = np.flatnonzero(got != want)
+    assert len(bad) == 0, bad[:8]
+    for d in (d_src, d_int, d_buf):
+        c.free(d)
+
+
+# (T, byte offset of the destinations): 128 lanes of 16 bytes -- T = 2048 is exactly one trip, 2064 a second trip of one lane; the
+# byte path for T = 127 and 129 (T) and for destinations off a 16-byte boundary (alignment)
+@pytest.mark.parametrize("T,off,vec", [(2048, 0, True), (2064, 0, True), (127, 0, False), (129, 0, False), (64, 1, False)])
+def test_scatter_and_move_rows_trips_and_byte_path(G, T, off, vec):
+    """nrq_scatter_symbols_dev (row k of a packed buffer to the address dst[k]) and nrq_move_rows_dev (address pairs) into scattered
+    slots of a prefilled buffer with guard rows, a zero destination skipped: the whole buffer against numpy"""
+    import ctypes as C
+    c = G.ctx()
+    L = nanorq_amd.lib()
+    L.nrq_scatter_symbols_dev.restype = C.c_int
+    L.nrq_scatter_symbols_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.nrq_move_rows_dev.restype = C.c_int
+    L.nrq_move_rows_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]
+    n, slots, skipped = 37, 48, 5
+    rows = payload(n * T, seed=T + off).reshape(n, T).copy()
+    place = np.random.default_rng(T).permutation(slots)[:n]
+    total = T + off + slots * T + T
+    d_rows, d_list = c.alloc(n * T), c.alloc(2 * n * 8)
+    c.upload(d_rows, rows)
+    want = np.full(total, MOVER_FILL, np.uint8)
+    table = want[T + off:T + off + slots * T].reshape(slots, T)
+    for k in range(n):
+        if k != skipped:
+            table[place[k]] = rows[k]
+    for mover in ("scatter", "move"):
+        d_buf = _filled(c, total)
+        dst = (d_buf + T + off + place.astype(np.uint64) * np.uint64(T)).astype(np.uint64)
+        assert vec == (T % 16 == 0 and (d_rows | d_buf + T + off) % 16 == 0)  # (the kernels' own rule, for every row)
+        dst[skipped] = 0
+        if mover == "scatter":
+            c.upload(d_list, dst.view(np.uint8))
+            assert L.nrq_scatter_symbols_dev(c._h, 0, C.c_void_p(d_rows), n, T, C.c_void_p(d_list)) == 0
+        else:
+            pairs = np.zeros(2 * n, np.uint64)
+            pairs[0::2] = d_rows + np.arange(n, dtype=np.uint64) * np.uint64(T)
+            pairs[1::2] = dst
+            c.upload(d_list, pairs.view(np.uint8))
+            assert L.nrq_move_rows_dev(c._h, 0, C.c_void_p(d_list), n, T) == 0
+        c.sync()
+        got = c.download(d_buf, total)
+        bad = np.flatnonzero(got != want)
+        assert len(bad) == 0, (mover, bad[:8])
+        c.free(d_buf)
+    for d in (d_rows, d_list):
+        c.free(d)

@@ -1,5 +1,6 @@
 """GPU tier of the device-resident receiver (nrq_rx_*, nanorq_amd.Receiver): the ingest kernels against their CPU emulation,
-byte for byte; round trips from packets built on the device to recovered blocks, against the object layer
+byte for byte (the row tables prefilled and between guard rows, compared whole; nrq_ing_copy_kernel's three forms also at the
+symbol sizes that fill a trip of its loop and start the next, each case asserting the form from the addresses it hands over); round trips from packets built on the device to recovered blocks, against the object layer
 (nanorq_decoder_add_symbols + nanorq_repair_all) on the same packets in the same order and against the oracle."""
 import ctypes as C
 
@@ -9,6 +10,7 @@ import pytest
 import nanorq_amd
 from capi import api, mem_io
 from rx_support import UNTOUCHED, EmuRx, inline_packets, payloads_for, random_stream
+from tx_support import FILL, copy_forms
 
 pytestmark = pytest.mark.gpu
 
@@ -46,23 +48,45 @@ def _state(rx, torch, K, T, nblk, rep_cap, src_t, rep_t):
     (8200, 16, 2, 0, 40, 20000),          # 257 seen words per block: the list fill's second round (one live lane, the offset carried over)
 ])
 def test_device_ingest_matches_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, n, inline):
+    _ingest_against_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, n, inline,
+                              lambda call: T + 4 + 8 * call if inline else T + 16 * call)
+
+
+def _guarded_rows(torch, nblk, rows, T):
+    """[nblk, rows, T] row tables prefilled with FILL, a slice of one tensor with a guard row of FILL before and after it ->
+    (the whole tensor, the table)"""
+    whole = torch.full((nblk * rows + 2, T), FILL, dtype=torch.uint8, device="cuda")
+    return whole, whole[1:-1].view(nblk, rows, T)
+
+
+def _ingest_against_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, n, inline, stride_of, forms=None):
+    """two Receiver.add calls of a messy stream against the emulated ingest: codes, lists, and the source and repair tables whole,
+    rows no packet landed in and the guard rows around the tables included.  forms: the forms of nrq_ing_copy_kernel the packets
+    must take, by its rule on the addresses handed over (tx_support.copy_forms)"""
     Kp = nanorq_amd.params(K)["Kp"]
     rng = np.random.default_rng(n + T)
     emu = EmuRx(K, T, nblk, rep_cap, sbn0, Kp=Kp)
-    src_t = torch.zeros((nblk, K, T), dtype=torch.uint8, device="cuda")
-    rep_t = torch.zeros((nblk, rep_cap, T), dtype=torch.uint8, device="cuda")
+    emu.src[:] = FILL
+    emu.rep[:] = FILL
+    src_w, src_t = _guarded_rows(torch, nblk, K, T)
+    rep_w, rep_t = _guarded_rows(torch, nblk, rep_cap, T)
     with nanorq_amd.Receiver(ctx, K, T, nblk, rep_cap, sbn0=sbn0, src=src_t, src_stride=K * T, rep=rep_t, rep_stride=rep_cap * T) as rx:
         for call in range(2):
             tags = random_stream(rng, K, nblk, sbn0, 2 * Kp, n, sbn_span=2)
             pl = payloads_for(tags, T, salt=call)
+            stride = stride_of(call)
             if inline:
-                pk = inline_packets(pl, tags, T + 4 + 8 * call)
+                pk = inline_packets(pl, tags, stride)
             else:
-                pk = np.concatenate([pl, np.zeros((len(tags), 16 * call), np.uint8)], axis=1)
+                pk = np.concatenate([pl, np.zeros((len(tags), stride - T), np.uint8)], axis=1)
             res_d = torch.full((len(tags),), UNTOUCHED, dtype=torch.int32, device="cuda")
             pk_d = _dev(torch, pk)
+            if forms is not None:
+                assert copy_forms(pk_d.data_ptr(), stride, 4 if inline else 0, len(tags), T, [src_t.data_ptr(), rep_t.data_ptr()]) == forms
             tg_d = None if inline else _dev(torch, tags.view(np.int32))
+            torch.cuda.synchronize()
             rx.add(pk_d, tags=tg_d, inline=inline, results=res_d)
+            ctx.sync()
             r_emu = emu.add(pk, None if inline else tags)
             if K > 8192:  # (the second round has ESIs to place, behind those of the first)
                 assert all(emu.lost(b).min() < 32 and emu.lost(b).max() >= 8192 for b in range(nblk))
@@ -72,6 +96,33 @@ def test_device_ingest_matches_emulation(ctx, torch, K, T, nblk, sbn0, rep_cap, 
             for b in range(nblk):
                 assert np.array_equal(lost[b], emu.lost(b)) and np.array_equal(reps[b], emu.rep_list(b)), b
             assert np.array_equal(s, emu.src) and np.array_equal(r, emu.rep)
+            for w in (src_w, rep_w):
+                assert bool((w[0] == FILL).all()) and bool((w[-1] == FILL).all()), "guard rows"
+    return emu
+
+
+# the sizes at which a form of nrq_ing_copy_kernel fills a trip of its loop or starts the next (64 lanes, two accesses in flight:
+# 16-byte form 1024 + 1024 bytes a trip, dword form 256 + 256, byte form 64): (T, inline, stride, forms)
+COPY_EDGES = [
+    (1024, False, 1040, {"v16"}),   # no lane has a second access
+    (1040, False, 1056, {"v16"}),   # lane 0 alone has one
+    (2048, False, 2064, {"v16"}),   # every lane has one: one whole trip
+    (2064, False, 2080, {"v16"}),   # a second trip
+    (256, True, 272, {"dword"}),    # behind the 4-byte header (the payload at 4 mod 16): no second access
+    (260, True, 264, {"dword"}),    # lane 0 alone
+    (512, True, 528, {"dword"}),    # one whole trip
+    (516, True, 520, {"dword"}),    # a second trip
+    (63, False, 63, {"byte"}),      # 63 lanes
+    (65, True, 69, {"byte"}),       # a second trip
+    (64, False, 67, {"byte", "dword", "v16"}),  # an odd stride: three packets in four by bytes, exactly one trip; the others land on
+                                                # a 4- or 16-byte boundary and take that form (the kernel decides packet by packet)
+]
+
+
+@pytest.mark.parametrize("T,inline,stride,forms", COPY_EDGES, ids=["%d-%s-%d" % c[:3] for c in COPY_EDGES])
+def test_device_ingest_copy_at_trip_edges(ctx, torch, T, inline, stride, forms):
+    emu = _ingest_against_emulation(ctx, torch, 100, T, 2, 1, 20, 300, inline, lambda call: stride, forms=forms)
+    assert (emu.nrep > 0).all() and (emu.gaps < 100).all()  # (source and repair rows were written in every block)
 
 
 def _packets_on_device(torch, ctx, K, T, nblk, loss, seed, dup=0.03, late=0.01):

@@ -1,5 +1,6 @@
 """GPU tier of the reception sets (nrq_rxset_*, nanorq_amd.ReceiverSet): the set's ingest kernels against their CPU emulation
-(nanorq_amd/csrc/rxset_emu.cpp) byte for byte, against fresh Receivers fed the packets of their key through Receiver.add, whole
+(nanorq_amd/csrc/rxset_emu.cpp) byte for byte (the members' row tables prefilled and between guard rows, compared whole; the copy
+kernel's 16-byte, 4-byte and byte forms also at the symbol sizes that fill a trip of its loop and start the next), against fresh Receivers fed the packets of their key through Receiver.add, whole
 objects through one set call and back, the want -> emit -> add -> decode loop of two objects through a set, the API's refusals,
 lifetimes, and a failed scratch allocation."""
 import ctypes as C
@@ -11,6 +12,7 @@ import nanorq_amd
 from nanorq_amd import EXT_SUBBLOCKS, NrqError
 from rx_support import ADDED, ERR, FULL, IGN
 from rxset_support import MIX4, MIX360, UNKNOWN_KEY, UNTOUCHED, EmuRx, EmuSet, keyed_payloads, keyed_stream, packets, rep_cap_of, tag
+from tx_support import FILL, copy_forms
 from util import payload
 
 pytestmark = pytest.mark.gpu
@@ -41,17 +43,28 @@ def _kps(mix):
     return [nanorq_amd.params(m[1])["Kp"] for m in mix]
 
 
+def _guarded_rows(torch, nblk, rows, T):
+    """[nblk, rows, T] row tables prefilled with FILL, a slice of one tensor with a guard row of FILL before and after it ->
+    (the whole tensor, the table)"""
+    whole = torch.full((nblk * rows + 2, T), FILL, dtype=torch.uint8, device="cuda")
+    return whole, whole[1:-1].view(nblk, rows, T)
+
+
 class _Members:
-    """the receivers of a mix on the device, each over torch tensors for its rows, attached to one set"""
+    """the receivers of a mix on the device, each over torch tensors for its rows (prefilled with FILL, between guard rows),
+    attached to one set"""
 
     def __init__(self, ctx, torch, mix, T, small_cap, attach=True):
         self.ctx, self.mix, self.T = ctx, mix, T
         self.set = nanorq_amd.ReceiverSet(ctx, T) if attach else None
-        self.rx, self.src, self.rep = [], [], []
+        self.rx, self.src, self.rep, self.whole = [], [], [], []
         for key, K, nblk, sbn0 in mix:
             cap = rep_cap_of(K, small_cap)
-            self.src.append(torch.zeros((nblk, K, T), dtype=torch.uint8, device="cuda"))
-            self.rep.append(torch.zeros((nblk, cap, T), dtype=torch.uint8, device="cuda"))
+            for table, rows in ((self.src, K), (self.rep, cap)):
+                w, t = _guarded_rows(torch, nblk, rows, T)
+                self.whole.append(w)
+                table.append(t)
+            torch.cuda.synchronize()
             self.rx.append(nanorq_amd.Receiver(ctx, K, T, nblk, cap, sbn0=sbn0, src=self.src[-1], src_stride=K * T, rep=self.rep[-1],
                                                rep_stride=cap * T))
             if attach:
@@ -70,19 +83,26 @@ class _Members:
         assert list(nl) == [len(x) for x in lost] and list(nr) == [len(x) for x in reps]
         return lost, reps, self.src[i].cpu().numpy(), self.rep[i].cpu().numpy()
 
+    def guards_whole(self):
+        return all(bool((w[0] == FILL).all()) and bool((w[-1] == FILL).all()) for w in self.whole)
+
 
 def _emu_members(mix, T, small_cap):
     st, mem = EmuSet(), []
     for (key, K, nblk, sbn0), Kp in zip(mix, _kps(mix)):
         mem.append(EmuRx(K, T, nblk, rep_cap_of(K, small_cap), sbn0, Kp=Kp))
+        mem[-1].src[:] = FILL  # (as the device tables: a row no packet landed in keeps it)
+        mem[-1].rep[:] = FILL
         st.attach(key, mem[-1])
     return st, mem
 
 
-def _set_add(torch, ctx, st, pk, keys, tags, inl, kinl):
-    """one ReceiverSet.add of host-built packets -> the result codes (numpy)"""
+def _set_add(torch, ctx, st, pk, keys, tags, inl, kinl, check=None):
+    """one ReceiverSet.add of host-built packets -> the result codes (numpy); check: called with the packets' device address"""
     res = torch.full((pk.shape[0],), UNTOUCHED, dtype=torch.int32, device="cuda")
     pk_d = _dev(torch, pk)
+    if check is not None:
+        check(pk_d.data_ptr())
     k_d = None if keys is None else _i32(torch, keys)
     t_d = None if tags is None else _i32(torch, tags)
     torch.cuda.synchronize()
@@ -91,7 +111,10 @@ def _set_add(torch, ctx, st, pk, keys, tags, inl, kinl):
     return res.cpu().numpy()
 
 
-def _against_emulation(ctx, torch, mix, T, n, carrier, small_cap, calls=2):
+def _against_emulation(ctx, torch, mix, T, n, carrier, small_cap, calls=2, stride_extra=None, forms=None):
+    """ReceiverSet.add calls of a keyed stream against the emulated set ingest: codes, lists, every member's source and repair
+    tables whole and the guard rows around them.  stride_extra: bytes behind the packet (default: 16 or 4 times the call's number);
+    forms: the forms of nrq_ing_copy_kernel the packets must take, by its rule on the addresses handed over"""
     rng = np.random.default_rng(n * 31 + T)
     kps = _kps(mix)
     dev = _Members(ctx, torch, mix, T, small_cap)
@@ -103,8 +126,15 @@ def _against_emulation(ctx, torch, mix, T, n, carrier, small_cap, calls=2):
             if carrier == "nokeys":
                 keys = np.zeros_like(keys)
             pl = keyed_payloads(keys, tags, T)
-            pk, k_arg, t_arg, inl, kinl = packets(pl, keys, tags, carrier, stride_extra=(16 if carrier == "arrays" else 4) * call)
-            r_dev = _set_add(torch, ctx, dev.set, pk, k_arg, t_arg, inl, kinl)
+            extra = (16 if carrier == "arrays" else 4) * call if stride_extra is None else stride_extra
+            pk, k_arg, t_arg, inl, kinl = packets(pl, keys, tags, carrier, stride_extra=extra)
+            check = None
+            if forms is not None:
+                tables = [t.data_ptr() for t in dev.src + dev.rep]
+
+                def check(ptr):
+                    assert copy_forms(ptr, pk.shape[1], 8 if kinl else 4 if inl else 0, len(pk), T, tables) == forms
+            r_dev = _set_add(torch, ctx, dev.set, pk, k_arg, t_arg, inl, kinl, check)
             r_emu = emu.add(pk, k_arg, t_arg, kinl)
             assert np.array_equal(r_dev, r_emu), np.flatnonzero(r_dev != r_emu)[:10]
             codes |= set(np.unique(r_dev).tolist())
@@ -113,6 +143,7 @@ def _against_emulation(ctx, torch, mix, T, n, carrier, small_cap, calls=2):
                 for b in range(e.nblk):
                     assert np.array_equal(lost[b], e.lost(b)) and np.array_equal(reps[b], e.rep_list(b)), (i, b)
                 assert np.array_equal(s, e.src) and np.array_equal(r, e.rep), i
+            assert dev.guards_whole(), "guard rows"
     finally:
         dev.close()
     return codes
@@ -126,6 +157,23 @@ CARRIERS = ("arrays", "nokeys", "inline", "keyinline")
 def test_device_matches_emulation(ctx, torch, T, n, carrier):
     """the four-member mix at T = 16, 36 and 13 (the 16-byte, 4-byte and byte copy paths), every carrier of keys and tags"""
     _against_emulation(ctx, torch, MIX4, T, n, carrier, small_cap=n == 257)
+
+
+# the sizes at which a form of nrq_ing_copy_kernel fills a trip of its loop or starts the next (64 lanes, two accesses in flight:
+# 16-byte form 1024 + 1024 bytes a trip, dword form 256 + 256, byte form 64): (T, carrier, bytes behind the packet, forms)
+COPY_EDGES = [(T, "arrays", 16, {"v16"}) for T in (1024, 1040, 2048, 2064)]                  # tags beside rows of a 16-byte stride
+COPY_EDGES += [(T, "inline", (12 - T) % 16, {"dword"}) for T in (256, 260, 512, 516)]        # the payload at 4 (mod 16)
+COPY_EDGES += [(T, "keyinline", (8 - T) % 16, {"dword"}) for T in (256, 260, 512, 516)]      # the payload at 8 (mod 16)
+COPY_EDGES += [(63, "arrays", 0, {"byte"}), (65, "keyinline", 0, {"byte"}),
+               (64, "arrays", 3, {"byte", "dword", "v16"})]  # an odd stride: three packets in four by bytes, exactly one trip; the
+#                                                              others land on a 4- or 16-byte boundary and take that form
+
+
+@pytest.mark.parametrize("T,carrier,extra,forms", COPY_EDGES, ids=["%d-%s" % c[:2] for c in COPY_EDGES])
+def test_device_copy_at_trip_edges(ctx, torch, T, carrier, extra, forms):
+    """one add of about 300 packets over the four-member mix at each edge size of the copy kernel's three forms"""
+    codes = _against_emulation(ctx, torch, MIX4, T, 300, carrier, small_cap=False, calls=1, stride_extra=extra, forms=forms)
+    assert ADDED in codes
 
 
 def test_device_matches_emulation_360_blocks(ctx, torch):

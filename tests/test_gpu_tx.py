@@ -9,7 +9,7 @@ import pytest
 
 import nanorq_amd
 from capi import api, mem_io
-from tx_support import FILL, check_packets, emu_emit, emu_emit_range, oracle_blocks, random_tags, range_tags
+from tx_support import FILL, check_packets, emit_mode, emu_emit, emu_emit_range, oracle_blocks, params_L, random_tags, range_tags
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +42,25 @@ def _stride(kind, T, inline):
     return {"tight": need, "pad4": need + 4, "r16": (need + 15) // 16 * 16, "odd": need + 3 if need % 2 == 0 else need + 2}[kind]
 
 
+def _guarded(torch, n, stride):
+    """n packet rows prefilled with FILL between two guard rows of one tensor -> (the whole tensor, the rows)"""
+    buf = torch.full((n + 2, stride), FILL, dtype=torch.uint8, device="cuda")
+    return buf, buf[1:n + 1]
+
+
+def _guards_whole(buf):
+    return bool((buf[0] == FILL).all()) and bool((buf[-1] == FILL).all())
+
+
+# the instance nrq_emit_kernel<MODE, false> each case below is listed for, by (T, stride kind, inline)
+MODES = {(48, "tight", False): "TX_V16", (48, "r16", True): "TX_V16_SHIFT", (1280, "r16", True): "TX_V16_SHIFT",
+         (1280, "pad4", True): "TX_DWORD", (16, "r16", True): "TX_V16_SHIFT", (20, "tight", False): "TX_DWORD",
+         (13, "tight", True): "TX_BYTE", (48, "odd", False): "TX_BYTE",
+         (1024, "r16", True): "TX_V16_SHIFT", (1040, "r16", True): "TX_V16_SHIFT", (1024, "tight", False): "TX_V16",
+         (2064, "tight", False): "TX_V16", (256, "pad4", True): "TX_DWORD", (260, "tight", False): "TX_DWORD",
+         (65, "tight", False): "TX_BYTE", (64, "odd", False): "TX_BYTE"}
+
+
 # (T, stride kind, inline): the 16-byte path (tag mode and under an inline header), the 4-byte path, the byte path
 @pytest.mark.parametrize("K,T,nblk,sbn0,kp_of,stride_kind,inline", [
     (100, 48, 3, 5, None, "tight", False),   # 16-byte
@@ -52,6 +71,15 @@ def _stride(kind, T, inline):
     (100, 20, 4, 254 - 3, None, "tight", False),  # 4-byte, T not a multiple of 16, SBNs up to 255
     (300, 13, 3, 0, None, "tight", True),    # bytes: T odd
     (300, 48, 3, 0, None, "odd", False),     # bytes: odd stride
+    # the edges of a wave's round (64 lanes of 16, 4 or 1 bytes)
+    (100, 1024, 2, 0, None, "r16", True),    # shifted 16-byte: a full wave, the tail from lane 63, a carry computed and never used
+    (100, 1040, 2, 0, None, "r16", True),    # a second round of one live lane whose left neighbour is the carry
+    (100, 1024, 2, 0, None, "tight", False),  # 16-byte: exactly one round
+    (100, 2064, 2, 0, None, "tight", False),  # a third round of one lane
+    (100, 256, 2, 0, None, "pad4", True),    # 4-byte: exactly one round
+    (100, 260, 2, 0, None, "tight", False),  # a second round of one lane
+    (100, 65, 2, 0, None, "tight", False),   # bytes: a second round
+    (100, 64, 2, 0, None, "odd", False),     # exactly one round
 ])
 def test_device_emit_matches_emulation(ctx, torch, orc, K, T, nblk, sbn0, kp_of, stride_kind, inline):
     Kp = nanorq_amd.params(kp_of or K)["Kp"]
@@ -67,11 +95,14 @@ def test_device_emit_matches_emulation(ctx, torch, orc, K, T, nblk, sbn0, kp_of,
     src_d = _dev(torch, src)
     with nanorq_amd.Sender(ctx, K, T, nblk, src_d, sbn0=sbn0, Kp=Kp) as tx:
         tx.encode()
-        out = torch.full((len(tags), stride), FILL, dtype=torch.uint8, device="cuda")
+        buf, out = _guarded(torch, len(tags), stride)
+        rows = [(src_d.data_ptr(), K * T), (tx.inter_ptr, params_L(Kp) * T)]
+        assert emit_mode(out.data_ptr(), stride, T, 4 if inline else 0, rows) == MODES[T, stride_kind, inline]
         res = torch.full((len(tags),), 77, dtype=torch.int32, device="cuda")
         tg_d = _dev(torch, tags.view(np.int32))
         tx.emit(tg_d, out=out, inline=inline, results=res)
         ctx.sync()
+        assert _guards_whole(buf), "guard rows"
         pk_e, res_e = emu_emit(K, Kp, T, src, inter, tags, inline, stride, sbn0=sbn0)
         pk_d, res_d = out.cpu().numpy(), res.cpu().numpy()
         assert np.array_equal(res_d, res_e)
@@ -82,11 +113,13 @@ def test_device_emit_matches_emulation(ctx, torch, orc, K, T, nblk, sbn0, kp_of,
         assert np.array_equal(d_inter, inter)
         for interleave in (False, True):
             n = K + 10
-            out = torch.full((n * nblk, stride), FILL, dtype=torch.uint8, device="cuda")
+            buf, out = _guarded(torch, n * nblk, stride)
+            assert emit_mode(out.data_ptr(), stride, T, 4 if inline else 0, rows) == MODES[T, stride_kind, inline]
             tg = torch.zeros((n * nblk,), dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
             tx.emit_range(0, n, interleave=interleave, inline=inline, out=out, tags_out=tg)
             ctx.sync()
+            assert _guards_whole(buf), "guard rows"
             pk_r, tg_r = emu_emit_range(K, Kp, T, src, inter, 0, n, interleave, inline, stride, sbn0=sbn0)
             assert np.array_equal(tg.cpu().numpy().view(np.uint32), tg_r)
             assert np.array_equal(tg_r, range_tags(nblk, sbn0, 0, n, interleave))

@@ -6,8 +6,15 @@ ReceiverSet with no repacking in between, the API's refusals, lifetimes, and fai
 nrq_emit_set_kernel<MODE, HELD> instances and the cases that launch them (T, header bytes):
   <TX_V16, false> (16, 0)   <TX_V16_SHIFT, false> (16, 4)   <TXS_V16_KEY, false> (16, 8)   <TX_DWORD, false> (36, *)   <TX_BYTE, false> (13, *)
       test_device_matches_emulation
+  <TX_V16, false> (T, 0)    <TX_V16_SHIFT, false> (T, 4)    <TXS_V16_KEY, false> (T, 8)    T = 32, 1024, 1040, 2064: a lane takes its
+      neighbour's dwords, a full wave, a second round of one lane fed by the carry, a carry out of a round that began with one
+  <TX_DWORD, false> (T, *)  T = 252, 256 (a stride of 4 mod 16), 260: 63 lanes, one round, a second round of one lane
+  <TX_BYTE, false> (T, *)   T = 63, 64 (an odd stride), 65
+      test_device_matches_emulation_at_wave_edges
   <TX_V16, true> (16, 0)    <TX_V16_SHIFT, true> (16, 4)    <TXS_V16_KEY, true> (16, 8)    <TX_DWORD, true> (36, 4)   <TX_BYTE, true> (13, 8)
-      test_held_device_matches_emulation"""
+  <TX_V16, true> (1040, 0)  <TX_V16_SHIFT, true> (1040, 4)  <TXS_V16_KEY, true> (1040, 8)  <TX_DWORD, true> (260, 4)  <TX_BYTE, true> (65, 8)
+      test_held_device_matches_emulation
+Every case asserts, by tx_support.emit_mode on the addresses and strides it hands over, that it runs the instance it is listed for."""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +24,7 @@ import nanorq_amd
 from nanorq_amd import EXT_SUBBLOCKS, NrqError
 from rx_support import ADDED, EmuRx, payloads_for
 from rxset_support import MIX4, MIX360
+from tx_support import emit_mode
 from txset_support import FILL, FOREIGN, NOT_READY, UNKNOWN_KEY, Seg, be32, emu_txset_emit, global_blocks, keyed_tags, tag
 from util import payload
 
@@ -69,16 +77,25 @@ class _Senders:
             self.segs.append(Seg(key, K, Kp, T, sbn0, src, inter))
             self.set.attach(key, tx)
 
+    def rows(self):
+        """(address, stride) of every row table an emit reads: the source rows and the intermediate symbols of each member"""
+        return [(src.data_ptr(), s.K * s.T) for src, s in zip(self.src, self.segs)] + \
+               [(tx.inter_ptr, _L(s.Kp) * s.T) for tx, s in zip(self.tx, self.segs)]
+
     def close(self):
         self.set.close()
         for t in self.tx:
             t.close()
 
 
-def _emit(torch, ctx, st, keys, tags, hdr, stride, held=False):
-    """one SenderSet.emit into a FILLed buffer -> (packets, results) as numpy"""
+def _emit(torch, ctx, st, keys, tags, hdr, stride, held=False, mode=None, rows=()):
+    """one SenderSet.emit into a FILLed buffer with a guard row of FILL on either side -> (packets, results) as numpy; mode: the
+    instance the call must take by the launch rule, from the buffer's address, the stride, the set's T and the row tables `rows`"""
     n = len(tags)
-    out = torch.full((n, stride), FILL, dtype=torch.uint8, device="cuda")
+    buf = torch.full((n + 2, stride), FILL, dtype=torch.uint8, device="cuda")
+    out = buf[1:n + 1]
+    if mode is not None:
+        assert emit_mode(out.data_ptr(), stride, st.T, hdr, rows) == mode
     res = torch.full((n,), 77, dtype=torch.int32, device="cuda")
     k_d = None if keys is None else _i32(torch, keys)
     t_d = _i32(torch, tags)
@@ -86,6 +103,7 @@ def _emit(torch, ctx, st, keys, tags, hdr, stride, held=False):
     got = st.emit(k_d, t_d, out=out, inline=hdr >= 4, key_inline=hdr == 8, results=res, held=held)
     ctx.sync()
     assert got is out
+    assert bool((buf[0] == FILL).all()) and bool((buf[n + 1] == FILL).all()), "guard rows"
     return out.cpu().numpy(), res.cpu().numpy()
 
 
@@ -126,6 +144,42 @@ def test_device_matches_emulation(ctx, torch, mix4, T, hdr, n):
         assert (res == 0).any() and (res == FOREIGN).any()
 
 
+def _edge_stride(T, hdr, mode):
+    """a stride for T bytes behind hdr that leaves the packets on `mode`: 16-byte aligned with a 16-byte slack; 4 (mod 16); odd"""
+    need = T + hdr
+    if mode in ("TX_V16", "TX_V16_SHIFT", "TXS_V16_KEY"):
+        return (need + 15) // 16 * 16 + 16
+    if mode == "TX_DWORD":
+        return need + (4 - need) % 16
+    return need | 1
+
+
+_V16 = {0: "TX_V16", 4: "TX_V16_SHIFT", 8: "TXS_V16_KEY"}
+# (T, mode): the sizes at which each form first fills a wave's round (64 lanes of 16, 4 or 1 bytes) and first wraps into the next
+EDGES = [(T, None) for T in (32, 1024, 1040, 2064)] + [(T, "TX_DWORD") for T in (252, 256, 260)] + [(T, "TX_BYTE") for T in (63, 64, 65)]
+
+
+@pytest.mark.parametrize("hdr", [0, 4, 8])
+@pytest.mark.parametrize("T,mode", EDGES)
+def test_device_matches_emulation_at_wave_edges(ctx, torch, mix4, T, mode, hdr):
+    """the four-member mix at the symbol sizes where a payload form fills or wraps a wave: the shifted 16-byte forms take a
+    neighbour lane's dwords (T = 32), the tail comes from lane 63 (1024), a second round has one live lane fed by the carry (1040),
+    a third a carry out of a round that began with one (2064); the dword and byte forms at 63 lanes, one round and one lane more.
+    About 300 packets: source, repair (multi-row gathers) and foreign ones; buffer, stride slack and guard rows compared whole."""
+    m = mix4(T)
+    mode = mode or _V16[hdr]
+    rng = np.random.default_rng(T * 100 + hdr)
+    keys, tags = keyed_tags(rng, m.segs, 300)
+    stride = _edge_stride(T, hdr, mode)
+    pk, res = _emit(torch, ctx, m.set, keys, tags, hdr, stride, mode=mode, rows=m.rows())
+    epk, eres, _ = emu_txset_emit(m.segs, keys, tags, hdr, stride)
+    assert np.array_equal(res, eres), np.flatnonzero(res != eres)[:10]
+    assert np.array_equal(pk, epk), np.flatnonzero((pk != epk).any(axis=1))[:10]
+    assert (res == 0).any() and (res == FOREIGN).any()
+    esi = tags & 0xFFFFFF
+    assert (res[esi < 10] == 0).any() and (res[esi >= 100] == 0).any()  # (source and repair packets of some member)
+
+
 def test_device_matches_emulation_no_keys(ctx, torch, mix4):
     """d_keys NULL: every packet has key 0"""
     m = mix4(16)
@@ -160,7 +214,7 @@ class _Relays:
     def __init__(self, ctx, torch, T, seed):
         rng = np.random.default_rng(seed)
         self.set = nanorq_amd.SenderSet(ctx, T)
-        self.hs, self.segs, self.sent = [], [], []
+        self.hs, self.segs, self.sent, self.tables = [], [], [], []
         for key, K, nblk, sbn0, cap in ((7, 31, 3, 2, 6), (7, 30, 2, 5, 40), (2, 10, 2, 2, 3)):
             Kp = nanorq_amd.params(K)["Kp"]
             rx = nanorq_amd.Receiver(ctx, K, T, nblk, cap, sbn0=sbn0)
@@ -183,6 +237,7 @@ class _Relays:
             assert ready[0] and not ready[1:].any()
             inter = ctx.download(relay.inter_ptr, nblk * _L(Kp) * T).reshape(nblk, _L(Kp), T)
             self.segs.append(Seg(key, K, Kp, T, sbn0, emu.src, inter, rx=emu, ready=ready))
+            self.tables += [(rx.src_ptr, K * T), (relay.inter_ptr, _L(Kp) * T), (rx.rep_ptr, cap * T)]
             self.sent.append((key, sent, emu))
             self.set.attach(key, relay)
             self.hs += [relay, rx]
@@ -191,6 +246,11 @@ class _Relays:
         self.plain.set.detach(9)
         self.set.attach(9, tx)
         self.segs += self.plain.segs
+
+    def rows(self):
+        """(address, stride) of every row table a held emit reads: the receptions' source and repair rows, the relays' intermediate
+        symbols, the plain sender's tables"""
+        return self.tables + self.plain.rows()
 
     def tags(self, rng):
         ks, ts = [], []
@@ -211,15 +271,17 @@ class _Relays:
         self.plain.close()
 
 
-@pytest.mark.parametrize("T,hdr", [(16, 0), (16, 4), (16, 8), (36, 4), (13, 8)])
+@pytest.mark.parametrize("T,hdr", [(16, 0), (16, 4), (16, 8), (36, 4), (13, 8), (1040, 0), (1040, 4), (1040, 8), (260, 4), (65, 8)])
 def test_held_device_matches_emulation(ctx, torch, T, hdr):
     """NRQ_TX_HELD over relay members beside a plain sender, in every payload mode: blocks that are ready, held source and repair
-    symbols of blocks that are not, symbols not held, ESIs behind the bitmap, foreign SBNs"""
+    symbols of blocks that are not, symbols not held, ESIs behind the bitmap, foreign SBNs; each mode also at a size that takes
+    the wave into a second round (T = 1040, 260, 65)"""
     m = _Relays(ctx, torch, T, seed=T + hdr)
     try:
         keys, tags = m.tags(np.random.default_rng(T))
         stride = _stride(T, hdr, 1)
-        pk, res = _emit(torch, ctx, m.set, keys, tags, hdr, stride, held=True)
+        mode = _V16[hdr] if T % 16 == 0 else "TX_DWORD" if T % 4 == 0 else "TX_BYTE"
+        pk, res = _emit(torch, ctx, m.set, keys, tags, hdr, stride, held=True, mode=mode, rows=m.rows())
         epk, eres, _ = emu_txset_emit(m.segs, keys, tags, hdr, stride, held=True)
         assert np.array_equal(res, eres), np.flatnonzero(res != eres)[:10]
         assert np.array_equal(pk, epk), np.flatnonzero((pk != epk).any(axis=1))[:10]

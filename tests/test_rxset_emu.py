@@ -19,7 +19,7 @@ def _kps(mix):
     return [nanorq_amd.params(m[1])["Kp"] for m in mix]
 
 
-def _build(mix, small_cap, obj_key=None, objZ=0):
+def _build(mix, small_cap, obj_key=None, objZ=0, T=T):
     """the set under test, and per member an EmuRx twin and a ModelRx twin"""
     kps = _kps(mix)
     st, mem, twins, models = EmuSet(), [], [], []
@@ -44,7 +44,7 @@ def _same_books(mem, twins, models):
             assert int(m.gaps[b]) == len(mo.missing[b])
 
 
-def _one_call(rng, mix, kps, st, twins, models, n, carrier, exact=False, stride_extra=0, objects=()):
+def _one_call(rng, mix, kps, st, twins, models, n, carrier, exact=False, stride_extra=0, objects=(), T=T):
     keys, tags = keyed_stream(rng, mix, kps, n, exact=exact)
     if carrier == "nokeys":
         keys = np.zeros_like(keys)
@@ -73,6 +73,17 @@ def test_set_matches_members_alone(n, carrier):
             assert (got[keys == UNKNOWN_KEY] == UNTOUCHED).all() and (keys == UNKNOWN_KEY).any()
     if n == 3000 and carrier != "nokeys":
         assert seen_codes == {ERR, ADDED, IGN, DUP, FULL, UNTOUCHED}
+
+
+@pytest.mark.parametrize("carrier", ["arrays", "keyinline"])
+def test_set_matches_members_alone_at_t_1040(carrier):
+    """T = 1040, where the device's 16-byte copy gives lane 0 alone a second access (tests/test_gpu_rxset.py compares the device
+    with this emulation there): the reference itself against the members alone"""
+    rng = np.random.default_rng(1040)
+    kps, st, mem, twins, models = _build(MIX4, small_cap=False, T=1040)
+    _, _, got = _one_call(rng, MIX4, kps, st, twins, models, 300, carrier, exact=True, stride_extra=8, T=1040)
+    _same_books(mem, twins, models)
+    assert ADDED in got and UNTOUCHED in got
 
 
 @pytest.mark.parametrize("stride_extra", [0, 4])

@@ -48,13 +48,28 @@ def check_against_members(segs, keys, tags, pk, res, T, hdr, held_ref=None):
 @pytest.mark.parametrize("hdr,slack", FORMS)
 @pytest.mark.parametrize("mix", sorted(MIXES))
 def test_set_emit_is_each_members_emit(mix, hdr, slack):
-    rng = np.random.default_rng(len(mix) * 100 + hdr * 10 + slack)
-    T = 12
+    _set_emit_is_each_members_emit(mix, 12, hdr, slack, 700)
+
+
+def _set_emit_is_each_members_emit(mix, T, hdr, slack, n):
+    rng = np.random.default_rng(len(mix) * 100 + hdr * 10 + slack + T - 12)
     segs = mix_segs(rng, MIXES[mix], T)
-    keys, tags = keyed_tags(rng, segs, 700)
+    keys, tags = keyed_tags(rng, segs, n)
     pk, res, _ = emu_txset_emit(segs, keys, tags, hdr, T + hdr + slack)
     assert check_against_members(segs, keys, tags, pk, res, T, hdr) > 0
     assert (res[keys == UNKNOWN_KEY] == FOREIGN).all()
+    return res
+
+
+@pytest.mark.parametrize("hdr", [0, 4, 8])
+@pytest.mark.parametrize("T", [32, 1040, 2064, 260, 65])
+def test_set_emit_is_each_members_emit_at_wave_edges(T, hdr):
+    """the symbol sizes at which the device's lane forms wrap into a second and third round of the wave (tests/test_gpu_txset.py
+    compares the device with this emulation there): the reference itself against each member's own emulated emit, with the
+    stride slack the device cases use"""
+    slack = (-(T + hdr)) % 16 + 16 if T % 16 == 0 else (4 - T - hdr) % 16 if T % 4 == 0 else 1 - (T + hdr) % 2
+    res = _set_emit_is_each_members_emit("mix4", T, hdr, slack, 300)
+    assert (res == 0).any() and (res == FOREIGN).any()
 
 
 def test_object_key_with_sbn_beyond_Z_and_no_keys():

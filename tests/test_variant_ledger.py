@@ -81,4 +81,7 @@ def test_ledger_has_no_stale_rows(inst):
         rows.add(("nrq_solve_kernel", args))
     rows |= {("nrq_backsub_kernel", (str(s),)) for s in V.BACKSUB}
     rows |= {("nrq_plan_kernel", (str(n), str(c))) for n, c in V.PLAN}
+    for kernel, table in (("nrq_emit_kernel", V.EMIT), ("nrq_emit_held_kernel", V.EMIT_HELD), ("nrq_emit_set_kernel", V.EMIT_SET)):
+        rows |= {(kernel, (str(m), "true" if flag else "false")) for m, flag in table}
+    assert len(V.EMIT) == 8 and len(V.EMIT_HELD) == 8 and len(V.EMIT_SET) == 10
     assert rows <= keys, sorted(rows - keys)

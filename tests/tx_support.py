@@ -159,3 +159,32 @@ def random_tags(rng, K, nblk, sbn0, n, foreign=True):
 
 def params_L(Kp):
     return nanorq_amd.params(Kp)["L"]
+
+
+def emit_mode(out_ptr, stride, T, hdr, rows=()):
+    """The payload path an emit takes, by the rule of tx_launch / nrq_txset_emit restated: OR the packet buffer's address, its
+    stride, T and every row table's address and stride (rows: (address, stride) pairs -- the source rows, the intermediate
+    symbols at inter_ptr with stride L * T, for a held emit the receptions' repair rows); all 16-byte aligned: the 16-byte form of
+    the header (hdr = 0, 4 or 8 bytes), 4-byte aligned: dwords, else bytes.  There is no statistic for the mode: a test asserts
+    this on what it hands to the call, so that a case cannot pass on another path than the one it is listed for."""
+    al = int(out_ptr) | int(stride) | int(T)
+    for addr, step in rows:
+        al |= int(addr) | int(step)
+    if al % 16 == 0:
+        return {0: "TX_V16", 4: "TX_V16_SHIFT", 8: "TXS_V16_KEY"}[hdr]
+    return "TX_DWORD" if al % 4 == 0 else "TX_BYTE"
+
+
+def copy_forms(pkt_ptr, pkt_stride, payload_off, n, T, row_ptrs):
+    """The forms nrq_ing_copy_kernel takes over n packets, by its rule restated: per packet the payload's address (packet k at
+    pkt_ptr + k * pkt_stride, the payload payload_off bytes in), the row's address and T ORed; 16-byte aligned: "v16", 4-byte
+    aligned: "dword", else "byte".  row_ptrs: the addresses of the row tables a packet may land in (rows lie T bytes apart, so a
+    row is as aligned as its table and T allow).  Returns the set of forms."""
+    d = int(T)
+    for p in row_ptrs:
+        d |= int(p)
+    out = set()
+    for k in range(min(n, 16)):  # (the low four bits of k * stride repeat after 16 packets)
+        al = (int(pkt_ptr) + k * int(pkt_stride) + payload_off) | d
+        out.add("v16" if al % 16 == 0 else "dword" if al % 4 == 0 else "byte")
+    return out

@@ -120,6 +120,24 @@ EMIT = {
 }
 EMIT.update({(m, True): dict(status="default", test="tests/test_gpu_variants.py::test_object_emit_modes",
                              why=TX_MODES[m] + ", an object of three segments") for m in TX_MODES})
+# the held emit nrq_emit_held_kernel<MODE, MULTI> (a relay's tag-list emit with NRQ_TX_HELD: one reception, or an object's table of
+# several segments) and the set emit nrq_emit_set_kernel<MODE, HELD> (MODE 4: the 16-byte form under key + FEC Payload ID)
+_HELD_PARTIAL = "tests/test_gpu_held.py::test_partial_blocks"
+EMIT_HELD = {
+    (0, False): dict(status="default", test=_HELD_PARTIAL, why="T = 1280, tags in a list"),
+    (1, False): dict(status="default", test="tests/test_gpu_held.py::test_second_round_of_the_shifted_form_matches_emulation",
+                     why="T = 1040 behind the inline header, a 16-byte stride"),
+    (2, False): dict(status="default", test=_HELD_PARTIAL, why="a packet stride of T + 4"),
+    (3, False): dict(status="default", test=_HELD_PARTIAL, why="an odd packet stride"),
+}
+EMIT_HELD.update({(m, True): dict(status="default", test="tests/test_gpu_held.py::test_object_held_emit_modes",
+                                  why=TX_MODES[m] + ", an object relay's table of two block classes") for m in TX_MODES})
+TXS_MODES = dict(TX_MODES)
+TXS_MODES[4] = "TXS_V16_KEY"
+EMIT_SET = {(m, False): dict(status="default", test="tests/test_gpu_txset.py::test_device_matches_emulation_at_wave_edges",
+                             why=TXS_MODES[m] + ": below one round of the wave, exactly one round, a later round") for m in TXS_MODES}
+EMIT_SET.update({(m, True): dict(status="default", test="tests/test_gpu_txset.py::test_held_device_matches_emulation",
+                                 why=TXS_MODES[m] + " over relays with NRQ_TX_HELD: one round and a second round") for m in TXS_MODES})
 OBJ_LAYOUT = {
     16: dict(status="default", test="tests/test_gpu_obj.py::test_receiver_matches_host_decoder", why="T = 64, N = 1"),
     8: dict(status="default", test="tests/test_gpu_obj.py::test_receiver_matches_host_decoder", why="T = 1280, N = 3, Al = 8"),
@@ -142,9 +160,14 @@ def ledger_row(kernel, args):
         return PLAN.get((int(args[0]), int(args[1]) if len(args) > 1 else 0))
     if kernel == "nrq_emit_kernel":
         return EMIT.get((int(args[0]), args[1] == "true"))
+    if kernel == "nrq_emit_held_kernel":
+        return EMIT_HELD.get((int(args[0]), args[1] == "true"))
+    if kernel == "nrq_emit_set_kernel":
+        return EMIT_SET.get((int(args[0]), args[1] == "true"))
     if kernel == "nrq_obj_layout_kernel":
         return OBJ_LAYOUT.get(OBJ_WORD.get(args[0]))
     raise KeyError(kernel)
 
 
-KERNELS = ("nrq_solve_kernel", "nrq_backsub_kernel", "nrq_plan_kernel", "nrq_emit_kernel", "nrq_obj_layout_kernel")
+KERNELS = ("nrq_solve_kernel", "nrq_backsub_kernel", "nrq_plan_kernel", "nrq_emit_kernel", "nrq_emit_held_kernel", "nrq_emit_set_kernel",
+           "nrq_obj_layout_kernel")
