@@ -454,7 +454,60 @@ int nrq_orx_write(nrq_orx *rx, void *d_out);
  * receiver (else it is detached). */
 int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
 
-/* ---- reception sets: the packets of MANY receptions in one buffer, ingested in one pass ----
+/* ---- packets of several symbols (RFC 6330 section 4.4.2) ----
+ * A packet may carry up to G symbols (1 <= G <= NRQ_PKT_SYMS_MAX) of ONE source block, all source or all repair, with consecutive
+ * ESIs: packet k has a first tag (SBN, e_k) -- d_tags[k], or the inline FEC Payload ID -- and a count c_k; symbol i < c_k has ESI
+ * e_k + i (in ESI space: the SBN never changes inside a packet, an ESI above 2^24 - 1 does not exist) and its payload at
+ * hdr + i * T in the packet (hdr = 0, or 4 with the tag inline); pkt_stride >= hdr + G * T.  Slot (k, i) has index k * G + i; the
+ * EXPANSION of a packet list is its one-symbol packets in slot order.  d_nsym (device, uint8 per packet, nullable) gives the
+ * counts; NULL is the sender's rule: c_k = G, except that a packet whose first ESI is below the block's K carries
+ * min(G, K - e_k) (each block class of an object with its own K).
+ *
+ * nrq_rx_add_syms / nrq_orx_add_syms: as nrq_rx_add / nrq_orx_add.  d_results (nullable) has n * G entries: slot (k, i), i < c_k,
+ * gets the code nrq_rx_add gives that symbol in the expansion (a duplicate inside the list and the ERR of an ESI above max_esi
+ * included; a symbol whose ESI would pass 2^24 - 1 is ERR); slots i >= c_k and the slots of SBNs outside the reception are left
+ * untouched.  A receiver is liberal: a given count 1..G is taken as it is, also where the packet runs from source into repair
+ * ESIs.  A given count of 0 or above G is malformed: slot k * G gets ERR, nothing of the packet is booked, its other slots are
+ * untouched.  (Object form, SBN >= Z: c slots get ERR / IGN as in nrq_orx_add, c = d_nsym[k], or G without d_nsym; a count of 0
+ * or above G gives slot k * G ERR there too.)
+ * After the call the reception is in exactly the state nrq_rx_add leaves after the expansion -- seen bits, gaps, repair rows and
+ * their ESIs in arrival order, source rows -- so counts, lists, decode, held, want and relays need nothing new.  G = 1 with
+ * d_nsym NULL is nrq_rx_add.  Refused (-1 and a text, nothing enqueued): G outside 1..NRQ_PKT_SYMS_MAX, a stride too small,
+ * n * G > 0x7FFFFFFF, an unknown flag, d_tags together with (or without either of) NRQ_RX_TAG_INLINE.
+ *
+ * nrq_tx_emit_syms / nrq_otx_emit_syms: as nrq_tx_emit / nrq_otx_emit.  A written packet is the FEC Payload ID of (SBN, e_k)
+ * when inline, then c_k payloads, each byte for byte what nrq_tx_emit writes for that (SBN, ESI); the bytes of the packet behind
+ * hdr + c_k * T are untouched.  d_results[k] (n entries, nullable): 0 written; -1 SBN outside the span; NRQ_TX_NOT_READY a relay's
+ * block that is not ready; NRQ_TX_BAD_RANGE a count of 0 or above G, a GIVEN count that takes a packet starting below K to K or
+ * beyond (a sender is strict), or e_k + c_k - 1 > 0xFFFFFF -- in all but the first case the packet is untouched.  Admission is
+ * per packet (every symbol of a packet has the packet's block): no packet is ever half written.  NRQ_TX_HELD is refused here
+ * (-1): held symbols are decided per symbol.
+ *
+ * nrq_tx_emit_range_syms / nrq_otx_emit_all_syms: ESIs esi0 .. esi0+n-1 (0 .. K+nrep-1) of every block, packetised per block: the
+ * source run [esi0, min(K, esi0+n)) cut into packets of G from its start, the last one short, then the repair run
+ * [max(K, esi0), esi0+n) likewise -- nrq_pkt_count(K, esi0, n, G) packets per block.  order 0: block-major; order 1: round j holds
+ * packet j of every block that has one, in SBN order (a class with fewer packets drops out of the later rounds).  d_tags_out
+ * (first tags) and d_nsym_out (counts), both nullable, are in packet order.  *h_npkt (nullable) receives the number of packets.
+ * A relay with a block that is not ready is refused, as nrq_tx_emit_range.
+ *
+ * Reception sets and sender sets (nrq_rxset_*, nrq_txset_*) keep one symbol per packet. */
+#define NRQ_PKT_SYMS_MAX 64u
+#define NRQ_TX_BAD_RANGE (-3)
+uint32_t nrq_pkt_count(uint32_t K, uint32_t esi0, uint32_t n, uint32_t G);
+int nrq_rx_add_syms(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                    uint32_t flags, int32_t *d_results);
+int nrq_orx_add_syms(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                     uint32_t flags, int32_t *d_results);
+int nrq_tx_emit_syms(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym, void *d_pkts, size_t pkt_stride,
+                     uint32_t flags, int32_t *d_results);
+int nrq_otx_emit_syms(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym, void *d_pkts, size_t pkt_stride,
+                      uint32_t flags, int32_t *d_results);
+int nrq_tx_emit_range_syms(nrq_tx *tx, uint32_t esi0, uint32_t n, uint32_t G, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                           uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt);
+int nrq_otx_emit_all_syms(nrq_otx *tx, uint32_t nrep, uint32_t G, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                          uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt);
+
+/* ---- reception sets:the packets of MANY receptions in one buffer, ingested in one pass ----
  * A set is a table of member receptions of one context and one T, each under a 32-bit KEY the caller chooses (a TOI, a flow
  * number): a tag names (SBN, ESI) and nothing more, the key names the reception or object the SBN belongs to.  nrq_rxset_add
  * runs the passes of nrq_rx_add once over all packets with the table in device memory, where today R receptions fed from one

@@ -163,6 +163,16 @@ def lib():
         L.nrq_txset_detach.argtypes = [vp, C.c_uint32]
         L.nrq_txset_blocks.argtypes = [vp, u32p, u32p, C.c_uint32, u32p]
         L.nrq_txset_emit.argtypes = [vp, vp, vp, C.c_uint32, vp, sz, C.c_uint32, vp]
+    if hasattr(L, "nrq_rx_add_syms"):  # (likewise a build from before the packets of several symbols: the *_syms methods then raise)
+        u32 = C.c_uint32
+        L.nrq_pkt_count.argtypes = [u32, u32, u32, u32]
+        L.nrq_pkt_count.restype = u32
+        L.nrq_rx_add_syms.argtypes = [vp, vp, sz, vp, u32, u32, vp, u32, vp]
+        L.nrq_orx_add_syms.argtypes = [vp, vp, sz, vp, u32, u32, vp, u32, vp]
+        L.nrq_tx_emit_syms.argtypes = [vp, vp, u32, u32, vp, vp, sz, u32, vp]
+        L.nrq_otx_emit_syms.argtypes = [vp, vp, u32, u32, vp, vp, sz, u32, vp]
+        L.nrq_tx_emit_range_syms.argtypes = [vp, u32, u32, u32, C.c_int, vp, sz, u32, vp, vp, u32p]
+        L.nrq_otx_emit_all_syms.argtypes = [vp, u32, u32, C.c_int, vp, sz, u32, vp, vp, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -475,6 +485,13 @@ class Receiver(_Handle):
         self.ctx._chk(self._L.nrq_rx_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(tags)), n,
                                          RX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
 
+    def add_syms(self, payload, G, tags=None, nsym=None, inline=False, results=None, n=None, stride=None):
+        """Ingest packets of up to G symbols each (nrq_rx_add_syms; enqueue only): tags / the inline FEC Payload ID name each
+        packet's FIRST symbol, nsym ([n] uint8 device tensor, or None for the sender's rule) its count; symbol i of packet k lies
+        at hdr + i * T and reports into results[k * G + i] ([n * G] int32 device tensor, optional).  The reception ends in the
+        state add() leaves after the one-symbol packets in slot order."""
+        _add_syms(self, payload, G, tags, nsym, inline, results, n, stride)
+
     def counts(self):
         """(missing source symbols, repair rows used) per block, as numpy arrays (waits)."""
         nl = np.zeros(self.nblk, np.uint32)
@@ -522,6 +539,31 @@ class Receiver(_Handle):
         return RelaySender(self)
 
 
+PKT_SYMS_MAX = 64  # NRQ_PKT_SYMS_MAX
+
+
+def _syms_fn(obj, name):
+    fn = getattr(obj._L, obj._api + name, None)
+    if fn is None or not hasattr(obj._L, "nrq_rx_add_syms"):
+        raise NrqError("this build of the library has no packets of several symbols (%s%s)" % (obj._api, name))
+    return fn
+
+
+def _add_syms(rx, payload, G, tags, nsym, inline, results, n, stride):
+    if hasattr(payload, "data_ptr"):
+        n = payload.shape[0] if n is None else n
+        stride = payload.stride(0) * payload.element_size() if stride is None else stride
+    if n is None or stride is None:
+        raise ValueError("a raw payload address needs n and stride")
+    rx.ctx._chk(_syms_fn(rx, "_add_syms")(rx._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(tags)), n, G,
+                                          C.c_void_p(_dptr(nsym)), RX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+
+
+def pkt_count(K, esi0, n, G):
+    """packets that carry ESIs esi0 .. esi0+n-1 of a block of K source symbols, G symbols a packet (nrq_pkt_count)"""
+    return int(lib().nrq_pkt_count(K, esi0, n, G))
+
+
 def _held(rx):
     """<_api>_held: the count first, then the tags into a tensor of that size"""
     import torch
@@ -555,6 +597,7 @@ def _want(rx, extra, source, esi_from):
 TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
 TX_HELD = 2         # NRQ_TX_HELD
 TX_NOT_READY = -2   # NRQ_TX_NOT_READY
+TX_BAD_RANGE = -3   # NRQ_TX_BAD_RANGE
 
 
 def _tx_flags(inline, held):
@@ -591,6 +634,40 @@ class _Emitter(_Handle):
                                                             _tx_flags(inline, held), C.c_void_p(_dptr(results))))
         return out
 
+    def stride_syms(self, G, inline=False):
+        """the packet stride of out=None for packets of G symbols: G * T, or G * T + 4 rounded up to 16 with the inline header"""
+        return (G * self.T + 4 + 15) // 16 * 16 if inline else G * self.T
+
+    def _out_syms(self, n, G, inline, out):
+        if out is not None:
+            return out, out.stride(0) * out.element_size()
+        import torch
+        out = torch.empty((n, self.stride_syms(G, inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        return out, out.shape[1]
+
+    def emit_syms(self, tags, G, nsym=None, out=None, inline=False, results=None):
+        """Packet k of up to G symbols for the first tag tags[k] in row k of out (<_api>_emit_syms): nsym[k] symbols ([n] uint8
+        device tensor), or by the sender's rule with nsym None -- G, but a packet of source symbols ends with the block's last
+        one.  results: optional [n] int32 device tensor (0, -1, TX_NOT_READY, TX_BAD_RANGE; only a 0 packet is written, and
+        whole).  Held symbols are not offered.  Returns out."""
+        n = int(tags.shape[0])
+        out, stride = self._out_syms(n, G, inline, out)
+        self.ctx._chk(_syms_fn(self, "_emit_syms")(self._h, C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)), C.c_void_p(_dptr(out)),
+                                                   stride, _tx_flags(inline, False), C.c_void_p(_dptr(results))))
+        return out
+
+    def _range_syms(self, fn, head, npkt, G, interleave, inline, out):
+        import torch
+        dev = "cuda:%d" % self.ctx.device
+        out, stride = self._out_syms(npkt, G, inline, out)
+        tags = torch.zeros(npkt, dtype=torch.int32, device=dev)
+        nsym = torch.zeros(npkt, dtype=torch.uint8, device=dev)
+        got = C.c_uint32()
+        self.ctx._chk(fn(self._h, *head, G, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride, _tx_flags(inline, False),
+                         C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), C.byref(got)))
+        assert got.value == npkt, (got.value, npkt)
+        return out, tags, nsym
+
 
 class Sender(_Emitter):
     """A device-resident transmission (nrq_tx, include/nanorq_hip.h): nblk blocks of equal (K, K', T), SBNs sbn0 .. sbn0+nblk-1,
@@ -622,6 +699,13 @@ class Sender(_Emitter):
         self.ctx._chk(self._L.nrq_tx_emit_range(self._h, esi0, n, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride,
                                                 _tx_flags(inline, held), C.c_void_p(_dptr(tags_out))))
         return out
+
+    def emit_range_syms(self, esi0, n, G, interleave=True, inline=False, out=None):
+        """ESIs esi0 .. esi0+n-1 of every block in packets of G symbols (nrq_tx_emit_range_syms): per block the source run, then
+        the repair run, each cut into packets of G from its start; interleaved (round j: packet j of every block) or
+        block-major.  Returns (out [packets, stride] uint8, first tags [packets] int32, counts [packets] uint8)."""
+        return self._range_syms(_syms_fn(self, "_emit_range_syms"), (esi0, n), pkt_count(self.K, esi0, n, G) * self.nblk, G, interleave,
+                                inline, out)
 
 
 class _Relay:
@@ -717,6 +801,16 @@ class ObjectSender(_Emitter):
                                                _tx_flags(inline, held), C.c_void_p(_dptr(tags_out))))
         return out
 
+    def count_all_syms(self, nrep, G):
+        p = self.params
+        return ((p.ZL * pkt_count(p.KL, 0, p.KL + nrep, G) if p.ZL else 0) +
+                (p.ZS * pkt_count(p.KS, 0, p.KS + nrep, G) if p.ZS else 0))
+
+    def emit_all_syms(self, nrep, G, interleave=True, inline=False, out=None):
+        """ESIs 0 .. K_b + nrep - 1 of every block b in packets of G symbols (nrq_otx_emit_all_syms), each block class cut by
+        its own K; returns (out, first tags, counts) as Sender.emit_range_syms."""
+        return self._range_syms(_syms_fn(self, "_emit_all_syms"), (nrep,), self.count_all_syms(nrep, G), G, interleave, inline, out)
+
 
 class RelayObjectSender(_Relay, ObjectSender):
     """ObjectReceiver.relay(): an ObjectSender (emit, emit_all, oti, blocks) over the receiver's row images, in place."""
@@ -761,6 +855,10 @@ class ObjectReceiver(_Handle):
             raise ValueError("give either tags or inline=True")
         self.ctx._chk(self._L.nrq_orx_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(tags)), n,
                                           RX_TAG_INLINE if inline else 0, C.c_void_p(_dptr(results))))
+
+    def add_syms(self, payload, G, tags=None, nsym=None, inline=False, results=None, n=None, stride=None):
+        """as Receiver.add_syms, over every block of the object (the sender's rule with each block class's own K)"""
+        _add_syms(self, payload, G, tags, nsym, inline, results, n, stride)
 
     def counts(self):
         nl = np.zeros(self.Z, np.uint32)

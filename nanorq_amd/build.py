@@ -29,6 +29,7 @@ REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
+YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
 ROWS = os.path.join(ROOT, "tests", "gpu", "librows_probe.so")
@@ -189,6 +190,12 @@ def build_txset_emu(force=False):
     return _build_emu(TEMU, os.path.join(CSRC, "txset_emu.cpp"), ("emit_set_body.h", "emit_body.h", "rq_math.h"), force)
 
 
+def build_syms_emu(force=False):
+    """tests/emu/libsyms_emu.so: CPU emulation of the emit and ingest of packets of several symbols (csrc/syms_emu.cpp over
+    syms_body.h), with the count rule, the range packetisation and the path rules behind C entry points."""
+    return _build_emu(YEMU, os.path.join(CSRC, "syms_emu.cpp"), ("syms_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -290,6 +297,7 @@ if __name__ == "__main__":
     build_rxset_lists_emu(force="-f" in sys.argv)
     build_rxset_want_emu(force="-f" in sys.argv)
     build_txset_emu(force="-f" in sys.argv)
+    build_syms_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)

@@ -42,6 +42,7 @@
 #include "want_set_body.h"
 #include "emit_body.h"
 #include "emit_set_body.h"
+#include "syms_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
@@ -4056,6 +4057,427 @@ int nrq_orx_write(nrq_orx *rx, void *d_out) {
   }
   if (incomplete < (int)Z && (rc = obj_layout_launch(ctx, l))) return rc;
   return incomplete;
+}
+
+} /* extern "C" */
+
+/* ================================================ packets of several symbols (nrq_*_syms, syms_body.h) ==== */
+/* Kernels of their own beside the one-symbol ones: every instantiation of those is compiled from the code it always was.
+ *
+ * Ingest: the chain of nrq_rx_add over n * G slots.  Passes 2 and 4 are per block and are nrq_rx_add's kernels; passes 1, 3, 5, 7
+ * are these, which ask syms_body.h what a slot is; pass 6 walks a packet's payloads as one contiguous run. */
+__global__ __launch_bounds__(256) void nrq_ing_first_syms_kernel(ing_rx r, ing_call c, sy_rx y) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s < c.n) sy_first(&r, &c, &y, s);
+}
+
+__global__ __launch_bounds__(256) void nrq_ing_hist_syms_kernel(ing_rx r, ing_call c, sy_rx y) {
+  __shared__ uint32_t h[256];
+  const uint32_t t = threadIdx.x, s = blockIdx.x * ING_TILE + t;
+  h[t] = 0;
+  __syncthreads();
+  if (s < c.n) {
+    const uint32_t b = sy_cand(&r, &c, &y, s);
+    if (b != ING_NONE) atomicAdd(&h[b], 1u);
+  }
+  __syncthreads();
+  if (t < r.nblk) c.base[(size_t)t * c.ntiles + blockIdx.x] = h[t];
+}
+
+/* (the ranking of nrq_ing_classify_kernel: a ballot per distinct block present in the wave, in slot order) */
+__global__ __launch_bounds__(256) void nrq_ing_classify_syms_kernel(ing_rx r, ing_call c, sy_rx y) {
+  __shared__ uint32_t wc[4][256];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6, s = blockIdx.x * ING_TILE + t;
+  for (uint32_t i = t; i < 4u * 256u; i += 256u) wc[i >> 8][i & 255u] = 0;
+  __syncthreads();
+  const uint32_t b = s < c.n ? sy_cand(&r, &c, &y, s) : ING_NONE;
+  const bool cand = b != ING_NONE;
+  uint64_t todo = __ballot(cand);
+  uint32_t rank = 0;
+  while (todo) { /* (wave-uniform) */
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t lb = __shfl(b, leader);
+    const bool mine = cand && b == lb;
+    const uint64_t m = __ballot(mine);
+    if (mine) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if ((int)lane == leader) wc[w][lb] = (uint32_t)__popcll(m);
+    todo &= ~m;
+  }
+  __syncthreads();
+  uint32_t row = ING_NONE;
+  if (cand) {
+    row = c.base[(size_t)b * c.ntiles + blockIdx.x] + rank;
+    for (uint32_t w2 = 0; w2 < w; w2++) row += wc[w2][b];
+  }
+  if (s < c.n) sy_classify(&r, &c, &y, s, row);
+}
+
+__global__ __launch_bounds__(256) void nrq_ing_fold_syms_kernel(ing_rx r, ing_call c, sy_rx y) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s < c.n) sy_fold(&r, &c, &y, s);
+}
+
+/* One wave per packet: lane i holds the destination of slot (k, i); the wave walks the payloads up to the last slot that has
+ * one as ONE contiguous run, a W-byte word per lane and trip whatever symbol boundaries fall inside (T is a multiple of W: a
+ * word lies in one symbol), and each lane stores its word into the row of the slot it falls into.  A destination of 0: skip.
+ * W = the widest word every address of the call allows (sy_copy_word, decided by the launcher). */
+template <typename W>
+__global__ __launch_bounds__(256) void nrq_ing_copy_syms_kernel(const uint8_t *__restrict__ pkts, uint64_t pkt_stride,
+                                                                const uint64_t *__restrict__ dst, uint32_t n, uint32_t G, uint32_t T,
+                                                                uint32_t payload_off) {
+  const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (k >= n) return; /* (wave-uniform) */
+  const uint64_t d = lane < G ? dst[(uint64_t)k * G + lane] : 0ull;
+  const uint64_t m = __ballot(d != 0ull);
+  if (!m) return;
+  const uint32_t len = (64u - (uint32_t)__clzll((long long)m)) * T; /* (G * T fits 32 bits: the launcher checked) */
+  const uint32_t dlo = (uint32_t)d, dhi = (uint32_t)(d >> 32);
+  const uint8_t *__restrict__ s = pkts + (size_t)k * pkt_stride + payload_off;
+  constexpr uint32_t WB = (uint32_t)sizeof(W);
+  for (uint32_t o0 = 0; o0 < len; o0 += 64u * WB) { /* (wave-uniform: every lane takes part in the shuffles) */
+    const uint32_t off = o0 + lane * WB;
+    const bool act = off < len;
+    const uint32_t i = act ? off / T : 0u;
+    const uint64_t di = ((uint64_t)(uint32_t)__shfl((int)dhi, (int)i) << 32) | (uint32_t)__shfl((int)dlo, (int)i);
+    if (act && di) *reinterpret_cast<W *>(reinterpret_cast<uint8_t *>(di) + (off - i * T)) = *reinterpret_cast<const W *>(s + off);
+  }
+}
+
+/* the codes of an object's packets of SBN >= Z, slot by slot (nrq_orx_foreign_kernel's rule over the expansion) */
+__global__ __launch_bounds__(256) void nrq_orx_foreign_syms_kernel(const uint8_t *pkts, uint64_t pkt_stride, const uint32_t *tags, uint32_t n,
+                                                                   uint32_t G, const uint8_t *nsym, uint32_t Z, uint32_t max_esi,
+                                                                   int32_t *results) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= n * G) return;
+  const uint32_t k = s / G, i = s - k * G;
+  ing_call c{};
+  c.pkts = pkts; c.pkt_stride = pkt_stride; c.tags = tags;
+  const uint32_t tag = sy_first_tag(&c, k);
+  if ((tag >> 24) < Z) return;
+  const uint32_t cnt = nsym ? nsym[k] : G;
+  if (cnt == 0u || cnt > G) {
+    if (i == 0u) results[s] = ING_ERR;
+  } else if (i < cnt) {
+    results[s] = (tag & SY_ESI_MAX) + i > max_esi ? ING_ERR : ING_IGN;
+  }
+}
+
+/* Emit.  The wave shape of nrq_emit_kernel with SLOTS as work items: a wave takes 64 / G packets of the work order (block-major;
+ * a tag list bucketed by block), lane l the slot (l / G, l % G) -- a packet's slots are adjacent and never split across waves.
+ * Each lane admits its packet (sy_tx_admit: per packet, so every lane of a packet decides alike) and builds its slot's column
+ * list into LDS; then the wave writes the admitted packets one after the other, each as ONE run of c_k * T bytes with lanes across
+ * the symbol boundaries: a lane gathers with the column list of the slot its word lies in. */
+template <int MODE>
+__device__ __forceinline__ void sy_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t (*cols)[TX_COLS], const uint32_t *ns,
+                                           uint32_t cnt, uint32_t tag, uint8_t *__restrict__ P, uint32_t inl, uint32_t lane) {
+  const uint32_t len = cnt * T;
+  if constexpr (MODE == TX_V16) {
+    for (uint32_t off = lane * 16u; off < len; off += 64u * 16u) {
+      const uint32_t i = off / T;
+      *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
+    }
+  } else if constexpr (MODE == TX_V16_SHIFT) {
+    /* tx_payload's shift over the run: packet chunk j = run dwords 4j-1 .. 4j+2, the first of them the previous lane's .w (the
+     * header for j = 0) whether or not a symbol boundary lies between the two; the run's last .w goes to +len */
+    const uint32_t nch = len >> 4;
+    uint32_t carry = tx_header_word(tag);
+    for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
+      const uint32_t j = j0 + lane;
+      const bool act = j < nch;
+      tx_u128 v{0u, 0u, 0u, 0u};
+      if (act) {
+        const uint32_t off = j * 16u, i = off / T;
+        v = tx_gather<tx_u128>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
+      }
+      uint32_t prev = __shfl_up(v.w, 1u);
+      if (lane == 0) prev = carry;
+      if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
+      if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + len) = v.w;
+      carry = __shfl(v.w, 63);
+    }
+  } else if constexpr (MODE == TX_DWORD) {
+    if (inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
+    uint8_t *D = P + (inl ? 4u : 0u);
+    for (uint32_t off = lane * 4u; off < len; off += 64u * 4u) {
+      const uint32_t i = off / T;
+      *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
+    }
+  } else {
+    if (inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
+    uint8_t *D = P + (inl ? 4u : 0u);
+    for (uint32_t off = lane; off < len; off += 64u) {
+      const uint32_t i = off / T;
+      D[off] = tx_gather<uint8_t>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
+    }
+  }
+}
+
+template <int MODE, bool MULTI>
+__global__ __launch_bounds__(256) void nrq_emit_syms_kernel(tx_src s, tx_call c, sy_tx y) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS]; /* (MULTI only: unused LDS is not allocated) */
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t G = y.G, per = 64u / G, p = lane / G, i = lane - p * G;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * per; /* the wave's first packet in the work order */
+  {
+    uint32_t n = 0, cnt = 0, tag0 = 0, k = 0, sg = TX_SEGS;
+    if (p < per && w0 + p < c.n) {
+      k = tx_packet_of<MULTI>(&s, &c, (uint32_t)(w0 + p));
+      if (k < c.n) { /* (always: the work order is a permutation) */
+        bool ranged;
+        int32_t code;
+        tag0 = sy_tx_packet<MULTI>(&s, &c, &y, k, &cnt, &ranged);
+        sg = sy_tx_admit<MULTI>(&s, &y, tag0, k, ranged, &code, &cnt);
+        const tx_blk sb = MULTI ? tx_pick(&s, sg) : s.seg[0];
+        if (sg < TX_SEGS && i < cnt) n = tx_rows(&sb, tag0 + i, s_cols[wv][lane]);
+        if (i == 0u) {
+          if (c.results) c.results[k] = code;
+          if (c.tags_out) c.tags_out[k] = tag0;
+          if (y.nsym_out) y.nsym_out[k] = (uint8_t)cnt;
+        }
+      }
+    }
+    s_n[wv][lane] = n | (cnt << 8); /* (cnt = 0: the packet stays untouched) */
+    s_tag[wv][lane] = tag0;
+    s_k[wv][lane] = k;
+    if (MULTI) s_seg[wv][lane] = sg;
+  }
+  __syncthreads();
+  const uint32_t T = s.seg[0].T;
+  for (uint32_t q = 0; q < per && w0 + q < c.n; q++) { /* (wave-uniform) */
+    const uint32_t l0 = q * G;
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][l0]), cnt = nk >> 8;
+    if (!cnt) continue;
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][l0]);
+    const uint8_t *base;
+    if constexpr (MULTI) {
+      const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][l0]);
+      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
+    } else {
+      base = tx_base(&s.seg[0], tag);
+    }
+    uint8_t *P = c.pkts + (uint64_t)s_k[wv][l0] * c.pkt_stride;
+    if (cnt == 1u) tx_payload<MODE>(base, T, s_cols[wv][l0], nk & 0xFFu, tag, P, c.inl, lane); /* (no boundary to look for: the one-symbol walk) */
+    else sy_payload<MODE>(base, T, &s_cols[wv][l0], &s_n[wv][l0], cnt, tag, P, c.inl, lane);
+  }
+}
+
+static int rx_add_syms(nrq_rx *rx, const char *who, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G,
+                       const uint8_t *d_nsym, uint32_t flags, int32_t *d_results) {
+  nrq_ctx *ctx = rx->ctx;
+  const ing_rx &r = rx->r;
+  const bool inl = (flags & NRQ_RX_TAG_INLINE) != 0;
+  if (flags & ~(uint32_t)NRQ_RX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  if (n == 0) return 0;
+  if (!d_pkts || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad packets (n=%u, G=%u)", who, n, G);
+  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "%s: give either d_tags or NRQ_RX_TAG_INLINE", who);
+  if ((uint64_t)G * r.T > 0xFFFFFFFFu || pkt_stride < (size_t)G * r.T + (inl ? 4u : 0u))
+    return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t ns = n * G;
+  ing_call c{};
+  c.pkts = (const uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.tags = d_tags;
+  c.n = ns;
+  c.ntiles = (ns + ING_TILE - 1u) / ING_TILE;
+  const size_t o_codes = rx_al((size_t)ns * 4u), o_fidx = o_codes + rx_al((size_t)ns * 4u), o_dst = o_fidx + rx_al((size_t)ns * 4u),
+               o_base = o_dst + rx_al((size_t)ns * 8u), o_kind = o_base + rx_al((size_t)r.nblk * c.ntiles * 4u), need = o_kind + rx_al(ns);
+  const int rc = rx->scratch.ensure(ctx, need);
+  if (rc) return rc;
+  uint8_t *s = (uint8_t *)rx->scratch.p;
+  c.tagv = (uint32_t *)s;
+  c.codes = d_results ? d_results : (int32_t *)(s + o_codes);
+  c.fidx = (uint32_t *)(s + o_fidx);
+  c.dst = (uint64_t *)(s + o_dst);
+  c.base = (uint32_t *)(s + o_base);
+  sy_rx y{};
+  y.G = G; y.nsym = d_nsym; y.kind = s + o_kind;
+  const uint32_t hdr = ing_payload_off(&c);
+  const uint32_t word = sy_copy_word(reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | hdr | r.T | reinterpret_cast<uintptr_t>(r.src) |
+                                     r.src_stride | reinterpret_cast<uintptr_t>(r.rep) | r.rep_stride);
+  hipStream_t st = ctx->stream;
+  const uint32_t g = (ns + 255u) / 256u;
+  hipLaunchKernelGGL(nrq_ing_first_syms_kernel, dim3(g), dim3(256), 0, st, r, c, y);
+  hipLaunchKernelGGL(nrq_ing_done_kernel, dim3(r.nblk), dim3(256), 0, st, r);
+  hipLaunchKernelGGL(nrq_ing_hist_syms_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c, y);
+  hipLaunchKernelGGL(nrq_ing_scan_kernel, dim3(r.nblk), dim3(256), 0, st, r, c);
+  hipLaunchKernelGGL(nrq_ing_classify_syms_kernel, dim3(c.ntiles), dim3(256), 0, st, r, c, y);
+  const dim3 cg((n + 3u) / 4u);
+  if (word == 16u)
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint4>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, r.T, hdr);
+  else if (word == 4u)
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint32_t>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, r.T, hdr);
+  else
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint8_t>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, r.T, hdr);
+  hipLaunchKernelGGL(nrq_ing_fold_syms_kernel, dim3(g), dim3(256), 0, st, r, c, y);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* checks of the several-symbol emits on top of tx_check */
+static int sy_tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t G, uint32_t flags) {
+  nrq_ctx *ctx = tx->ctx;
+  if (flags & NRQ_TX_HELD) return fail(ctx, -1, "%s: NRQ_TX_HELD is not offered with packets of several symbols (held symbols are decided per symbol)", who);
+  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags);
+  if (rc) return rc;
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  const uint32_t T = tx->s.seg[0].T;
+  if ((uint64_t)G * T > 0xFFFFFFFFu || pkt_stride < (size_t)G * T + ((flags & NRQ_TX_TAG_INLINE) ? 4u : 0u))
+    return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G);
+  return 0;
+}
+
+static int sy_tx_launch(tx_sender *tx, const tx_call &c, const sy_tx &y) {
+  using emit_fn = void (*)(tx_src, tx_call, sy_tx);
+  static const emit_fn kern[2][4] = { /* [multi-segment][path] */
+      {nrq_emit_syms_kernel<TX_V16, false>, nrq_emit_syms_kernel<TX_V16_SHIFT, false>, nrq_emit_syms_kernel<TX_DWORD, false>,
+       nrq_emit_syms_kernel<TX_BYTE, false>},
+      {nrq_emit_syms_kernel<TX_V16, true>, nrq_emit_syms_kernel<TX_V16_SHIFT, true>, nrq_emit_syms_kernel<TX_DWORD, true>,
+       nrq_emit_syms_kernel<TX_BYTE, true>}};
+  static_assert(SY_PATH_V16 == TX_V16 && SY_PATH_V16_SHIFT == TX_V16_SHIFT && SY_PATH_DWORD == TX_DWORD && SY_PATH_BYTE == TX_BYTE,
+                "sy_emit_path names the emit kernels' modes");
+  nrq_ctx *ctx = tx->ctx;
+  const tx_src &s = tx->s;
+  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | s.seg[0].T;
+  for (uint32_t g = 0; g < s.nseg; g++)
+    al |= reinterpret_cast<uintptr_t>(s.seg[g].src) | s.seg[g].src_stride | reinterpret_cast<uintptr_t>(s.seg[g].inter) | s.seg[g].inter_stride;
+  const int mode = sy_emit_path(al, c.inl, ctx->tune.tx_dword ? 1u : 0u);
+  const uint32_t per = 64u / y.G, waves = (c.n + per - 1u) / per;
+  hipLaunchKernelGGL(kern[s.nseg > 1u][mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, s, c, y);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+static int sy_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym, void *d_pkts,
+                        size_t pkt_stride, uint32_t flags, int32_t *d_results) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  if (!d_tags || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u, G=%u)", who, n, G);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
+  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
+  if ((rc = tx->scratch.ensure(ctx, need))) return rc;
+  uint32_t *cnt = (uint32_t *)tx->scratch.p, *order = (uint32_t *)((uint8_t *)tx->scratch.p + o_order);
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt, order);
+  HIPCHK(ctx, hipGetLastError());
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.tags = d_tags;
+  c.order = order;
+  c.results = d_results;
+  sy_tx y{};
+  y.G = G; y.nsym = d_nsym;
+  return sy_tx_launch(tx, c, y);
+}
+
+/* range mode: ESIs esi0 .. esi0+eL-1 of the blocks of K = KL, esi0 .. esi0+eS-1 of those of K = KS, packetised per block */
+static int sy_emit_span(tx_sender *tx, const char *who, uint32_t KL, uint32_t KS, uint32_t esi0, uint32_t eL, uint32_t eS, uint32_t G, int order,
+                        void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt) {
+  nrq_ctx *ctx = tx->ctx;
+  if (tx->relay)
+    for (uint32_t b = 0; b < tx->s.Z; b++)
+      if (!tx_is_ready(tx, b)) return fail(ctx, -1, "%s: blocks of the relay are not ready: SBN %s", who, relay_missing(tx).c_str());
+  const uint32_t ZL = tx->s.ZL, ZS = tx->s.Z - ZL;
+  if (!ZL) { KL = KS; eL = eS; } /* (a table of one class has its counts in both: the one-segment maps) */
+  const uint32_t pL = sy_pkt_count(KL, esi0, eL, G), pS = ZS ? sy_pkt_count(KS, esi0, eS, G) : pL;
+  const uint64_t total = (uint64_t)ZL * pL + (uint64_t)ZS * pS;
+  if (total * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: %llu packets of %u symbols are too many", who, (unsigned long long)total, G);
+  if (h_npkt) *h_npkt = (uint32_t)total;
+  if (total == 0) return 0;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = (uint32_t)total;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  c.esi0 = esi0;
+  c.nL = ZL ? pL : pS;
+  c.nS = pS;
+  c.interleave = (uint32_t)order;
+  c.tags_out = d_tags_out;
+  sy_tx y{};
+  y.G = G; y.nsym_out = d_nsym_out; y.eL = eL; y.eS = eS;
+  return sy_tx_launch(tx, c, y);
+}
+
+extern "C" {
+
+uint32_t nrq_pkt_count(uint32_t K, uint32_t esi0, uint32_t n, uint32_t G) { return G ? sy_pkt_count(K, esi0, n, G) : 0u; }
+
+int nrq_rx_add_syms(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                    uint32_t flags, int32_t *d_results) {
+  if (!rx) return -1;
+  return rx_add_syms(rx, "nrq_rx_add_syms", d_pkts, pkt_stride, d_tags, n, G, d_nsym, flags, d_results);
+}
+
+int nrq_orx_add_syms(nrq_orx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                     uint32_t flags, int32_t *d_results) {
+  if (!rx) return -1;
+  nrq_ctx *ctx = rx->ctx;
+  for (nrq_rx *r : rx->rx) {
+    if (!r) continue;
+    const int rc = rx_add_syms(r, "nrq_orx_add_syms", d_pkts, pkt_stride, d_tags, n, G, d_nsym, flags, d_results);
+    if (rc) return rc;
+  }
+  if (n == 0 || !d_results) return 0;
+  hipLaunchKernelGGL(nrq_orx_foreign_syms_kernel, dim3((n * G + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint8_t *)d_pkts,
+                     (uint64_t)pkt_stride, d_tags, n, G, d_nsym, rx->prm.Z, rx->prm.max_esi, d_results);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int nrq_tx_emit_syms(nrq_tx *tx, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym, void *d_pkts, size_t pkt_stride,
+                     uint32_t flags, int32_t *d_results) {
+  return sy_emit_list(tx, "nrq_tx_emit_syms", d_tags, n, G, d_nsym, d_pkts, pkt_stride, flags, d_results);
+}
+
+int nrq_otx_emit_syms(nrq_otx *tx, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym, void *d_pkts, size_t pkt_stride,
+                      uint32_t flags, int32_t *d_results) {
+  return sy_emit_list(tx, "nrq_otx_emit_syms", d_tags, n, G, d_nsym, d_pkts, pkt_stride, flags, d_results);
+}
+
+int nrq_tx_emit_range_syms(nrq_tx *tx, uint32_t esi0, uint32_t n, uint32_t G, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                           uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  const char *who = "nrq_tx_emit_range_syms";
+  if (h_npkt) *h_npkt = 0;
+  int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
+  if (rc) return rc;
+  if (order != 0 && order != 1) return fail(ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
+  if (n == 0) return 0;
+  if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "%s: ESIs %u + %u reach past 2^24", who, esi0, n);
+  const uint32_t K = tx->s.seg[0].K;
+  return sy_emit_span(tx, who, K, K, esi0, n, n, G, order, d_pkts, pkt_stride, flags, d_tags_out, d_nsym_out, h_npkt);
+}
+
+int nrq_otx_emit_all_syms(nrq_otx *tx, uint32_t nrep, uint32_t G, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                          uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt) {
+  if (!tx) return -1;
+  nrq_ctx *ctx = tx->ctx;
+  const char *who = "nrq_otx_emit_all_syms";
+  if (h_npkt) *h_npkt = 0;
+  int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
+  if (rc) return rc;
+  if (order != 0 && order != 1) return fail(ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
+  const nrq_obj_params &p = tx->prm;
+  const uint64_t kmax = std::max(p.ZL ? p.KL : 0u, p.KS);
+  if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "%s: ESIs up to %llu + %u reach past 2^24", who, (unsigned long long)kmax, nrep);
+  return sy_emit_span(tx, who, p.KL, p.KS, 0, p.KL + nrep, p.KS + nrep, G, order, d_pkts, pkt_stride, flags, d_tags_out, d_nsym_out, h_npkt);
 }
 
 } /* extern "C" */
