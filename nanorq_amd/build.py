@@ -152,13 +152,13 @@ def build_ingest_emu(force=False):
 
 def build_emit_emu(force=False):
     """tests/emu/libemit_emu.so: CPU emulation of the device-resident emit kernel (csrc/emit_emu.cpp over emit_body.h)."""
-    return _build_emu(XEMU, os.path.join(CSRC, "emit_emu.cpp"), ("emit_body.h", "rq_math.h"), force)
+    return _build_emu(XEMU, os.path.join(CSRC, "emit_emu.cpp"), ("emit_emu.h", "emit_body.h", "rq_math.h"), force)
 
 
 def build_held_emu(force=False):
     """tests/emu/libheld_emu.so: CPU emulation of the held-symbol emit and of the held listing (csrc/held_emu.cpp over emit_body.h
     and held_body.h)."""
-    return _build_emu(HEMU, os.path.join(CSRC, "held_emu.cpp"), ("emit_body.h", "held_body.h", "ingest_body.h", "rq_math.h"), force)
+    return _build_emu(HEMU, os.path.join(CSRC, "held_emu.cpp"), ("emit_emu.h", "emit_body.h", "held_body.h", "ingest_body.h", "rq_math.h"), force)
 
 
 def build_want_emu(force=False):
@@ -193,7 +193,7 @@ def build_txset_emu(force=False):
 def build_syms_emu(force=False):
     """tests/emu/libsyms_emu.so: CPU emulation of the emit and ingest of packets of several symbols (csrc/syms_emu.cpp over
     syms_body.h), with the count rule, the range packetisation and the path rules behind C entry points."""
-    return _build_emu(YEMU, os.path.join(CSRC, "syms_emu.cpp"), ("syms_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
+    return _build_emu(YEMU, os.path.join(CSRC, "syms_emu.cpp"), ("emit_emu.h", "syms_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
 
 
 def build_obj_emu(force=False):

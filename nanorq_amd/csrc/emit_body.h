@@ -298,6 +298,32 @@ struct alignas(16) tx_u128 {
 };
 TX_HD tx_u128 operator^(tx_u128 a, tx_u128 b) { return tx_u128{a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w}; }
 
+/* payload paths of the emit kernels, chosen per call from the alignment of the rows, the packets and T */
+enum : int {
+  TX_V16 = 0,       /* 16-byte loads and stores (payload at +0) */
+  TX_V16_SHIFT = 1, /* 16-byte loads and stores under an inline header: the payload moves up one dword across the lanes */
+  TX_DWORD = 2,     /* 4-byte loads and stores */
+  TX_BYTE = 3
+};
+
+/* what decides the path: the OR of the packet buffer's address and stride, T and every row table's address and stride (h: the
+ * held table of an NRQ_TX_HELD call, whose repair rows are copied too; else NULL) */
+TX_HD uint64_t tx_align(const struct tx_src *s, const struct tx_call *c, const struct tx_held *h) {
+  uint64_t al = (uint64_t)(uintptr_t)c->pkts | c->pkt_stride | s->seg[0].T;
+  for (uint32_t g = 0; g < s->nseg; g++) {
+    const struct tx_blk *t = &s->seg[g];
+    al |= (uint64_t)(uintptr_t)t->src | t->src_stride | (uint64_t)(uintptr_t)t->inter | t->inter_stride;
+    if (h) al |= (uint64_t)(uintptr_t)h->seg[g].rep | h->seg[g].rep_stride;
+  }
+  return al;
+}
+
+/* the path: the widest word every address of the call allows (force_dword: the tuning knob that keeps a call off the 16-byte paths) */
+TX_HD int tx_emit_path(uint64_t al, uint32_t inl, uint32_t force_dword) {
+  if ((al & 15u) == 0 && !force_dword) return inl ? TX_V16_SHIFT : TX_V16;
+  return (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
+}
+
 /* one whole packet, a byte at a time (the emulation; the kernels' byte path does the same with a lane per byte) */
 TX_HD void tx_emit_bytes(const struct tx_blk *t, const struct tx_call *c, uint32_t k, uint32_t tag, const uint32_t *cols, uint32_t n) {
   const uint8_t *base = tx_base(t, tag);

@@ -8,7 +8,7 @@
 
 #include <vector>
 
-#include "emit_body.h"
+#include "emit_emu.h"
 
 /* every work item in order; -2: the work order is not a permutation of the packets */
 template <bool MULTI>
@@ -34,7 +34,7 @@ extern "C" {
 
 /* The emit from a table of nseg segments WITH A READY MASK (a relay's table): ready = 8 words, bit b = block b of the span may
  * be emitted; a packet of another block of the span is left untouched with the result -2.  Otherwise as emu_emit_table, which
- * is this with all ones. */
+ * is this with all ones (ready = NULL). */
 int emu_emit_table_ready(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
                          const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
                          uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out, const uint32_t *ready);
@@ -45,38 +45,21 @@ int emu_emit_table_ready(const uint32_t *prm, uint32_t nseg, const uint32_t *spa
 int emu_emit_table(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
                    const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
                    uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out) {
-  const uint32_t all[8] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
   return emu_emit_table_ready(prm, nseg, span, src, src_stride, inter, inter_stride, tags, n, range, inl, pkts, pkt_stride, results,
-                              tags_out, all);
+                              tags_out, nullptr);
 }
 
 int emu_emit_table_ready(const uint32_t *prm, uint32_t nseg, const uint32_t *span, const uint8_t *const *src, const uint64_t *src_stride,
                          const uint8_t *const *inter, const uint64_t *inter_stride, const uint32_t *tags, uint32_t n, const uint32_t *range,
                          uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results, uint32_t *tags_out, const uint32_t *ready) {
   tx_src s;
-  memset(&s, 0, sizeof(s));
-  if (nseg == 0 || nseg > TX_SEGS) return -1;
-  for (uint32_t g = 0; g < nseg; g++) {
-    const uint32_t *q = prm + 5u * g;
-    tx_blk &t = s.seg[g];
-    if (!rq_params_init(q[1], &t.p) || t.p.Kp != q[1] || q[0] == 0 || q[0] > q[1]) return -1;
-    t.p.K = q[0];
-    t.K = q[0]; t.T = q[2]; t.nblk = q[3]; t.sbn0 = q[4];
-    t.src = src[g]; t.src_stride = src_stride[g]; t.inter = inter[g]; t.inter_stride = inter_stride[g];
-  }
-  s.nseg = nseg; s.sbn0 = span[0]; s.Z = span[1]; s.ZL = span[2];
-  memcpy(s.ready, ready, sizeof(s.ready));
+  if (!emu_tx_table(&s, prm, nseg, span, src, src_stride, inter, inter_stride, ready)) return -1;
   tx_call c;
   memset(&c, 0, sizeof(c));
   c.pkts = pkts; c.pkt_stride = pkt_stride; c.inl = inl;
-  std::vector<uint32_t> order(tags && n ? n : 1u);
+  std::vector<uint32_t> order;
   if (tags) {
-    /* the bucketing passes: per-bucket counts, exclusive scan, placement (the kernels place inside a bucket in any order) */
-    std::vector<uint32_t> cnt(s.Z + 1u, 0);
-    for (uint32_t k = 0; k < n; k++) cnt[tx_bin(s.sbn0, s.Z, tags[k])]++;
-    uint32_t run_ = 0;
-    for (uint32_t b = 0; b <= s.Z; b++) { const uint32_t v = cnt[b]; cnt[b] = run_; run_ += v; }
-    for (uint32_t k = 0; k < n; k++) order[cnt[tx_bin(s.sbn0, s.Z, tags[k])]++] = k;
+    order = emu_tx_bucket(&s, tags, n);
     c.n = n; c.tags = tags; c.order = order.data(); c.results = results;
   } else {
     c.esi0 = range[0]; c.nL = range[1]; c.nS = range[2]; c.interleave = range[3]; c.tags_out = tags_out;

@@ -4,14 +4,14 @@
  * nrq_emit_held_kernel does it per wave (each lane probes rep_esi[b][q0 + lane], a ballot and a find-first give the row, the
  * result is written after the trips, n and kind travel packed through a readfirstlane) and picks the row's base itself; that
  * wave-level code is covered by the byte-exact GPU tests only (tests/test_gpu_held.py).  Test support, not part of the library:
- * build.build_held_emu() makes tests/emu/libheld_emu.so of it.  The plain emit's emulation (emit_emu.cpp) is left as it is; this
- * file repeats its table set-up for the form with a held table. */
+ * build.build_held_emu() makes tests/emu/libheld_emu.so of it.  The table set-up and the bucketing are emit_emu.h's, shared with the
+ * plain emit's emulation (emit_emu.cpp). */
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
-#include "emit_body.h"
+#include "emit_emu.h"
 #include "held_body.h"
 
 /* every work item in order, as nrq_emit_held_kernel; -2: the work order is not a permutation of the packets */
@@ -63,31 +63,17 @@ int emu_emit_held(const uint32_t *prm, uint32_t nseg, const uint32_t *span, cons
                   uint64_t pkt_stride, int32_t *results) {
   tx_src s;
   tx_held h;
-  memset(&s, 0, sizeof(s));
   memset(&h, 0, sizeof(h));
-  if (nseg == 0 || nseg > TX_SEGS || !tags) return -1;
+  if (!tags || !emu_tx_table(&s, prm, nseg, span, src, src_stride, inter, inter_stride, ready)) return -1;
   for (uint32_t g = 0; g < nseg; g++) {
-    const uint32_t *q = prm + 5u * g;
-    tx_blk &t = s.seg[g];
-    if (!rq_params_init(q[1], &t.p) || t.p.Kp != q[1] || q[0] == 0 || q[0] > q[1]) return -1;
-    t.p.K = q[0];
-    t.K = q[0]; t.T = q[2]; t.nblk = q[3]; t.sbn0 = q[4];
-    t.src = src[g]; t.src_stride = src_stride[g]; t.inter = inter[g]; t.inter_stride = inter_stride[g];
     tx_held_seg &hs = h.seg[g];
     hs.seen = seen[g]; hs.bm_words = bm_words[g]; hs.rep_esi = rep_esi[g]; hs.nrep = nrep[g]; hs.rep_cap = rep_cap[g];
     hs.rep = rep[g]; hs.rep_stride = rep_stride[g];
   }
-  s.nseg = nseg; s.sbn0 = span[0]; s.Z = span[1]; s.ZL = span[2];
-  memcpy(s.ready, ready, sizeof(s.ready));
   tx_call c;
   memset(&c, 0, sizeof(c));
   c.pkts = pkts; c.pkt_stride = pkt_stride; c.inl = inl;
-  /* the bucketing passes: per-bucket counts, exclusive scan, placement */
-  std::vector<uint32_t> order(n ? n : 1u), cnt(s.Z + 1u, 0);
-  for (uint32_t k = 0; k < n; k++) cnt[tx_bin(s.sbn0, s.Z, tags[k])]++;
-  uint32_t run_ = 0;
-  for (uint32_t b = 0; b <= s.Z; b++) { const uint32_t v = cnt[b]; cnt[b] = run_; run_ += v; }
-  for (uint32_t k = 0; k < n; k++) order[cnt[tx_bin(s.sbn0, s.Z, tags[k])]++] = k;
+  const std::vector<uint32_t> order = emu_tx_bucket(&s, tags, n);
   c.n = n; c.tags = tags; c.order = order.data(); c.results = results;
   return nseg > 1u ? run_held<true>(&s, &h, &c) : run_held<false>(&s, &h, &c);
 }

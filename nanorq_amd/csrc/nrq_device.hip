@@ -2715,7 +2715,10 @@ __device__ __forceinline__ uint32_t wg_scan_runs(uint32_t *ps, uint32_t t, uint3
 
 /* ================================================ device-resident receiver (nrq_rx_*, ingest_body.h) ==== */
 /* The per-block passes as workgroup bodies of (reception, block): nrq_ing_*_kernel runs them on its by-value reception and
- * blockIdx.x, nrq_ings_*_kernel on the member and block it finds in the set's table (lss_block). */
+ * blockIdx.x, nrq_ings_*_kernel on the member and block it finds in the set's table (lss_block).  The per-tile ranking of the
+ * classify pass is a body too (ing_rank_wg), behind the one-symbol, the several-symbol and the set's classify kernel.  The three
+ * tile histogram kernels keep their own few lines: the single forms count in 256 static words, a word per thread, the set's in
+ * a dynamic array walked by loops, and one body for both would change the single forms' code. */
 
 /* done: the max and the count of ing_done_part over the block's K source ESIs */
 __device__ __forceinline__ void ing_done_wg(const ing_rx *r, uint32_t b, uint32_t *smx, uint32_t *scnt) {
@@ -2762,6 +2765,33 @@ __device__ __forceinline__ void ing_lists_fill_wg(const ing_rx *r, uint32_t b, u
   }
 }
 
+/* rank: the row of the thread's repair candidate (block g of the `stride` the tile counts per wave, or ING_NONE) -- the tile's
+ * first row for the block, from the scan, plus the candidate's rank among the block's candidates in the tile, in packet order:
+ * wave by wave a ballot per distinct block present in the wave, whose count goes to wc[wave * stride + block] (zeroed by the
+ * caller, a barrier behind it) for the waves after it.  ING_NONE for no candidate. */
+__device__ __forceinline__ uint32_t ing_rank_wg(uint32_t *wc, uint32_t stride, uint32_t g, const uint32_t *base, uint32_t ntiles) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const bool cand = g != ING_NONE;
+  uint64_t todo = __ballot(cand);
+  uint32_t rank = 0;
+  while (todo) { /* (wave-uniform) */
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t lg = __shfl(g, leader);
+    const bool mine = cand && g == lg;
+    const uint64_t m = __ballot(mine);
+    if (mine) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if ((int)lane == leader) wc[w * stride + lg] = (uint32_t)__popcll(m);
+    todo &= ~m;
+  }
+  __syncthreads();
+  uint32_t row = ING_NONE;
+  if (cand) {
+    row = base[(size_t)g * ntiles + blockIdx.x] + rank;
+    for (uint32_t w2 = 0; w2 < w; w2++) row += wc[w2 * stride + g];
+  }
+  return row;
+}
+
 __global__ __launch_bounds__(256) void nrq_ing_init_kernel(ing_rx r) {
   const uint32_t b = blockIdx.x * 256u + threadIdx.x;
   if (b < r.nblk) { r.gaps[b] = r.K; r.nrep[b] = 0; }
@@ -2798,32 +2828,14 @@ __global__ __launch_bounds__(256) void nrq_ing_scan_kernel(ing_rx r, ing_call c)
   ing_scan_wg(&r, blockIdx.x, c.base + (size_t)blockIdx.x * c.ntiles, c.ntiles, ps);
 }
 
-/* one workgroup per tile: a candidate's rank among its block's candidates in the tile, in packet order (wave by wave: a ballot
- * per distinct block present in the wave), then the result of every packet */
+/* one workgroup per tile: the row of every repair candidate (ing_rank_wg, 256 counters per wave), then the result of every packet */
 __global__ __launch_bounds__(256) void nrq_ing_classify_kernel(ing_rx r, ing_call c) {
   __shared__ uint32_t wc[4][256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6, k = blockIdx.x * ING_TILE + t;
+  const uint32_t t = threadIdx.x, k = blockIdx.x * ING_TILE + t;
   for (uint32_t i = t; i < 4u * 256u; i += 256u) wc[i >> 8][i & 255u] = 0;
   __syncthreads();
   const uint32_t b = k < c.n ? ing_cand(&r, &c, k) : ING_NONE;
-  const bool cand = b != ING_NONE;
-  uint64_t todo = __ballot(cand);
-  uint32_t rank = 0;
-  while (todo) { /* (wave-uniform) */
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(b, leader);
-    const bool mine = cand && b == lb;
-    const uint64_t m = __ballot(mine);
-    if (mine) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if ((int)lane == leader) wc[w][lb] = (uint32_t)__popcll(m);
-    todo &= ~m;
-  }
-  __syncthreads();
-  uint32_t row = ING_NONE;
-  if (cand) {
-    row = c.base[(size_t)b * c.ntiles + blockIdx.x] + rank;
-    for (uint32_t w2 = 0; w2 < w; w2++) row += wc[w2][b];
-  }
+  const uint32_t row = ing_rank_wg(&wc[0][0], 256u, b, c.base, c.ntiles);
   if (k < c.n) ing_classify(&r, &c, k, row);
 }
 
@@ -2926,6 +2938,41 @@ static int rx_init_state(nrq_rx *rx) {
   return 0;
 }
 
+/* What the add calls share once the flags are read and there is something to do: the checks of the packet arguments (G: symbols a
+ * packet can carry, 0 in the one-symbol forms, whose texts do not speak of it; pkt_len: the shortest stride a packet fits) and the
+ * ing_call over n items -- packets, or slots -- of nblk blocks, its arrays carved out of `scratch` with `tail` more bytes behind them
+ * at *tailp for the form's own array. */
+static int ing_call_of(nrq_ctx *ctx, DevScratch &scratch, const char *who, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags,
+                       uint32_t n, uint32_t G, size_t pkt_len, bool inl, uint32_t nblk, int32_t *d_results, size_t tail, ing_call *c,
+                       uint8_t **tailp) {
+  const uint64_t items = (uint64_t)n * (G ? G : 1u);
+  if (!d_pkts || items > 0x7FFFFFFFu) return G ? fail(ctx, -1, "%s: bad packets (n=%u, G=%u)", who, n, G) : fail(ctx, -1, "%s: bad packets (n=%u)", who, n);
+  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "%s: give either d_tags or NRQ_RX_TAG_INLINE", who);
+  if (pkt_stride < pkt_len)
+    return G ? fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G)
+             : fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet", who, pkt_stride);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t ni = (uint32_t)items;
+  *c = ing_call{};
+  c->pkts = (const uint8_t *)d_pkts;
+  c->pkt_stride = pkt_stride;
+  c->tags = d_tags;
+  c->n = ni;
+  c->ntiles = (ni + ING_TILE - 1u) / ING_TILE;
+  const size_t o_codes = rx_al((size_t)ni * 4u), o_fidx = o_codes + rx_al((size_t)ni * 4u), o_dst = o_fidx + rx_al((size_t)ni * 4u),
+               o_base = o_dst + rx_al((size_t)ni * 8u), o_tail = o_base + rx_al((size_t)nblk * c->ntiles * 4u);
+  const int rc = scratch.ensure(ctx, o_tail + rx_al(tail));
+  if (rc) return rc;
+  uint8_t *s = (uint8_t *)scratch.p;
+  c->tagv = (uint32_t *)s;
+  c->codes = d_results ? d_results : (int32_t *)(s + o_codes);
+  c->fidx = (uint32_t *)(s + o_fidx);
+  c->dst = (uint64_t *)(s + o_dst);
+  c->base = (uint32_t *)(s + o_base);
+  if (tailp) *tailp = s + o_tail;
+  return 0;
+}
+
 extern "C" {
 
 int nrq_rx_create(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint32_t nblk, uint32_t sbn0, uint32_t max_esi, uint32_t rep_cap,
@@ -3011,26 +3058,10 @@ int nrq_rx_add(nrq_rx *rx, const void *d_pkts, size_t pkt_stride, const uint32_t
   const bool inl = (flags & NRQ_RX_TAG_INLINE) != 0;
   if (flags & ~(uint32_t)NRQ_RX_TAG_INLINE) return fail(ctx, -1, "nrq_rx_add: unknown flags 0x%x", flags);
   if (n == 0) return 0;
-  if (!d_pkts || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_rx_add: bad packets (n=%u)", n);
-  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "nrq_rx_add: give either d_tags or NRQ_RX_TAG_INLINE");
-  if (pkt_stride < (size_t)r.T + (inl ? 4u : 0u)) return fail(ctx, -1, "nrq_rx_add: pkt_stride %zu shorter than a packet", pkt_stride);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  ing_call c{};
-  c.pkts = (const uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.tags = d_tags;
-  c.n = n;
-  c.ntiles = (n + ING_TILE - 1u) / ING_TILE;
-  const size_t o_codes = rx_al((size_t)n * 4u), o_fidx = o_codes + rx_al((size_t)n * 4u), o_dst = o_fidx + rx_al((size_t)n * 4u),
-               o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)r.nblk * c.ntiles * 4u);
-  const int rc = rx->scratch.ensure(ctx, need);
+  ing_call c;
+  const int rc = ing_call_of(ctx, rx->scratch, "nrq_rx_add", d_pkts, pkt_stride, d_tags, n, 0, (size_t)r.T + (inl ? 4u : 0u), inl, r.nblk,
+                             d_results, 0, &c, nullptr);
   if (rc) return rc;
-  uint8_t *s = (uint8_t *)rx->scratch.p;
-  c.tagv = (uint32_t *)s;
-  c.codes = d_results ? d_results : (int32_t *)(s + o_codes);
-  c.fidx = (uint32_t *)(s + o_fidx);
-  c.dst = (uint64_t *)(s + o_dst);
-  c.base = (uint32_t *)(s + o_base);
   hipStream_t st = ctx->stream;
   const uint32_t g = (n + 255u) / 256u;
   hipLaunchKernelGGL(nrq_ing_first_kernel, dim3(g), dim3(256), 0, st, r, c);
@@ -3199,47 +3230,93 @@ int nrq_rx_decode(nrq_rx *rx, int *h_status, uint32_t *h_used) {
 #define TX_WAVES 4u        /* waves per emit workgroup */
 #define TX_BIN_TILE 4096u  /* packets per workgroup of the bucketing passes */
 
-/* payload paths of the emit kernel, chosen per call from the alignment of the rows, the packets and T */
-enum : int {
-  TX_V16 = 0,       /* 16-byte loads and stores (payload at +0) */
-  TX_V16_SHIFT = 1, /* 16-byte loads and stores under an inline header: the payload moves up one dword across the lanes */
-  TX_DWORD = 2,     /* 4-byte loads and stores */
-  TX_BYTE = 3
+/* (the payload paths TX_V16 .. TX_BYTE and the rule that picks one per call: tx_emit_path, emit_body.h)
+ *
+ * Shared by every emit kernel -- the plain, held, several-symbol and set forms, each a kernel of its own so that the older ones'
+ * instantiations are compiled from the code they always were -- are the bodies that follow: the payload walk (tx_payload, over one
+ * symbol or a run of them), the wave-uniform segment base (TX_SEG_BASE) and the held repair row lookup (tx_held_row). */
+
+/* What a payload walk reads, a compile-time choice: the rows of ONE symbol -- the walk is T bytes long and every word takes the
+ * one column list -- or a RUN of cnt symbols of one block with consecutive ESIs (syms_body.h), cnt * T bytes long, where the word
+ * at byte off takes the list of slot off / T (slot i's list at cols[i], its length in the low byte of ns[i]; T is a multiple of
+ * the word: a word lies in one symbol). */
+struct tx_one {
+  const uint32_t *cols;
+  uint32_t n;
+  __device__ __forceinline__ uint32_t len(uint32_t T) const { return T; }
+  template <typename W>
+  __device__ __forceinline__ W word(const uint8_t *__restrict__ base, uint32_t T, uint64_t off) const {
+    return tx_gather<W>(base, T, cols, n, off);
+  }
+};
+struct tx_run {
+  const uint32_t (*cols)[TX_COLS];
+  const uint32_t *ns;
+  uint32_t cnt;
+  __device__ __forceinline__ uint32_t len(uint32_t T) const { return cnt * T; }
+  template <typename W>
+  __device__ __forceinline__ W word(const uint8_t *__restrict__ base, uint32_t T, uint64_t off) const {
+    const uint32_t o = (uint32_t)off, i = o / T; /* (cnt * T fits 32 bits: the launcher checked) */
+    return tx_gather<W>(base, T, cols[i], ns[i] & 0xFFu, o - i * T);
+  }
 };
 
-/* the packet of `tag` at P: its payload is the XOR of rows cols[0..n) from base (one wave; a 16/4/1-byte word per lane) */
-template <int MODE>
-__device__ __forceinline__ void tx_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t *cols, uint32_t n, uint32_t tag,
+/* the packet of `tag` at P: its payload is, word by word, the XOR of the rows `rows` names from base (one wave; a 16/4/1-byte word
+ * per lane) */
+template <int MODE, class ROWS>
+__device__ __forceinline__ void tx_payload(const uint8_t *__restrict__ base, uint32_t T, const ROWS rows, uint32_t tag,
                                            uint8_t *__restrict__ P, uint32_t inl, uint32_t lane) {
+  const uint32_t len = rows.len(T);
   if constexpr (MODE == TX_V16) {
-    for (uint32_t off = lane * 16u; off < T; off += 64u * 16u)
-      *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols, n, off);
+    for (uint32_t off = lane * 16u; off < len; off += 64u * 16u)
+      *reinterpret_cast<tx_u128 *>(P + off) = rows.template word<tx_u128>(base, T, off);
   } else if constexpr (MODE == TX_V16_SHIFT) {
     /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-1 .. 4j+2: the previous lane's .w (the header for j = 0, the
-     * wave's last lane of the previous round for its first lane), then this chunk's .x .y .z; the last .w goes to +T */
-    const uint32_t nch = T >> 4;
+     * wave's last lane of the previous round for its first lane) whether or not a symbol boundary lies between the two, then
+     * this chunk's .x .y .z; the last .w goes to +len */
+    const uint32_t nch = len >> 4;
     uint32_t carry = tx_header_word(tag);
     for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
       const uint32_t j = j0 + lane;
       const bool act = j < nch;
       tx_u128 v{0u, 0u, 0u, 0u};
-      if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
+      if (act) v = rows.template word<tx_u128>(base, T, (uint64_t)j * 16u);
       uint32_t prev = __shfl_up(v.w, 1u);
       if (lane == 0) prev = carry;
       if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
-      if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + T) = v.w;
+      if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + len) = v.w;
       carry = __shfl(v.w, 63);
     }
   } else if constexpr (MODE == TX_DWORD) {
     if (inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
     uint8_t *D = P + (inl ? 4u : 0u);
-    for (uint32_t off = lane * 4u; off < T; off += 64u * 4u)
-      *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols, n, off);
+    for (uint32_t off = lane * 4u; off < len; off += 64u * 4u)
+      *reinterpret_cast<uint32_t *>(D + off) = rows.template word<uint32_t>(base, T, off);
   } else {
     if (inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
     uint8_t *D = P + (inl ? 4u : 0u);
-    for (uint32_t off = lane; off < T; off += 64u) D[off] = tx_gather<uint8_t>(base, T, cols, n, off);
+    for (uint32_t off = lane; off < len; off += 64u) D[off] = rows.template word<uint8_t>(base, T, off);
   }
+}
+
+/* the rows of a packet of `tag` in segment sg of the kernel's by-value table s, sg wave-uniform: rebuilt from the kernel arguments (a
+ * pointer kept in LDS would come back as a generic one: flat loads, and waits that also cover the LDS reads), and only the chosen
+ * segment's fields are read (segment 0's base, replaced after a test, costs two dependent argument loads per packet).  MULTI =
+ * false: a one-segment table.  A macro: the same select in a function that takes the table by reference, pointer or value makes
+ * the compiler index the table with sg, and the multi-segment kernels then copy their arguments to 344 bytes of scratch. */
+#define TX_SEG_BASE(MULTI, s, sg, tag) \
+  (!(MULTI) || (sg) == 0u ? tx_base(&(s).seg[0], tag) : (sg) == 1u ? tx_base(&(s).seg[1], tag) : tx_base(&(s).seg[2], tag))
+
+/* the repair row of block b of a reception that holds ESI `esi`, or TX_NONE: each lane probes one entry of the block's repair list
+ * per trip (64 consecutive entries, one coalesced load), a ballot gives the wave-uniform row (tx_held_find, a wave at a time) */
+__device__ __forceinline__ uint32_t tx_held_row(const tx_held_seg *hs, uint32_t b, uint32_t esi, uint32_t lane) {
+  const uint32_t nrep = tx_held_nrep(hs, b);
+  uint32_t q = TX_NONE;
+  for (uint32_t q0 = 0; q0 < nrep && q == TX_NONE; q0 += 64u) {
+    const uint64_t m = __ballot(tx_held_hit(hs, b, q0 + lane, nrep, esi));
+    if (m) q = q0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+  }
+  return q;
 }
 
 /* One wave per TX_WAVE_PKTS work items, in block-major order: each lane builds the column list of one item into LDS, then the
@@ -3274,24 +3351,15 @@ __global__ __launch_bounds__(256) void nrq_emit_kernel(tx_src s, tx_call c) {
     const uint32_t n = s_n[wv][i];
     if (!n) continue; /* SBN outside the span, or a block that is not ready: the packet stays untouched */
     const uint32_t tag = s_tag[wv][i];
-    const uint8_t *base;
-    if constexpr (MULTI) {
-      /* the rows' base rebuilt from the kernel arguments with a wave-uniform segment (a pointer kept in LDS would come back as a
-       * generic one: flat loads, and waits that also cover the LDS reads); only the chosen segment's fields are read (segment
-       * 0's base, replaced after a test, costs two dependent argument loads per packet) */
-      const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][i]);
-      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
-    } else {
-      base = tx_base(&s.seg[0], tag);
-    }
-    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
+    const uint32_t sg = MULTI ? __builtin_amdgcn_readfirstlane(s_seg[wv][i]) : 0u;
+    tx_payload<MODE>(TX_SEG_BASE(MULTI, s, sg, tag), T, tx_one{s_cols[wv][i], n}, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl,
+                     lane);
   }
 }
 
 /* The emit kernel with held symbols (NRQ_TX_HELD; relays only, a tag list only): as nrq_emit_kernel, but a packet of a block that is
  * not ready is still written when the reception holds its symbol (tx_admit_held) -- a copy of the source row, or of the repair
- * row whose ESI it is.  That row is found by the wave that writes the packet: each lane probes one entry of the block's repair
- * list per trip (64 consecutive ESIs, one coalesced load), a ballot gives the wave-uniform row.  A kernel of its own, so that the
+ * row whose ESI it is.  That row is found by the wave that writes the packet (tx_held_row).  A kernel of its own, so that the
  * plain emit's instantiations are compiled from the code they always were. */
 template <int MODE, bool MULTI>
 __global__ __launch_bounds__(256) void nrq_emit_held_kernel(tx_src s, tx_held h, tx_call c) {
@@ -3330,21 +3398,14 @@ __global__ __launch_bounds__(256) void nrq_emit_held_kernel(tx_src s, tx_held h,
     if ((nk >> 8) == TX_HELD_REP) {
       const tx_held_seg hs = sg == 0u ? h.seg[0] : sg == 1u ? h.seg[1] : h.seg[2];
       const uint32_t b = (tag >> 24) - (sg == 0u ? s.seg[0].sbn0 : sg == 1u ? s.seg[1].sbn0 : s.seg[2].sbn0);
-      const uint32_t nrep = tx_held_nrep(&hs, b), esi = tag & 0xFFFFFFu;
-      uint32_t q = TX_NONE;
-      for (uint32_t q0 = 0; q0 < nrep && q == TX_NONE; q0 += 64u) {
-        const uint64_t m = __ballot(tx_held_hit(&hs, b, q0 + lane, nrep, esi));
-        if (m) q = q0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
-      }
+      const uint32_t q = tx_held_row(&hs, b, tag & 0xFFFFFFu, lane);
       if (c.results && lane == 0) c.results[s_k[wv][i]] = q == TX_NONE ? TX_NOT_READY : 0;
       if (q == TX_NONE) continue; /* (the books say otherwise: a marked repair ESI has its row) */
       base = tx_held_rep_base(&hs, b) + (uint64_t)q * T;
-    } else if constexpr (MULTI) {
-      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
     } else {
-      base = tx_base(&s.seg[0], tag);
+      base = TX_SEG_BASE(MULTI, s, sg, tag);
     }
-    tx_payload<MODE>(base, T, s_cols[wv][i], n, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
+    tx_payload<MODE>(base, T, tx_one{s_cols[wv][i], n}, tag, c.pkts + (uint64_t)s_k[wv][i] * c.pkt_stride, c.inl, lane);
   }
 }
 
@@ -3549,19 +3610,55 @@ static int tx_launch(tx_sender *tx, const tx_call &c, bool held = false) {
        nrq_emit_kernel<TX_BYTE, true>}};
   nrq_ctx *ctx = tx->ctx;
   const tx_src &s = tx->s;
-  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | s.seg[0].T;
-  for (uint32_t g = 0; g < s.nseg; g++)
-    al |= reinterpret_cast<uintptr_t>(s.seg[g].src) | s.seg[g].src_stride | reinterpret_cast<uintptr_t>(s.seg[g].inter) | s.seg[g].inter_stride;
-  tx_held h{};
-  if (held) {
-    h = tx_held_table(tx);
-    for (uint32_t g = 0; g < s.nseg; g++) al |= reinterpret_cast<uintptr_t>(h.seg[g].rep) | h.seg[g].rep_stride; /* (held repair rows are copied too) */
-  }
-  const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (c.inl ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
+  const tx_held h = held ? tx_held_table(tx) : tx_held{};
+  const int mode = tx_emit_path(tx_align(&s, &c, held ? &h : nullptr), c.inl, ctx->tune.tx_dword ? 1u : 0u);
   const dim3 grid((c.n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
   if (held) hipLaunchKernelGGL(hkern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, h, c);
   else hipLaunchKernelGGL(kern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, c);
   HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* a call's packet buffer: n packets at d_pkts, the header form of `flags` */
+static tx_call tx_call_of(void *d_pkts, size_t pkt_stride, uint32_t n, uint32_t flags) {
+  tx_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  return c;
+}
+
+/* list mode: the n tags bucketed by block of the span into the sender's scratch -- bucket counts, then the work order *order */
+static int tx_bucket(tx_sender *tx, const uint32_t *d_tags, uint32_t n, const uint32_t **order) {
+  nrq_ctx *ctx = tx->ctx;
+  const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
+  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
+  const int rc = tx->scratch.ensure(ctx, need);
+  if (rc) return rc;
+  uint32_t *cnt = (uint32_t *)tx->scratch.p, *ord = (uint32_t *)((uint8_t *)tx->scratch.p + o_order);
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt);
+  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt, ord);
+  HIPCHK(ctx, hipGetLastError());
+  *order = ord;
+  return 0;
+}
+
+/* range mode on a relay: every block of the span must be ready (the packet maps are analytic over all blocks: no holes) */
+static int tx_span_ready(tx_sender *tx, const char *who) {
+  if (tx->relay)
+    for (uint32_t b = 0; b < tx->s.Z; b++)
+      if (!tx_is_ready(tx, b)) return fail(tx->ctx, -1, "%s: blocks of the relay are not ready: SBN %s", who, relay_missing(tx).c_str());
+  return 0;
+}
+
+/* range mode: the packet order a caller asks for */
+static int tx_check_order(tx_sender *tx, const char *who, int order) {
+  if (order != 0 && order != 1) return fail(tx->ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
   return 0;
 }
 
@@ -3575,24 +3672,9 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
   if (n == 0) return 0;
   if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u)", who, n);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
-  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if ((rc = tx->scratch.ensure(ctx, need))) return rc;
-  uint32_t *cnt = (uint32_t *)tx->scratch.p, *order = (uint32_t *)((uint8_t *)tx->scratch.p + o_order);
-  hipStream_t st = ctx->stream;
-  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
-  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt);
-  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
-  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt, order);
-  HIPCHK(ctx, hipGetLastError());
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  tx_call c = tx_call_of(d_pkts, pkt_stride, n, flags);
+  if ((rc = tx_bucket(tx, d_tags, n, &c.order))) return rc;
   c.tags = d_tags;
-  c.order = order;
   c.results = d_results;
   return tx_launch(tx, c, (flags & NRQ_TX_HELD) != 0);
 }
@@ -3602,15 +3684,10 @@ static int tx_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
 static int tx_emit_span(tx_sender *tx, const char *who, uint32_t esi0, uint32_t nL, uint32_t nS, int order, void *d_pkts, size_t pkt_stride,
                         uint32_t flags, uint32_t *d_tags_out) {
   nrq_ctx *ctx = tx->ctx;
-  if (tx->relay) /* (the packet maps are analytic over all blocks: no holes) */
-    for (uint32_t b = 0; b < tx->s.Z; b++)
-      if (!tx_is_ready(tx, b)) return fail(ctx, -1, "%s: blocks of the relay are not ready: SBN %s", who, relay_missing(tx).c_str());
+  const int rc = tx_span_ready(tx, who);
+  if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = tx->s.ZL * nL + (tx->s.Z - tx->s.ZL) * nS;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  tx_call c = tx_call_of(d_pkts, pkt_stride, tx->s.ZL * nL + (tx->s.Z - tx->s.ZL) * nS, flags);
   c.esi0 = esi0;
   c.nL = tx->s.ZL ? nL : nS; /* (a table of one class has nL packets per block: the one-segment maps) */
   c.nS = nS;
@@ -3712,7 +3789,7 @@ int nrq_tx_emit_range(nrq_tx *tx, uint32_t esi0, uint32_t n, int order, void *d_
   nrq_ctx *ctx = tx->ctx;
   int rc = tx_check(tx, "nrq_tx_emit_range", d_pkts, pkt_stride, flags);
   if (rc) return rc;
-  if (order != 0 && order != 1) return fail(ctx, -1, "nrq_tx_emit_range: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
+  if ((rc = tx_check_order(tx, "nrq_tx_emit_range", order))) return rc;
   if (n == 0) return 0;
   if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "nrq_tx_emit_range: ESIs %u + %u reach past 2^24", esi0, n);
   if ((uint64_t)n * tx->s.Z > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_tx_emit_range: %u packets per block is too many", n);
@@ -3914,7 +3991,7 @@ int nrq_otx_emit_all(nrq_otx *tx, uint32_t nrep, int order, void *d_pkts, size_t
   nrq_ctx *ctx = tx->ctx;
   int rc = tx_check(tx, "nrq_otx_emit_all", d_pkts, pkt_stride, flags);
   if (rc) return rc;
-  if (order != 0 && order != 1) return fail(ctx, -1, "nrq_otx_emit_all: order %d is neither 0 (block-major) nor 1 (interleaved)", order);
+  if ((rc = tx_check_order(tx, "nrq_otx_emit_all", order))) return rc;
   const nrq_obj_params &p = tx->prm;
   const uint64_t kmax = std::max(p.ZL ? p.KL : 0u, p.KS);
   if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "nrq_otx_emit_all: ESIs up to %llu + %u reach past 2^24", (unsigned long long)kmax, nrep);
@@ -4062,7 +4139,9 @@ int nrq_orx_write(nrq_orx *rx, void *d_out) {
 } /* extern "C" */
 
 /* ================================================ packets of several symbols (nrq_*_syms, syms_body.h) ==== */
-/* Kernels of their own beside the one-symbol ones: every instantiation of those is compiled from the code it always was.
+/* Kernels of their own beside the one-symbol ones: every instantiation of those is compiled from the code it always was.  What is
+ * inside them is shared with those: the ranking (ing_rank_wg), the payload walk (tx_payload over a tx_run), the segment base, and
+ * on the host the path rule, the bucketing (tx_bucket) and the ingest call (ing_call_of).
  *
  * Ingest: the chain of nrq_rx_add over n * G slots.  Passes 2 and 4 are per block and are nrq_rx_add's kernels; passes 1, 3, 5, 7
  * are these, which ask syms_body.h what a slot is; pass 6 walks a packet's payloads as one contiguous run. */
@@ -4084,31 +4163,14 @@ __global__ __launch_bounds__(256) void nrq_ing_hist_syms_kernel(ing_rx r, ing_ca
   if (t < r.nblk) c.base[(size_t)t * c.ntiles + blockIdx.x] = h[t];
 }
 
-/* (the ranking of nrq_ing_classify_kernel: a ballot per distinct block present in the wave, in slot order) */
+/* (nrq_ing_classify_kernel over slots: the same ranking, in slot order) */
 __global__ __launch_bounds__(256) void nrq_ing_classify_syms_kernel(ing_rx r, ing_call c, sy_rx y) {
   __shared__ uint32_t wc[4][256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6, s = blockIdx.x * ING_TILE + t;
+  const uint32_t t = threadIdx.x, s = blockIdx.x * ING_TILE + t;
   for (uint32_t i = t; i < 4u * 256u; i += 256u) wc[i >> 8][i & 255u] = 0;
   __syncthreads();
   const uint32_t b = s < c.n ? sy_cand(&r, &c, &y, s) : ING_NONE;
-  const bool cand = b != ING_NONE;
-  uint64_t todo = __ballot(cand);
-  uint32_t rank = 0;
-  while (todo) { /* (wave-uniform) */
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lb = __shfl(b, leader);
-    const bool mine = cand && b == lb;
-    const uint64_t m = __ballot(mine);
-    if (mine) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if ((int)lane == leader) wc[w][lb] = (uint32_t)__popcll(m);
-    todo &= ~m;
-  }
-  __syncthreads();
-  uint32_t row = ING_NONE;
-  if (cand) {
-    row = c.base[(size_t)b * c.ntiles + blockIdx.x] + rank;
-    for (uint32_t w2 = 0; w2 < w; w2++) row += wc[w2][b];
-  }
+  const uint32_t row = ing_rank_wg(&wc[0][0], 256u, b, c.base, c.ntiles);
   if (s < c.n) sy_classify(&r, &c, &y, s, row);
 }
 
@@ -4166,52 +4228,8 @@ __global__ __launch_bounds__(256) void nrq_orx_foreign_syms_kernel(const uint8_t
  * a tag list bucketed by block), lane l the slot (l / G, l % G) -- a packet's slots are adjacent and never split across waves.
  * Each lane admits its packet (sy_tx_admit: per packet, so every lane of a packet decides alike) and builds its slot's column
  * list into LDS; then the wave writes the admitted packets one after the other, each as ONE run of c_k * T bytes with lanes across
- * the symbol boundaries: a lane gathers with the column list of the slot its word lies in. */
-template <int MODE>
-__device__ __forceinline__ void sy_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t (*cols)[TX_COLS], const uint32_t *ns,
-                                           uint32_t cnt, uint32_t tag, uint8_t *__restrict__ P, uint32_t inl, uint32_t lane) {
-  const uint32_t len = cnt * T;
-  if constexpr (MODE == TX_V16) {
-    for (uint32_t off = lane * 16u; off < len; off += 64u * 16u) {
-      const uint32_t i = off / T;
-      *reinterpret_cast<tx_u128 *>(P + off) = tx_gather<tx_u128>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
-    }
-  } else if constexpr (MODE == TX_V16_SHIFT) {
-    /* tx_payload's shift over the run: packet chunk j = run dwords 4j-1 .. 4j+2, the first of them the previous lane's .w (the
-     * header for j = 0) whether or not a symbol boundary lies between the two; the run's last .w goes to +len */
-    const uint32_t nch = len >> 4;
-    uint32_t carry = tx_header_word(tag);
-    for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
-      const uint32_t j = j0 + lane;
-      const bool act = j < nch;
-      tx_u128 v{0u, 0u, 0u, 0u};
-      if (act) {
-        const uint32_t off = j * 16u, i = off / T;
-        v = tx_gather<tx_u128>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
-      }
-      uint32_t prev = __shfl_up(v.w, 1u);
-      if (lane == 0) prev = carry;
-      if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{prev, v.x, v.y, v.z};
-      if (j == nch - 1u) *reinterpret_cast<uint32_t *>(P + len) = v.w;
-      carry = __shfl(v.w, 63);
-    }
-  } else if constexpr (MODE == TX_DWORD) {
-    if (inl && lane == 0) *reinterpret_cast<uint32_t *>(P) = tx_header_word(tag);
-    uint8_t *D = P + (inl ? 4u : 0u);
-    for (uint32_t off = lane * 4u; off < len; off += 64u * 4u) {
-      const uint32_t i = off / T;
-      *reinterpret_cast<uint32_t *>(D + off) = tx_gather<uint32_t>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
-    }
-  } else {
-    if (inl && lane < 4u) P[lane] = (uint8_t)(tx_header_word(tag) >> (8u * lane));
-    uint8_t *D = P + (inl ? 4u : 0u);
-    for (uint32_t off = lane; off < len; off += 64u) {
-      const uint32_t i = off / T;
-      D[off] = tx_gather<uint8_t>(base, T, cols[i], ns[i] & 0xFFu, off - i * T);
-    }
-  }
-}
-
+ * the symbol boundaries: a lane gathers with the column list of the slot its word lies in (tx_payload over a tx_run; a packet of
+ * one symbol takes the one-symbol walk: no boundary to look for). */
 template <int MODE, bool MULTI>
 __global__ __launch_bounds__(256) void nrq_emit_syms_kernel(tx_src s, tx_call c, sy_tx y) {
   __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
@@ -4250,16 +4268,11 @@ __global__ __launch_bounds__(256) void nrq_emit_syms_kernel(tx_src s, tx_call c,
     const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][l0]), cnt = nk >> 8;
     if (!cnt) continue;
     const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][l0]);
-    const uint8_t *base;
-    if constexpr (MULTI) {
-      const uint32_t sg = __builtin_amdgcn_readfirstlane(s_seg[wv][l0]);
-      base = sg == 0u ? tx_base(&s.seg[0], tag) : sg == 1u ? tx_base(&s.seg[1], tag) : tx_base(&s.seg[2], tag);
-    } else {
-      base = tx_base(&s.seg[0], tag);
-    }
+    const uint32_t sg = MULTI ? __builtin_amdgcn_readfirstlane(s_seg[wv][l0]) : 0u;
+    const uint8_t *base = TX_SEG_BASE(MULTI, s, sg, tag);
     uint8_t *P = c.pkts + (uint64_t)s_k[wv][l0] * c.pkt_stride;
-    if (cnt == 1u) tx_payload<MODE>(base, T, s_cols[wv][l0], nk & 0xFFu, tag, P, c.inl, lane); /* (no boundary to look for: the one-symbol walk) */
-    else sy_payload<MODE>(base, T, &s_cols[wv][l0], &s_n[wv][l0], cnt, tag, P, c.inl, lane);
+    if (cnt == 1u) tx_payload<MODE>(base, T, tx_one{s_cols[wv][l0], nk & 0xFFu}, tag, P, c.inl, lane);
+    else tx_payload<MODE>(base, T, tx_run{&s_cols[wv][l0], &s_n[wv][l0], cnt}, tag, P, c.inl, lane);
   }
 }
 
@@ -4271,30 +4284,13 @@ static int rx_add_syms(nrq_rx *rx, const char *who, const void *d_pkts, size_t p
   if (flags & ~(uint32_t)NRQ_RX_TAG_INLINE) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
   if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
   if (n == 0) return 0;
-  if (!d_pkts || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad packets (n=%u, G=%u)", who, n, G);
-  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "%s: give either d_tags or NRQ_RX_TAG_INLINE", who);
-  if ((uint64_t)G * r.T > 0xFFFFFFFFu || pkt_stride < (size_t)G * r.T + (inl ? 4u : 0u))
-    return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t pkt_len = (uint64_t)G * r.T > 0xFFFFFFFFu ? SIZE_MAX : (size_t)G * r.T + (inl ? 4u : 0u);
   const uint32_t ns = n * G;
-  ing_call c{};
-  c.pkts = (const uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.tags = d_tags;
-  c.n = ns;
-  c.ntiles = (ns + ING_TILE - 1u) / ING_TILE;
-  const size_t o_codes = rx_al((size_t)ns * 4u), o_fidx = o_codes + rx_al((size_t)ns * 4u), o_dst = o_fidx + rx_al((size_t)ns * 4u),
-               o_base = o_dst + rx_al((size_t)ns * 8u), o_kind = o_base + rx_al((size_t)r.nblk * c.ntiles * 4u), need = o_kind + rx_al(ns);
-  const int rc = rx->scratch.ensure(ctx, need);
-  if (rc) return rc;
-  uint8_t *s = (uint8_t *)rx->scratch.p;
-  c.tagv = (uint32_t *)s;
-  c.codes = d_results ? d_results : (int32_t *)(s + o_codes);
-  c.fidx = (uint32_t *)(s + o_fidx);
-  c.dst = (uint64_t *)(s + o_dst);
-  c.base = (uint32_t *)(s + o_base);
+  ing_call c;
   sy_rx y{};
-  y.G = G; y.nsym = d_nsym; y.kind = s + o_kind;
+  y.G = G; y.nsym = d_nsym;
+  const int rc = ing_call_of(ctx, rx->scratch, who, d_pkts, pkt_stride, d_tags, n, G, pkt_len, inl, r.nblk, d_results, ns, &c, &y.kind);
+  if (rc) return rc;
   const uint32_t hdr = ing_payload_off(&c);
   const uint32_t word = sy_copy_word(reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | hdr | r.T | reinterpret_cast<uintptr_t>(r.src) |
                                      r.src_stride | reinterpret_cast<uintptr_t>(r.rep) | r.rep_stride);
@@ -4337,14 +4333,9 @@ static int sy_tx_launch(tx_sender *tx, const tx_call &c, const sy_tx &y) {
        nrq_emit_syms_kernel<TX_BYTE, false>},
       {nrq_emit_syms_kernel<TX_V16, true>, nrq_emit_syms_kernel<TX_V16_SHIFT, true>, nrq_emit_syms_kernel<TX_DWORD, true>,
        nrq_emit_syms_kernel<TX_BYTE, true>}};
-  static_assert(SY_PATH_V16 == TX_V16 && SY_PATH_V16_SHIFT == TX_V16_SHIFT && SY_PATH_DWORD == TX_DWORD && SY_PATH_BYTE == TX_BYTE,
-                "sy_emit_path names the emit kernels' modes");
   nrq_ctx *ctx = tx->ctx;
   const tx_src &s = tx->s;
-  uintptr_t al = reinterpret_cast<uintptr_t>(c.pkts) | c.pkt_stride | s.seg[0].T;
-  for (uint32_t g = 0; g < s.nseg; g++)
-    al |= reinterpret_cast<uintptr_t>(s.seg[g].src) | s.seg[g].src_stride | reinterpret_cast<uintptr_t>(s.seg[g].inter) | s.seg[g].inter_stride;
-  const int mode = sy_emit_path(al, c.inl, ctx->tune.tx_dword ? 1u : 0u);
+  const int mode = tx_emit_path(tx_align(&s, &c, nullptr), c.inl, ctx->tune.tx_dword ? 1u : 0u);
   const uint32_t per = 64u / y.G, waves = (c.n + per - 1u) / per;
   hipLaunchKernelGGL(kern[s.nseg > 1u][mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, s, c, y);
   HIPCHK(ctx, hipGetLastError());
@@ -4360,24 +4351,9 @@ static int sy_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
   if (n == 0) return 0;
   if (!d_tags || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u, G=%u)", who, n, G);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t sbn0 = tx->s.sbn0, nblk = tx->s.Z, nbins = nblk + 1u;
-  const size_t o_order = rx_al((size_t)nbins * 4u), need = o_order + rx_al((size_t)n * 4u);
-  if ((rc = tx->scratch.ensure(ctx, need))) return rc;
-  uint32_t *cnt = (uint32_t *)tx->scratch.p, *order = (uint32_t *)((uint8_t *)tx->scratch.p + o_order);
-  hipStream_t st = ctx->stream;
-  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
-  hipLaunchKernelGGL(nrq_tx_hist_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt);
-  hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, st, nbins, cnt);
-  hipLaunchKernelGGL(nrq_tx_place_kernel, dim3(tiles), dim3(256), 0, st, sbn0, nblk, d_tags, n, cnt, order);
-  HIPCHK(ctx, hipGetLastError());
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  tx_call c = tx_call_of(d_pkts, pkt_stride, n, flags);
+  if ((rc = tx_bucket(tx, d_tags, n, &c.order))) return rc;
   c.tags = d_tags;
-  c.order = order;
   c.results = d_results;
   sy_tx y{};
   y.G = G; y.nsym = d_nsym;
@@ -4388,9 +4364,8 @@ static int sy_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
 static int sy_emit_span(tx_sender *tx, const char *who, uint32_t KL, uint32_t KS, uint32_t esi0, uint32_t eL, uint32_t eS, uint32_t G, int order,
                         void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt) {
   nrq_ctx *ctx = tx->ctx;
-  if (tx->relay)
-    for (uint32_t b = 0; b < tx->s.Z; b++)
-      if (!tx_is_ready(tx, b)) return fail(ctx, -1, "%s: blocks of the relay are not ready: SBN %s", who, relay_missing(tx).c_str());
+  const int rc = tx_span_ready(tx, who);
+  if (rc) return rc;
   const uint32_t ZL = tx->s.ZL, ZS = tx->s.Z - ZL;
   if (!ZL) { KL = KS; eL = eS; } /* (a table of one class has its counts in both: the one-segment maps) */
   const uint32_t pL = sy_pkt_count(KL, esi0, eL, G), pS = ZS ? sy_pkt_count(KS, esi0, eS, G) : pL;
@@ -4399,11 +4374,7 @@ static int sy_emit_span(tx_sender *tx, const char *who, uint32_t KL, uint32_t KS
   if (h_npkt) *h_npkt = (uint32_t)total;
   if (total == 0) return 0;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  tx_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = (uint32_t)total;
-  c.inl = (flags & NRQ_TX_TAG_INLINE) ? 1u : 0u;
+  tx_call c = tx_call_of(d_pkts, pkt_stride, (uint32_t)total, flags);
   c.esi0 = esi0;
   c.nL = ZL ? pL : pS;
   c.nS = pS;
@@ -4458,7 +4429,7 @@ int nrq_tx_emit_range_syms(nrq_tx *tx, uint32_t esi0, uint32_t n, uint32_t G, in
   if (h_npkt) *h_npkt = 0;
   int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
   if (rc) return rc;
-  if (order != 0 && order != 1) return fail(ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
+  if ((rc = tx_check_order(tx, who, order))) return rc;
   if (n == 0) return 0;
   if (esi0 >= (1u << 24) || n > (1u << 24) - esi0) return fail(ctx, -1, "%s: ESIs %u + %u reach past 2^24", who, esi0, n);
   const uint32_t K = tx->s.seg[0].K;
@@ -4473,7 +4444,7 @@ int nrq_otx_emit_all_syms(nrq_otx *tx, uint32_t nrep, uint32_t G, int order, voi
   if (h_npkt) *h_npkt = 0;
   int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
   if (rc) return rc;
-  if (order != 0 && order != 1) return fail(ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
+  if ((rc = tx_check_order(tx, who, order))) return rc;
   const nrq_obj_params &p = tx->prm;
   const uint64_t kmax = std::max(p.ZL ? p.KL : 0u, p.KS);
   if (kmax + nrep > (1u << 24)) return fail(ctx, -1, "%s: ESIs up to %llu + %u reach past 2^24", who, (unsigned long long)kmax, nrep);
@@ -4719,32 +4690,15 @@ __global__ __launch_bounds__(256) void nrq_ings_scan_kernel(const ings_tab *__re
   ing_scan_wg(r, b, s.c.base + (size_t)blockIdx.x * s.c.ntiles, s.c.ntiles, ps);
 }
 
-/* dynamic LDS: 4 * t->nblk counters (per wave, per global block).  The ballot loop is the one of nrq_ing_classify_kernel with the
- * global block in place of the local one: a wave may hold candidates of several members. */
+/* dynamic LDS: 4 * t->nblk counters (per wave, per global block).  The ranking is ing_rank_wg with the global block in place of
+ * the local one: a wave may hold candidates of several members. */
 __global__ __launch_bounds__(256) void nrq_ings_classify_kernel(const ings_tab *__restrict__ t, ings_call s) {
   extern __shared__ uint32_t ings_wc[];
-  const uint32_t i = threadIdx.x, lane = i & 63u, w = i >> 6, k = blockIdx.x * ING_TILE + i, nb = t->nblk;
+  const uint32_t i = threadIdx.x, k = blockIdx.x * ING_TILE + i, nb = t->nblk;
   for (uint32_t j = i; j < 4u * nb; j += 256u) ings_wc[j] = 0;
   __syncthreads();
   const uint32_t g = k < s.c.n ? ings_cand(t, &s, k) : ING_NONE;
-  const bool cand = g != ING_NONE;
-  uint64_t todo = __ballot(cand);
-  uint32_t rank = 0;
-  while (todo) { /* (wave-uniform) */
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t lg = __shfl(g, leader);
-    const bool mine = cand && g == lg;
-    const uint64_t mk = __ballot(mine);
-    if (mine) rank = (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
-    if ((int)lane == leader) ings_wc[w * nb + lg] = (uint32_t)__popcll(mk);
-    todo &= ~mk;
-  }
-  __syncthreads();
-  uint32_t row = ING_NONE;
-  if (cand) {
-    row = s.c.base[(size_t)g * s.c.ntiles + blockIdx.x] + rank;
-    for (uint32_t w2 = 0; w2 < w; w2++) row += ings_wc[w2 * nb + g];
-  }
+  const uint32_t row = ing_rank_wg(ings_wc, nb, g, s.c.base, s.c.ntiles);
   if (k < s.c.n) ings_classify(t, &s, k, row);
 }
 
@@ -4926,31 +4880,16 @@ int nrq_rxset_add(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const u
   if (kinl && !inl) return fail(ctx, -1, "nrq_rxset_add: NRQ_RX_KEY_INLINE needs NRQ_RX_TAG_INLINE");
   if (kinl && d_keys) return fail(ctx, -1, "nrq_rxset_add: give either d_keys or NRQ_RX_KEY_INLINE");
   if (n == 0 || set->mem.empty()) return 0;
-  if (!d_pkts || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_rxset_add: bad packets (n=%u)", n);
-  if (inl == (d_tags != nullptr)) return fail(ctx, -1, "nrq_rxset_add: give either d_tags or NRQ_RX_TAG_INLINE");
   const uint32_t poff = kinl ? 8u : inl ? 4u : 0u;
-  if (pkt_stride < (size_t)set->T + poff) return fail(ctx, -1, "nrq_rxset_add: pkt_stride %zu shorter than a packet", pkt_stride);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   ings_call s{};
   ing_call &c = s.c;
-  c.pkts = (const uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.tags = d_tags;
-  c.n = n;
-  c.ntiles = (n + ING_TILE - 1u) / ING_TILE;
+  uint8_t *mem; /* (the packets' members: the set's own array, behind the call's) */
+  const int rc = ing_call_of(ctx, set->scratch, "nrq_rxset_add", d_pkts, pkt_stride, d_tags, n, 0, (size_t)set->T + poff, inl, set->nblk,
+                             d_results, (size_t)n * 4u, &c, &mem);
+  if (rc) return rc;
   s.keys = d_keys;
   s.key_inline = kinl ? 1u : 0u;
-  const size_t a4 = rx_al((size_t)n * 4u), o_mem = a4, o_codes = o_mem + a4, o_fidx = o_codes + a4, o_dst = o_fidx + a4,
-               o_base = o_dst + rx_al((size_t)n * 8u), need = o_base + rx_al((size_t)set->nblk * c.ntiles * 4u);
-  const int rc = set->scratch.ensure(ctx, need);
-  if (rc) return rc;
-  uint8_t *p = (uint8_t *)set->scratch.p;
-  c.tagv = (uint32_t *)p;
-  s.mem = (uint32_t *)(p + o_mem);
-  c.codes = d_results ? d_results : (int32_t *)(p + o_codes);
-  c.fidx = (uint32_t *)(p + o_fidx);
-  c.dst = (uint64_t *)(p + o_dst);
-  c.base = (uint32_t *)(p + o_base);
+  s.mem = (uint32_t *)mem;
   const ings_tab *t = (const ings_tab *)set->tab;
   hipStream_t st = ctx->stream;
   const uint32_t g = (n + 255u) / 256u, nb = set->nblk;
@@ -5249,7 +5188,8 @@ int nrq_rxset_held(nrq_rxset *set, uint32_t *d_keys, uint32_t *d_tags, uint32_t 
  * buffer.  Three bucketing passes make the block-major work order over the set's global blocks -- the histogram pass also finds
  * each packet's segment (a linear search over the compact arrays staged in LDS; every lane reads the same entry) and leaves it
  * in c.seg[] for the passes behind it -- then nrq_emit_set_kernel writes the packets.  Kernels of their own: every nrq_emit_kernel
- * and nrq_emit_held_kernel instantiation is compiled from the code it always was. */
+ * and nrq_emit_held_kernel instantiation is compiled from the code it always was.  The payload walk (tx_payload, under
+ * txs_payload's key word) and the held repair row lookup (tx_held_row) are those kernels' bodies. */
 enum : int { TXS_V16_KEY = 4 }; /* beside TX_V16 .. TX_BYTE: 16-byte loads and stores under the 8-byte header (key, FEC Payload ID) */
 
 __global__ __launch_bounds__(256) void nrq_txs_hist_kernel(const txs_tab *__restrict__ t, txs_call c, uint32_t *__restrict__ cnt) {
@@ -5326,15 +5266,15 @@ __device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, ui
       if (lane == 0) *reinterpret_cast<uint32_t *>(P) = txs_key_word(key);
       P += 4;
     }
-    tx_payload<TX_DWORD>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane);
+    tx_payload<TX_DWORD>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane);
   } else if constexpr (MODE == TX_BYTE) {
     if (hdr == 8u) {
       if (lane < 4u) P[lane] = (uint8_t)(txs_key_word(key) >> (8u * lane));
       P += 4;
     }
-    tx_payload<TX_BYTE>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane);
+    tx_payload<TX_BYTE>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane);
   } else {
-    tx_payload<MODE>(base, T, cols, n, tag, P, hdr ? 1u : 0u, lane); /* (TX_V16: hdr = 0; TX_V16_SHIFT: hdr = 4) */
+    tx_payload<MODE>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane); /* (TX_V16: hdr = 0; TX_V16_SHIFT: hdr = 4) */
   }
 }
 
@@ -5342,7 +5282,7 @@ __device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, ui
  * one item and builds its column list into LDS from its segment's parameters, read from the table (lanes of one block read the
  * same entry); then the wave writes the items' packets one after the other, the segment index made wave-uniform so that its
  * fields come through the uniform table pointer.  HELD: a packet of a block that is not ready is still written when the segment's
- * reception holds its symbol, the repair row found by the 64-entry ballot lookup of nrq_emit_held_kernel. */
+ * reception holds its symbol, the repair row found as in nrq_emit_held_kernel (tx_held_row). */
 template <int MODE, bool HELD>
 __global__ __launch_bounds__(256) void nrq_emit_set_kernel(const txs_tab *__restrict__ t, txs_ready rdy, txs_call c) {
   __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
@@ -5387,12 +5327,7 @@ __global__ __launch_bounds__(256) void nrq_emit_set_kernel(const txs_tab *__rest
     if (HELD && (nk >> 8) == TX_HELD_REP) {
       const tx_held_seg *hs = &S->h;
       const uint32_t b = (tag >> 24) - S->b.sbn0;
-      const uint32_t nrep = tx_held_nrep(hs, b), esi = tag & 0xFFFFFFu;
-      uint32_t q = TX_NONE;
-      for (uint32_t q0 = 0; q0 < nrep && q == TX_NONE; q0 += 64u) {
-        const uint64_t m = __ballot(tx_held_hit(hs, b, q0 + lane, nrep, esi));
-        if (m) q = q0 + (uint32_t)__ffsll((unsigned long long)m) - 1u;
-      }
+      const uint32_t q = tx_held_row(hs, b, tag & 0xFFFFFFu, lane);
       if (c.results && lane == 0) c.results[k] = q == TX_NONE ? TX_NOT_READY : 0;
       if (q == TX_NONE) continue; /* (the books say otherwise: a marked repair ESI has its row) */
       base = tx_held_rep_base(hs, b) + (uint64_t)q * T;

@@ -17,7 +17,10 @@
  * contiguous run.  Range forms cut every block's source run and repair run into packets of G (sy_range_pkt) and reuse the
  * block-major / interleaved maps of emit_body.h with packets per block in place of ESIs per block.
  *
- * nrq_device.hip instantiates these in kernels of their own; syms_emu.cpp runs them sequentially on the CPU.
+ * What is NOT here, because the one-symbol forms' code serves as it is: the payload path rule (tx_emit_path / tx_align,
+ * emit_body.h), the payload walk (the kernels' tx_payload over a run of symbols), the ranking of repair candidates (ing_rank_wg)
+ * and the host set-up of a call (bucketing, the ingest call's scratch).  nrq_device.hip instantiates the bodies below in kernels of
+ * their own -- entry points only, around those shared bodies; syms_emu.cpp runs them sequentially on the CPU.
  */
 #ifndef NRQ_SYMS_BODY_H
 #define NRQ_SYMS_BODY_H
@@ -35,12 +38,6 @@
 #define SY_ABSENT 0u /* not a symbol of this reception: behaves as a packet of no reception (result untouched) */
 #define SY_LIVE 1u   /* a symbol: goes through the passes as a packet of its own */
 #define SY_BAD 2u    /* ERR and nothing else: slot 0 of a packet with a malformed count, or a symbol whose ESI would pass 2^24 - 1 */
-
-/* payload paths: the widest word every address of a call allows */
-#define SY_PATH_V16 0
-#define SY_PATH_V16_SHIFT 1
-#define SY_PATH_DWORD 2
-#define SY_PATH_BYTE 3
 
 /* ---- the count rule ---- */
 /* symbols of a packet with first ESI e of a block of K source symbols when no count is given: G, but a packet of source symbols
@@ -129,12 +126,6 @@ TX_HD uint32_t sy_tx_admit(const struct tx_src *s, const struct sy_tx *y, uint32
   }
   if (*cnt == 0u) { *code = TX_BAD_RANGE; return TX_SEGS; }
   return g;
-}
-
-/* the emit's payload path, from the OR of the packet buffer's address and stride, T and every row table's address and stride */
-TX_HD int sy_emit_path(uint64_t al, uint32_t inl, uint32_t force_dword) {
-  if ((al & 15u) == 0 && !force_dword) return inl ? SY_PATH_V16_SHIFT : SY_PATH_V16;
-  return (al & 3u) == 0 ? SY_PATH_DWORD : SY_PATH_BYTE;
 }
 
 /* ---- ingest ---- */

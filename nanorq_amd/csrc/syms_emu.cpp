@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "emit_emu.h"
 #include "syms_body.h"
 
 /* every packet in work order; -2: the work order is not a permutation of the packets */
@@ -47,7 +48,7 @@ void emu_sy_range_pkt(uint32_t K, uint32_t esi0, uint32_t n, uint32_t G, uint32_
   sy_range_pkt(K, esi0, n, G, j, first, cnt);
 }
 uint32_t emu_sy_range_index(uint32_t K, uint32_t esi0, uint32_t n, uint32_t G, uint32_t e) { return sy_range_index(K, esi0, n, G, e); }
-int emu_sy_emit_path(uint64_t al, uint32_t inl) { return sy_emit_path(al, inl, 0u); }
+int emu_sy_emit_path(uint64_t al, uint32_t inl) { return tx_emit_path(al, inl, 0u); }
 uint32_t emu_sy_copy_word(uint64_t al) { return sy_copy_word(al); }
 
 /* The emit from a table of nseg segments (as emu_emit_table_ready of emit_emu.cpp): list mode when tags is not NULL (n first
@@ -59,32 +60,16 @@ int emu_sy_emit_table(const uint32_t *prm, uint32_t nseg, const uint32_t *span, 
                       uint32_t G, const uint32_t *range, uint32_t inl, uint8_t *pkts, uint64_t pkt_stride, int32_t *results,
                       uint32_t *tags_out, uint8_t *nsym_out, uint32_t *back_out, uint32_t *npkt_out, const uint32_t *ready) {
   tx_src s;
-  memset(&s, 0, sizeof(s));
-  if (nseg == 0 || nseg > TX_SEGS || G == 0 || G > SY_G_MAX) return -1;
-  for (uint32_t g = 0; g < nseg; g++) {
-    const uint32_t *q = prm + 5u * g;
-    tx_blk &t = s.seg[g];
-    if (!rq_params_init(q[1], &t.p) || t.p.Kp != q[1] || q[0] == 0 || q[0] > q[1]) return -1;
-    t.p.K = q[0];
-    t.K = q[0]; t.T = q[2]; t.nblk = q[3]; t.sbn0 = q[4];
-    if (src) { t.src = src[g]; t.src_stride = src_stride[g]; t.inter = inter[g]; t.inter_stride = inter_stride[g]; }
-  }
-  s.nseg = nseg; s.sbn0 = span[0]; s.Z = span[1]; s.ZL = span[2];
-  if (ready) memcpy(s.ready, ready, sizeof(s.ready));
-  else memset(s.ready, 0xFF, sizeof(s.ready));
+  if (G == 0 || G > SY_G_MAX || !emu_tx_table(&s, prm, nseg, span, src, src_stride, inter, inter_stride, ready)) return -1;
   tx_call c;
   memset(&c, 0, sizeof(c));
   sy_tx y;
   memset(&y, 0, sizeof(y));
   y.G = G;
   c.pkts = pkts; c.pkt_stride = pkt_stride; c.inl = inl;
-  std::vector<uint32_t> order(tags && n ? n : 1u);
+  std::vector<uint32_t> order;
   if (tags) {
-    std::vector<uint32_t> cnt(s.Z + 1u, 0);
-    for (uint32_t k = 0; k < n; k++) cnt[tx_bin(s.sbn0, s.Z, tags[k])]++;
-    uint32_t run_ = 0;
-    for (uint32_t b = 0; b <= s.Z; b++) { const uint32_t v = cnt[b]; cnt[b] = run_; run_ += v; }
-    for (uint32_t k = 0; k < n; k++) order[cnt[tx_bin(s.sbn0, s.Z, tags[k])]++] = k;
+    order = emu_tx_bucket(&s, tags, n);
     c.n = n; c.tags = tags; c.order = order.data(); c.results = results;
     y.nsym = nsym;
   } else {
