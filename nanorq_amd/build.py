@@ -31,6 +31,7 @@ QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
+UEMU = os.path.join(ROOT, "tests", "emu", "libout_lists_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
 ROWS = os.path.join(ROOT, "tests", "gpu", "librows_probe.so")
 
@@ -143,6 +144,12 @@ def build_launch_emu(force=False):
 def build_planner_emu(force=False):
     return _build_emu(PEMU, os.path.join(ROOT, "tests", "emu", "planner_emu.cpp"),
                       ("planner_body.h", "planner_seq.h", "solve_body.h", "plan.h", "rq_math.h"), force)
+
+
+def build_out_lists_emu(force=False):
+    """tests/emu/libout_lists_emu.so: the host's builder of a job's output lists (out_lists.h) behind a C interface; host code as
+    it is, no emulation."""
+    return _build_emu(UEMU, os.path.join(ROOT, "tests", "emu", "out_lists_emu.cpp"), ("out_lists.h", "rq_math.h"), force)
 
 
 def build_ingest_emu(force=False):
@@ -301,6 +308,7 @@ if __name__ == "__main__":
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)
+    build_out_lists_emu(force="-f" in sys.argv)
     build_model_lib(force="-f" in sys.argv)
     build_rows_probe(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

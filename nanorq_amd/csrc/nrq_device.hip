@@ -30,6 +30,7 @@
 #include "plan.h"
 #include "planner_host.h"
 #include "rq_math.h"
+#include "out_lists.h"
 #include "solve_body.h"
 #include "split_body.h"
 #include "planner_body.h"
@@ -1312,22 +1313,6 @@ int get_encplan(nrq_ctx *ctx, uint32_t K, uint32_t Kp, EncPlan **out, bool finis
   return finish ? encplan_finish(ctx, p, K, kc, ep) : 0;
 }
 
-/* LT neighbour lists of the symbols to generate, already translated to LDS slots through the plan's
- * colslot[], in the layout ph_store() reads */
-void build_out_lists(const rq_params &p, const uint16_t *colslot, uint32_t n, const uint32_t *isis,
-                     std::vector<uint32_t> &cptr, std::vector<uint16_t> &cols) {
-  cptr.resize(n + 1);
-  cols.clear();
-  cols.reserve((size_t)n * 9);
-  uint32_t tmp[RQ_MAX_LT_COLS];
-  for (uint32_t q = 0; q < n; q++) {
-    cptr[q] = (uint32_t)cols.size();
-    uint32_t m = rq_lt_columns(&p, isis[q], tmp);
-    for (uint32_t k = 0; k < m; k++) cols.push_back(colslot[tmp[k]]); /* slot that holds C[col] */
-  }
-  cptr[n] = (uint32_t)cols.size();
-}
-
 /* nrq_solve_kernel<WB, NT, WV, G, AL>: row i is the instance of nrq_solve_keys[i] (launch_shape.h) */
 using solve_fn = void (*)(const nrq_job *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint8_t *, uint8_t *, uint32_t,
                           uint32_t, unsigned long long *, uint8_t *, size_t);
@@ -1675,10 +1660,10 @@ static int encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   ctx->stats.encplan_device = ep->dev_built ? 1u : 0u;
 
   /* per-call arrays: [jobs][isi->(cptr, cols, row)] */
-  std::vector<uint32_t> isis(nrep), cptr;
+  std::vector<uint32_t> isis(nrep), cptr, order;
   std::vector<uint16_t> cols;
   for (uint32_t q = 0; q < nrep; q++) isis[q] = h_esis[q] + (p.Kp - K);
-  build_out_lists(p, ep->colslot.data(), nrep, isis.data(), cptr, cols);
+  build_out_lists(p, ep->colslot.data(), nrep, isis.data(), cptr, cols, order);
   const size_t off_jobs = 0;
   const size_t off_cptr = r16(off_jobs + (size_t)nblk * sizeof(nrq_job));
   const size_t off_row = r16(off_cptr + (size_t)(nrep + 1) * 4);
@@ -1691,7 +1676,7 @@ static int encode_blocks(nrq_ctx *ctx, uint32_t K, uint32_t Kp, uint32_t T, uint
   if ((rc = ensure_dev(ctx, ctx->scratch[f], total))) return rc;
   uint8_t *hs = ctx->staging[f].p, *ds = ctx->scratch[f].p;
   memcpy(hs + off_cptr, cptr.data(), (size_t)(nrep + 1) * 4);
-  for (uint32_t q = 0; q < nrep; q++) reinterpret_cast<uint32_t *>(hs + off_row)[q] = q;
+  if (nrep) memcpy(hs + off_row, order.data(), (size_t)nrep * 4); /* (the list stored i-th is repair symbol order[i]'s: row order[i] of rep) */
   if (!cols.empty()) memcpy(hs + off_cols, cols.data(), cols.size() * 2);
   nrq_job *jobs = reinterpret_cast<nrq_job *>(hs + off_jobs);
   for (uint32_t b = 0; b < nblk; b++) {
@@ -1796,8 +1781,8 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
       if (use + 1 > avail) { pr.state = -1; return; } /* rank(A) < L with everything the caller holds */
     }
     build_out_lists(p, reinterpret_cast<const uint16_t *>(pr.plan.p + reinterpret_cast<const nrq_plan_hdr *>(pr.plan.p)->off_colslot),
-                    nl, lost, pr.cptr, pr.cols); /* ISI of a source symbol is its ESI */
-    pr.orow.assign(lost, lost + nl);
+                    nl, lost, pr.cptr, pr.cols, pr.orow); /* ISI of a source symbol is its ESI */
+    for (uint32_t &g : pr.orow) g = lost[g]; /* (the list stored i-th is that of missing symbol orow[i]: its row) */
     pr.state = 1;
   };
 

@@ -2165,6 +2165,37 @@ SB_HD uint32_t pl_deg_prefix(const PlanCtx &c, uint32_t g) {
   if (i < g) run += degq[i];
   return run;
 }
+/* The list lengths of the missing symbols, a byte each, staged in the (free) frontier queues by pl_final_c: nl <= 2 * PL_QCAP of them,
+ * the bytes up to the next word zero.  A length is at most NRQ_LT_LIST_MAX < 64, so a word of four compares against a length d in
+ * one addition: byte x + (128 - d) has bit 7 set when x >= d, x + (127 - d) when x > d, and no byte carries into the next. */
+static_assert(NRQ_LT_LIST_MAX < 64u, "pl_len_rank compares list lengths as bytes with bit 7 free");
+SB_HD uint8_t *pl_lenq(const PlanCtx &c) { return reinterpret_cast<uint8_t *>(c.queue(0u)); }
+/* of the bytes of w whose sum with the same byte of k reaches 128: how many (n), and their sum (sum) */
+SB_HD void pl_len_word(uint32_t w, uint32_t k, uint32_t &n, uint32_t &sum) {
+  const uint32_t t = ((w + k) >> 7) & 0x01010101u;
+  n += (uint32_t)__builtin_popcount(t);
+  sum += ((w & (t * 0xFFu)) * 0x01010101u) >> 24; /* (four bytes of at most 63: the sum fits the top byte) */
+}
+/* Where list g goes when the lists are put in non-increasing length, equal lengths in the order of g (a stable counting sort, told
+ * from the side of one list): pos = the lists before it -- the longer ones, and the equally long ones of smaller g --, off = the
+ * entries of those lists.  Reads of LDS only: every thread may ask for its own list at once. */
+SB_HD void pl_len_rank(const PlanCtx &c, uint32_t g, uint32_t nl, uint32_t &pos, uint32_t &off) {
+  const uint32_t *w4 = reinterpret_cast<const uint32_t *>(pl_lenq(c));
+  const uint32_t gw = g >> 2, nw = (nl + 3u) >> 2, sh = 8u * (g & 3u);
+  const uint32_t d = (w4[gw] >> sh) & 0xFFu;
+  const uint32_t ge = (128u - d) * 0x01010101u, gt = (127u - d) * 0x01010101u, below = (1u << sh) - 1u;
+  uint32_t n = 0, sum = 0;
+  for (uint32_t i = 0; i < gw; i++) pl_len_word(w4[i], ge, n, sum);
+  pl_len_word(w4[gw], (ge & below) | (gt & ~(below | (0xFFu << sh))), n, sum); /* (the list's own byte: never counted) */
+  for (uint32_t i = gw + 1u; i < nw; i++) pl_len_word(w4[i], gt, n, sum);
+  pos = n; off = sum;
+}
+SB_HD uint32_t pl_len_total(const PlanCtx &c, uint32_t nl) {
+  const uint32_t *w4 = reinterpret_cast<const uint32_t *>(pl_lenq(c));
+  uint32_t n = 0, sum = 0;
+  for (uint32_t i = 0; i < (nl + 3u) >> 2; i++) pl_len_word(w4[i], 0x80808080u, n, sum);
+  return sum;
+}
 /* rows of the stream that group l takes: the finishing ops first; the last NRQ_PIPE-1 rows hold early ops only (or
  * padding) -- also when the group is empty: early ops of the group before may complete rows that the group after reads */
 SB_HD uint32_t pl_group_span(uint32_t l, uint32_t nf, uint32_t n) {
@@ -3167,13 +3198,17 @@ template <int Z> SB_HD void pl_final_c(PlanCtx &c, uint32_t tid, uint32_t nt) {
   uint32_t *cptr = reinterpret_cast<uint32_t *>(c.arena + c.part()[2]);
   uint32_t *orow = reinterpret_cast<uint32_t *>(c.arena + c.part()[3]);
   uint16_t *osl = reinterpret_cast<uint16_t *>(c.arena + c.part()[4]);
-  /* list lengths of the missing symbols: to LDS when they fit (the frontier queues are free by now), so that the
-   * running sum in pl_final_d -- one thread -- does not walk an array in HBM */
-  uint16_t *degq = c.queue(0u);
+  /* list lengths of the missing symbols: to LDS when they fit (the frontier queues are free by now), so that pl_final_d,
+   * where every thread looks at all of them, does not walk an array in HBM */
+  uint8_t *lenq = pl_lenq(c); /* (a byte each: pl_len_rank compares four at a time) */
   const bool in_lds = nl <= 2u * c.qcap;
   struct ED { uint32_t e, dg; };
   pl_for_batched(tid, nt, nl, [&](uint32_t g) { const uint32_t e = c.lost[g]; return ED{e, c.b_rptr[p.S + p.H + e + 1] - c.b_rptr[p.S + p.H + e]}; },
-                 [&](uint32_t g, ED v) { if (in_lds) degq[g] = (uint16_t)v.dg; else c.pivdeg[g] = v.dg; orow[g] = v.e; });
+                 [&](uint32_t g, ED v) {
+                   if (in_lds) lenq[g] = (uint8_t)v.dg; /* (the lists go out by length: pl_final_d names their rows) */
+                   else { c.pivdeg[g] = v.dg; orow[g] = v.e; }
+                 });
+  if (in_lds && tid < 3u && nl + tid < ((nl + 3u) & ~3u)) lenq[nl + tid] = 0; /* (the last word's other bytes: lists of no entries) */
   (void)cptr; (void)osl;
   /* ops of the stream, summed by everybody (one thread walking nlev + 2 words of HBM: a trip each, 1.5 M clocks at K'=56403) */
   uint32_t ops = 0;
@@ -3209,11 +3244,20 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
   pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
   const rq_params &p = c.p;
   if (!sh->status && c.job.nlost <= 2u * c.qcap) {
-    /* the list offsets of the missing symbols: every thread sums the lengths before its own entry (LDS reads, no
-     * stores in between) -- a running sum by one thread is a chain of LDS round trips, one per entry */
+    /* the lists of the missing symbols in non-increasing length, equal lengths in the order of c.lost[] (ph_store deals them to
+     * its threads in this order: the 64 lists of a wave are then of near-equal length): every thread finds the place of its own
+     * list and the entries before it from the lengths in LDS (reads only, no stores in between) -- a running sum by one thread is
+     * a chain of LDS round trips, one per entry.  pivdeg[g] keeps the offset for pl_final_e, which walks the symbols in row order. */
+    const uint32_t nl = c.job.nlost;
     uint32_t *cptr = reinterpret_cast<uint32_t *>(c.arena + c.part()[2]);
-    for (uint32_t g = tid; g <= c.job.nlost; g += nt) cptr[g] = pl_deg_prefix(c, g);
-  } else if (!sh->status) { /* (pl_final_c2 / c3 left every thread's starting offset in the queues) */
+    uint32_t *orow = reinterpret_cast<uint32_t *>(c.arena + c.part()[3]);
+    for (uint32_t g = tid; g < nl; g += nt) {
+      uint32_t pos, off;
+      pl_len_rank(c, g, nl, pos, off);
+      cptr[pos] = off; orow[pos] = c.lost[g]; c.pivdeg[g] = off;
+    }
+    if (tid == 0) cptr[nl] = pl_len_total(c, nl);
+  } else if (!sh->status) { /* (pl_final_c2 / c3 left every thread's starting offset in the queues; the lists stay in row order) */
     const uint32_t nl = c.job.nlost, per = (nl + nt - 1u) / nt, a = tid * per < nl ? tid * per : nl, b = a + per < nl ? a + per : nl;
     const uint32_t *ps = reinterpret_cast<const uint32_t *>(c.queue(0u));
     uint32_t *cptr = reinterpret_cast<uint32_t *>(c.arena + c.part()[2]);
@@ -3250,7 +3294,7 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
     const uint32_t nl = c.job.nlost;
     uint32_t *cptr = reinterpret_cast<uint32_t *>(c.arena + c.part()[2]);
     uint32_t run = 0;
-    if (nl <= 2u * c.qcap) run = pl_deg_prefix(c, nl);
+    if (nl <= 2u * c.qcap) run = pl_len_total(c, nl);
     else run = reinterpret_cast<const uint32_t *>(c.queue(0u))[nt];
     (void)cptr;
     h.n_xor_ops = sh->tmp1 + run + sh->spare_fill; /* (tmp1: the level groups' ops, summed in pl_final_c) */
@@ -3306,7 +3350,8 @@ template <int Z> SB_HD void pl_final_e(PlanCtx &c, uint32_t tid, uint32_t nt) {
   uint16_t *osl = reinterpret_cast<uint16_t *>(c.arena + c.part()[4]);
   uint32_t *marks = c.part()[7] ? pl_need_marks(c) : nullptr; /* (uniform) */
   for (uint32_t g = tid; g < nl; g += nt) {
-    const uint32_t e = c.lost[g], a = c.b_rptr[p.S + p.H + e], n = c.b_rptr[p.S + p.H + e + 1] - a, o = cptr[g];
+    const uint32_t e = c.lost[g], a = c.b_rptr[p.S + p.H + e], n = c.b_rptr[p.S + p.H + e + 1] - a;
+    const uint32_t o = nl <= 2u * c.qcap ? c.pivdeg[g] : cptr[g]; /* (sorted by length: where pl_final_d put list g; else row order) */
     constexpr uint32_t CB = 8; /* entries whose two dependent loads are in flight together */
     for (uint32_t k0 = 0; k0 < n; k0 += CB) {
       uint32_t col[CB], sl[CB];

@@ -1743,7 +1743,8 @@ template <int WB, int G = 1, bool FAST = true> SB_HD void ph_store(const StripCt
    * the lane's scratch slot, which holds zeros (ph_clear; the padding ops of the stream XOR it into itself), so the loop body
    * has no branch and its LDS reads are in flight together.  (With a test per entry every read was waited for on its own: 14 k
    * clocks for the 860 symbols of a decode strip.)  The waves of a pass go on as long as one lane has entries left; an LT list
-   * has 7 entries on average and 33 at most. */
+   * has 7 entries on average and 33 at most.  The lists come in non-increasing length (out_lists.h, pl_final_d), so the 64 of a
+   * wave are of near-equal length and what a second pass takes are the shortest; any order gives the same rows (out_row[]). */
   const uint32_t nout = c.job->nout;
   constexpr uint32_t CH = NRQ_STORE_CHUNK;
   const uint32_t zero_at = tid & (NRQ_SCRATCH - 1u); /* (element index from the start of the image) */
