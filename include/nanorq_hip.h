@@ -490,7 +490,7 @@ int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
  * (first tags) and d_nsym_out (counts), both nullable, are in packet order.  *h_npkt (nullable) receives the number of packets.
  * A relay with a block that is not ready is refused, as nrq_tx_emit_range.
  *
- * Reception sets and sender sets (nrq_rxset_*, nrq_txset_*) keep one symbol per packet. */
+ * Reception sets and sender sets take such packets through nrq_rxset_add_syms and nrq_txset_emit_syms (below, behind the sets). */
 #define NRQ_PKT_SYMS_MAX 64u
 #define NRQ_TX_BAD_RANGE (-3)
 uint32_t nrq_pkt_count(uint32_t K, uint32_t esi0, uint32_t n, uint32_t G);
@@ -632,6 +632,32 @@ int nrq_txset_blocks(nrq_txset *set, uint32_t *h_keys, uint32_t *h_sbn, uint32_t
  * the key). */
 int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts, size_t pkt_stride,
                    uint32_t flags, int32_t *d_results);
+
+/* ---- sets: packets of several symbols ----
+ * The set forms of nrq_rx_add_syms and nrq_tx_emit_syms: packets, keys and flags as in nrq_rxset_add / nrq_txset_emit; G, d_nsym
+ * and the slot layout as in the several-symbol calls above, with hdr = 0, 4 (tag inline) or 8 (key and tag inline), symbol i at
+ * hdr + i * T and pkt_stride >= hdr + G * T.  With NRQ_TX_KEY_INLINE / NRQ_RX_KEY_INLINE what the sender set writes is what the
+ * reception set reads.  Both are enqueue-only on the context's stream.
+ *
+ * nrq_rxset_add_syms: every member ends with exactly what its own nrq_rx_add_syms (an attached object: nrq_orx_add_syms) gives
+ * for the packets that carry its key, in packet order -- the same codes in the same slots of d_results (n * G entries, nullable),
+ * the same rows, the same repair list in slot order, the same counts and seen bits.  With d_nsym NULL the count rule takes the K
+ * of the member the first tag names.  A packet of an attached object's key with SBN >= Z gets what nrq_orx_add_syms gives it
+ * (c slots ERR or IGN, c = d_nsym[k], or G without d_nsym; a count of 0 or above G: slot k * G ERR).  A packet of no member keeps
+ * all its slots untouched and nothing of it is copied.  G = 1 with d_nsym NULL is nrq_rxset_add.  Refused: what nrq_rxset_add
+ * refuses, G outside 1..NRQ_PKT_SYMS_MAX, a stride too small, n * G > 0x7FFFFFFF.
+ *
+ * nrq_txset_emit_syms: packet k is named by (d_keys[k], first tag d_tags[k], count).  A packet whose (key, SBN) names a member
+ * gets, byte for byte, the header, the run of c_k payloads and the d_results[k] entry (n entries, nullable) that member's own
+ * nrq_tx_emit_syms / nrq_otx_emit_syms gives: 0 written, NRQ_TX_NOT_READY a relay's block that is not ready, NRQ_TX_BAD_RANGE (a
+ * sender is strict; the K of the member's segment decides the range); with NRQ_TX_KEY_INLINE the key goes in front of the FEC
+ * Payload ID.  A packet of no member is wholly untouched and gets -1; the bytes behind hdr + c_k * T are untouched; no packet is
+ * ever half written.  Ready bits are taken as they are at the call.  Refused: what nrq_txset_emit refuses, NRQ_TX_HELD (as in
+ * every several-symbol emit), G outside 1..NRQ_PKT_SYMS_MAX, a stride too small, n * G > 0x7FFFFFFF. */
+int nrq_rxset_add_syms(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
+                       uint32_t G, const uint8_t *d_nsym, uint32_t flags, int32_t *d_results);
+int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                        void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
 
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()

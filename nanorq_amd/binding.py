@@ -173,6 +173,10 @@ def lib():
         L.nrq_otx_emit_syms.argtypes = [vp, vp, u32, u32, vp, vp, sz, u32, vp]
         L.nrq_tx_emit_range_syms.argtypes = [vp, u32, u32, u32, C.c_int, vp, sz, u32, vp, vp, u32p]
         L.nrq_otx_emit_all_syms.argtypes = [vp, u32, u32, C.c_int, vp, sz, u32, vp, vp, u32p]
+    if hasattr(L, "nrq_rxset_add_syms"):  # (likewise a build from before the sets' packets of several symbols: those methods then raise)
+        u32 = C.c_uint32
+        L.nrq_rxset_add_syms.argtypes = [vp, vp, sz, vp, vp, u32, u32, vp, u32, vp]
+        L.nrq_txset_emit_syms.argtypes = [vp, vp, vp, u32, u32, vp, vp, sz, u32, vp]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -945,6 +949,25 @@ class ReceiverSet(_Handle):
         self.ctx._chk(self._L.nrq_rxset_add(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)),
                                             n, flags, C.c_void_p(_dptr(results))))
 
+    def add_syms(self, payload, G, keys=None, tags=None, nsym=None, inline=False, key_inline=False, results=None, n=None, stride=None):
+        """Ingest packets of up to G symbols each of all members (nrq_rxset_add_syms; enqueue only): payload, keys, tags, inline,
+        key_inline, n, stride as in add(), with the first tag of each packet; G, nsym and results ([n * G] int32 device tensor, one
+        entry per slot) as in Receiver.add_syms.  Symbol i of a packet lies at hdr + i * T, hdr = 0, 4 (inline) or 8 (key_inline).
+        Every member ends as its own add_syms over the packets of its key would leave it."""
+        if hasattr(payload, "data_ptr"):
+            n = payload.shape[0] if n is None else n
+            stride = payload.stride(0) * payload.element_size() if stride is None else stride
+        if n is None or stride is None:
+            raise ValueError("a raw payload address needs n and stride")
+        if inline == (tags is not None):
+            raise ValueError("give either tags or inline=True")
+        if key_inline and (not inline or keys is not None):
+            raise ValueError("key_inline=True goes with inline=True and without keys")
+        flags = (RX_TAG_INLINE if inline else 0) | (RX_KEY_INLINE if key_inline else 0)
+        self.ctx._chk(self._fn("nrq_rxset_add_syms")(self._h, C.c_void_p(_dptr(payload)), stride, C.c_void_p(_dptr(keys)),
+                                                     C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)), flags,
+                                                     C.c_void_p(_dptr(results))))
+
     def _fn(self, name):
         if not hasattr(self._L, name):
             raise NrqError("this library build has no %s" % name)
@@ -1076,6 +1099,29 @@ class SenderSet(_Handle):
         flags = _tx_flags(inline, held) | (TX_KEY_INLINE if key_inline else 0)
         self.ctx._chk(self._L.nrq_txset_emit(self._h, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n, C.c_void_p(_dptr(out)), stride,
                                              flags, C.c_void_p(_dptr(results))))
+        return out
+
+    def stride_syms(self, G, inline=False, key_inline=False):
+        """the packet stride of out=None for packets of G symbols: G * T, or G * T + 4 (inline) or + 8 (key_inline) rounded up to 16"""
+        hdr = 8 if key_inline else 4 if inline else 0
+        return (G * self.T + hdr + 15) // 16 * 16 if hdr else G * self.T
+
+    def emit_syms(self, keys, tags, G, nsym=None, out=None, inline=False, key_inline=False, results=None):
+        """Packet k of up to G symbols for (keys[k], first tag tags[k]) in row k of out (nrq_txset_emit_syms): keys, tags, out,
+        inline, key_inline as in emit(); G, nsym and results (0, -1, TX_NOT_READY, TX_BAD_RANGE; only a 0 packet is written, and
+        whole) as in _Emitter.emit_syms, each member with its own K.  Held symbols are not offered.  Enqueue only.  Returns out."""
+        if not hasattr(self._L, "nrq_txset_emit_syms"):
+            raise NrqError("this library build has no nrq_txset_emit_syms")
+        n = int(tags.shape[0])
+        if out is None:
+            import torch
+            out = torch.empty((n, self.stride_syms(G, inline, key_inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            stride = out.shape[1]
+        else:
+            stride = out.stride(0) * out.element_size()
+        flags = _tx_flags(inline, False) | (TX_KEY_INLINE if key_inline else 0)
+        self.ctx._chk(self._L.nrq_txset_emit_syms(self._h, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)),
+                                                  C.c_void_p(_dptr(out)), stride, flags, C.c_void_p(_dptr(results))))
         return out
 
 

@@ -30,6 +30,7 @@ LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
+ZEMU = os.path.join(ROOT, "tests", "emu", "libsyms_set_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 UEMU = os.path.join(ROOT, "tests", "emu", "libout_lists_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
@@ -203,6 +204,13 @@ def build_syms_emu(force=False):
     return _build_emu(YEMU, os.path.join(CSRC, "syms_emu.cpp"), ("emit_emu.h", "syms_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
 
 
+def build_syms_set_emu(force=False):
+    """tests/emu/libsyms_set_emu.so: CPU emulation of a reception set's ingest and a sender set's emit of packets of several
+    symbols (csrc/syms_set_emu.cpp over syms_set_body.h), with the set's path and word rules behind C entry points."""
+    return _build_emu(ZEMU, os.path.join(CSRC, "syms_set_emu.cpp"),
+                      ("syms_set_body.h", "syms_body.h", "ingest_set_body.h", "emit_set_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -305,6 +313,7 @@ if __name__ == "__main__":
     build_rxset_want_emu(force="-f" in sys.argv)
     build_txset_emu(force="-f" in sys.argv)
     build_syms_emu(force="-f" in sys.argv)
+    build_syms_set_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)

@@ -44,6 +44,7 @@
 #include "emit_body.h"
 #include "emit_set_body.h"
 #include "syms_body.h"
+#include "syms_set_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
@@ -5176,6 +5177,7 @@ int nrq_rxset_held(nrq_rxset *set, uint32_t *d_keys, uint32_t *d_tags, uint32_t 
  * and nrq_emit_held_kernel instantiation is compiled from the code it always was.  The payload walk (tx_payload, under
  * txs_payload's key word) and the held repair row lookup (tx_held_row) are those kernels' bodies. */
 enum : int { TXS_V16_KEY = 4 }; /* beside TX_V16 .. TX_BYTE: 16-byte loads and stores under the 8-byte header (key, FEC Payload ID) */
+static_assert(TXS_V16_KEY == 4, "sys_emit_path (syms_set_body.h) names this path by its number");
 
 __global__ __launch_bounds__(256) void nrq_txs_hist_kernel(const txs_tab *__restrict__ t, txs_call c, uint32_t *__restrict__ cnt) {
   __shared__ uint32_t skey[TXS_MAX_SEGS], ssbn0[TXS_MAX_SEGS], scnt[TXS_MAX_SEGS], sblk0[TXS_MAX_SEGS];
@@ -5225,24 +5227,25 @@ __global__ __launch_bounds__(256) void nrq_txs_place_kernel(const txs_tab *__res
 }
 
 /* the packet of (key, tag) at P in the call's header form (hdr = 0 / 4 / 8): tx_payload under the key word, or the 16-byte form
- * of the 8-byte header */
-template <int MODE>
-__device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, uint32_t T, const uint32_t *cols, uint32_t n, uint32_t key,
-                                            uint32_t tag, uint8_t *__restrict__ P, uint32_t hdr, uint32_t lane) {
+ * of the 8-byte header; `rows` as in tx_payload (one symbol, or a run of them: the payloads of a run are contiguous, so the carry
+ * crosses a symbol boundary as it crosses any chunk boundary) */
+template <int MODE, class ROWS>
+__device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, uint32_t T, const ROWS rows, uint32_t key, uint32_t tag,
+                                            uint8_t *__restrict__ P, uint32_t hdr, uint32_t lane) {
   if constexpr (MODE == TXS_V16_KEY) {
     /* packet chunk j (bytes 16j .. 16j+15) = payload dwords 4j-2 .. 4j+1: the previous lane's .z .w (the key word and the header
-     * for j = 0, the wave's last lane of the previous round for its first lane), then this chunk's .x .y; the last .z .w go to +T */
-    const uint32_t nch = T >> 4;
+     * for j = 0, the wave's last lane of the previous round for its first lane), then this chunk's .x .y; the last .z .w go to +len */
+    const uint32_t len = rows.len(T), nch = len >> 4;
     uint32_t cz = txs_key_word(key), cw = tx_header_word(tag);
     for (uint32_t j0 = 0; j0 < nch; j0 += 64u) {
       const uint32_t j = j0 + lane;
       const bool act = j < nch;
       tx_u128 v{0u, 0u, 0u, 0u};
-      if (act) v = tx_gather<tx_u128>(base, T, cols, n, (uint64_t)j * 16u);
+      if (act) v = rows.template word<tx_u128>(base, T, (uint64_t)j * 16u);
       uint32_t pz = __shfl_up(v.z, 1u), pw = __shfl_up(v.w, 1u);
       if (lane == 0) { pz = cz; pw = cw; }
       if (act) *reinterpret_cast<tx_u128 *>(P + (uint64_t)j * 16u) = tx_u128{pz, pw, v.x, v.y};
-      if (j == nch - 1u) *reinterpret_cast<uint2 *>(P + T) = make_uint2(v.z, v.w);
+      if (j == nch - 1u) *reinterpret_cast<uint2 *>(P + len) = make_uint2(v.z, v.w);
       cz = __shfl(v.z, 63);
       cw = __shfl(v.w, 63);
     }
@@ -5251,15 +5254,15 @@ __device__ __forceinline__ void txs_payload(const uint8_t *__restrict__ base, ui
       if (lane == 0) *reinterpret_cast<uint32_t *>(P) = txs_key_word(key);
       P += 4;
     }
-    tx_payload<TX_DWORD>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane);
+    tx_payload<TX_DWORD>(base, T, rows, tag, P, hdr ? 1u : 0u, lane);
   } else if constexpr (MODE == TX_BYTE) {
     if (hdr == 8u) {
       if (lane < 4u) P[lane] = (uint8_t)(txs_key_word(key) >> (8u * lane));
       P += 4;
     }
-    tx_payload<TX_BYTE>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane);
+    tx_payload<TX_BYTE>(base, T, rows, tag, P, hdr ? 1u : 0u, lane);
   } else {
-    tx_payload<MODE>(base, T, tx_one{cols, n}, tag, P, hdr ? 1u : 0u, lane); /* (TX_V16: hdr = 0; TX_V16_SHIFT: hdr = 4) */
+    tx_payload<MODE>(base, T, rows, tag, P, hdr ? 1u : 0u, lane); /* (TX_V16: hdr = 0; TX_V16_SHIFT: hdr = 4) */
   }
 }
 
@@ -5319,7 +5322,7 @@ __global__ __launch_bounds__(256) void nrq_emit_set_kernel(const txs_tab *__rest
     } else {
       base = tx_base(&S->b, tag);
     }
-    txs_payload<MODE>(base, T, s_cols[wv][i], n, key, tag, c.pkts + (uint64_t)k * c.pkt_stride, c.hdr, lane);
+    txs_payload<MODE>(base, T, tx_one{s_cols[wv][i], n}, key, tag, c.pkts + (uint64_t)k * c.pkt_stride, c.hdr, lane);
   }
 }
 
@@ -5438,6 +5441,64 @@ static int txset_attach(nrq_txset *set, const char *who, uint32_t key, tx_sender
   return txset_commit(set, mem);
 }
 
+/* What the set's emits share once their arguments are checked: the members' state, the ready bits of the global blocks, the payload
+ * path (*mode: TX_V16 .. TX_BYTE or TXS_V16_KEY), the call over n packets with its arrays carved out of the set's scratch, and the
+ * three bucketing passes over the tags, enqueued.  The emit kernel is the caller's. */
+static int txset_call_of(nrq_txset *set, const char *who, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts,
+                         size_t pkt_stride, uint32_t hdr, bool held, int32_t *d_results, txs_ready *rdyp, txs_call *cp, int *mode) {
+  nrq_ctx *ctx = set->ctx;
+  for (const txset_member &m : set->mem) {
+    if (m.tx->detached) return fail(ctx, -1, "%s: the reception of the relay under key %u was destroyed", who, m.key);
+    if (!m.tx->encoded) return fail(ctx, -1, "%s: the member under key %u is not encoded (%s)", who, m.key, m.tx->unencoded);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint32_t nb = set->nblk, nbins = nb + 1u;
+  const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
+  const int rc = set->scratch.ensure(ctx, need);
+  if (rc) return rc;
+  /* the ready bits of the global blocks as the members have them NOW, by value into this call's kernel arguments: a relay's mask
+   * changes in decodes, encodes and resets without any call on the set, and an emit still queued keeps the bits it was given */
+  txs_ready rdy{};
+  uintptr_t al = reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | set->T;
+  uint32_t g0 = 0;
+  for (const txset_seg &r : set->segs) {
+    const tx_sender *tx = r.tx;
+    const tx_blk &t = tx->s.seg[r.g];
+    for (uint32_t b = 0; b < t.nblk; b++)
+      if (!tx->relay || tx_is_ready(tx, t.sbn0 + b - tx->s.sbn0)) rdy.w[(g0 + b) >> 5] |= 1u << ((g0 + b) & 31u);
+    g0 += t.nblk;
+    al |= reinterpret_cast<uintptr_t>(t.src) | t.src_stride | reinterpret_cast<uintptr_t>(t.inter) | t.inter_stride;
+    if (held && tx->relay) { /* (held repair rows are copied too) */
+      const ing_rx &rr = tx->from[r.g]->r;
+      al |= reinterpret_cast<uintptr_t>(rr.rep) | rr.rep_stride;
+    }
+  }
+  *mode = sys_emit_path(al, hdr, ctx->tune.tx_dword ? 1u : 0u);
+  *rdyp = rdy;
+  uint8_t *p = (uint8_t *)set->scratch.p;
+  uint32_t *cnt = (uint32_t *)p;
+  txs_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.hdr = hdr;
+  c.T = set->T;
+  c.keys = d_keys;
+  c.tags = d_tags;
+  c.seg = (uint32_t *)(p + o_seg);
+  c.order = (uint32_t *)(p + o_order);
+  c.results = d_results;
+  *cp = c;
+  const txs_tab *t = (const txs_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
+  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
+  hipLaunchKernelGGL(nrq_txs_hist_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
+  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, st, nbins, cnt);
+  hipLaunchKernelGGL(nrq_txs_place_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
+  return 0;
+}
+
 static_assert(NRQ_TXSET_MAX_SEGS == TXS_MAX_SEGS && NRQ_TXSET_MAX_BLOCKS == TXS_MAX_BLOCKS, "the header's caps are the table's");
 
 extern "C" {
@@ -5527,55 +5588,200 @@ int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tag
   if (!d_tags || n > 0x7FFFFFFFu) return fail(ctx, -1, "nrq_txset_emit: bad tags (n=%u)", n);
   const uint32_t hdr = kinl ? 8u : inl ? 4u : 0u;
   if (pkt_stride < (size_t)set->T + hdr) return fail(ctx, -1, "nrq_txset_emit: pkt_stride %zu shorter than a packet", pkt_stride);
-  for (const txset_member &m : set->mem) {
-    if (m.tx->detached) return fail(ctx, -1, "nrq_txset_emit: the reception of the relay under key %u was destroyed", m.key);
-    if (!m.tx->encoded) return fail(ctx, -1, "nrq_txset_emit: the member under key %u is not encoded (%s)", m.key, m.tx->unencoded);
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t nb = set->nblk, nbins = nb + 1u;
-  const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
-  const int rc = set->scratch.ensure(ctx, need);
+  txs_ready rdy;
+  txs_call c;
+  int mode;
+  const int rc = txset_call_of(set, "nrq_txset_emit", d_keys, d_tags, n, d_pkts, pkt_stride, hdr, held, d_results, &rdy, &c, &mode);
   if (rc) return rc;
-  /* the ready bits of the global blocks as the members have them NOW, by value into this call's kernel arguments: a relay's mask
-   * changes in decodes, encodes and resets without any call on the set, and an emit still queued keeps the bits it was given */
-  txs_ready rdy{};
-  uintptr_t al = reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | set->T;
-  uint32_t g0 = 0;
-  for (const txset_seg &r : set->segs) {
-    const tx_sender *tx = r.tx;
-    const tx_blk &t = tx->s.seg[r.g];
-    for (uint32_t b = 0; b < t.nblk; b++)
-      if (!tx->relay || tx_is_ready(tx, t.sbn0 + b - tx->s.sbn0)) rdy.w[(g0 + b) >> 5] |= 1u << ((g0 + b) & 31u);
-    g0 += t.nblk;
-    al |= reinterpret_cast<uintptr_t>(t.src) | t.src_stride | reinterpret_cast<uintptr_t>(t.inter) | t.inter_stride;
-    if (held && tx->relay) { /* (held repair rows are copied too) */
-      const ing_rx &rr = tx->from[r.g]->r;
-      al |= reinterpret_cast<uintptr_t>(rr.rep) | rr.rep_stride;
-    }
-  }
-  const int mode = (al & 15u) == 0 && !ctx->tune.tx_dword ? (hdr == 8u ? TXS_V16_KEY : hdr ? TX_V16_SHIFT : TX_V16) : (al & 3u) == 0 ? TX_DWORD : TX_BYTE;
-  uint8_t *p = (uint8_t *)set->scratch.p;
-  uint32_t *cnt = (uint32_t *)p;
-  txs_call c{};
-  c.pkts = (uint8_t *)d_pkts;
-  c.pkt_stride = pkt_stride;
-  c.n = n;
-  c.hdr = hdr;
-  c.T = set->T;
-  c.keys = d_keys;
-  c.tags = d_tags;
-  c.seg = (uint32_t *)(p + o_seg);
-  c.order = (uint32_t *)(p + o_order);
-  c.results = d_results;
-  const txs_tab *t = (const txs_tab *)set->tab;
-  hipStream_t st = ctx->stream;
-  const uint32_t tiles = (n + TX_BIN_TILE - 1u) / TX_BIN_TILE;
-  HIPCHK(ctx, hipMemsetAsync(cnt, 0, (size_t)nbins * 4u, st));
-  hipLaunchKernelGGL(nrq_txs_hist_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
-  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, st, nbins, cnt);
-  hipLaunchKernelGGL(nrq_txs_place_kernel, dim3(tiles), dim3(256), 0, st, t, c, cnt);
   const dim3 grid((n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), wg(64u * TX_WAVES);
-  hipLaunchKernelGGL(kern[held][mode], grid, wg, 0, st, t, rdy, c);
+  hipLaunchKernelGGL(kern[held][mode], grid, wg, 0, ctx->stream, (const txs_tab *)set->tab, rdy, c);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+} /* extern "C" */
+
+/* ================================================ sets: packets of several symbols (nrq_*set_*_syms, syms_set_body.h) ==== */
+/* The two layers above put together, in kernels of their own: every kernel of the sets and of the single several-symbol forms is
+ * compiled from the code it always was.
+ *
+ * Ingest: the chain of nrq_rxset_add over n * G slots.  Passes 2 and 4 are per global block and are nrq_rxset_add's kernels, the
+ * copy is nrq_rx_add_syms'; passes 1, 3, 5, 7 are these, with the geometry of the nrq_ings_* kernels, and ask syms_set_body.h what
+ * a slot is.  Pass 1 decodes and searches once per SLOT: the slots of a packet may lie in two waves, and the search reads LDS. */
+__global__ __launch_bounds__(256) void nrq_ings_first_syms_kernel(const ings_tab *__restrict__ t, ings_call s, sy_rx y) {
+  __shared__ uint32_t skey[INGS_MAX_MEMBERS], ssbn0[INGS_MAX_MEMBERS], scnt[INGS_MAX_MEMBERS], sobjZ[INGS_MAX_MEMBERS];
+  const uint32_t nmem = min(t->nmem, INGS_MAX_MEMBERS), i = threadIdx.x;
+  if (i < nmem) { skey[i] = t->key[i]; ssbn0[i] = t->sbn0[i]; scnt[i] = t->cnt[i]; sobjZ[i] = t->objZ[i]; }
+  __syncthreads();
+  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
+  if (sl >= s.c.n) return;
+  uint32_t key, tag;
+  ings_decode(&s, sl / y.G, &key, &tag);
+  sys_first(t, &s, &y, sl, tag, ings_find(skey, ssbn0, scnt, sobjZ, nmem, key, tag >> 24));
+}
+
+/* dynamic LDS: t->nblk counters */
+__global__ __launch_bounds__(256) void nrq_ings_hist_syms_kernel(const ings_tab *__restrict__ t, ings_call s, sy_rx y) {
+  extern __shared__ uint32_t ings_h[];
+  const uint32_t i = threadIdx.x, sl = blockIdx.x * ING_TILE + i, nb = t->nblk;
+  for (uint32_t g = i; g < nb; g += 256u) ings_h[g] = 0;
+  __syncthreads();
+  if (sl < s.c.n) {
+    const uint32_t g = sys_cand(t, &s, &y, sl);
+    if (g != ING_NONE) atomicAdd(&ings_h[g], 1u);
+  }
+  __syncthreads();
+  for (uint32_t g = i; g < nb; g += 256u) s.c.base[(size_t)g * s.c.ntiles + blockIdx.x] = ings_h[g];
+}
+
+/* dynamic LDS: 4 * t->nblk counters (nrq_ings_classify_kernel over slots: the same ranking, in slot order) */
+__global__ __launch_bounds__(256) void nrq_ings_classify_syms_kernel(const ings_tab *__restrict__ t, ings_call s, sy_rx y) {
+  extern __shared__ uint32_t ings_wc[];
+  const uint32_t i = threadIdx.x, sl = blockIdx.x * ING_TILE + i, nb = t->nblk;
+  for (uint32_t j = i; j < 4u * nb; j += 256u) ings_wc[j] = 0;
+  __syncthreads();
+  const uint32_t g = sl < s.c.n ? sys_cand(t, &s, &y, sl) : ING_NONE;
+  const uint32_t row = ing_rank_wg(ings_wc, nb, g, s.c.base, s.c.ntiles);
+  if (sl < s.c.n) sys_classify(t, &s, &y, sl, row);
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_fold_syms_kernel(const ings_tab *__restrict__ t, ings_call s, sy_rx y) {
+  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
+  if (sl < s.c.n) sys_fold(t, &s, &y, sl);
+}
+
+/* Emit.  The wave shape of nrq_emit_syms_kernel over the segment table of nrq_emit_set_kernel: a wave takes 64 / G packets of the
+ * work order (block-major over the set's global blocks: nrq_txs_hist_kernel, the scan and nrq_txs_place_kernel over the first
+ * tags), lane l the slot (l / G, l % G).  Each lane admits its packet (sys_tx_admit: per packet, so every lane of a packet decides
+ * alike) and builds its slot's column list into LDS from its segment's parameters, read through the table pointer; then the wave
+ * writes the admitted packets one after the other, each as ONE run of c_k * T bytes (txs_payload over a tx_run; a packet of one
+ * symbol takes the one-symbol walk), the segment index made wave-uniform as in nrq_emit_set_kernel. */
+template <int MODE>
+__global__ __launch_bounds__(256) void nrq_emit_set_syms_kernel(const txs_tab *__restrict__ t, txs_ready rdy, txs_call c, sy_tx y) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS], s_key[TX_WAVES][TX_WAVE_PKTS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t G = y.G, per = 64u / G, p = lane / G, i = lane - p * G;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * per; /* the wave's first packet in the work order */
+  {
+    uint32_t n = 0, cnt = 0, tag0 = 0, k = 0, sg = TXS_NONE, key = 0;
+    if (p < per && w0 + p < c.n) {
+      k = c.order[w0 + p];
+      if (k < c.n) { /* (always: the work order is a permutation) */
+        tag0 = c.tags[k];
+        key = txs_key_of(&c, k);
+        sg = c.seg[k];
+        int32_t code;
+        if (sys_tx_admit(t, &rdy, &y, k, tag0, sg, &code, &cnt) && i < cnt) n = tx_rows(&t->seg[sg].b, tag0 + i, s_cols[wv][lane]);
+        if (i == 0u && c.results) c.results[k] = code;
+      }
+    }
+    s_n[wv][lane] = n | (cnt << 8); /* (cnt = 0: the packet stays untouched) */
+    s_tag[wv][lane] = tag0;
+    s_k[wv][lane] = k;
+    s_seg[wv][lane] = sg;
+    s_key[wv][lane] = key;
+  }
+  __syncthreads();
+  const uint32_t T = c.T;
+  for (uint32_t q = 0; q < per && w0 + q < c.n; q++) { /* (wave-uniform) */
+    const uint32_t l0 = q * G;
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][l0]), cnt = nk >> 8;
+    if (!cnt) continue; /* no member, a block that is not ready, a refused range */
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][l0]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(s_k[wv][l0]);
+    const uint32_t key = __builtin_amdgcn_readfirstlane(s_key[wv][l0]);
+    const txs_seg *S = &t->seg[__builtin_amdgcn_readfirstlane(s_seg[wv][l0])];
+    const uint8_t *base = tx_base(&S->b, tag); /* (a sender's packet never runs from source into repair ESIs: sy_tx_count) */
+    uint8_t *P = c.pkts + (uint64_t)k * c.pkt_stride;
+    if (cnt == 1u) txs_payload<MODE>(base, T, tx_one{s_cols[wv][l0], nk & 0xFFu}, key, tag, P, c.hdr, lane);
+    else txs_payload<MODE>(base, T, tx_run{&s_cols[wv][l0], &s_n[wv][l0], cnt}, key, tag, P, c.hdr, lane);
+  }
+}
+
+extern "C" {
+
+int nrq_rxset_add_syms(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
+                       uint32_t G, const uint8_t *d_nsym, uint32_t flags, int32_t *d_results) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_rxset_add_syms";
+  const bool inl = (flags & NRQ_RX_TAG_INLINE) != 0, kinl = (flags & NRQ_RX_KEY_INLINE) != 0;
+  if (flags & ~(uint32_t)(NRQ_RX_TAG_INLINE | NRQ_RX_KEY_INLINE)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (kinl && !inl) return fail(ctx, -1, "%s: NRQ_RX_KEY_INLINE needs NRQ_RX_TAG_INLINE", who);
+  if (kinl && d_keys) return fail(ctx, -1, "%s: give either d_keys or NRQ_RX_KEY_INLINE", who);
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  if (n == 0 || set->mem.empty()) return 0;
+  const uint32_t T = set->T, poff = kinl ? 8u : inl ? 4u : 0u;
+  const size_t pkt_len = (uint64_t)G * T > 0xFFFFFFFFu ? SIZE_MAX : (size_t)G * T + poff;
+  ings_call s{};
+  ing_call &c = s.c;
+  sy_rx y{};
+  y.G = G; y.nsym = d_nsym;
+  uint8_t *tail; /* the packets' members (a word per packet), then the slots' kinds (a byte per slot) */
+  const int rc = ing_call_of(ctx, set->scratch, who, d_pkts, pkt_stride, d_tags, n, G, pkt_len, inl, set->nblk, d_results,
+                             rx_al((size_t)n * 4u) + (size_t)n * G, &c, &tail);
+  if (rc) return rc;
+  s.keys = d_keys;
+  s.key_inline = kinl ? 1u : 0u;
+  s.mem = (uint32_t *)tail;
+  y.kind = tail + rx_al((size_t)n * 4u);
+  uintptr_t al = reinterpret_cast<uintptr_t>(d_pkts) | pkt_stride | poff | T;
+  for (const rxset_member &m : set->mem) {
+    const ing_rx &r = m.rx->r;
+    al |= reinterpret_cast<uintptr_t>(r.src) | r.src_stride | reinterpret_cast<uintptr_t>(r.rep) | r.rep_stride;
+  }
+  const uint32_t word = sy_copy_word(al);
+  const ings_tab *t = (const ings_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  const uint32_t g = (c.n + 255u) / 256u, nb = set->nblk;
+  hipLaunchKernelGGL(nrq_ings_first_syms_kernel, dim3(g), dim3(256), 0, st, t, s, y);
+  hipLaunchKernelGGL(nrq_ings_done_kernel, dim3(nb), dim3(256), 0, st, t);
+  hipLaunchKernelGGL(nrq_ings_hist_syms_kernel, dim3(c.ntiles), dim3(256), nb * 4u, st, t, s, y);
+  hipLaunchKernelGGL(nrq_ings_scan_kernel, dim3(nb), dim3(256), 0, st, t, s);
+  hipLaunchKernelGGL(nrq_ings_classify_syms_kernel, dim3(c.ntiles), dim3(256), nb * 16u, st, t, s, y);
+  const dim3 cg((n + 3u) / 4u);
+  if (word == 16u)
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint4>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, T, poff);
+  else if (word == 4u)
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint32_t>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, T, poff);
+  else
+    hipLaunchKernelGGL(nrq_ing_copy_syms_kernel<uint8_t>, cg, dim3(256), 0, st, c.pkts, c.pkt_stride, (const uint64_t *)c.dst, n, G, T, poff);
+  hipLaunchKernelGGL(nrq_ings_fold_syms_kernel, dim3(g), dim3(256), 0, st, t, s, y);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
+                        void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results) {
+  using set_fn = void (*)(const txs_tab *, txs_ready, txs_call, sy_tx);
+  static const set_fn kern[5] = {nrq_emit_set_syms_kernel<TX_V16>, nrq_emit_set_syms_kernel<TX_V16_SHIFT>, nrq_emit_set_syms_kernel<TX_DWORD>,
+                                 nrq_emit_set_syms_kernel<TX_BYTE>, nrq_emit_set_syms_kernel<TXS_V16_KEY>}; /* [mode] */
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_txset_emit_syms";
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0, kinl = (flags & NRQ_TX_KEY_INLINE) != 0;
+  if (flags & NRQ_TX_HELD) return fail(ctx, -1, "%s: NRQ_TX_HELD is not offered with packets of several symbols (held symbols are decided per symbol)", who);
+  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_KEY_INLINE)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (kinl && !inl) return fail(ctx, -1, "%s: NRQ_TX_KEY_INLINE needs NRQ_TX_TAG_INLINE", who);
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  if (n == 0 || set->mem.empty()) return 0;
+  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
+  if (!d_tags || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u, G=%u)", who, n, G);
+  const uint32_t hdr = kinl ? 8u : inl ? 4u : 0u;
+  if ((uint64_t)G * set->T > 0xFFFFFFFFu || pkt_stride < (size_t)G * set->T + hdr)
+    return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G);
+  txs_ready rdy;
+  txs_call c;
+  int mode;
+  const int rc = txset_call_of(set, who, d_keys, d_tags, n, d_pkts, pkt_stride, hdr, false, d_results, &rdy, &c, &mode);
+  if (rc) return rc;
+  sy_tx y{};
+  y.G = G; y.nsym = d_nsym;
+  const uint32_t per = 64u / G, waves = (n + per - 1u) / per;
+  hipLaunchKernelGGL(kern[mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, (const txs_tab *)set->tab, rdy,
+                     c, y);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
