@@ -480,15 +480,39 @@ int nrq_orx_relay(nrq_orx *rx, nrq_otx **out);
  * hdr + c_k * T are untouched.  d_results[k] (n entries, nullable): 0 written; -1 SBN outside the span; NRQ_TX_NOT_READY a relay's
  * block that is not ready; NRQ_TX_BAD_RANGE a count of 0 or above G, a GIVEN count that takes a packet starting below K to K or
  * beyond (a sender is strict), or e_k + c_k - 1 > 0xFFFFFF -- in all but the first case the packet is untouched.  Admission is
- * per packet (every symbol of a packet has the packet's block): no packet is ever half written.  NRQ_TX_HELD is refused here
- * (-1): held symbols are decided per symbol.
+ * per packet (every symbol of a packet has the packet's block): no packet is ever half written.
+ * NRQ_TX_HELD (a relay or an object's relay only; a sender refuses it, -1): packet k = (SBN, e, c) of a block that is NOT ready,
+ * with an admissible range, is written iff the reception holds EVERY symbol e .. e+c-1 (nrq_rx_held's meaning) -- all or nothing,
+ * so that the flag leaves no packet half written either: 0 and the header if inline, then c payloads, payload i byte for byte what
+ * nrq_tx_emit with NRQ_TX_HELD writes for (SBN, e+i) at that moment; else NRQ_TX_NOT_READY and the packet untouched.  An
+ * inadmissible range (above) is NRQ_TX_BAD_RANGE whether or not the block is ready; a ready block and an SBN outside the span are
+ * as without the flag.  c is d_nsym[k], or the sender's rule.  The list nrq_rx_held_syms gives is answered in full.
  *
  * nrq_tx_emit_range_syms / nrq_otx_emit_all_syms: ESIs esi0 .. esi0+n-1 (0 .. K+nrep-1) of every block, packetised per block: the
  * source run [esi0, min(K, esi0+n)) cut into packets of G from its start, the last one short, then the repair run
  * [max(K, esi0), esi0+n) likewise -- nrq_pkt_count(K, esi0, n, G) packets per block.  order 0: block-major; order 1: round j holds
  * packet j of every block that has one, in SBN order (a class with fewer packets drops out of the later rounds).  d_tags_out
  * (first tags) and d_nsym_out (counts), both nullable, are in packet order.  *h_npkt (nullable) receives the number of packets.
- * A relay with a block that is not ready is refused, as nrq_tx_emit_range.
+ * A relay with a block that is not ready is refused, as nrq_tx_emit_range; so is NRQ_TX_HELD.
+ *
+ * nrq_rx_want_syms / nrq_rx_held_syms (and nrq_orx_*): what nrq_rx_want / nrq_rx_held list for the same reception and the same
+ * flags, extra, esi_from, as PACKETS of up to G symbols: d_tags[k] a first tag, d_nsym[k] its count -- the form nrq_tx_emit_syms
+ * takes (d_tags, d_nsym) and nrq_rx_add_syms takes (d_nsym).  The PACKETISATION of the one-symbol list L of one block, in L's
+ * order: a RUN is a maximal stretch L[i..j] with L[i+m] == L[i] + m (consecutive ESIs in list order); a run never holds both an ESI
+ * below K and one at or above K (the source part and the repair part of a held list are packetised apart, also where ESI K - 1 is
+ * followed by ESI K); every run is cut into packets of G from its START, the last one short.  The packetisation of a listing is
+ * that of its blocks, one behind the other (SBN order; an object: class L, then class S, each with its own K).  Its expansion is
+ * L word for word; with G = 1 the first tags are L and every count is 1.
+ *   want, repair mode    the truncation at the block's `need` only shortens the tail: the last packet may be cut short by it
+ *   held, source part    the seen source ESIs ascending
+ *   held, repair part    arrival order: a run is rep_esi[q+1] == rep_esi[q] + 1, it lies in consecutive repair rows (arrival 12, 13,
+ *                        14 is one packet (12, 3); arrival 14, 13, 12 is three packets of 1)
+ * The calling contract is nrq_rx_want's: the call waits for the work enqueued before it; *h_npkt (required) is the number of
+ * packets, *h_nsym (nullable) the number of symbols -- exactly the one-symbol call's *h_n -- both final on return and from ONE
+ * wait; d_tags and d_nsym both NULL: the counts only; cap is in packets, cap < *h_npkt gives -1 with both totals still filled and
+ * nothing written; otherwise the writing is enqueued on the context's stream, so an emit behind it sees the list without a host
+ * wait.  The calls only read the reception's books.  Refused (-1 and a text, nothing enqueued): what nrq_rx_want refuses, G
+ * outside 1..NRQ_PKT_SYMS_MAX, exactly one of d_tags / d_nsym given, h_npkt NULL.
  *
  * Reception sets and sender sets take such packets through nrq_rxset_add_syms and nrq_txset_emit_syms (below, behind the sets). */
 #define NRQ_PKT_SYMS_MAX 64u
@@ -506,6 +530,12 @@ int nrq_tx_emit_range_syms(nrq_tx *tx, uint32_t esi0, uint32_t n, uint32_t G, in
                            uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt);
 int nrq_otx_emit_all_syms(nrq_otx *tx, uint32_t nrep, uint32_t G, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
                           uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt);
+int nrq_rx_want_syms(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap,
+                     uint32_t *h_npkt, uint32_t *h_nsym);
+int nrq_orx_want_syms(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap,
+                      uint32_t *h_npkt, uint32_t *h_nsym);
+int nrq_rx_held_syms(nrq_rx *rx, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym);
+int nrq_orx_held_syms(nrq_orx *rx, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym);
 
 /* ---- reception sets:the packets of MANY receptions in one buffer, ingested in one pass ----
  * A set is a table of member receptions of one context and one T, each under a 32-bit KEY the caller chooses (a TOI, a flow

@@ -177,6 +177,12 @@ def lib():
         u32 = C.c_uint32
         L.nrq_rxset_add_syms.argtypes = [vp, vp, sz, vp, vp, u32, u32, vp, u32, vp]
         L.nrq_txset_emit_syms.argtypes = [vp, vp, vp, u32, u32, vp, vp, sz, u32, vp]
+    if hasattr(L, "nrq_rx_want_syms"):  # (likewise a build from before the listings as runs: want_syms / held_syms then raise)
+        u32 = C.c_uint32
+        L.nrq_rx_want_syms.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, u32p, u32p]
+        L.nrq_orx_want_syms.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, u32p, u32p]
+        L.nrq_rx_held_syms.argtypes = [vp, u32, vp, vp, u32, u32p, u32p]
+        L.nrq_orx_held_syms.argtypes = [vp, u32, vp, vp, u32, u32p, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -537,6 +543,19 @@ class Receiver(_Handle):
         wants nothing until extra exceeds its surplus."""
         return _want(self, extra, source, esi_from)
 
+    def want_syms(self, G, extra=0, source=False, esi_from=0):
+        """want() as packets of up to G symbols (nrq_rx_want_syms): (tags int32 [n], nsym uint8 [n]) device tensors, packet k the
+        first tag tags[k] and its count nsym[k] -- every run of consecutive ESIs of want()'s list cut into packets of G from its
+        start, the last one short.  The form parent.emit_syms(tags, G, nsym, held=...) and add_syms(..., nsym=nsym) take; its
+        expansion is want()'s list word for word (waits)."""
+        return _list_syms(self, "_want_syms", (WANT_SOURCE if source else 0, extra, esi_from, G))
+
+    def held_syms(self, G):
+        """held() as packets of up to G symbols (nrq_rx_held_syms), as want_syms: per block the runs of its seen source ESIs, then
+        those of its repair ESIs in arrival order (a run lies in consecutive repair rows).  It is the list
+        relay().emit_syms(tags, G, nsym, held=True) writes in full (waits)."""
+        return _list_syms(self, "_held_syms", (G,))
+
     def relay(self):
         """A Sender over this reception's own rows (nrq_rx_relay): it emits any (SBN, ESI) of every block that is ready -- decoded
         while the relay was attached, or complete and made ready by its encode().  One per reception."""
@@ -598,6 +617,23 @@ def _want(rx, extra, source, esi_from):
     return out
 
 
+def _list_syms(rx, name, args):
+    """<_api>_want_syms / <_api>_held_syms: the counts first, then the packets into two tensors of that size"""
+    import torch
+    fn = getattr(rx._L, rx._api + name, None)
+    if fn is None:
+        raise NrqError("this build of the library has no listings in packets of several symbols (%s%s)" % (rx._api, name))
+    npkt = C.c_uint32(0)
+    rx.ctx._chk(fn(rx._h, *args, None, None, 0, C.byref(npkt), None))
+    dev = "cuda:%d" % rx.ctx.device
+    tags = torch.empty(npkt.value, dtype=torch.int32, device=dev)
+    nsym = torch.empty(npkt.value, dtype=torch.uint8, device=dev)
+    if npkt.value:
+        rx.ctx._chk(fn(rx._h, *args, C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), npkt.value, C.byref(npkt), None))
+        rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
+    return tags, nsym
+
+
 TX_TAG_INLINE = 1   # NRQ_TX_TAG_INLINE
 TX_HELD = 2         # NRQ_TX_HELD
 TX_NOT_READY = -2   # NRQ_TX_NOT_READY
@@ -649,15 +685,17 @@ class _Emitter(_Handle):
         out = torch.empty((n, self.stride_syms(G, inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
         return out, out.shape[1]
 
-    def emit_syms(self, tags, G, nsym=None, out=None, inline=False, results=None):
+    def emit_syms(self, tags, G, nsym=None, out=None, inline=False, results=None, held=False):
         """Packet k of up to G symbols for the first tag tags[k] in row k of out (<_api>_emit_syms): nsym[k] symbols ([n] uint8
         device tensor), or by the sender's rule with nsym None -- G, but a packet of source symbols ends with the block's last
         one.  results: optional [n] int32 device tensor (0, -1, TX_NOT_READY, TX_BAD_RANGE; only a 0 packet is written, and
-        whole).  Held symbols are not offered.  Returns out."""
+        whole).  held (relays only; a sender refuses it): a packet of a block that is not ready is still written when its
+        reception holds EVERY one of its symbols (TX_HELD) -- all or nothing, else TX_NOT_READY; what Receiver.held_syms lists is
+        written in full.  Returns out."""
         n = int(tags.shape[0])
         out, stride = self._out_syms(n, G, inline, out)
         self.ctx._chk(_syms_fn(self, "_emit_syms")(self._h, C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)), C.c_void_p(_dptr(out)),
-                                                   stride, _tx_flags(inline, False), C.c_void_p(_dptr(results))))
+                                                   stride, _tx_flags(inline, held), C.c_void_p(_dptr(results))))
         return out
 
     def _range_syms(self, fn, head, npkt, G, interleave, inline, out):
@@ -879,6 +917,14 @@ class ObjectReceiver(_Handle):
     def held(self):
         """as Receiver.held, over both block classes in SBN order"""
         return _held(self)
+
+    def want_syms(self, G, extra=0, source=False, esi_from=0):
+        """as Receiver.want_syms, over both block classes in SBN order, each with its own K"""
+        return _list_syms(self, "_want_syms", (WANT_SOURCE if source else 0, extra, esi_from, G))
+
+    def held_syms(self, G):
+        """as Receiver.held_syms, over both block classes in SBN order, each with its own K"""
+        return _list_syms(self, "_held_syms", (G,))
 
     def want(self, extra=0, source=False, esi_from=0):
         """as Receiver.want, over both block classes in SBN order (each class with its own K)"""

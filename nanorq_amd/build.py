@@ -31,6 +31,7 @@ QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
 ZEMU = os.path.join(ROOT, "tests", "emu", "libsyms_set_emu.so")
+GEMU = os.path.join(ROOT, "tests", "emu", "libruns_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 UEMU = os.path.join(ROOT, "tests", "emu", "libout_lists_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
@@ -211,6 +212,13 @@ def build_syms_set_emu(force=False):
                       ("syms_set_body.h", "syms_body.h", "ingest_set_body.h", "emit_set_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
 
 
+def build_runs_emu(force=False):
+    """tests/emu/libruns_emu.so: CPU emulation of the want and held listings as runs and of the held emit of packets of several
+    symbols (csrc/runs_emu.cpp over runs_body.h)."""
+    return _build_emu(GEMU, os.path.join(CSRC, "runs_emu.cpp"),
+                      ("emit_emu.h", "runs_body.h", "syms_body.h", "want_body.h", "held_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
+
+
 def build_obj_emu(force=False):
     """tests/emu/libobj_emu.so: CPU emulation of the device-resident object layout kernel (obj_body.h)."""
     return _build_emu(OEMU, os.path.join(ROOT, "tests", "emu", "obj_emu.cpp"), ("obj_body.h", "emit_body.h", "rq_math.h"), force)
@@ -314,6 +322,7 @@ if __name__ == "__main__":
     build_txset_emu(force="-f" in sys.argv)
     build_syms_emu(force="-f" in sys.argv)
     build_syms_set_emu(force="-f" in sys.argv)
+    build_runs_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)

@@ -45,6 +45,7 @@
 #include "emit_set_body.h"
 #include "syms_body.h"
 #include "syms_set_body.h"
+#include "runs_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
@@ -4262,6 +4263,91 @@ __global__ __launch_bounds__(256) void nrq_emit_syms_kernel(tx_src s, tx_call c,
   }
 }
 
+/* The tag-list emit of several symbols with held symbols (NRQ_TX_HELD; relays only): the wave shape of nrq_emit_syms_kernel, a
+ * kernel of its own so that its instantiations and nrq_emit_held_kernel's are compiled from the code they always were.  Admission
+ * (hs_packet, runs_body.h): a ready block's packet goes the usual way; one of a block that is not ready is written iff the
+ * reception holds EVERY one of its symbols -- each lane asks for its slot's seen bit, a ballot over the packet's lanes decides, so
+ * a packet is written whole or not at all.  Held source symbols are source rows e .. e+c-1.  The rows of held repair symbols are
+ * found per packet by the wave that writes it: one walk over the block's repair list in trips of 64, a lane whose entry lies in
+ * [e, e+c) stores its row index into the LDS word of slot entry - e (the head of that slot's column list); the packet is then one
+ * run over single-row lists from the base of the block's repair rows. */
+template <int MODE, bool MULTI>
+__global__ __launch_bounds__(256) void nrq_emit_held_syms_kernel(tx_src s, tx_held h, tx_call c, sy_tx y) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS]; /* (MULTI only: unused LDS is not allocated) */
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t G = y.G, per = 64u / G, p = lane / G, i = lane - p * G;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * per; /* the wave's first packet in the work order */
+  {
+    uint32_t n = 0, cnt = 0, tag0 = 0, k = 0, sg = TX_SEGS, ready = 0, kind = TX_READY;
+    int32_t code = TX_FOREIGN;
+    const bool mine = p < per && w0 + p < c.n;
+    if (mine) {
+      k = c.order[w0 + p];
+      tag0 = c.tags[k];
+      sg = hs_packet<MULTI>(&s, &y, tag0, k, &code, &cnt, &ready);
+    }
+    const tx_blk sb = MULTI ? tx_pick(&s, sg) : s.seg[0];
+    const uint32_t e = tag0 & SY_ESI_MAX;
+    /* all or nothing: every slot of a packet of a block that is not ready must be held (every lane of the wave takes the ballot) */
+    bool ok = true;
+    if (sg < TX_SEGS && !ready && i < cnt) { /* (a branch per segment: a select over the by-value table would be indexed from scratch) */
+      const uint32_t b = tx_block(&sb, tag0);
+      if (!MULTI || sg == 0u) ok = hs_slot_held(&h.seg[0], b, e + i);
+      else if (sg == 1u) ok = hs_slot_held(&h.seg[1], b, e + i);
+      else ok = hs_slot_held(&h.seg[2], b, e + i);
+    }
+    const uint64_t held = __ballot(ok), pmask = (cnt >= 64u ? ~0ull : (1ull << cnt) - 1ull) << (p * G);
+    if (sg < TX_SEGS && !ready) {
+      if ((held & pmask) != pmask) { code = TX_NOT_READY; cnt = 0u; sg = TX_SEGS; }
+      else kind = e < sb.K ? TX_HELD_SRC : TX_HELD_REP;
+    }
+    if (sg < TX_SEGS && i < cnt) {
+      if (kind == TX_HELD_REP) { s_cols[wv][lane][0] = TX_NONE; n = 1u; } /* (the row index: found below) */
+      else n = tx_rows(&sb, tag0 + i, s_cols[wv][lane]);                  /* (a held source symbol: row e + i, as a ready one) */
+    }
+    if (mine && i == 0u && c.results && kind != TX_HELD_REP) c.results[k] = code; /* (held repair symbols: once the rows are found) */
+    s_n[wv][lane] = n | (cnt << 8) | (kind << 16); /* (cnt = 0: the packet stays untouched) */
+    s_tag[wv][lane] = tag0;
+    s_k[wv][lane] = k;
+    if (MULTI) s_seg[wv][lane] = sg;
+  }
+  __syncthreads();
+  const uint32_t T = s.seg[0].T;
+  for (uint32_t q = 0; q < per && w0 + q < c.n; q++) { /* (wave-uniform) */
+    const uint32_t l0 = q * G;
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][l0]), cnt = (nk >> 8) & 0xFFu;
+    if (!cnt) continue;
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][l0]);
+    const uint32_t sg = MULTI ? __builtin_amdgcn_readfirstlane(s_seg[wv][l0]) : 0u;
+    const uint8_t *base;
+    if ((nk >> 16) == TX_HELD_REP) {
+      const tx_held_seg hs = sg == 0u ? h.seg[0] : sg == 1u ? h.seg[1] : h.seg[2];
+      const uint32_t b = (tag >> 24) - (sg == 0u ? s.seg[0].sbn0 : sg == 1u ? s.seg[1].sbn0 : s.seg[2].sbn0);
+      const uint32_t nrep = tx_held_nrep(&hs, b), e = tag & SY_ESI_MAX;
+      for (uint32_t q0 = 0; q0 < nrep; q0 += 64u) {
+        const uint32_t x = q0 + lane < nrep ? hs.rep_esi[(uint64_t)b * hs.rep_cap + q0 + lane] - e : TX_NONE;
+        if (x < cnt) s_cols[wv][l0 + x][0] = q0 + lane;
+      }
+      /* the wave reads what its other lanes wrote: LDS operations of one wave complete in order; the fence keeps the compiler from
+       * moving the reads above the writes */
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const bool found = lane >= cnt || s_cols[wv][l0 + lane][0] != TX_NONE;
+      const bool all = __ballot(!found) == 0ull;
+      if (c.results && lane == 0) c.results[s_k[wv][l0]] = all ? 0 : TX_NOT_READY;
+      if (!all) continue; /* (the books say otherwise: a marked repair ESI has its row) */
+      base = tx_held_rep_base(&hs, b);
+    } else {
+      base = TX_SEG_BASE(MULTI, s, sg, tag);
+    }
+    uint8_t *P = c.pkts + (uint64_t)s_k[wv][l0] * c.pkt_stride;
+    if (cnt == 1u) tx_payload<MODE>(base, T, tx_one{s_cols[wv][l0], nk & 0xFFu}, tag, P, c.inl, lane);
+    else tx_payload<MODE>(base, T, tx_run{&s_cols[wv][l0], &s_n[wv][l0], cnt}, tag, P, c.inl, lane);
+  }
+}
+
 static int rx_add_syms(nrq_rx *rx, const char *who, const void *d_pkts, size_t pkt_stride, const uint32_t *d_tags, uint32_t n, uint32_t G,
                        const uint8_t *d_nsym, uint32_t flags, int32_t *d_results) {
   nrq_ctx *ctx = rx->ctx;
@@ -4299,11 +4385,11 @@ static int rx_add_syms(nrq_rx *rx, const char *who, const void *d_pkts, size_t p
   return 0;
 }
 
-/* checks of the several-symbol emits on top of tx_check */
-static int sy_tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t G, uint32_t flags) {
+/* checks of the several-symbol emits on top of tx_check; list: the tag-list form, which alone takes NRQ_TX_HELD, and only on a relay
+ * (tx_check says so for a range form and for a sender) */
+static int sy_tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_t pkt_stride, uint32_t G, uint32_t flags, bool list = false) {
   nrq_ctx *ctx = tx->ctx;
-  if (flags & NRQ_TX_HELD) return fail(ctx, -1, "%s: NRQ_TX_HELD is not offered with packets of several symbols (held symbols are decided per symbol)", who);
-  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags);
+  int rc = tx_check(tx, who, d_pkts, pkt_stride, flags, list);
   if (rc) return rc;
   if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
   const uint32_t T = tx->s.seg[0].T;
@@ -4312,8 +4398,14 @@ static int sy_tx_check(tx_sender *tx, const char *who, const void *d_pkts, size_
   return 0;
 }
 
-static int sy_tx_launch(tx_sender *tx, const tx_call &c, const sy_tx &y) {
+static int sy_tx_launch(tx_sender *tx, const tx_call &c, const sy_tx &y, bool held = false) {
   using emit_fn = void (*)(tx_src, tx_call, sy_tx);
+  using held_fn = void (*)(tx_src, tx_held, tx_call, sy_tx);
+  static const held_fn hkern[2][4] = { /* [multi-segment][path] */
+      {nrq_emit_held_syms_kernel<TX_V16, false>, nrq_emit_held_syms_kernel<TX_V16_SHIFT, false>, nrq_emit_held_syms_kernel<TX_DWORD, false>,
+       nrq_emit_held_syms_kernel<TX_BYTE, false>},
+      {nrq_emit_held_syms_kernel<TX_V16, true>, nrq_emit_held_syms_kernel<TX_V16_SHIFT, true>, nrq_emit_held_syms_kernel<TX_DWORD, true>,
+       nrq_emit_held_syms_kernel<TX_BYTE, true>}};
   static const emit_fn kern[2][4] = { /* [multi-segment][path] */
       {nrq_emit_syms_kernel<TX_V16, false>, nrq_emit_syms_kernel<TX_V16_SHIFT, false>, nrq_emit_syms_kernel<TX_DWORD, false>,
        nrq_emit_syms_kernel<TX_BYTE, false>},
@@ -4321,9 +4413,12 @@ static int sy_tx_launch(tx_sender *tx, const tx_call &c, const sy_tx &y) {
        nrq_emit_syms_kernel<TX_BYTE, true>}};
   nrq_ctx *ctx = tx->ctx;
   const tx_src &s = tx->s;
-  const int mode = tx_emit_path(tx_align(&s, &c, nullptr), c.inl, ctx->tune.tx_dword ? 1u : 0u);
+  const tx_held h = held ? tx_held_table(tx) : tx_held{};
+  const int mode = tx_emit_path(tx_align(&s, &c, held ? &h : nullptr), c.inl, ctx->tune.tx_dword ? 1u : 0u); /* (held: the repair rows too) */
   const uint32_t per = 64u / y.G, waves = (c.n + per - 1u) / per;
-  hipLaunchKernelGGL(kern[s.nseg > 1u][mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, s, c, y);
+  const dim3 grid((waves + TX_WAVES - 1u) / TX_WAVES), wg(64u * TX_WAVES);
+  if (held) hipLaunchKernelGGL(hkern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, h, c, y);
+  else hipLaunchKernelGGL(kern[s.nseg > 1u][mode], grid, wg, 0, ctx->stream, s, c, y);
   HIPCHK(ctx, hipGetLastError());
   return 0;
 }
@@ -4332,7 +4427,7 @@ static int sy_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
                         size_t pkt_stride, uint32_t flags, int32_t *d_results) {
   if (!tx) return -1;
   nrq_ctx *ctx = tx->ctx;
-  int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags);
+  int rc = sy_tx_check(tx, who, d_pkts, pkt_stride, G, flags, true);
   if (rc) return rc;
   if (n == 0) return 0;
   if (!d_tags || (uint64_t)n * G > 0x7FFFFFFFu) return fail(ctx, -1, "%s: bad tags (n=%u, G=%u)", who, n, G);
@@ -4343,7 +4438,7 @@ static int sy_emit_list(tx_sender *tx, const char *who, const uint32_t *d_tags, 
   c.results = d_results;
   sy_tx y{};
   y.G = G; y.nsym = d_nsym;
-  return sy_tx_launch(tx, c, y);
+  return sy_tx_launch(tx, c, y, (flags & NRQ_TX_HELD) != 0);
 }
 
 /* range mode: ESIs esi0 .. esi0+eL-1 of the blocks of K = KL, esi0 .. esi0+eS-1 of those of K = KS, packetised per block */
@@ -4626,6 +4721,240 @@ int nrq_rx_want(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, u
 int nrq_orx_want(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t *d_tags, uint32_t cap, uint32_t *h_n) {
   if (!rx) return -1;
   return want_list(rx->ctx, "nrq_orx_want", rx->rx, 2, flags, extra, esi_from, d_tags, cap, h_n); /* (class L, then class S: SBN order) */
+}
+
+} /* extern "C" */
+
+/* ================================================ want and held lists as runs (nrq_rx_want_syms / nrq_rx_held_syms, runs_body.h) ==== */
+/* The listings above in the packet form of syms_body.h: (first tag, count) per packet of up to G symbols.  Kernels of their own in
+ * the same count / scan / fill shape -- one workgroup of 256 per block, rounds of WN_ROUND words or rows -- so that the one-symbol
+ * listings are compiled from the code they always were.  What a round adds to those: the run start entering each word (a max-scan
+ * beside the sum-scan), carried across rounds with the symbols found and the packets placed. */
+
+/* inclusive sum-scan of the threads' v and inclusive max-scan of their m in one pass (Hillis-Steele over two arrays of 256 words):
+ * returns the sum, *mx = the maximum of threads 0 .. t; ps[255] and pm[255] are the totals.  Ends with a barrier behind its last
+ * write, as wg_scan. */
+__device__ __forceinline__ uint32_t wg_scan_sum_max(uint32_t *ps, uint32_t *pm, uint32_t t, uint32_t v, uint32_t m, uint32_t *mx) {
+  ps[t] = v;
+  pm[t] = m;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256u; d <<= 1) {
+    const uint32_t u = t >= d ? ps[t - d] : 0u, x = t >= d ? pm[t - d] : 0u;
+    __syncthreads();
+    ps[t] += u;
+    pm[t] = max(pm[t], x);
+    __syncthreads();
+  }
+  *mx = pm[t];
+  return ps[t];
+}
+
+/* The bitmap walk of one block (rn_walk): per round each thread takes a word, the scans give it the rank of its first listed ESI
+ * and the run start entering it, rn_word_pkts the packets that start in it.  out == NULL: count -- returns the packets, *syms = the
+ * symbols listed (both the same in every thread).  Else the packets are written to tags[at ..] / nsym[at ..]; returns `at` behind
+ * them. */
+__device__ __forceinline__ uint32_t rn_bits_wg(const ing_rx *r, const rn_walk *k, uint32_t G, uint32_t *tags, uint8_t *nsym, uint32_t at,
+                                               uint32_t *syms, uint32_t *ps, uint32_t *pm) {
+  const uint32_t t = threadIdx.x;
+  uint32_t found = 0, pk = 0, S = k->lo;
+  for (uint32_t w0 = k->w_first; w0 < k->w_end && found < k->need; w0 += WN_ROUND) { /* (found, need: the same in every thread) */
+    const uint32_t w = w0 + t;
+    const uint32_t bits = rn_word(r, k, w), c = ing_popc(bits);
+    uint32_t mx;
+    const uint32_t rank = found + wg_scan_sum_max(ps, pm, t, c, rn_mark(w, bits), &mx) - c;
+    const uint32_t Sin = max(S, t ? pm[t - 1u] : 0u);
+    const uint32_t tot = ps[255], smax = pm[255];
+    __syncthreads();
+    const uint32_t n = rn_word_pkts(r, k, G, w, bits, Sin, rank, nullptr, nullptr);
+    if (tags) {
+      const uint32_t o = at + pk + wg_scan(ps, t, n) - n;
+      rn_word_pkts(r, k, G, w, bits, Sin, rank, tags + o, nsym + o);
+      pk += ps[255];
+    } else {
+      pk += wg_sum(ps, t, n);
+    }
+    __syncthreads();
+    found += tot;
+    S = max(S, smax);
+  }
+  if (syms) *syms = min(found, k->need);
+  return tags ? at + pk : pk;
+}
+
+/* The row walk of one block: the repair part of its held list, a row per thread and round; as rn_bits_wg. */
+__device__ __forceinline__ uint32_t rn_rows_wg(const ing_rx *r, uint32_t b, uint32_t G, uint32_t *tags, uint8_t *nsym, uint32_t at, uint32_t *ps,
+                                               uint32_t *pm) {
+  const uint32_t t = threadIdx.x, nrep = hl_nrep(r, b);
+  uint32_t pk = 0, M = 0;
+  for (uint32_t q0 = 0; q0 < nrep; q0 += WN_ROUND) {
+    const uint32_t q = q0 + t;
+    uint32_t mx;
+    (void)wg_scan_sum_max(ps, pm, t, 0u, rn_rep_mark(r, b, q, nrep), &mx);
+    const uint32_t smax = pm[255];
+    __syncthreads();
+    const uint32_t n = rn_rep_starts(q, nrep, max(M, mx) - 1u, G) ? 1u : 0u; /* (row 0 begins a run: the maximum is at least 1) */
+    if (tags) {
+      const uint32_t o = at + pk + wg_scan(ps, t, n) - n;
+      if (n) rn_rep_put(r, b, q, nrep, G, tags + o, nsym + o);
+      pk += ps[255];
+    } else {
+      pk += wg_sum(ps, t, n);
+    }
+    __syncthreads();
+    M = max(M, smax);
+  }
+  return tags ? at + pk : pk;
+}
+
+/* one workgroup per block: the packets it lists -> cnt[b], its symbols added to *nsym_total */
+__global__ __launch_bounds__(256) void nrq_want_syms_count_kernel(ing_rx r, wn_q q, uint32_t G, uint32_t *cnt, uint32_t *nsym_total) {
+  __shared__ uint32_t ps[256], pm[256];
+  const rn_walk k = rn_walk_want(&r, &q, blockIdx.x);
+  uint32_t syms;
+  const uint32_t pk = rn_bits_wg(&r, &k, G, nullptr, nullptr, 0u, &syms, ps, pm);
+  if (threadIdx.x == 0) {
+    cnt[blockIdx.x] = pk;
+    if (syms) atomicAdd(nsym_total, syms);
+  }
+}
+
+/* one workgroup per block: its packets to tags / nsym + off[b] */
+__global__ __launch_bounds__(256) void nrq_want_syms_fill_kernel(ing_rx r, wn_q q, uint32_t G, const uint32_t *off, uint32_t *tags, uint8_t *nsym) {
+  __shared__ uint32_t ps[256], pm[256];
+  const rn_walk k = rn_walk_want(&r, &q, blockIdx.x);
+  (void)rn_bits_wg(&r, &k, G, tags, nsym, off[blockIdx.x], nullptr, ps, pm);
+}
+
+/* one workgroup per block: the packets of its source part and of its repair part -> cnt[b], its symbols added to *nsym_total */
+__global__ __launch_bounds__(256) void nrq_held_syms_count_kernel(ing_rx r, uint32_t G, uint32_t *cnt, uint32_t *nsym_total) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t b = blockIdx.x;
+  const rn_walk k = rn_walk_held(&r, b);
+  uint32_t syms;
+  uint32_t pk = rn_bits_wg(&r, &k, G, nullptr, nullptr, 0u, &syms, ps, pm);
+  pk += rn_rows_wg(&r, b, G, nullptr, nullptr, 0u, ps, pm);
+  if (threadIdx.x == 0) {
+    cnt[b] = pk;
+    syms += hl_nrep(&r, b);
+    if (syms) atomicAdd(nsym_total, syms);
+  }
+}
+
+/* one workgroup per block: the packets of its source part, then those of its repair part, to tags / nsym + off[b] */
+__global__ __launch_bounds__(256) void nrq_held_syms_fill_kernel(ing_rx r, uint32_t G, const uint32_t *off, uint32_t *tags, uint8_t *nsym) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t b = blockIdx.x;
+  const rn_walk k = rn_walk_held(&r, b);
+  const uint32_t at = rn_bits_wg(&r, &k, G, tags, nsym, off[b], nullptr, ps, pm);
+  (void)rn_rows_wg(&r, b, G, tags, nsym, at, ps, pm);
+}
+
+/* A listing in packets of up to two receptions, one behind the other (rx_list's shape).  Per reception the list buffer holds, under
+ * rx_list_count's rule, nblk + 2 words: the blocks' packet counts, scanned in place into exclusive offsets with the packet total
+ * behind them, and the symbol total the count kernel adds up (2 * nblk + nblk * K words are there: enough for any nblk, K >= 1).
+ * Both totals of both receptions come down in ONE wait.  `count(i, rx, cnt, nsym_total)` and `fill(i, rx, off, tags, nsym)` launch
+ * the kernels. */
+template <class Count, class Fill>
+static int rx_list_syms(nrq_ctx *ctx, const char *who, const char *what, nrq_rx *const *rxs, int nrx, uint32_t *d_tags, uint8_t *d_nsym,
+                        uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym, Count count, Fill fill) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t n[2][2] = {{0, 0}, {0, 0}}; /* per reception: packets, symbols */
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    uint32_t *cnt = (uint32_t *)rxs[i]->lists;
+    const uint32_t nblk = rxs[i]->r.nblk;
+    HIPCHK(ctx, hipMemsetAsync(cnt + nblk, 0, 8u, ctx->stream));
+    count(i, rxs[i], cnt, cnt + nblk + 1u);
+    hipLaunchKernelGGL(nrq_tx_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, nblk + 1u, cnt);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(n[i], cnt + nblk, 8u, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *h_npkt = n[0][0] + n[1][0];
+  if (h_nsym) *h_nsym = n[0][1] + n[1][1];
+  if (!d_tags) return 0;
+  if (cap < *h_npkt) return fail(ctx, -1, "%s: %u packets are %s, d_tags and d_nsym have room for %u", who, *h_npkt, what, cap);
+  uint32_t at = 0;
+  for (int i = 0; i < nrx; i++) {
+    if (!rxs[i]) continue;
+    if (n[i][0]) fill(i, rxs[i], (const uint32_t *)rxs[i]->lists, d_tags + at, d_nsym + at);
+    at += n[i][0];
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+/* what every listing in packets refuses beside its one-symbol form's arguments */
+static int rn_check(nrq_ctx *ctx, const char *who, uint32_t G, const uint32_t *d_tags, const uint8_t *d_nsym, uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!h_npkt) return fail(ctx, -1, "%s: h_npkt is NULL", who);
+  *h_npkt = 0;
+  if (h_nsym) *h_nsym = 0;
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  if (!d_tags != !d_nsym) return fail(ctx, -1, "%s: d_tags and d_nsym go together (both, or neither for the counts alone)", who);
+  return 0;
+}
+
+static int want_list_syms(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t flags, uint32_t extra, uint32_t esi_from,
+                          uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym) {
+  const int rc = rn_check(ctx, who, G, d_tags, d_nsym, h_npkt, h_nsym);
+  if (rc) return rc;
+  switch (wn_check(flags, extra, esi_from)) {
+    case 1: return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+    case 2: return fail(ctx, -1, "%s: NRQ_WANT_SOURCE takes neither extra nor esi_from (%u, %u)", who, extra, esi_from);
+    case 3: return fail(ctx, -1, "%s: extra %u is above 2^24", who, extra);
+    default: break;
+  }
+  wn_q q[2] = {};
+  for (int i = 0; i < nrx; i++)
+    if (rxs[i]) q[i] = wn_query(&rxs[i]->r, flags, extra, esi_from);
+  hipStream_t st = ctx->stream;
+  return rx_list_syms(
+      ctx, who, "wanted", rxs, nrx, d_tags, d_nsym, cap, h_npkt, h_nsym,
+      [&](int i, nrq_rx *rx, uint32_t *cnt, uint32_t *tot) {
+        hipLaunchKernelGGL(nrq_want_syms_count_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, q[i], G, cnt, tot);
+      },
+      [&](int i, nrq_rx *rx, const uint32_t *off, uint32_t *tags, uint8_t *nsym) {
+        hipLaunchKernelGGL(nrq_want_syms_fill_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, q[i], G, off, tags, nsym);
+      });
+}
+
+static int held_list_syms(nrq_ctx *ctx, const char *who, nrq_rx *const *rxs, int nrx, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym,
+                          uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym) {
+  const int rc = rn_check(ctx, who, G, d_tags, d_nsym, h_npkt, h_nsym);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  return rx_list_syms(
+      ctx, who, "held", rxs, nrx, d_tags, d_nsym, cap, h_npkt, h_nsym,
+      [&](int, nrq_rx *rx, uint32_t *cnt, uint32_t *tot) {
+        hipLaunchKernelGGL(nrq_held_syms_count_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, G, cnt, tot);
+      },
+      [&](int, nrq_rx *rx, const uint32_t *off, uint32_t *tags, uint8_t *nsym) {
+        hipLaunchKernelGGL(nrq_held_syms_fill_kernel, dim3(rx->r.nblk), dim3(256), 0, st, rx->r, G, off, tags, nsym);
+      });
+}
+
+extern "C" {
+
+int nrq_rx_want_syms(nrq_rx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap,
+                     uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!rx) return -1;
+  return want_list_syms(rx->ctx, "nrq_rx_want_syms", &rx, 1, flags, extra, esi_from, G, d_tags, d_nsym, cap, h_npkt, h_nsym);
+}
+
+int nrq_orx_want_syms(nrq_orx *rx, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap,
+                      uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!rx) return -1;
+  return want_list_syms(rx->ctx, "nrq_orx_want_syms", rx->rx, 2, flags, extra, esi_from, G, d_tags, d_nsym, cap, h_npkt, h_nsym);
+}
+
+int nrq_rx_held_syms(nrq_rx *rx, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!rx) return -1;
+  return held_list_syms(rx->ctx, "nrq_rx_held_syms", &rx, 1, G, d_tags, d_nsym, cap, h_npkt, h_nsym);
+}
+
+int nrq_orx_held_syms(nrq_orx *rx, uint32_t G, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!rx) return -1;
+  return held_list_syms(rx->ctx, "nrq_orx_held_syms", rx->rx, 2, G, d_tags, d_nsym, cap, h_npkt, h_nsym); /* (class L, then class S) */
 }
 
 } /* extern "C" */
