@@ -186,6 +186,7 @@ def lib():
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
+    L.nrq_host_plan_build_forced.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p, C.c_uint32]
     L.nrq_host_free.argtypes = [vp]
     L.nrq_host_free.restype = None
     _LIB = L
@@ -221,13 +222,14 @@ def host_kconst(K):
     return buf
 
 
-def host_plan(K, isis, kconst):
-    """Host planner: returns the plan arena as bytes (header status tells solvable/singular)."""
+def host_plan(K, isis, kconst, extra_inact=0):
+    """Host planner: returns the plan arena as bytes (header status tells solvable/singular).  extra_inact (tests): that many
+    columns more are inactive before peeling begins -- the same system and solution at a chosen number of inactive columns."""
     isis = np.ascontiguousarray(isis, dtype=np.uint32)
     kc = (C.c_uint8 * len(kconst)).from_buffer_copy(kconst)
     out = C.POINTER(C.c_uint8)()
     n = C.c_uint32()
-    rc = lib().nrq_host_plan_build(K, len(isis), _u32(isis), kc, C.byref(out), C.byref(n))
+    rc = lib().nrq_host_plan_build_forced(K, len(isis), _u32(isis), kc, C.byref(out), C.byref(n), int(extra_inact))
     if rc != 0:
         raise NrqError("plan build failed: %d" % rc)
     buf = bytes(C.string_at(out, n.value))

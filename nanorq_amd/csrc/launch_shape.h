@@ -124,7 +124,11 @@ enum KnobKind { KNOB_FLAG, KNOB_NFLAG, KNOB_NUM, KNOB_BOOLNUM, KNOB_WIDEG, KNOB_
   K(uint32_t, plan_ucap, 0, 0, "plan_ucap", KNOB_NUM)                                                                                                   \
   /* (tests) strip bytes of the split solve's back-substitution: 0 = by the W words per row (solve_shape), 16 = 16-byte strips                          \
    * whatever they are.  (Nothing forces 32: beyond 20 words its tables do not fit beside a second workgroup.) */                                      \
-  K(uint32_t, backsub_sb, 0, 0, "backsub_sb", KNOB_NUM)
+  K(uint32_t, backsub_sb, 0, 0, "backsub_sb", KNOB_NUM)                                                                                                 \
+  /* (tests) every plan the context builds on the HOST (decode, encode, the capacity fallback) starts with this many columns                            \
+   * more inactive (planner_host.h nrq_host_plan_build_forced): same results, a chosen number of inactive columns u -- and with                         \
+   * it the back-substitution form the solve runs (solve_body.h: by wpr = ceil(u / 32)).  0: the plans are what they are */                             \
+  K(uint32_t, plan_force_inact, 0, 0, "plan_force_inact", KNOB_NUM)
 
 static inline long long knob_norm(KnobKind kind, long long v) {
   switch (kind) {
@@ -432,7 +436,7 @@ static inline SolveShape solve_shape(const Tuning &t, int ncu, uint32_t ahead_hi
     /* 32-byte strips while the tables (4 KiB per W word) leave room for two workgroups per CU, 16-byte strips beyond */
     const uint32_t sb = in.max_wpr <= 20u && t.backsub_sb != 16u ? 32u : 16u, nsb = (T + sb - 1u) / sb;
     s.backsub_strip = sb; s.backsub_nsb = nsb; s.backsub_tbl = in.max_wpr * 8u * 16u * sb;
-    if (s.backsub_tbl > NRQ_LDS_MAX) { s.err = SHAPE_BACKSUB_TABLES; return s; } /* (reported behind the solve kernel's launch, as ever) */
+    if (s.backsub_tbl > NRQ_LDS_MAX) { s.err = SHAPE_BACKSUB_TABLES; return s; } /* (launch_solve refuses the call, before any launch) */
     uint32_t nchunks = (2048u + nsb * nblk - 1u) / (nsb * nblk);
     if (nchunks < 1u) nchunks = 1u;
     if (nchunks > 16u) nchunks = 16u;

@@ -1176,7 +1176,7 @@ int encplan_host_build(nrq_ctx *ctx, const rq_params &p, uint32_t K, KConst *kc,
   for (uint32_t j = 0; j < p.Kp; j++) isis[j] = j;
   HostBuf arena;
   uint32_t bytes = 0;
-  if (nrq_host_plan_build(p.Kp, p.Kp, isis.data(), kc->host.p, &arena.p, &bytes) != 0)
+  if (nrq_host_plan_build_forced(p.Kp, p.Kp, isis.data(), kc->host.p, &arena.p, &bytes, ctx->tune.plan_force_inact) != 0)
     return fail(ctx, -2, "encode plan build failed for K=%u", K);
   memcpy(&ep.hdr, arena.p, sizeof(ep.hdr));
   if (ep.hdr.status) return fail(ctx, -3, "encode matrix singular for K=%u (cannot happen)", K);
@@ -1337,6 +1337,8 @@ static int launch_solve(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &h
   }
   const SolveShape s = solve_shape(ctx->tune, ctx->ncu, ctx->ahead_hint, in);
   if (s.err == SHAPE_GRID_TOO_LARGE) return fail(ctx, -4, "grid too large");
+  /* (refused before anything is launched: it was reported behind the solve kernel's launch, whose work buffers nobody then read) */
+  if (s.err == SHAPE_BACKSUB_TABLES) return fail(ctx, -5, "back-substitution tables do not fit the LDS (wpr=%u)", in.max_wpr);
   if (s.key.NT == 64 && ctx->tune.diag) fprintf(stderr, "[NRQ_DIAG] single-wave workgroups: %u bytes of LDS each, %u per CU\n", s.lds_bytes, s.occ);
   const int inst = solve_key_index(s.key);
   if (inst < 0)
@@ -1380,7 +1382,6 @@ static int launch_solve(nrq_ctx *ctx, const std::vector<const nrq_plan_hdr *> &h
   if (s.key.G == 1) ctx->stats.movers_aligned = s.key.AL ? 1u : 0u; /* (a wide-strip launch leaves it as the call's reset gave it) */
   HIPCHK(ctx, hipGetLastError());
   if (s.split) {
-    if (s.err == SHAPE_BACKSUB_TABLES) return fail(ctx, -5, "back-substitution tables do not fit the LDS (wpr=%u)", in.max_wpr);
     const dim3 bgrid(s.backsub_nsb, s.nchunks, nblk);
     if (s.backsub_strip == 32u)
       hipLaunchKernelGGL(nrq_backsub_kernel<32>, bgrid, dim3(256), s.backsub_tbl, ctx->stream, d_jobs, T, ybuf, s.ybuf_stride, s.nchunks);
@@ -1775,7 +1776,7 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
         pr.rowsrc[p.L + e] = NRQ_ROW_REP | (nl + e);
       }
       pr.plan = HostBuf();
-      if (nrq_host_plan_build(p.Kp, p.Kp + overhead, isis.data(), kc->host.p, &pr.plan.p, &pr.plan_bytes) != 0) {
+      if (nrq_host_plan_build_forced(p.Kp, p.Kp + overhead, isis.data(), kc->host.p, &pr.plan.p, &pr.plan_bytes, ctx->tune.plan_force_inact) != 0) {
         pr.state = -1;
         return;
       }

@@ -170,9 +170,12 @@ extern "C" void nrq_host_free(void *p) { free(p); }
 /* comp_rows: 0 = an inactivation event takes the first open rows with two columns in V it finds, one after the other (what the
  * device planner does); n > 0 = RFC 6330 section 5.4.2.2's choice -- a row from the LARGEST component of the graph whose edges
  * are those rows -- and, in the same event, one row from each of the next n - 1 components (rows of one component must not
- * share an event: the first inactivation lets the whole component peel, a second one in it is a column wasted). */
+ * share an event: the first inactivation lets the whole component peel, a second one in it is a column wasted).
+ * extra_inact (tests): n > 0 = the n highest-numbered columns below W are inactive before peeling begins (all of V when n >= W).
+ * Any column may be inactivated: rank(A), the solution, the verdict and nfree stay what they are, work moves from the peel to the
+ * dense stage -- which is how a test chooses u, the number that picks the solve kernel's back-substitution form. */
 static int host_plan_build_with(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out, uint32_t *out_bytes,
-                                uint32_t comp_rows) {
+                                uint32_t comp_rows, uint32_t extra_inact) {
   rq_params p;
   if (!rq_params_init(K, &p)) return -1;
   if (nrows < p.Kp) return -1;
@@ -229,18 +232,19 @@ static int host_plan_build_with(uint32_t K, uint32_t nrows, const uint32_t *isis
   enum : uint8_t { IN_V = 0, PIVOT = 1, INACTIVE = 2 };
   std::vector<uint8_t> cstate(L, IN_V);
   for (uint32_t c = W; c < L; c++) cstate[c] = INACTIVE; /* PI columns start inactive */
+  std::vector<uint32_t> inact_order; /* V columns in the order they were inactivated */
+  uint32_t nV = W, nlev = 0;
+  for (uint32_t c = W; c-- > 0 && W - nV < extra_inact;) { cstate[c] = INACTIVE; inact_order.push_back(c); nV--; } /* (tests) */
   std::vector<uint32_t> cnt(M, 0), xs(M, 0);
   for (uint32_t r = 0; r < M; r++)
     for (uint32_t e = rptr[r]; e < rptr[r + 1]; e++)
-      if (cidx[e] < W) { cnt[r]++; xs[r] ^= cidx[e]; }
+      if (cstate[cidx[e]] == IN_V) { cnt[r]++; xs[r] ^= cidx[e]; }
   std::vector<uint8_t> assigned(M, 0);
   std::vector<uint16_t> owner(L, NRQ_NOSLOT); /* pivot row of a column */
   std::vector<uint32_t> kof(L, 0);            /* pivot index of a column */
   std::vector<uint32_t> level(M, 0);
   std::vector<uint16_t> pivslot, pivcol;
-  std::vector<uint32_t> inact_order; /* V columns in the order they were inactivated */
   pivslot.reserve(L); pivcol.reserve(L);
-  uint32_t nV = W, nlev = 0;
   std::vector<uint32_t> frontier, next;
   for (uint32_t r = 0; r < M; r++)
     if (cnt[r] == 1) frontier.push_back(r);
@@ -737,12 +741,17 @@ static int host_plan_build_with(uint32_t K, uint32_t nrows, const uint32_t *isis
  * below.  (Building all four and keeping the cheapest by a fitted cost was tried: four builds a step no longer hide behind the
  * GPU.)  The build takes ~1.5 x the first-found one.  A decoder's plan is used once: it keeps the first-found rule, which is
  * also what the device planner implements.  NRQ_HOST_WAY=n forces n rows an event (0: first-found) for measurements. */
-extern "C" int nrq_host_plan_build(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out, uint32_t *out_bytes) {
+extern "C" int nrq_host_plan_build_forced(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out, uint32_t *out_bytes,
+                                          uint32_t extra_inact) {
   rq_params p;
   if (!rq_params_init(K, &p)) return -1;
   bool encoder = nrows == p.Kp;
   for (uint32_t k = 0; encoder && k < nrows; k++) encoder = isis[k] == k;
   uint32_t way = !encoder ? 0u : p.Kp >= 1500u ? 1u : 6u;
   if (const char *e = getenv("NRQ_HOST_WAY")) { if (encoder) way = (uint32_t)atoi(e); }
-  return host_plan_build_with(K, nrows, isis, kconst, out, out_bytes, way);
+  return host_plan_build_with(K, nrows, isis, kconst, out, out_bytes, way, extra_inact);
+}
+
+extern "C" int nrq_host_plan_build(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out, uint32_t *out_bytes) {
+  return nrq_host_plan_build_forced(K, nrows, isis, kconst, out, out_bytes, 0u);
 }

@@ -13,6 +13,10 @@ int nrq_host_kconst_build(uint32_t K, uint8_t **out, uint32_t *out_bytes);
  * Returns 0 and a malloc'ed arena (hdr.status tells solvable / singular); <0 on bad arguments. */
 int nrq_host_plan_build(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out,
                         uint32_t *out_bytes);
+/* (tests) The same with the extra_inact highest-numbered columns below W inactive before peeling begins: a plan of the same
+ * system with that many inactive columns more (or every column of V), same solution, same verdict.  0: nrq_host_plan_build. */
+int nrq_host_plan_build_forced(uint32_t K, uint32_t nrows, const uint32_t *isis, const uint8_t *kconst, uint8_t **out,
+                               uint32_t *out_bytes, uint32_t extra_inact);
 void nrq_host_free(void *p);
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ def lib():
         L.orc_decode_block_kpm.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u8p, u8p,
                                            C.POINTER(Stats), C.c_uint32]
         L.orc_plan_probe.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(Stats)]
+        L.orc_plan_exec.argtypes = [u8p, u8p, C.c_uint32, u8p]
         L.orc_encode_block_cached.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_uint32, u32p, u8p]
         _LIB = L
     return _LIB
@@ -163,3 +164,15 @@ def plan_probe(K, isis):
     st = Stats()
     r = lib().orc_plan_probe(K, len(isis), _u32(isis), C.byref(st))
     return r, st.as_dict()
+
+
+def plan_exec(plan, din, T):
+    """oracle/plan_exec_ref.c: a device plan (nanorq_amd/csrc/plan.h) applied to whole rows by plain loops.  din[M, T]: the symbols in
+    their rows, zero elsewhere.  Returns (r, C[L, T]); r = 1 done, 0 the plan is marked singular, < 0 not a plan."""
+    hdr = np.frombuffer(plan, np.uint32, count=16)
+    M, L = int(hdr[12]), int(hdr[8])  # nrq_plan_hdr: magic status K Kp J S H W L P P1 B M ...
+    buf = np.frombuffer(plan, np.uint8).copy()
+    din = np.ascontiguousarray(din, np.uint8).reshape(M, T).copy()
+    out = np.zeros((L, T), np.uint8)
+    r = lib().orc_plan_exec(_u8(buf), _u8(din), T, _u8(out))
+    return r, out

@@ -48,12 +48,14 @@ int orc_plan_exec(const uint8_t *plan, uint8_t *Din, uint32_t T, uint8_t *C) {
   const uint16_t *uslot = (const uint16_t *)(plan + h->off_uslot);
   const uint32_t H = h->H, n_hd = h->Kp + h->S;
 #define ROW(r) (D + (size_t)(r) * T)
-  /* 1+2: forward substitution through X, then the leftover rows */
-  size_t nops = (size_t)h->nrows * NRQ_ROW;
-  for (size_t e = 0; e < nops; e++) {
-    if (NRQ_OP_IS_NOP(ops[e])) continue;
-    xor_row(ROW(NRQ_OP_DST(ops[e])), ROW(NRQ_OP_SRC(ops[e])), T);
-  }
+  /* 1+2: forward substitution through X, then the leftover rows: the stream row by row (it is stored quad-interleaved, word
+   * (row, lane) at NRQ_OP_INDEX; a row's sources are final NRQ_PIPE rows before it, so one op after the other is the pipeline's result) */
+  for (uint32_t r = 0; r < h->nrows; r++)
+    for (uint32_t l = 0; l < NRQ_ROW; l++) {
+      const uint32_t op = ops[NRQ_OP_INDEX(r, l)];
+      if (NRQ_OP_IS_NOP(op)) continue;
+      xor_row(ROW(NRQ_OP_DST(op)), ROW(NRQ_OP_SRC(op)), T);
+    }
   /* 3: HDPC right-hand sides */
   uint8_t *G = (uint8_t *)malloc((size_t)H * n_hd);
   orc_hdpc(h->K, G);

@@ -585,7 +585,47 @@ def group_sync():
     return out
 
 
-GROUPS = {"detector": group_detector, "pool": group_pool, "fuzz0": group_fuzz0, "sync": group_sync}
+# ------------------------------------------------------------------ d2. a launch that is refused starts nothing ----
+def group_refusal():
+    """K = 3000 with every column of V forced inactive (the option plan_force_inact: 3135 inactive columns, 98 W words) on 4-byte
+    strips: the tables of the split solve's back-substitution would take 196 KiB of LDS.  The decode must come back with the
+    library's status for it and NO kernel launched; the context then decodes the same blocks as ever."""
+    model()
+    hazards()
+    K, T, nblk = 3000, 48, 2
+    c = nanorq_amd.Context(0)
+    c.set_planner(False)
+    c.set_option("max_wb", 4)
+    src = np.stack([payload(K * T, seed=9, block=b).reshape(K, T) for b in range(nblk)])
+    lost = loss_pattern(K, 0.1, seed=K + 17)
+    la, nl = np.tile(lost, (nblk, 1)), np.full(nblk, len(lost), np.uint32)
+    re = np.tile(np.arange(K, K + len(lost) + 2, dtype=np.uint32), (nblk, 1))
+    d_src, d_rep = c.alloc(nblk * K * T), c.alloc(nblk * re.shape[1] * T)
+    c.upload(d_src, src)
+    c.sync()
+    out = {}
+    c.set_option("plan_force_inact", nanorq_amd.params(K)["W"])
+    before = counters()["launches"]
+    try:
+        c.decode_blocks(K, T, nblk, d_src, K * T, la, nl, re, nl + 2, d_rep, re.shape[1] * T)
+        out["error"] = None
+    except nanorq_amd.NrqError as e:
+        out["error"] = str(e)
+    out["launches_of_the_refused_call"] = counters()["launches"] - before
+    c.sync()
+    c.set_option("plan_force_inact", 0)
+    st = c.decode_blocks(K, T, nblk, d_src, K * T, la, nl, re, nl + 2, d_rep, re.shape[1] * T)
+    s = c.stats()
+    out["launches_of_the_next_call"] = counters()["launches"] - before
+    out["next"] = dict(status=[int(x) for x in st], strip_bytes=s["strip_bytes"], backsub_strip=s["backsub_strip"], u=s["u"])
+    c.sync()
+    c.free(d_src); c.free(d_rep)
+    c.close()
+    out["hazards"] = brief(hazards())
+    return out
+
+
+GROUPS = {"detector": group_detector, "pool": group_pool, "fuzz0": group_fuzz0, "sync": group_sync, "refusal": group_refusal}
 
 
 if __name__ == "__main__":

@@ -157,8 +157,36 @@ def seed0_cases():
         yield dict(kind="encode", K=K, T=T, nblk=nblk, nrep=nrep, want_inter=True, opts=CONTEXTS["forced"], mis=0, tag="seed0/trial%d" % i)
 
 
+def forced_cases(orc, K):
+    """the calls of tests/test_gpu_backsub_forms.py at block size K, one for one (forced_inact_support.GPU_CASES: plans at a forced
+    number of inactive columns, which moves the cu, x and t4 regions of the image to sizes no other launch has): the same options,
+    blocks, symbol sizes, reception and n; the launch must be the one the row names"""
+    import forced_inact_support as F
+    for i, (form, u, n_enc, n_dec, strip, threads, sb) in enumerate(F.GPU_CASES):
+        f = F.FORMS[form]
+        if f["K"] != K:
+            continue
+        common = dict(K=K, nblk=F.NBLK, opts=dict(F.GPU_FORCED, **f["opts"]), mis=0, expect=dict(wb=strip, NT=threads, backsub_strip=sb),
+                      tag="forced/%s u=%d" % (form, u))
+        for kind, T, want_inter in F.calls_of(i):
+            if kind == "encode":
+                yield dict(common, kind="encode", T=T, nrep=F.NREP, want_inter=want_inter, extra_inact=n_enc)
+            else:
+                yield dict(common, kind="decode", T=T, loss=0.1, overhead=2, want_inter=want_inter, site="host", bad_block=None,
+                           extra_inact=n_dec, lost_all=F.gpu_reception(orc, K)[0])
+
+
+def forced_must(K):
+    """every row of the table at this K, reached at its number of inactive columns by the encode and by the decode"""
+    import forced_inact_support as F
+    return [dict(u=u, wb=strip, NT=threads, backsub_strip=sb, skipped=0) for form, u, _, _, strip, threads, sb in F.GPU_CASES
+            if F.FORMS[form]["K"] == K]
+
+
+FORCED_KS = (100, 1000, 3000, 5200, 10000, 15000)
 GROUPS = {w: (lambda orc, w=w: sweep(w)) for w in WIDTHS}
 GROUPS.update(decode=lambda orc: decode_cases(), big=lambda orc: big_cases(), seed0=lambda orc: seed0_cases(), edge=edge_cases)
+GROUPS.update({"forced_k%d" % K: (lambda orc, K=K: forced_cases(orc, K)) for K in FORCED_KS})
 
 # the forms a group must have reached (checked at its end): keys of the launch record
 MUST = {
@@ -177,6 +205,7 @@ MUST = {
     "edge": [dict(NT=768, wb=16, split=0), dict(NT=768, wb=12), dict(NT=768, wb=4, split=0), dict(multi=1, lsub=3, wb=16, NT=64),
              dict(multi=1, lsub=3, wb=16, NT=256), dict(multi=1, lsub=3, wb=16, NT=768), dict(multi=1, G=2)],
 }
+MUST.update({"forced_k%d" % K: forced_must(K) for K in FORCED_KS})
 
 
 def main():

@@ -89,11 +89,12 @@ def kconst(K):
     return _KC[K]
 
 
-def encode_plan(K):
-    if K not in _ENCPLAN:
+def encode_plan(K, extra_inact=0):
+    """the host's encode plan; extra_inact: with that many columns more inactive from the start (the option plan_force_inact)"""
+    if (K, extra_inact) not in _ENCPLAN:
         Kp = nanorq_amd.params(K)["Kp"]
-        _ENCPLAN[K] = nanorq_amd.host_plan(K, np.arange(Kp, dtype=np.uint32), kconst(K))
-    return _ENCPLAN[K]
+        _ENCPLAN[(K, extra_inact)] = nanorq_amd.host_plan(K, np.arange(Kp, dtype=np.uint32), kconst(K), extra_inact=extra_inact)
+    return _ENCPLAN[(K, extra_inact)]
 
 
 def out_lists(orc, K, isis, plan):
@@ -138,13 +139,13 @@ def launch(rec, A, jobs, nblk, T, kc_ptr):
     assert bad is None, "bytes next to the array '%s' were written" % bad.decode()
 
 
-def run_encode(orc, K, T, nblk, nrep, opts, want_inter=True, side=0, mis=0, expect=None, seed=1, lists=None):
+def run_encode(orc, K, T, nblk, nrep, opts, want_inter=True, side=0, mis=0, expect=None, seed=1, lists=None, extra_inact=0):
     """One nrq_encode_blocks call (host site: encode_blocks, out_slots[] of r16(cols * 2 + NRQ_STORE_SLACK) bytes).
-    Returns the launch record as a dict."""
+    extra_inact: the plan of a context with the option plan_force_inact.  Returns the launch record as a dict."""
     L = lemu()
     p = nanorq_amd.params(K)
     Lsym, Kp = p["L"], p["Kp"]
-    plan = encode_plan(K)
+    plan = encode_plan(K, extra_inact)
     hdr = nanorq_amd.plan_header(plan)
     assert hdr["status"] == 0 and hdr["M"] == Lsym
     A = Arena(side, mis)
@@ -204,6 +205,7 @@ def run_encode(orc, K, T, nblk, nrep, opts, want_inter=True, side=0, mis=0, expe
         L.lemu_release_all()
     d = rec.as_dict()
     d["io_aligned"] = io_aligned
+    d["u"] = hdr["u"]
     return d
 
 
@@ -232,10 +234,13 @@ def device_plan(K, lost, rep_esis):
     return arena[:total].copy(), hdr, offs, int(job.nout)
 
 
-def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, mis=0, site="host", bad_block=None, expect=None, seed=2):
+def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, mis=0, site="host", bad_block=None, expect=None, seed=2,
+               extra_inact=0, lost_all=None):
     """One nrq_decode_blocks call.  site "host": decode_host's arrays (out_slots[] of r16(cols * 2 + NRQ_STORE_SLACK) bytes per block);
     "device": the planner's arena, cut at total_bytes, with rowsrc / out_cptr / out_row / out_slots inside it (pl_final_b).
-    bad_block: that block's reception is rank deficient -- the launch must skip it and leave its rows alone."""
+    bad_block: that block's reception is rank deficient -- the launch must skip it and leave its rows alone.
+    extra_inact (site "host"): the plans of a context with the option plan_force_inact; lost_all: every block misses these symbols
+    (the option is the context's: blocks with one reception have one plan, and so one number of inactive columns)."""
     L = lemu()
     p = nanorq_amd.params(K)
     Lsym = p["L"]
@@ -249,7 +254,7 @@ def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, 
     blocks, plan_ptrs, max_out, bits = [], [], 0, T
     for b in range(nblk):
         src = payload(K * T, seed=seed, block=b).reshape(K, T)
-        lost = undecodable(orc, K, b) if b == bad_block else loss_pattern(K, loss, seed=seed * 31 + 5, block=b)
+        lost = undecodable(orc, K, b) if b == bad_block else lost_all if lost_all is not None else loss_pattern(K, loss, seed=seed * 31 + 5, block=b)
         oh = 0 if b == bad_block else (overhead if len(lost) else 0)
         esis = np.arange(K, K + len(lost) + oh, dtype=np.uint32)
         rep, r_int, _ = orc.encode_block(src, K, T, esis, want_inter=True)
@@ -270,7 +275,7 @@ def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, 
             continue
         if site == "host":
             isis, rowsrc = decode_setup(orc, K, lost, esis)
-            plan = nanorq_amd.host_plan(K, isis, kc)
+            plan = nanorq_amd.host_plan(K, isis, kc, extra_inact=extra_inact)
             hdr = nanorq_amd.plan_header(plan)
             assert (hdr["status"] == 0) == ok, ("verdict", b, hdr["status"], ok)
             if hdr["status"]:
@@ -296,7 +301,7 @@ def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, 
         j.plan, j.src, j.rep, j.inter, j.out = plan_p, wp, rp or 0, ip or 0, wp
         plan_ptrs.append(plan_p)
         max_out = max(max_out, len(lost))
-        blk["solved"] = True
+        blk["solved"], blk["u"] = True, hdr["u"]
     io_aligned = (bits & 15) == 0
     rec = shape(opts, plan_ptrs, True, nblk, T, (Lsym if want_inter else 0) + max_out, io_aligned)
     assert rec.err == 0 and not rec.two_lists, rec.as_dict()
@@ -321,4 +326,5 @@ def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, 
     d = rec.as_dict()
     d["io_aligned"] = io_aligned
     d["solved"] = sum(1 for x in blocks if x["solved"])
+    d["u"] = max([x["u"] for x in blocks if x["solved"]] or [0])  # (inactive columns of the plans that ran)
     return d

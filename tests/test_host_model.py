@@ -151,6 +151,19 @@ def test_after_ctx_sync_nothing_pending_touches_the_caller_s_buffers(planner):
     assert s["hazards"] == [], s["hazards"][:6]
 
 
+def test_a_split_launch_whose_tables_exceed_the_lds_is_refused_before_any_launch():
+    """A host plan may have more inactive columns than the device planner's 1280 (the option plan_force_inact makes one: K = 3000,
+    all 3135 columns, 98 W words).  On 4-byte strips the split solve's back-substitution tables are then 196 KiB: the call ends
+    with a status and has launched nothing -- it used to launch the solve kernel first and report afterwards -- and the next
+    call on the context runs as ever (three launches: solve, back-substitution, collect)."""
+    r = run("refusal")
+    assert r["error"] and "back-substitution tables do not fit the LDS (wpr=98)" in r["error"], r
+    assert r["launches_of_the_refused_call"] == 0, r
+    assert r["next"]["status"] == [1, 1] and r["next"]["strip_bytes"] == 4 and r["next"]["backsub_strip"] == 32 and r["next"]["u"] < 200, r
+    assert r["launches_of_the_next_call"] == 3, r
+    assert r["hazards"] == [], r["hazards"][:6]
+
+
 # ------------------------------------------------------------- e. the object layer under fault injection, f. ----
 FLOORS = {   # scenario: (runs that met their injected failure, batches taken back) at least -- the floors of tests/test_gpu_faults.py
     "batch_sync": (20, 3), "batch_async": (20, 3), "repair_all_device": (10, 0), "repair_all_host": (10, 0), "per_block": (10, 0),

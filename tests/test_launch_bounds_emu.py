@@ -30,7 +30,8 @@ import sys
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-GROUPS = ("w16", "w12", "w8", "w4", "w2", "w4sb16", "w4nosplit", "wide2", "wide4", "decode", "big", "edge", "seed0")
+GROUPS = ("w16", "w12", "w8", "w4", "w2", "w4sb16", "w4nosplit", "wide2", "wide4", "decode", "big", "edge", "seed0",
+          "forced_k100", "forced_k1000", "forced_k3000", "forced_k5200", "forced_k10000", "forced_k15000")
 
 
 @pytest.mark.parametrize("group", GROUPS)
@@ -39,7 +40,8 @@ def test_launch_stays_inside_its_arrays(group):
     contexts; decode: lost symbols, overhead 0 and 5, an undecodable block that nrq_next_group must skip, arrays as decode_host and as
     the device planner lay them out; big: K = 1024 and 3100; edge: the slack behind out_slots[] with lists of 33 entries and the
     output staging stride at 1, 17 and 33 elements; seed0: the 30 encodes tests/test_gpu_fuzz.py::test_random_shapes[0] draws, on the
-    forced context's options with the intermediate symbols wanted."""
+    forced context's options with the intermediate symbols wanted; forced_k*: every call of tests/test_gpu_backsub_forms.py -- plans at
+    a forced number of inactive columns, up to 1281 of them (forced_inact_support.GPU_CASES) -- before it may run on a GPU."""
     r = subprocess.run([sys.executable, os.path.join(HERE, "launch_bounds_worker.py"), group], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     out = r.stdout.decode(errors="replace")
     hits = [line for line in out.splitlines() if line.startswith("FENCE HIT")]

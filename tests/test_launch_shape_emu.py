@@ -80,7 +80,7 @@ def test_knob_names(emu):
     """an option name the table does not hold is refused; fault injection is not a knob"""
     with Tuning(emu, {}) as t:
         for name in (b"no_lists", b"no_wb12", b"max_wb", b"no_split", b"wide_g", b"lds_max", b"plan_ucap", b"tx_dword", b"host_plan_auto",
-                     b"backsub_sb"):
+                     b"backsub_sb", b"plan_force_inact"):
             assert emu.emu_tuning_set(t.p, name, 1) == 0, name
         for name in (b"fail_after", b"faults_injected", b"nonsense", b"NRQ_NO_LISTS", b""):
             assert emu.emu_tuning_set(t.p, name, 1) == -1, name

@@ -85,3 +85,16 @@ def test_ledger_has_no_stale_rows(inst):
         rows |= {(kernel, (str(m), "true" if flag else "false")) for m, flag in table}
     assert len(V.EMIT) == 8 and len(V.EMIT_HELD) == 8 and len(V.EMIT_SET) == 10
     assert rows <= keys, sorted(rows - keys)
+
+
+def test_every_back_substitution_form_names_its_test():
+    """BACKSUB_FORMS: every row's test exists, and the rows are exactly what the GPU case table (tests/forced_inact_support.py) runs"""
+    import forced_inact_support as F
+    for key, row in V.BACKSUB_FORMS.items():
+        assert _test_exists(row["test"]), key
+    ran = {}
+    for form, u, _, _, strip, threads, sb in F.GPU_CASES:
+        w = F.wpr_of(u)
+        cls = F.nw_class(w) if not sb else "split<%d>x%d" % (sb, (w + 19) // 20)
+        ran.setdefault((strip, threads, cls), set()).add((F.FORMS[form]["K"], u))
+    assert {k: set(r["at"]) for k, r in V.BACKSUB_FORMS.items()} == ran

@@ -86,6 +86,48 @@ BACKSUB = {
              pinned="tests/test_gpu_split.py::test_backsub16_second_word_batch"),
 }
 
+# The forms of the back-substitution INSIDE an instance: ph_backsub (solve_body.h) takes backsub_fixed<NW> for plans of at most 4 / 8 /
+# 12 / 24 W words per row (wpr = ceil(u / 32), u the plan's inactive columns) and a plain loop beyond (class 0 here), in a fast form
+# on 768 threads and a lean one on 256 and 64, with device-only bodies for 16-, 12- and 8-byte strips; the split solve's
+# nrq_backsub_kernel<SB> asks for a pivot's W words in batches of 20 ("split<SB>xN": N batches).  One row per (strip bytes,
+# threads, class) that a context can reach, the test that runs it on plans at a forced u (the option plan_force_inact) and the
+# (K, u) it runs it at -- tests/forced_inact_support.py GPU_CASES is the table behind this one, tests/test_variant_ledger.py holds
+# the two against each other.  What no context reaches, and why: the docstring of the test's module.
+_FORMS_TEST = "tests/test_gpu_backsub_forms.py::test_backsub_form"
+BACKSUB_FORMS = {
+    (16, 768, 8): dict(test=_FORMS_TEST, at=[(5200, 255), (5200, 256)]),
+    (16, 768, 12): dict(test=_FORMS_TEST, at=[(3000, 383), (3000, 384), (5200, 257), (5200, 383), (5200, 384)]),
+    (16, 768, 24): dict(test=_FORMS_TEST, at=[(1000, 767), (1000, 768), (3000, 385), (3000, 767), (3000, 768), (5200, 385), (5200, 767), (5200, 768)]),
+    (16, 768, 0): dict(test=_FORMS_TEST, at=[(1000, 769), (1000, 1071), (3000, 769), (5200, 769)]),
+    (16, 256, 4): dict(test=_FORMS_TEST, at=[(1000, 127), (1000, 128), (3000, 127), (3000, 128)]),
+    (16, 256, 8): dict(test=_FORMS_TEST, at=[(1000, 129), (1000, 255), (1000, 256), (3000, 129), (3000, 255), (3000, 256)]),
+    (16, 256, 12): dict(test=_FORMS_TEST, at=[(1000, 257), (1000, 383), (1000, 384), (3000, 257)]),
+    (16, 256, 24): dict(test=_FORMS_TEST, at=[(1000, 385)]),
+    (16, 64, 4): dict(test=_FORMS_TEST, at=[(100, 31), (100, 32), (100, 33), (100, 63), (100, 64), (100, 65), (100, 95), (100, 96), (100, 97), (100, 127), (100, 128)]),
+    (12, 768, 8): dict(test=_FORMS_TEST, at=[(10000, 255), (10000, 256)]),
+    (12, 768, 12): dict(test=_FORMS_TEST, at=[(10000, 257), (10000, 383), (10000, 384)]),
+    (12, 768, 24): dict(test=_FORMS_TEST, at=[(5200, 767), (5200, 768), (10000, 385)]),
+    (12, 768, 0): dict(test=_FORMS_TEST, at=[(3000, 1279), (3000, 1280), (3000, 1281), (5200, 769)]),
+    (8, 768, 8): dict(test=_FORMS_TEST, at=[(10000, 255), (10000, 256)]),
+    (8, 768, 12): dict(test=_FORMS_TEST, at=[(10000, 257), (15000, 383), (15000, 384)]),
+    (8, 768, 24): dict(test=_FORMS_TEST, at=[(15000, 385), (15000, 767), (15000, 768)]),
+    (8, 768, 0): dict(test=_FORMS_TEST, at=[(15000, 769)]),
+    (8, 256, 12): dict(test=_FORMS_TEST, at=[(1000, 383), (1000, 384)]),
+    (8, 256, 24): dict(test=_FORMS_TEST, at=[(1000, 385), (1000, 767), (1000, 768)]),
+    (8, 256, 0): dict(test=_FORMS_TEST, at=[(1000, 769), (1000, 1071)]),
+    (8, 64, 4): dict(test=_FORMS_TEST, at=[(1000, 127), (1000, 128)]),
+    (8, 64, 8): dict(test=_FORMS_TEST, at=[(1000, 129), (1000, 255), (1000, 256)]),
+    (8, 64, 12): dict(test=_FORMS_TEST, at=[(1000, 257)]),
+    (4, 768, 'split<16>x2'): dict(test=_FORMS_TEST, at=[(15000, 1280)]),
+    (4, 768, 'split<16>x3'): dict(test=_FORMS_TEST, at=[(15000, 1281)]),
+    (4, 256, 'split<16>x2'): dict(test=_FORMS_TEST, at=[(3000, 641), (3000, 1279), (3000, 1280)]),
+    (4, 256, 'split<16>x3'): dict(test=_FORMS_TEST, at=[(3000, 1281)]),
+    (4, 256, 'split<32>x1'): dict(test=_FORMS_TEST, at=[(3000, 639), (3000, 640)]),
+    (2, 64, 'split<16>x2'): dict(test=_FORMS_TEST, at=[(3000, 641), (3000, 1279), (3000, 1280)]),
+    (2, 64, 'split<16>x3'): dict(test=_FORMS_TEST, at=[(3000, 1281)]),
+    (2, 64, 'split<32>x1'): dict(test=_FORMS_TEST, at=[(3000, 639), (3000, 640)]),
+}
+
 # nrq_plan_kernel<NT, compact>: the decode planner; stats plan_wg_threads, plan_compact_state (and plan_segmented)
 PLAN = {
     (1024, 0): dict(status="default", shape=dict(K=1000, T=16, nblk=64, loss=0.2),
