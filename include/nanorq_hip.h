@@ -682,8 +682,36 @@ int nrq_txset_emit(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tag
  * nrq_tx_emit_syms / nrq_otx_emit_syms gives: 0 written, NRQ_TX_NOT_READY a relay's block that is not ready, NRQ_TX_BAD_RANGE (a
  * sender is strict; the K of the member's segment decides the range); with NRQ_TX_KEY_INLINE the key goes in front of the FEC
  * Payload ID.  A packet of no member is wholly untouched and gets -1; the bytes behind hdr + c_k * T are untouched; no packet is
- * ever half written.  Ready bits are taken as they are at the call.  Refused: what nrq_txset_emit refuses, NRQ_TX_HELD (as in
- * every several-symbol emit), G outside 1..NRQ_PKT_SYMS_MAX, a stride too small, n * G > 0x7FFFFFFF. */
+ * ever half written.  Ready bits are taken as they are at the call.  With NRQ_TX_HELD a member's packet gets what that member's
+ * own call gives under the same bit (the table at nrq_tx_emit_syms): a ready block's packet is written as without the flag; one
+ * of a block that is not ready, with an admissible range, is written iff the member's reception holds EVERY symbol e .. e+c-1 --
+ * copies of the source rows, or of the repair rows found for the c ESIs -- else NRQ_TX_NOT_READY and untouched; an inadmissible
+ * range is NRQ_TX_BAD_RANGE whether or not the block is ready; a member that is a plain sender answers as without the flag.
+ * Refused: what nrq_txset_emit refuses, NRQ_TX_HELD on a set with NO relay member (the flag could do nothing there, as
+ * nrq_tx_emit_syms refuses it on a sender; it is accepted as soon as one member is a relay or an object's relay; an EMPTY set has no relay member, so it refuses the flag
+ * too, and so does a call with n = 0 on a set without one, although both return 0 at once without the flag), G outside
+ * 1..NRQ_PKT_SYMS_MAX, a stride too small, n * G > 0x7FFFFFFF.
+ *
+ * nrq_rxset_want_syms / nrq_rxset_held_syms: the list is the concatenation, in the set's block order, of what each member's own
+ * nrq_rx_want_syms / nrq_rx_held_syms (an attached object: nrq_orx_want_syms / nrq_orx_held_syms -- class L, then class S, each
+ * with its own K, under the object's one key) gives for the same arguments, word for word: d_tags[k] a first tag, d_nsym[k] its
+ * count, d_keys[k] the key of the member the packet belongs to.  Equivalently it is the packetisation (at nrq_rx_want_syms) of
+ * nrq_rxset_want's / nrq_rxset_held's one-symbol list with each member's own K; its expansion is that list word for word, and
+ * with G = 1 the first tags are that list and every count is 1.  (keys, tags, nsym) is the form nrq_txset_emit_syms takes: want
+ * -> emit -> nrq_rxset_add_syms -> nrq_rxset_decode runs in packets for all members without a per-member call or a host-built
+ * list.  The calling contract is nrq_rxset_want's and nrq_rx_want_syms' combined: the call waits for the work enqueued before it;
+ * *h_npkt (required) is the number of packets, *h_nsym (nullable) the number of symbols -- the one-symbol call's *h_n -- and h_cnt
+ * (nullable) one entry per block in block order, that block's number of PACKETS; all three are final on return and come from ONE
+ * download and ONE wait.  d_tags and d_nsym both NULL: the counts only.  cap is in packets; cap < *h_npkt: -1 with the totals and
+ * h_cnt still filled and nothing written; else the writing is enqueued on the context's stream, so an nrq_txset_emit_syms behind
+ * it needs no host wait.  d_keys is nullable when the lists are given.  An empty set: 0 with zeros and no launch; a set that lists
+ * nothing runs no fill launch.  Refused (-1 and a text, nothing enqueued): what nrq_rxset_want refuses, G outside
+ * 1..NRQ_PKT_SYMS_MAX, exactly one of d_tags / d_nsym, d_keys without d_tags, h_npkt NULL.  The calls only read the members'
+ * books. */
+int nrq_rxset_want_syms(nrq_rxset *set, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_keys, uint32_t *d_tags,
+                        uint8_t *d_nsym, uint32_t cap, uint32_t *h_cnt, uint32_t *h_npkt, uint32_t *h_nsym);
+int nrq_rxset_held_syms(nrq_rxset *set, uint32_t G, uint32_t *d_keys, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_cnt,
+                        uint32_t *h_npkt, uint32_t *h_nsym);
 int nrq_rxset_add_syms(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
                        uint32_t G, const uint8_t *d_nsym, uint32_t flags, int32_t *d_results);
 int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,

@@ -183,6 +183,10 @@ def lib():
         L.nrq_orx_want_syms.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, u32p, u32p]
         L.nrq_rx_held_syms.argtypes = [vp, u32, vp, vp, u32, u32p, u32p]
         L.nrq_orx_held_syms.argtypes = [vp, u32, vp, vp, u32, u32p, u32p]
+    if hasattr(L, "nrq_rxset_want_syms"):  # (likewise a build from before the sets' listings as runs: those methods then raise)
+        u32 = C.c_uint32
+        L.nrq_rxset_want_syms.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, u32, u32p, u32p, u32p]
+        L.nrq_rxset_held_syms.argtypes = [vp, u32, vp, vp, vp, u32, u32p, u32p, u32p]
     u8pp = C.POINTER(C.POINTER(C.c_uint8))
     L.nrq_host_kconst_build.argtypes = [C.c_uint32, u8pp, u32p]
     L.nrq_host_plan_build.argtypes = [C.c_uint32, C.c_uint32, u32p, C.POINTER(C.c_uint8), u8pp, u32p]
@@ -1087,6 +1091,34 @@ class ReceiverSet(_Handle):
         want() -- the list SenderSet.emit(keys, tags, held=True) over the members' relays writes in full."""
         return self._listing(self._fn("nrq_rxset_held"), (), per_block)
 
+    def _listing_syms(self, fn, args, per_block):
+        """a set-wide listing in packets with keys, as _listing: the count call, three tensors of that size, the fill call"""
+        import torch
+        npkt = C.c_uint32(0)
+        cnt = np.zeros(len(self.blocks()[0]), np.uint32)
+        self.ctx._chk(fn(self._h, *args, None, None, None, 0, _u32(cnt) if per_block else None, C.byref(npkt), None))
+        dev = "cuda:%d" % self.ctx.device
+        keys = torch.empty(npkt.value, dtype=torch.int32, device=dev)
+        tags = torch.empty(npkt.value, dtype=torch.int32, device=dev)
+        nsym = torch.empty(npkt.value, dtype=torch.uint8, device=dev)
+        if npkt.value:
+            self.ctx._chk(fn(self._h, *args, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), npkt.value, None,
+                             C.byref(npkt), None))
+            self.ctx.sync()  # (torch's stream and the library's are not ordered: the lists are complete on return)
+        return (keys, tags, nsym, cnt) if per_block else (keys, tags, nsym)
+
+    def want_syms(self, G, extra=0, source=False, esi_from=0, per_block=False):
+        """(keys, tags, nsym): want() as packets of up to G symbols (nrq_rxset_want_syms) -- what every member's own
+        want_syms(G, extra, source, esi_from) lists, one behind the other in block order, with each packet's key: int32 / int32 /
+        uint8 [n] device tensors, the form SenderSet.emit_syms(keys, tags, G, nsym=nsym, ...) takes.  Each member's list is cut with
+        its own K.  per_block=True: also the number of PACKETS per block, a uint32 array in blocks() order."""
+        return self._listing_syms(self._fn("nrq_rxset_want_syms"), (WANT_SOURCE if source else 0, extra, esi_from, G), per_block)
+
+    def held_syms(self, G, per_block=False):
+        """(keys, tags, nsym): held() as packets of up to G symbols (nrq_rxset_held_syms), as want_syms -- the list
+        SenderSet.emit_syms(keys, tags, G, nsym=nsym, held=True) over the members' relays writes in full."""
+        return self._listing_syms(self._fn("nrq_rxset_held_syms"), (G,), per_block)
+
 
 class SenderSet(_Handle):
     """A set of device-resident transmissions of one T (nrq_txset, include/nanorq_hip.h): Senders, RelaySenders, ObjectSenders and
@@ -1154,10 +1186,12 @@ class SenderSet(_Handle):
         hdr = 8 if key_inline else 4 if inline else 0
         return (G * self.T + hdr + 15) // 16 * 16 if hdr else G * self.T
 
-    def emit_syms(self, keys, tags, G, nsym=None, out=None, inline=False, key_inline=False, results=None):
+    def emit_syms(self, keys, tags, G, nsym=None, out=None, inline=False, key_inline=False, results=None, held=False):
         """Packet k of up to G symbols for (keys[k], first tag tags[k]) in row k of out (nrq_txset_emit_syms): keys, tags, out,
         inline, key_inline as in emit(); G, nsym and results (0, -1, TX_NOT_READY, TX_BAD_RANGE; only a 0 packet is written, and
-        whole) as in _Emitter.emit_syms, each member with its own K.  Held symbols are not offered.  Enqueue only.  Returns out."""
+        whole) as in _Emitter.emit_syms, each member with its own K.  held: as _Emitter.emit_syms on the relay members -- a packet
+        of a block that is not ready is written iff the member's reception holds EVERY one of its symbols; plain senders answer as
+        without it, and a set with no relay member refuses it.  Enqueue only.  Returns out."""
         if not hasattr(self._L, "nrq_txset_emit_syms"):
             raise NrqError("this library build has no nrq_txset_emit_syms")
         n = int(tags.shape[0])
@@ -1167,7 +1201,7 @@ class SenderSet(_Handle):
             stride = out.shape[1]
         else:
             stride = out.stride(0) * out.element_size()
-        flags = _tx_flags(inline, False) | (TX_KEY_INLINE if key_inline else 0)
+        flags = _tx_flags(inline, held) | (TX_KEY_INLINE if key_inline else 0)
         self.ctx._chk(self._L.nrq_txset_emit_syms(self._h, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)),
                                                   C.c_void_p(_dptr(out)), stride, flags, C.c_void_p(_dptr(results))))
         return out

@@ -32,6 +32,7 @@ TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
 YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
 ZEMU = os.path.join(ROOT, "tests", "emu", "libsyms_set_emu.so")
 GEMU = os.path.join(ROOT, "tests", "emu", "libruns_emu.so")
+JEMU = os.path.join(ROOT, "tests", "emu", "librxset_runs_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 UEMU = os.path.join(ROOT, "tests", "emu", "libout_lists_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
@@ -191,7 +192,7 @@ def build_rxset_want_emu(force=False):
     """tests/emu/librxset_want_emu.so: CPU emulation of a reception set's want and held listings with keys
     (csrc/rxset_want_emu.cpp over want_set_body.h)."""
     return _build_emu(QEMU, os.path.join(CSRC, "rxset_want_emu.cpp"),
-                      ("want_set_body.h", "lists_set_body.h", "want_body.h", "held_body.h", "ingest_set_body.h", "ingest_body.h"), force)
+                      ("emu_scan.h", "want_set_body.h", "lists_set_body.h", "want_body.h", "held_body.h", "ingest_set_body.h", "ingest_body.h"), force)
 
 
 def build_txset_emu(force=False):
@@ -216,7 +217,16 @@ def build_runs_emu(force=False):
     """tests/emu/libruns_emu.so: CPU emulation of the want and held listings as runs and of the held emit of packets of several
     symbols (csrc/runs_emu.cpp over runs_body.h)."""
     return _build_emu(GEMU, os.path.join(CSRC, "runs_emu.cpp"),
-                      ("emit_emu.h", "runs_body.h", "syms_body.h", "want_body.h", "held_body.h", "emit_body.h", "ingest_body.h", "rq_math.h"), force)
+                      ("emit_emu.h", "runs_emu_walks.h", "runs_body.h", "syms_body.h", "want_body.h", "held_body.h", "emit_body.h", "ingest_body.h",
+                       "rq_math.h"), force)
+
+
+def build_rxset_runs_emu(force=False):
+    """tests/emu/librxset_runs_emu.so: CPU emulation of a reception set's want and held listings as runs and of a sender set's
+    held emit of packets of several symbols (csrc/rxset_runs_emu.cpp over runs_set_body.h)."""
+    return _build_emu(JEMU, os.path.join(CSRC, "rxset_runs_emu.cpp"),
+                      ("emu_scan.h", "runs_emu_walks.h", "runs_set_body.h", "runs_body.h", "syms_set_body.h", "want_set_body.h", "lists_set_body.h",
+                       "syms_body.h", "want_body.h", "held_body.h", "emit_set_body.h", "emit_body.h", "ingest_set_body.h", "ingest_body.h", "rq_math.h"), force)
 
 
 def build_obj_emu(force=False):
@@ -323,6 +333,7 @@ if __name__ == "__main__":
     build_syms_emu(force="-f" in sys.argv)
     build_syms_set_emu(force="-f" in sys.argv)
     build_runs_emu(force="-f" in sys.argv)
+    build_rxset_runs_emu(force="-f" in sys.argv)
     build_obj_emu(force="-f" in sys.argv)
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)

@@ -46,6 +46,7 @@
 #include "syms_body.h"
 #include "syms_set_body.h"
 #include "runs_body.h"
+#include "runs_set_body.h"
 #include "obj_body.h"
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
@@ -5499,6 +5500,156 @@ int nrq_rxset_held(nrq_rxset *set, uint32_t *d_keys, uint32_t *d_tags, uint32_t 
 
 } /* extern "C" */
 
+/* ================================================ a set's want and held lists as runs (nrq_rxset_want_syms / _held_syms) ==== */
+/* The two layers above put together: nrq_rx_want_syms and nrq_rx_held_syms over all members of a set at once, with the member's
+ * key beside every packet -- the (keys, tags, nsym) form nrq_txset_emit_syms takes.  Kernels of their own in the count / scan /
+ * fill shape of nrq_ings_want_*_kernel, so that the one-symbol set listings and the single-reception runs kernels are compiled
+ * from the code they always were: one workgroup of 256 per GLOBAL block finds its member and key (lss_block / wns_block), forms
+ * that member's wn_q (wns_query) and runs the workgroup walks of the single form on it (rn_bits_wg, for held rn_rows_wg behind
+ * it).  The set's list buffer holds, under rx_list_count's rule, nb + 2 words: the blocks' packet counts, scanned in place into
+ * exclusive offsets with the packet total behind them, and the symbol total the count kernel adds up. */
+__global__ __launch_bounds__(256) void nrq_ings_want_syms_count_kernel(const ings_tab *__restrict__ t, wns_call c, uint32_t G,
+                                                                       uint32_t *__restrict__ cnt, uint32_t *__restrict__ nsym_total) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t g = blockIdx.x;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  const wn_q q = wns_query(r, &c);
+  const rn_walk k = rn_walk_want(r, &q, b);
+  uint32_t syms;
+  const uint32_t pk = rn_bits_wg(r, &k, G, nullptr, nullptr, 0u, &syms, ps, pm);
+  if (threadIdx.x == 0) {
+    cnt[g] = pk;
+    wns_count_end(t, g, cnt);
+    if (syms) atomicAdd(nsym_total, syms);
+  }
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_held_syms_count_kernel(const ings_tab *__restrict__ t, uint32_t G, uint32_t *__restrict__ cnt,
+                                                                       uint32_t *__restrict__ nsym_total) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t g = blockIdx.x;
+  uint32_t b;
+  const ing_rx *r = lss_block(t, g, &b);
+  const rn_walk k = rn_walk_held(r, b);
+  uint32_t syms;
+  uint32_t pk = rn_bits_wg(r, &k, G, nullptr, nullptr, 0u, &syms, ps, pm);
+  pk += rn_rows_wg(r, b, G, nullptr, nullptr, 0u, ps, pm);
+  if (threadIdx.x == 0) {
+    cnt[g] = pk;
+    wns_count_end(t, g, cnt);
+    syms += hl_nrep(r, b);
+    if (syms) atomicAdd(nsym_total, syms);
+  }
+}
+
+/* one workgroup per global block: its packets to tags / nsym [off[g] .. off[g + 1]), then its key to the same entries of keys
+ * (nullable), the stores coalesced as in nrq_ings_want_fill_kernel.  A block that lists nothing is left at once. */
+__global__ __launch_bounds__(256) void nrq_ings_want_syms_fill_kernel(const ings_tab *__restrict__ t, wns_call c, uint32_t G,
+                                                                      const uint32_t *__restrict__ off, uint32_t *__restrict__ tags,
+                                                                      uint8_t *__restrict__ nsym, uint32_t *__restrict__ keys) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t g = blockIdx.x, lo = off[g], hi = off[g + 1u];
+  if (lo == hi) return; /* (the same in every thread) */
+  uint32_t b, key;
+  const ing_rx *r = wns_block(t, g, &b, &key);
+  const wn_q q = wns_query(r, &c);
+  const rn_walk k = rn_walk_want(r, &q, b);
+  (void)rn_bits_wg(r, &k, G, tags, nsym, lo, nullptr, ps, pm);
+  if (keys) wns_put_keys(keys, lo, hi, key, threadIdx.x, 256u);
+}
+
+__global__ __launch_bounds__(256) void nrq_ings_held_syms_fill_kernel(const ings_tab *__restrict__ t, uint32_t G, const uint32_t *__restrict__ off,
+                                                                      uint32_t *__restrict__ tags, uint8_t *__restrict__ nsym,
+                                                                      uint32_t *__restrict__ keys) {
+  __shared__ uint32_t ps[256], pm[256];
+  const uint32_t g = blockIdx.x, lo = off[g], hi = off[g + 1u];
+  if (lo == hi) return;
+  uint32_t b, key;
+  const ing_rx *r = wns_block(t, g, &b, &key);
+  const rn_walk k = rn_walk_held(r, b);
+  const uint32_t at = rn_bits_wg(r, &k, G, tags, nsym, lo, nullptr, ps, pm);
+  (void)rn_rows_wg(r, b, G, tags, nsym, at, ps, pm);
+  if (keys) wns_put_keys(keys, lo, hi, key, threadIdx.x, 256u);
+}
+
+/* a listing in packets of all members with keys, shaped like rxset_list: the symbol total zeroed, `count(cnt, nsym_total)`, ONE
+ * scan, ONE download (the nb + 1 offsets when the per-block counts are asked for, and the two totals) and wait, then `fill(off)` */
+template <class Count, class Fill>
+static int rxset_list_syms(nrq_rxset *set, const char *who, const char *what, uint32_t *d_tags, uint32_t cap, uint32_t *h_cnt, uint32_t *h_npkt,
+                           uint32_t *h_nsym, Count count, Fill fill) {
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t *off = (uint32_t *)set->lists;
+  HIPCHK(ctx, hipMemsetAsync(off + nb + 1u, 0, 4u, ctx->stream));
+  count(off, off + nb + 1u);
+  hipLaunchKernelGGL(nrq_ings_lists_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, nb + 1u, off);
+  HIPCHK(ctx, hipGetLastError());
+  std::vector<uint32_t> h(h_cnt ? (size_t)nb + 2u : 2u, 0); /* (the last two words: packets, symbols) */
+  HIPCHK(ctx, hipMemcpyAsync(h.data(), h_cnt ? off : off + nb, h.size() * 4u, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *h_npkt = h[h.size() - 2u];
+  if (h_nsym) *h_nsym = h.back();
+  if (h_cnt)
+    for (uint32_t g = 0; g < nb; g++) h_cnt[g] = h[g + 1u] - h[g];
+  if (!d_tags) return 0;
+  if (cap < *h_npkt) return fail(ctx, -1, "%s: %u packets are %s, d_tags and d_nsym have room for %u", who, *h_npkt, what, cap);
+  if (*h_npkt == 0) return 0;
+  fill((const uint32_t *)off);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int nrq_rxset_want_syms(nrq_rxset *set, uint32_t flags, uint32_t extra, uint32_t esi_from, uint32_t G, uint32_t *d_keys, uint32_t *d_tags,
+                        uint8_t *d_nsym, uint32_t cap, uint32_t *h_cnt, uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_rxset_want_syms";
+  const int rc = rn_check(ctx, who, G, d_tags, d_nsym, h_npkt, h_nsym);
+  if (rc) return rc;
+  switch (wn_check(flags, extra, esi_from)) {
+    case 1: return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+    case 2: return fail(ctx, -1, "%s: NRQ_WANT_SOURCE takes neither extra nor esi_from (%u, %u)", who, extra, esi_from);
+    case 3: return fail(ctx, -1, "%s: extra %u is above 2^24", who, extra);
+    default: break;
+  }
+  if (d_keys && !d_tags) return fail(ctx, -1, "%s: d_keys without d_tags", who);
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  const ings_tab *t = (const ings_tab *)set->tab;
+  const wns_call c{flags, extra, esi_from};
+  hipStream_t st = ctx->stream;
+  return rxset_list_syms(
+      set, who, "wanted", d_tags, cap, h_cnt, h_npkt, h_nsym,
+      [&](uint32_t *cnt, uint32_t *tot) { hipLaunchKernelGGL(nrq_ings_want_syms_count_kernel, dim3(nb), dim3(256), 0, st, t, c, G, cnt, tot); },
+      [&](const uint32_t *off) {
+        hipLaunchKernelGGL(nrq_ings_want_syms_fill_kernel, dim3(nb), dim3(256), 0, st, t, c, G, off, d_tags, d_nsym, d_keys);
+      });
+}
+
+int nrq_rxset_held_syms(nrq_rxset *set, uint32_t G, uint32_t *d_keys, uint32_t *d_tags, uint8_t *d_nsym, uint32_t cap, uint32_t *h_cnt,
+                        uint32_t *h_npkt, uint32_t *h_nsym) {
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const char *who = "nrq_rxset_held_syms";
+  const int rc = rn_check(ctx, who, G, d_tags, d_nsym, h_npkt, h_nsym);
+  if (rc) return rc;
+  if (d_keys && !d_tags) return fail(ctx, -1, "%s: d_keys without d_tags", who);
+  const uint32_t nb = set->nblk;
+  if (nb == 0) return 0;
+  const ings_tab *t = (const ings_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  return rxset_list_syms(
+      set, who, "held", d_tags, cap, h_cnt, h_npkt, h_nsym,
+      [&](uint32_t *cnt, uint32_t *tot) { hipLaunchKernelGGL(nrq_ings_held_syms_count_kernel, dim3(nb), dim3(256), 0, st, t, G, cnt, tot); },
+      [&](const uint32_t *off) { hipLaunchKernelGGL(nrq_ings_held_syms_fill_kernel, dim3(nb), dim3(256), 0, st, t, G, off, d_tags, d_nsym, d_keys); });
+}
+
+} /* extern "C" */
+
 /* ================================================ sender sets (nrq_txset_*, emit_set_body.h) ==== */
 /* The tag-list emit over a segment table in device memory: one chain of kernels writes the packets of all members into one
  * buffer.  Three bucketing passes make the block-major work order over the set's global blocks -- the histogram pass also finds
@@ -6030,6 +6181,92 @@ __global__ __launch_bounds__(256) void nrq_emit_set_syms_kernel(const txs_tab *_
   }
 }
 
+/* The emit with held symbols (NRQ_TX_HELD): the wave shape of nrq_emit_set_syms_kernel with the admission of
+ * nrq_emit_held_syms_kernel, a kernel of its own so that both are compiled from the code they always were.  Admission (hss_packet,
+ * runs_set_body.h): a ready block's packet goes the usual way; one of a block that is not ready is written iff the reception behind
+ * its segment holds EVERY one of its symbols -- each lane asks for its slot's seen bit in the segment's books, read through the
+ * table pointer, and a ballot over the packet's lanes decides, so a packet is written whole or not at all.  Held source symbols
+ * are source rows e .. e+c-1; the rows of held repair symbols are found per packet by the wave that writes it, in one walk over the
+ * block's repair list in trips of 64 into the LDS slot heads, and the packet is then one run over single-row lists from the base
+ * of the block's repair rows. */
+template <int MODE>
+__global__ __launch_bounds__(256) void nrq_emit_set_held_syms_kernel(const txs_tab *__restrict__ t, txs_ready rdy, txs_call c, sy_tx y) {
+  __shared__ uint32_t s_cols[TX_WAVES][TX_WAVE_PKTS][TX_COLS];
+  __shared__ uint32_t s_n[TX_WAVES][TX_WAVE_PKTS], s_tag[TX_WAVES][TX_WAVE_PKTS], s_k[TX_WAVES][TX_WAVE_PKTS];
+  __shared__ uint32_t s_seg[TX_WAVES][TX_WAVE_PKTS], s_key[TX_WAVES][TX_WAVE_PKTS];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t G = y.G, per = 64u / G, p = lane / G, i = lane - p * G;
+  const uint64_t w0 = ((uint64_t)blockIdx.x * TX_WAVES + wv) * per; /* the wave's first packet in the work order */
+  {
+    uint32_t n = 0, cnt = 0, tag0 = 0, k = 0, sg = TXS_NONE, key = 0, ready = 0, kind = TX_READY;
+    int32_t code = TX_FOREIGN;
+    bool mine = p < per && w0 + p < c.n;
+    if (mine) {
+      k = c.order[w0 + p];
+      mine = k < c.n; /* (always: the work order is a permutation) */
+      if (mine) {
+        tag0 = c.tags[k];
+        key = txs_key_of(&c, k);
+        sg = hss_packet(t, &rdy, &y, k, tag0, c.seg[k], &code, &cnt, &ready);
+      }
+    }
+    const uint32_t e = tag0 & SY_ESI_MAX;
+    /* all or nothing: every slot of a packet of a block that is not ready must be held (every lane of the wave takes the ballot) */
+    bool ok = true;
+    if (sg < TXS_MAX_SEGS && !ready && i < cnt) ok = hss_slot_held(t, sg, tag0, e + i);
+    const uint64_t held = __ballot(ok), pmask = (cnt >= 64u ? ~0ull : (1ull << cnt) - 1ull) << (p * G);
+    if (sg < TXS_MAX_SEGS && !ready) {
+      if ((held & pmask) != pmask) { code = TX_NOT_READY; cnt = 0u; sg = TXS_NONE; }
+      else kind = hss_kind(t, sg, tag0);
+    }
+    if (sg < TXS_MAX_SEGS && i < cnt) {
+      if (kind == TX_HELD_REP) { s_cols[wv][lane][0] = TX_NONE; n = 1u; } /* (the row index: found below) */
+      else n = tx_rows(&t->seg[sg].b, tag0 + i, s_cols[wv][lane]);        /* (a held source symbol: row e + i, as a ready one) */
+    }
+    if (mine && i == 0u && c.results && kind != TX_HELD_REP) c.results[k] = code; /* (held repair symbols: once the rows are found) */
+    s_n[wv][lane] = n | (cnt << 8) | (kind << 16); /* (cnt = 0: the packet stays untouched) */
+    s_tag[wv][lane] = tag0;
+    s_k[wv][lane] = k;
+    s_seg[wv][lane] = sg;
+    s_key[wv][lane] = key;
+  }
+  __syncthreads();
+  const uint32_t T = c.T;
+  for (uint32_t q = 0; q < per && w0 + q < c.n; q++) { /* (wave-uniform) */
+    const uint32_t l0 = q * G;
+    const uint32_t nk = __builtin_amdgcn_readfirstlane(s_n[wv][l0]), cnt = (nk >> 8) & 0xFFu;
+    if (!cnt) continue; /* no member, a refused range, a block that is not ready with a symbol that is not held */
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(s_tag[wv][l0]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(s_k[wv][l0]);
+    const uint32_t key = __builtin_amdgcn_readfirstlane(s_key[wv][l0]);
+    const txs_seg *S = &t->seg[__builtin_amdgcn_readfirstlane(s_seg[wv][l0])];
+    const uint8_t *base;
+    if ((nk >> 16) == TX_HELD_REP) {
+      const tx_held_seg *hs = &S->h;
+      const uint32_t b = (tag >> 24) - S->b.sbn0;
+      const uint32_t nrep = tx_held_nrep(hs, b), e = tag & SY_ESI_MAX;
+      for (uint32_t q0 = 0; q0 < nrep; q0 += 64u) {
+        const uint32_t x = q0 + lane < nrep ? hs->rep_esi[(uint64_t)b * hs->rep_cap + q0 + lane] - e : TX_NONE;
+        if (x < cnt) s_cols[wv][l0 + x][0] = q0 + lane;
+      }
+      /* the wave reads what its other lanes wrote: LDS operations of one wave complete in order; the fence keeps the compiler from
+       * moving the reads above the writes */
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const bool found = lane >= cnt || s_cols[wv][l0 + lane][0] != TX_NONE;
+      const bool all = __ballot(!found) == 0ull;
+      if (c.results && lane == 0) c.results[k] = all ? 0 : TX_NOT_READY;
+      if (!all) continue; /* (the books say otherwise: a marked repair ESI has its row) */
+      base = tx_held_rep_base(hs, b);
+    } else {
+      base = tx_base(&S->b, tag);
+    }
+    uint8_t *P = c.pkts + (uint64_t)k * c.pkt_stride;
+    if (cnt == 1u) txs_payload<MODE>(base, T, tx_one{s_cols[wv][l0], nk & 0xFFu}, key, tag, P, c.hdr, lane);
+    else txs_payload<MODE>(base, T, tx_run{&s_cols[wv][l0], &s_n[wv][l0], cnt}, key, tag, P, c.hdr, lane);
+  }
+}
+
 extern "C" {
 
 int nrq_rxset_add_syms(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n,
@@ -6088,12 +6325,20 @@ int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *
   using set_fn = void (*)(const txs_tab *, txs_ready, txs_call, sy_tx);
   static const set_fn kern[5] = {nrq_emit_set_syms_kernel<TX_V16>, nrq_emit_set_syms_kernel<TX_V16_SHIFT>, nrq_emit_set_syms_kernel<TX_DWORD>,
                                  nrq_emit_set_syms_kernel<TX_BYTE>, nrq_emit_set_syms_kernel<TXS_V16_KEY>}; /* [mode] */
+  static const set_fn hkern[5] = {nrq_emit_set_held_syms_kernel<TX_V16>, nrq_emit_set_held_syms_kernel<TX_V16_SHIFT>,
+                                  nrq_emit_set_held_syms_kernel<TX_DWORD>, nrq_emit_set_held_syms_kernel<TX_BYTE>,
+                                  nrq_emit_set_held_syms_kernel<TXS_V16_KEY>}; /* [mode] */
   if (!set) return -1;
   nrq_ctx *ctx = set->ctx;
   const char *who = "nrq_txset_emit_syms";
-  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0, kinl = (flags & NRQ_TX_KEY_INLINE) != 0;
-  if (flags & NRQ_TX_HELD) return fail(ctx, -1, "%s: NRQ_TX_HELD is not offered with packets of several symbols (held symbols are decided per symbol)", who);
-  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_KEY_INLINE)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0, kinl = (flags & NRQ_TX_KEY_INLINE) != 0, held = (flags & NRQ_TX_HELD) != 0;
+  if (held) { /* (as nrq_tx_emit_syms on a sender: where no member reads a reception the flag could do nothing; an empty set and
+               * n = 0 included -- the refusal comes before their early return) */
+    bool relay = false;
+    for (const txset_member &m : set->mem) relay = relay || m.tx->relay;
+    if (!relay) return fail(ctx, -1, "%s: NRQ_TX_HELD needs a relay among the members (a sender holds no reception)", who);
+  }
+  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_HELD | NRQ_TX_KEY_INLINE)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
   if (kinl && !inl) return fail(ctx, -1, "%s: NRQ_TX_KEY_INLINE needs NRQ_TX_TAG_INLINE", who);
   if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
   if (n == 0 || set->mem.empty()) return 0;
@@ -6105,12 +6350,12 @@ int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *
   txs_ready rdy;
   txs_call c;
   int mode;
-  const int rc = txset_call_of(set, who, d_keys, d_tags, n, d_pkts, pkt_stride, hdr, false, d_results, &rdy, &c, &mode);
+  const int rc = txset_call_of(set, who, d_keys, d_tags, n, d_pkts, pkt_stride, hdr, held, d_results, &rdy, &c, &mode);
   if (rc) return rc;
   sy_tx y{};
   y.G = G; y.nsym = d_nsym;
   const uint32_t per = 64u / G, waves = (n + per - 1u) / per;
-  hipLaunchKernelGGL(kern[mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, (const txs_tab *)set->tab, rdy,
+  hipLaunchKernelGGL((held ? hkern : kern)[mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, ctx->stream, (const txs_tab *)set->tab, rdy,
                      c, y);
   HIPCHK(ctx, hipGetLastError());
   return 0;

@@ -11,6 +11,7 @@
 #include <numeric>
 #include <vector>
 
+#include "emu_scan.h"
 #include "want_set_body.h"
 
 #define EMU_GUARD 64u /* words behind the nb + 1 counts / offsets that no pass may touch */
@@ -45,21 +46,6 @@ static bool emu_table(uint32_t nmem, const uint32_t *prm, const uint64_t *ptr, i
   }
   t.blk0[nmem] = t.nblk;
   return t.nblk <= INGS_MAX_BLOCKS;
-}
-
-/* nrq_ings_lists_scan_kernel: n entries in place, a run of entries per thread of the one workgroup, a scan over the threads' sums */
-static void emu_scan(uint32_t *cnt, uint32_t n) {
-  uint32_t ps[256];
-  const uint32_t per = (n + 255u) / 256u;
-  for (uint32_t i = 0; i < 256u; i++) {
-    const uint32_t j0 = std::min(n, i * per), j1 = std::min(n, j0 + per);
-    ps[i] = (i ? ps[i - 1u] : 0u) + std::accumulate(cnt + j0, cnt + j1, 0u);
-  }
-  for (uint32_t i = 0; i < 256u; i++) {
-    const uint32_t j0 = std::min(n, i * per), j1 = std::min(n, j0 + per);
-    uint32_t run = i ? ps[i - 1u] : 0u;
-    for (uint32_t j = j0; j < j1; j++) { const uint32_t v = cnt[j]; cnt[j] = run; run += v; }
-  }
 }
 
 /* wn_count_wg */
