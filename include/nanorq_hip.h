@@ -50,6 +50,7 @@ typedef struct nrq_call_stats {
   uint32_t plan_segmented;   /* 1: that run was segmented into parts (the biggest blocks) */
   uint32_t backsub_strip;    /* bytes per strip of the back-substitution kernel after a narrow-strip solve (32 / 16; 0: no split) */
   uint32_t encplan_device;   /* encode: the plan in use was built by the planner kernel (else by the host planner) */
+  uint32_t out_view;         /* decode: jobs of the call launched with the W' image of their lists (nrq_job out_w != 0: no back-substitution) */
 } nrq_call_stats;
 
 /* One context per GPU (one process per GPU: no cross-device state).  `stream` is a hipStream_t the

@@ -35,6 +35,7 @@ GEMU = os.path.join(ROOT, "tests", "emu", "libruns_emu.so")
 JEMU = os.path.join(ROOT, "tests", "emu", "librxset_runs_emu.so")
 NEMU = os.path.join(ROOT, "tests", "emu", "liblaunch_emu.so")
 UEMU = os.path.join(ROOT, "tests", "emu", "libout_lists_emu.so")
+VEMU = os.path.join(ROOT, "tests", "emu", "libout_view_emu.so")
 MODEL = os.path.join(ROOT, "tests", "emu", "libnanorq_model.so")
 ROWS = os.path.join(ROOT, "tests", "gpu", "librows_probe.so")
 
@@ -153,6 +154,12 @@ def build_out_lists_emu(force=False):
     """tests/emu/libout_lists_emu.so: the host's builder of a job's output lists (out_lists.h) behind a C interface; host code as
     it is, no emulation."""
     return _build_emu(UEMU, os.path.join(ROOT, "tests", "emu", "out_lists_emu.cpp"), ("out_lists.h", "rq_math.h"), force)
+
+
+def build_out_view_emu(force=False):
+    """tests/emu/libout_view_emu.so: the host's builder of the out view's image (out_lists.h build_out_w) behind a C interface;
+    host code as it is, no emulation."""
+    return _build_emu(VEMU, os.path.join(ROOT, "tests", "emu", "out_view_emu.cpp"), ("out_lists.h", "plan.h", "rq_math.h"), force)
 
 
 def build_ingest_emu(force=False):
@@ -338,6 +345,7 @@ if __name__ == "__main__":
     build_shape_emu(force="-f" in sys.argv)
     build_launch_emu(force="-f" in sys.argv)
     build_out_lists_emu(force="-f" in sys.argv)
+    build_out_view_emu(force="-f" in sys.argv)
     build_model_lib(force="-f" in sys.argv)
     build_rows_probe(force="-f" in sys.argv)
     build_tools(force="-f" in sys.argv)

@@ -538,6 +538,7 @@ enum {
   pl_tag_pl_final_e = 15,
   pl_tag_pl_need_a = 15,
   pl_tag_pl_need_b = 15,
+  pl_tag_pl_out_w = 15,
   pl_tag_pl_mark_failed = 15,
 };
 
@@ -1739,9 +1740,10 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
     uint32_t plan_bytes = 0;
     std::vector<uint32_t> rowsrc, cptr, orow;
     std::vector<uint16_t> cols;
+    std::vector<uint32_t> wout; /* the out view's image of these lists (plan.h off_wout): appended to the arena */
     int state = 0; /* 0 = nothing to do, 1 = solve, -1 = cannot */
     uint32_t used = 0;
-    size_t off_plan = 0, off_rowsrc = 0, off_cptr = 0, off_row = 0, off_cols = 0;
+    size_t off_plan = 0, off_wout = 0, off_rowsrc = 0, off_cptr = 0, off_row = 0, off_cols = 0;
   };
   std::vector<Prep> prep(nblk);
   const uint32_t pad = p.Kp - K;
@@ -1786,6 +1788,7 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
     }
     build_out_lists(p, reinterpret_cast<const uint16_t *>(pr.plan.p + reinterpret_cast<const nrq_plan_hdr *>(pr.plan.p)->off_colslot),
                     nl, lost, pr.cptr, pr.cols, pr.orow); /* ISI of a source symbol is its ESI */
+    if (!c.inter) build_out_w(pr.plan.p, pr.cptr, pr.cols, pr.wout); /* (before orow[] names rows; needs cptr / cols only) */
     for (uint32_t &g : pr.orow) g = lost[g]; /* (the list stored i-th is that of missing symbol orow[i]: its row) */
     pr.state = 1;
   };
@@ -1825,6 +1828,7 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
     if (pr.state != 1) continue;
     nsolve++;
     pr.off_plan = off;   off = r16(off + pr.plan_bytes);
+    pr.off_wout = off;   off = r16(off + pr.wout.size() * 4); /* (behind the arena: the job's out_w counts from the plan) */
     pr.off_rowsrc = off; off = r16(off + pr.rowsrc.size() * 4);
     pr.off_cptr = off;   off = r16(off + pr.cptr.size() * 4);
     pr.off_row = off;    off = r16(off + pr.orow.size() * 4);
@@ -1858,7 +1862,15 @@ static int decode_host(nrq_ctx *ctx, const DecodeCall &c, const uint8_t *select)
       memcpy(hs + pr.off_cptr, pr.cptr.data(), pr.cptr.size() * 4);
       memcpy(hs + pr.off_row, pr.orow.data(), pr.orow.size() * 4);
       if (!pr.cols.empty()) memcpy(hs + pr.off_cols, pr.cols.data(), pr.cols.size() * 2);
-      const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(hs + pr.off_plan);
+      nrq_plan_hdr *h = reinterpret_cast<nrq_plan_hdr *>(hs + pr.off_plan);
+      if (!pr.wout.empty()) { /* the lists' W' image: no back-substitution for this job (solve_body.h nrq_job_out_view) */
+        memcpy(hs + pr.off_wout, pr.wout.data(), pr.wout.size() * 4);
+        h->off_wout = j.out_w = (uint32_t)(pr.off_wout - pr.off_plan);
+        h->out_n = (uint32_t)pr.orow.size(); h->out_pad = (h->out_n + 63u) & ~63u;
+        h->total_bytes = h->off_wout + (uint32_t)pr.wout.size() * 4u;
+        ctx->stats.out_view++;
+        ctx->stats.plan_bytes += pr.wout.size() * 4;
+      }
       hdrs.push_back(h);
       if (ctx->stats.npiv == 0) {
         ctx->stats.npiv = h->npiv; ctx->stats.u = h->u; ctx->stats.nlev = h->nlev; ctx->stats.nfree = h->nfree;
@@ -2125,6 +2137,7 @@ static int decode_device(nrq_ctx *ctx, const DecodeCall &c, std::vector<uint8_t>
       }
       ctx->stats.xor_ops += hd[b].n_xor_ops;
       ctx->stats.plan_bytes += hd[b].total_bytes;
+      if (hd[b].off_wout) ctx->stats.out_view++; /* (pl_final_d gave the job the same offset as out_w) */
     } else if (hd[b].reserved[0] == PL_FAIL_CAPACITY) {
       if (ctx->tune.prof || ctx->tune.diag) fprintf(stderr, "[NRQ_PROF] block %u: device planner capacity exceeded at planner_body.h:%u (npiv %u u %u nlev %u nrows %u M %u nlost %u)\n", b, hd[b].fail_site, hd[b].npiv, hd[b].u, hd[b].nlev, hd[b].nrows, hd[b].M, c.h_nlost[b]);
       (*fallback)[b] = 1;

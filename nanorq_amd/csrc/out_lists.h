@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <vector>
+#include "plan.h"
 #include "rq_math.h"
 
 /* LT neighbour lists of the symbols to generate, already translated to LDS slots through the plan's
@@ -39,6 +40,27 @@ inline void build_out_lists(const rq_params &p, const uint16_t *colslot, uint32_
     o += m;
   }
   cptr[n] = o;
+}
+
+/* The out view's image of such lists over a host-built plan (plan.h off_wout): word w of list q's row at [w * out_pad + q],
+ * W'_q = XOR of the plan's W rows over the entries of list q that are a pivot's slot, entry for entry as cols[] holds them (an
+ * inactive column's slot adds nothing: ph_park puts the column's value itself there).  Empty when the plan has no inactive column. */
+inline void build_out_w(const uint8_t *plan, const std::vector<uint32_t> &cptr, const std::vector<uint16_t> &cols,
+                        std::vector<uint32_t> &wout) {
+  const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(plan);
+  const uint32_t n = cptr.empty() ? 0u : (uint32_t)cptr.size() - 1u, wpr = h->wpr, opad = (n + 63u) & ~63u;
+  wout.assign((size_t)wpr * opad, 0u);
+  if (!wpr || !n) return;
+  const uint16_t *pivslot = reinterpret_cast<const uint16_t *>(plan + h->off_pivslot);
+  const uint32_t *wt = reinterpret_cast<const uint32_t *>(plan + h->off_wt);
+  std::vector<uint32_t> pivot_of(h->M + h->r2 + 1u, 0xFFFFFFFFu); /* slot -> pivot */
+  for (uint32_t k = 0; k < h->npiv; k++) pivot_of[pivslot[k]] = k;
+  for (uint32_t q = 0; q < n; q++)
+    for (uint32_t e = cptr[q]; e < cptr[q + 1]; e++) {
+      const uint32_t k = pivot_of[cols[e]];
+      if (k == 0xFFFFFFFFu) continue;
+      for (uint32_t w = 0; w < wpr; w++) wout[(size_t)w * opad + q] ^= wt[(size_t)w * h->npiv_pad + k];
+    }
 }
 
 #endif

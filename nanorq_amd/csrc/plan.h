@@ -176,6 +176,23 @@ typedef struct nrq_plan_hdr {
   uint32_t need_pad;    /* stride (in needed pivots) of off_wneed, multiple of 64 */
   uint32_t off_needslot;/* u16[nneed]: slot of needed pivot j */
   uint32_t off_wneed;   /* u32[wpr*need_pad]: word w of needed pivot j's W row at [w*need_pad + j] (the form of off_wt) */
+  /* The out view of the same decodes: W folded into the missing symbols.  A missing symbol is the XOR of C(c) over its LT list, and
+   * C(c) = Y_c ^ W_c * C_u for a pivot column, C_u[x] for an inactive one (parked in its slot by ph_park), so with
+   *     W'_q = XOR of W_c over the entries of list q that are a pivot's slot
+   * symbol q is the walk of its list over the slots as the dense stage leaves them (Y_c at the pivots) XOR W'_q * C_u: NO pivot is
+   * back-substituted, and the table lookups run once per missing symbol (a tenth of the pivots at 10 % loss, where the needed-pivot
+   * view covers a third).  W'_q is summed over the list's own entries in out_slots[], entry for entry, so whatever ph_store's walk
+   * reads -- a repeated slot included -- cancels the same way in both.  The image belongs to the LISTS, in their stored order, not
+   * to the plan: a job points to it with nrq_job::out_w, and a job that brings other lists, or these in another order, runs on the
+   * needed-pivot view or the full back-substitution.  off_wout == 0: none (encode plans, plans with intermediate symbols asked
+   * for, an arena without room for it -- no failure: the needed-pivot view serves).  Host-built plans carry the image behind the
+   * arena the host planner returns (nrq_device.hip); the device planner fills it in pl_out_w, or nrq_wt_kernel after a
+   * segmented run, for which the header also says where the lists lie. */
+  uint32_t off_wout;    /* u32[wpr*out_pad]: word w of list q's row W'_q at [w*out_pad + q] (the form of off_wt); padding words zero */
+  uint32_t out_pad;     /* stride (in lists) of off_wout: (lists + 63) & ~63 */
+  uint32_t out_n;       /* lists the image covers (the job's nout) */
+  uint32_t off_out_cptr;  /* device planner: the job's out_cptr[] and out_slots[] inside this arena (0 in host-built plans, whose */
+  uint32_t off_out_slots; /* lists travel beside the arena) */
 } nrq_plan_hdr;
 /* (emu_device_plan and plan_header read the header from the first 256 bytes of a plan) */
 #ifdef __cplusplus

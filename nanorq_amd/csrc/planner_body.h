@@ -318,7 +318,8 @@ SB_HD uint32_t pl_arena_bound(uint32_t L, uint32_t Mcap, uint32_t ucap, uint32_t
   else ops += ((ucap + 3u) & ~3u) * ((PL_LOWCAP + 31u) / 32u) + 16u; /* (or as words of a bit matrix) */
   uint32_t b = 256u + L * 2u * 3u + (L + 16u) * 2u + ucap * 2u * 4u + ucap * 4u * 2u + PL_MAXH * ucap +
                NRQ_MAX_FREE * PL_MAXH + wprcap * npad * 4u * 2u + npad * 2u + 16u + ops * 4u +
-               Mcap * 4u + (nlost_cap + 1u) * 8u + nlost_cap * PL_PATCH_STRIDE * 2u + 1024u;
+               Mcap * 4u + (nlost_cap + 1u) * 8u + nlost_cap * PL_PATCH_STRIDE * 2u + 1024u +
+               wprcap * ((nlost_cap + 63u) & ~63u) * 4u + 16u; /* (the out view: plan.h off_wout) */
   return pl_r16(b);
 }
 
@@ -3113,6 +3114,12 @@ SB_HD bool pl_need_wanted(const PlanCtx &c) {
   return (c.job.mode & 0xFFu) == 0u && c.job.inter == 0u && c.sh->npiv != 0u &&
          (c.sh->M + 31u) / 32u * 4u <= 4u * c.qcap;
 }
+/* The out view (plan.h off_wout): for the same decodes, whatever the size; its arena offset and stride wait in part()[PL_OUTW],
+ * part()[PL_OUTW + 1] ([0, 8): arena offsets, [8, 24): pl_need_a's counts) */
+#define PL_OUTW 24u
+SB_HD bool pl_out_wanted(const PlanCtx &c) {
+  return (c.job.mode & 0xFFu) == 0u && c.job.inter == 0u && c.sh->npiv != 0u && c.sh->wpr != 0u && c.job.nlost != 0u;
+}
 SB_HD uint32_t *pl_need_marks(const PlanCtx &c) { uint32_t *q = reinterpret_cast<uint32_t *>(c.claim_l()); PL_ASSUME_LDS(q); return q; }
 template <int Z> SB_HD void pl_final_a(PlanCtx &c, uint32_t tid, uint32_t nt) {
   pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
@@ -3170,6 +3177,11 @@ template <int Z> SB_HD void pl_final_b(PlanCtx &c, uint32_t tid, uint32_t nt) {
     c.part()[5] = need ? o : 0u; if (need) o = pl_r16(o + sh->tmp0 * 2u);                 /* needslot (room for every pivot) */
     c.part()[6] = need ? o : 0u; if (need) o = pl_r16(o + sh->wpr * sh->tmp0 * 4u);       /* wneed */
     c.part()[7] = need;
+    /* (the out view comes last and only if there is room: without it the needed-pivot view serves, no failure) */
+    const uint32_t opad = (nl + 63u) & ~63u, oend = pl_r16(o + sh->wpr * opad * 4u);
+    const bool outw = pl_out_wanted(c) && o <= c.job.arena_cap && oend <= c.job.arena_cap;
+    c.part()[PL_OUTW] = outw ? o : 0u; c.part()[PL_OUTW + 1u] = outw ? opad : 0u;
+    if (outw) o = oend;
     sh->arena_top = o;
     if (o > c.job.arena_cap) (sh->fail_site = __LINE__, sh->status = PL_FAIL_CAPACITY);
     sh->tmp1 = 0; /* (sum of the level groups' op counts: pl_final_c) */
@@ -3187,6 +3199,11 @@ template <int Z> SB_HD void pl_final_c(PlanCtx &c, uint32_t tid, uint32_t nt) {
       const uint32_t w = e / stride, k = e - w * stride;
       wt[e] = k < sh->npiv ? c.wrows[(size_t)c.pivslot[k] * wpr + w] : 0u;
     }
+  /* the out view sums W rows over the slots of whole LT lists, and a list may name the slot an inactive column is parked in: the row
+   * of the workspace that goes with such a slot holds the leftover row's coefficients, not a pivot's W row.  Nobody reads them
+   * after the dense stage: cleared, so that a parked column adds nothing to W' (pl_out_w, pl_wt_fill) */
+  if (c.part()[PL_OUTW])
+    for (uint32_t e = tid; e < (p.L - sh->npiv) * wpr; e += nt) c.wrows[(size_t)c.uslot[e / wpr] * wpr + e % wpr] = 0u;
   uint32_t *rowsrc = reinterpret_cast<uint32_t *>(c.arena + c.part()[1]);
   pl_for_batched(tid, nt, sh->M, [&](uint32_t r) { return (uint32_t)c.patch_of[r]; }, [&](uint32_t r, uint32_t pi) {
     uint32_t v = NRQ_ROW_ZERO;
@@ -3290,6 +3307,10 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
   h.off_freex = c.off_freex; h.off_hinv = c.off_hinv; h.off_colslot = c.off_colslot; h.off_pivof = c.off_pivof;
   h.off_uslot = c.off_uslot; h.total_bytes = sh->arena_top;
   h.off_augt = sh->off_augt; h.lpr = pl_bin_in_stream(p.L) ? 0u : sh->lpr; h.aug_stride = sh->aug_stride;
+  if (!sh->status && c.part()[PL_OUTW]) { /* (filled by pl_out_w, or by pl_wt_fill after a segmented run) */
+    h.off_wout = c.part()[PL_OUTW]; h.out_pad = c.part()[PL_OUTW + 1u]; h.out_n = c.job.nlost;
+    h.off_out_cptr = c.part()[2]; h.off_out_slots = c.part()[4];
+  }
   if (!sh->status) {
     const uint32_t nl = c.job.nlost;
     uint32_t *cptr = reinterpret_cast<uint32_t *>(c.arena + c.part()[2]);
@@ -3312,8 +3333,42 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
       j.out_row = (uint64_t)(uintptr_t)(c.arena + c.part()[3]);
       j.out_slots = (uint64_t)(uintptr_t)(c.arena + c.part()[4]);
       j.nout = c.job.nlost;
+      j.out_w = c.part()[PL_OUTW]; /* (these lists' W' image, if the plan has one) */
     }
     *c.jobout = j;
+  }
+}
+
+/* The out view's image (plan.h off_wout), lists q0, q0 + step, ... of the out_pad the image has room for: W'_q = XOR of the workspace's
+ * W rows over the entries of list q, entry for entry as out_slots[] holds them (the rows of the parked columns' slots are zero by now:
+ * pl_final_c), word w at [w * out_pad + q]; zeros behind the last list.  A batch of entries at a time: their slots, then their rows'
+ * words, in flight together. */
+SB_HD void pl_wout_fill(uint32_t *wout, const uint32_t *cptr, const uint16_t *osl, const uint32_t *wrows, uint32_t wpr, uint32_t nout,
+                        uint32_t opad, uint32_t q0, uint32_t step) {
+  constexpr uint32_t WB = 8, EB = 4; /* words of a row and entries a trip */
+  for (uint32_t q = q0; q < opad; q += step) {
+    const uint32_t a = q < nout ? cptr[q] : 0u, b = q < nout ? cptr[q + 1u] : 0u;
+    for (uint32_t w0 = 0; w0 < wpr; w0 += WB) {
+      uint32_t acc[WB];
+#pragma unroll
+      for (uint32_t j = 0; j < WB; j++) acc[j] = 0u;
+      for (uint32_t e = a; e < b; e += EB) {
+        uint32_t s[EB], v[EB][WB];
+#pragma unroll
+        for (uint32_t i = 0; i < EB; i++) s[i] = osl[e + i < b ? e + i : e];
+#pragma unroll
+        for (uint32_t i = 0; i < EB; i++)
+#pragma unroll
+          for (uint32_t j = 0; j < WB; j++) v[i][j] = (e + i < b && w0 + j < wpr) ? wrows[(size_t)s[i] * wpr + w0 + j] : 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < EB; i++)
+#pragma unroll
+          for (uint32_t j = 0; j < WB; j++) acc[j] ^= v[i][j];
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < WB; j++)
+        if (w0 + j < wpr) wout[(size_t)(w0 + j) * opad + q] = acc[j];
+    }
   }
 }
 
@@ -3329,6 +3384,9 @@ SB_HD void pl_wt_fill(uint8_t *arena, const uint32_t *wrows, uint32_t e0, uint32
     const uint32_t w = e / stride, k = e - w * stride;
     wt[e] = k < npiv ? wrows[(size_t)pivslot[k] * wpr + w] : 0u;
   }
+  if (h->off_wout) /* (the out view's image: pl_out_w left it to this pass) */
+    pl_wout_fill(reinterpret_cast<uint32_t *>(arena + h->off_wout), reinterpret_cast<const uint32_t *>(arena + h->off_out_cptr),
+                 reinterpret_cast<const uint16_t *>(arena + h->off_out_slots), wrows, wpr, h->out_n, h->out_pad, e0, step);
   if (!h->off_needslot) return;
   /* (the needed-pivot view's W rows: pl_need_b left them to this pass) */
   const uint32_t pad = h->need_pad, nneed = h->nneed;
@@ -3437,6 +3495,15 @@ template <int Z> SB_HD void pl_need_b(PlanCtx &c, uint32_t tid, uint32_t nt) {
       ho->nneed = nneed; ho->need_pad = pad; ho->off_needslot = c.part()[5]; ho->off_wneed = c.part()[6];
     }
   }
+}
+
+/* The out view's image (plan.h off_wout), from the lists pl_final_e wrote: a list per thread (a segmented run leaves it to
+ * nrq_wt_kernel, pl_wt_fill, where the W rows are complete) */
+template <int Z> SB_HD void pl_out_w(PlanCtx &c, uint32_t tid, uint32_t nt) {
+  pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
+  if (sh->status || !c.part()[PL_OUTW] || sh->defer_wt) return;
+  pl_wout_fill(reinterpret_cast<uint32_t *>(c.arena + c.part()[PL_OUTW]), reinterpret_cast<const uint32_t *>(c.arena + c.part()[2]),
+               reinterpret_cast<const uint16_t *>(c.arena + c.part()[4]), c.wrows, sh->wpr, c.job.nlost, c.part()[PL_OUTW + 1u], tid, nt);
 }
 
 #endif /* NRQ_PLANNER_BODY_H */

@@ -236,5 +236,6 @@
     PL_PHASE(pl_final_e);
     PL_PHASE(pl_need_a); /* (the needed-pivot view: device-planned decodes without intermediate symbols) */
     PL_PHASE(pl_need_b);
+    PL_PHASE(pl_out_w); /* (the out view: W folded into the missing symbols' lists) */
   }
 }

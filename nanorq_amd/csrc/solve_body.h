@@ -62,8 +62,12 @@ typedef struct nrq_job {
   uint64_t out_slots;/* u16[]: slots (plan colslot[] of the LT neighbours) XORed into each generated symbol */
   uint64_t out_row;  /* u32[nout]: destination row in `out` */
   uint32_t nout;
-  uint32_t pad;
+  uint32_t out_w;    /* byte offset from `plan` of the W' image of THESE lists (plan.h off_wout), 0: none.  It belongs to the lists:
+                      * a job that brings lists of its own, or the plan's in another order, has 0 here */
 } nrq_job;
+/* A job whose lists come with their W' image and that wants no intermediate symbols: no pivot is back-substituted, ph_store adds
+ * W'_q * C_u to the walk of list q instead.  (The split solve of narrow strips does not look at out_w: it back-substitutes all.) */
+SB_HD bool nrq_job_out_view(const nrq_job *job) { return job->out_w != 0u && job->inter == 0; }
 
 /* true in every lane of the wave if the condition holds in one (a CPU emulation runs a thread at a time: the thread's own word --
  * unless it brings a NRQ_WAVE_ANY of its own that knows the wave's, tests/emu/wave_emu.h) */
@@ -1477,6 +1481,100 @@ template <int WB, int G = 1> SB_HD void ph_tables(const StripCtx<WB, G> &c, uint
   }
 }
 
+/* One word of a bit row over the inactive columns: acc ^= the eight entries its nibbles name in the tables of word w.  The body of
+ * both users of the tables: backsub_one (a pivot's W row) and ph_store (a generated symbol's W' row, plan.h off_wout). */
+template <int WB, int G = 1, bool FAST = true>
+SB_HD void t4_word(SV<WB> &acc, const uint8_t *t4, uint32_t w, uint32_t bits) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (WB == 16 && G == 1) {
+    /* the phase is bound by VALU issue and LDS reads about equally (the 4 XORs per lookup are a given): both
+     * nibbles of every byte are brought to "16 * nibble" in place with three operations per word, and a table
+     * address is ONE byte-select add (the compiler's own sequence is shift, mask, add per lookup).
+     * 8-bit tables in passes were measured too: half the lookups, but 64 lanes then read 64 different entries
+     * instead of at most 16, and the phase becomes LDS-bandwidth bound at 1.6x the time. */
+    uint32_t odd = bits & 0xF0F0F0F0u, even = (bits << 4) & 0xF0F0F0F0u;
+    asm volatile("" : "+v"(odd), "+v"(even)); /* keep the packed form */
+    /* all eight lookups of the word in flight together, each address one byte-select add with the table's offset in the
+     * instruction's immediate field, then the 32 dwords folded three at a time (v_bitop3_b32: a ^ b ^ c).  As it was -- four
+     * lookups in flight, then four one by one, each a full LDS round trip the wave waited for, and three VALU operations per
+     * address -- the phase was bound by those round trips (47 k clocks per strip at K=8192 against 33 k of LDS time). */
+    if constexpr (FAST) {
+    const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 2048u; /* (the word's tables; the lookup's own offset q * 256 is an immediate) */
+    uint4 d[8];
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint4, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 256u);
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q += 2) {
+      acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
+      acc.w[2] = nrq_xor3(acc.w[2], d[q].z, d[q + 1].z); acc.w[3] = nrq_xor3(acc.w[3], d[q].w, d[q + 1].w);
+    }
+    } else { /* (the register-lean form of the small workgroups) */
+      const uint32_t tb = (uint32_t)(uintptr_t)t4;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+      const uint32_t a = t4_addr(tb, (q & 1u) ? odd : even, q >> 1) + (w * 8u + q) * 256u;
+      const uint4 v = *NRQ_LDSP(uint4, a);
+      acc.w[0] ^= v.x; acc.w[1] ^= v.y; acc.w[2] ^= v.z; acc.w[3] ^= v.w;
+      if (q == 3) NRQ_SCHED_FENCE();
+    }
+    }
+    NRQ_SCHED_FENCE();
+    return;
+  }
+  if constexpr (WB == 8 && G == 1) {
+    /* the same for 8-byte strips (blocks whose 16-byte image does not fit the LDS: K from ~8500 on): table entries of 8
+     * bytes, so a nibble is brought to "8 * nibble" in place and a word's tables are 1 KB */
+    uint32_t odd = (bits >> 1) & 0x78787878u, even = (bits << 3) & 0x78787878u;
+    asm volatile("" : "+v"(odd), "+v"(even));
+    const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 1024u;
+    uint2 d[8];
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint2, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 128u);
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q += 2) {
+      acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
+    }
+    NRQ_SCHED_FENCE();
+    return;
+  }
+  if constexpr (WB == 12 && G == 1) {
+    /* 12-byte strips: entries 16 bytes apart (t4_get), looked up like the 16-byte strip's */
+    uint32_t odd = bits & 0xF0F0F0F0u, even = (bits << 4) & 0xF0F0F0F0u;
+    asm volatile("" : "+v"(odd), "+v"(even));
+    const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 2048u;
+    uint4 d[8];
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint4, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 256u);
+    uint32_t pad = 0; /* (the entries' fourth dword, zero: used, so that the read stays a ds_read_b128 -- left to itself the compiler
+                       * narrows it to ds_read_b96, which this LDS serves at half the rate: the phase took 116 k clocks against
+                       * 68 k with three dword reads per entry) */
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q += 2) {
+      acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
+      acc.w[2] = nrq_xor3(acc.w[2], d[q].z, d[q + 1].z); pad = nrq_xor3(pad, d[q].w, d[q + 1].w);
+    }
+    asm volatile("" : : "v"(pad));
+    NRQ_SCHED_FENCE();
+    return;
+  }
+#endif
+#pragma unroll
+  for (uint32_t q = 0; q < 8; q++) {
+    const uint32_t nib = (bits >> (4u * q)) & 15u;
+    SV<WB> t = t4_get<WB, G>(t4, (w * 8u + q) * 16u + nib);
+    sv_xor<WB>(acc, t);
+    if (q == 3) NRQ_SCHED_FENCE(); /* 4 lookups in flight are enough; hoisting all NW*8 of them costs ~100 more registers */
+  }
+  NRQ_SCHED_FENCE();
+}
+template <int WB, int NW, int G = 1, bool FAST = true>
+SB_HD void t4_row(SV<WB> &acc, const uint8_t *t4, const uint32_t (&bitsw)[NW], uint32_t wpr) {
+#pragma unroll
+  for (uint32_t w = 0; w < (uint32_t)NW; w++) {
+    if (w >= wpr) break; /* tables exist for wpr*8 groups only */
+    t4_word<WB, G, FAST>(acc, t4, w, bitsw[w]);
+  }
+}
 /* phase 5b: back substitution C(pivot k) = Y_k ^ W_k * C_u.  Two pivots per trip with separate
  * register sets: the W words of the second are in flight while the first does its table lookups
  * (no register hand-over between trips, so the compiler can leave the loads outstanding). */
@@ -1484,92 +1582,7 @@ template <int WB, int NW, int G = 1, bool FAST = true>
 SB_HD void backsub_one(const StripCtx<WB, G> &c, const uint8_t *t4, uint32_t slot, const uint32_t (&bitsw)[NW],
                        uint32_t wpr) {
   SV<WB> acc = lds_get<WB, G>(c.slots(), slot);
-#pragma unroll
-  for (uint32_t w = 0; w < (uint32_t)NW; w++) {
-    if (w >= wpr) break; /* tables exist for wpr*8 groups only */
-    const uint32_t bits = bitsw[w];
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (WB == 16 && G == 1) {
-      /* the phase is bound by VALU issue and LDS reads about equally (the 4 XORs per lookup are a given): both
-       * nibbles of every byte are brought to "16 * nibble" in place with three operations per word, and a table
-       * address is ONE byte-select add (the compiler's own sequence is shift, mask, add per lookup).
-       * 8-bit tables in passes were measured too: half the lookups, but 64 lanes then read 64 different entries
-       * instead of at most 16, and the phase becomes LDS-bandwidth bound at 1.6x the time. */
-      uint32_t odd = bits & 0xF0F0F0F0u, even = (bits << 4) & 0xF0F0F0F0u;
-      asm volatile("" : "+v"(odd), "+v"(even)); /* keep the packed form */
-      /* all eight lookups of the word in flight together, each address one byte-select add with the table's offset in the
-       * instruction's immediate field, then the 32 dwords folded three at a time (v_bitop3_b32: a ^ b ^ c).  As it was -- four
-       * lookups in flight, then four one by one, each a full LDS round trip the wave waited for, and three VALU operations per
-       * address -- the phase was bound by those round trips (47 k clocks per strip at K=8192 against 33 k of LDS time). */
-      if constexpr (FAST) {
-      const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 2048u; /* (the word's tables; the lookup's own offset q * 256 is an immediate) */
-      uint4 d[8];
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint4, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 256u);
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q += 2) {
-        acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
-        acc.w[2] = nrq_xor3(acc.w[2], d[q].z, d[q + 1].z); acc.w[3] = nrq_xor3(acc.w[3], d[q].w, d[q + 1].w);
-      }
-      } else { /* (the register-lean form of the small workgroups) */
-        const uint32_t tb = (uint32_t)(uintptr_t)t4;
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q++) {
-        const uint32_t a = t4_addr(tb, (q & 1u) ? odd : even, q >> 1) + (w * 8u + q) * 256u;
-        const uint4 v = *NRQ_LDSP(uint4, a);
-        acc.w[0] ^= v.x; acc.w[1] ^= v.y; acc.w[2] ^= v.z; acc.w[3] ^= v.w;
-        if (q == 3) NRQ_SCHED_FENCE();
-      }
-      }
-      NRQ_SCHED_FENCE();
-      continue;
-    }
-    if constexpr (WB == 8 && G == 1) {
-      /* the same for 8-byte strips (blocks whose 16-byte image does not fit the LDS: K from ~8500 on): table entries of 8
-       * bytes, so a nibble is brought to "8 * nibble" in place and a word's tables are 1 KB */
-      uint32_t odd = (bits >> 1) & 0x78787878u, even = (bits << 3) & 0x78787878u;
-      asm volatile("" : "+v"(odd), "+v"(even));
-      const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 1024u;
-      uint2 d[8];
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint2, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 128u);
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q += 2) {
-        acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
-      }
-      NRQ_SCHED_FENCE();
-      continue;
-    }
-    if constexpr (WB == 12 && G == 1) {
-      /* 12-byte strips: entries 16 bytes apart (t4_get), looked up like the 16-byte strip's */
-      uint32_t odd = bits & 0xF0F0F0F0u, even = (bits << 4) & 0xF0F0F0F0u;
-      asm volatile("" : "+v"(odd), "+v"(even));
-      const uint32_t tbw = (uint32_t)(uintptr_t)t4 + w * 2048u;
-      uint4 d[8];
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q++) d[q] = *NRQ_LDSP(uint4, t4_addr(tbw, (q & 1u) ? odd : even, q >> 1) + q * 256u);
-      uint32_t pad = 0; /* (the entries' fourth dword, zero: used, so that the read stays a ds_read_b128 -- left to itself the compiler
-                         * narrows it to ds_read_b96, which this LDS serves at half the rate: the phase took 116 k clocks against
-                         * 68 k with three dword reads per entry) */
-#pragma unroll
-      for (uint32_t q = 0; q < 8; q += 2) {
-        acc.w[0] = nrq_xor3(acc.w[0], d[q].x, d[q + 1].x); acc.w[1] = nrq_xor3(acc.w[1], d[q].y, d[q + 1].y);
-        acc.w[2] = nrq_xor3(acc.w[2], d[q].z, d[q + 1].z); pad = nrq_xor3(pad, d[q].w, d[q + 1].w);
-      }
-      asm volatile("" : : "v"(pad));
-      NRQ_SCHED_FENCE();
-      continue;
-    }
-#endif
-#pragma unroll
-    for (uint32_t q = 0; q < 8; q++) {
-      const uint32_t nib = (bits >> (4u * q)) & 15u;
-      SV<WB> t = t4_get<WB, G>(t4, (w * 8u + q) * 16u + nib);
-      sv_xor<WB>(acc, t);
-      if (q == 3) NRQ_SCHED_FENCE(); /* 4 lookups in flight are enough; hoisting all NW*8 of them costs ~100 more registers */
-    }
-    NRQ_SCHED_FENCE();
-  }
+  t4_row<WB, NW, G, FAST>(acc, t4, bitsw, wpr);
   lds_put<WB, G>(c.slots(), slot, acc);
 }
 
@@ -1630,8 +1643,10 @@ SB_HD void backsub_fixed(const StripCtx<WB, G> &c, bool need, uint32_t tid, uint
 
 /* A pivot's value is Y_k ^ W_k * C_u: it depends on no other pivot by now, so a job that reads only the out lists' slots (no
  * intermediate symbols) computes only the pivots the plan names as needed -- a third of them at 10 % loss -- and leaves the
- * others' slots as they are (ph_park still writes all u inactive columns) */
+ * others' slots as they are (ph_park still writes all u inactive columns).  And when the job's lists come with their W' image
+ * (nrq_job_out_view) no pivot at all: every pivot slot keeps Y_k, and ph_store applies W_k * C_u summed over a whole list. */
 template <int WB, int G = 1, bool FAST = true> SB_HD void ph_backsub(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt) {
+  if (nrq_job_out_view(c.job)) return; /* (uniform) */
   const uint32_t wpr = c.h->wpr;
   const bool need = c.job->inter == 0 && c.h->off_needslot != 0u; /* (chosen once per strip) */
   if (wpr <= 4) backsub_fixed<WB, 4, G, FAST>(c, need, tid, nt);
@@ -1718,25 +1733,36 @@ SB_HD void store_trip(const NRQ_GAS uint16_t *osl, uint32_t e, uint32_t end, uin
 SB_HD uint32_t store_slot(const uint32_t (&raw)[NRQ_STORE_TRIP / 2u], uint32_t k, uint32_t e, uint32_t end, uint32_t zero_at) {
   return e + k < end ? ((raw[k / 2u] >> (16u * (k & 1u))) & 0xFFFFu) + NRQ_SCRATCH : zero_at;
 }
-template <int WB, int G = 1, bool FAST = true> SB_HD void ph_store(const StripCtx<WB, G> &c, NRQ_GAS uint8_t *ostage, uint32_t tid, uint32_t nt) {
-  constexpr int STB = 8;
-  const NRQ_GAS uint16_t *colslot = c.template arr<uint16_t>(c.h->off_colslot);
-  const uint32_t L = c.h->L, ni = c.job->inter ? L : 0u;
-  for (uint32_t base = tid; base < ni; base += STB * nt) {
-    uint32_t sl[STB];
-#pragma unroll
-    for (int q = 0; q < STB; q++) {
-      uint32_t col = base + (uint32_t)q * nt;
-      sl[q] = col < L ? colslot[col] : 0u;
-    }
-#pragma unroll
-    for (int q = 0; q < STB; q++) {
-      uint32_t col = base + (uint32_t)q * nt;
-      if (col < L) g_put_stream<WB>(ostage + (size_t)col * (WB * G), WB, lds_get<WB, G>(c.slots(), sl[q]));
-    }
-  }
+/* The generated symbols of ph_store.  view: the job's lists come with their W' image (nrq_job_out_view; uniform): the slots of the
+ * pivots hold Y_k, not C(k), and symbol q is the walk of its list XOR W'_q * C_u, the row's words looked up in the tables of
+ * ph_tables (which stay where they are until the strip's last store: nothing in this phase writes LDS) by the per-word body of the
+ * back-substitution.  The row's words are requested together behind the walk, eight to a trip to L2 (W rows of up to 256 inactive
+ * columns: one trip).
+ * Measured on MI355X, headline shape (docs/LAB_NOTES.md): this path costs the ENCODE solve, which never takes it, through the
+ * registers of the whole kernel.  A copy of the loop per class of row width, as ph_backsub has them: 38 registers spilled instead of
+ * 34, twice the scalar ones, encode solve +0.3 ms; one loop for jobs with a view and one for those without, words requested before
+ * the walk: 36, +0.15 ms; this form -- one loop, the flag tested at run time, words behind the walk: 36, +0.09 ms, the decode the
+ * same in all three. */
+template <int WB, int G, bool FAST> SB_HD void store_gen(const StripCtx<WB, G> &c, NRQ_GAS uint8_t *ostage, uint32_t ni, bool view, uint32_t tid, uint32_t nt) {
   const NRQ_GAS uint32_t *cptr = gptr<uint32_t>(c.job->out_cptr);
   const NRQ_GAS uint16_t *osl = gptr<uint16_t>(c.job->out_slots);
+  const uint32_t wpr = c.h->wpr, nlist = c.job->nout, opad = (nlist + 63u) & ~63u;
+  const NRQ_GAS uint32_t *wout = gptr<uint32_t>(c.job->plan + (view ? c.job->out_w : 0u));
+  const uint8_t *t4 = c.t4();
+  /* acc ^= W'_q * C_u (the image is read for q < nout only; a lane without a list looks up the tables' zero entries) */
+  auto w_apply = [&](uint32_t q, SV<WB> &acc) {
+    if (!view) return;
+    for (uint32_t w0 = 0; w0 < wpr; w0 += 8u) {
+      uint32_t wb[8];
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; j++) wb[j] = (w0 + j < wpr && q < nlist) ? wout[(size_t)(w0 + j) * opad + q] : 0u;
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; j++) {
+        if (w0 + j >= wpr) break; /* tables exist for wpr*8 groups only */
+        t4_word<WB, G, FAST>(acc, t4, w0 + j, wb[j]);
+      }
+    }
+  };
   if constexpr (FAST) {
   /* A generated symbol per thread and pass: its list bounds (fetched a pass ahead), then the slot numbers NRQ_STORE_CHUNK at a
    * time in one trip, then the strips from LDS -- ALL of the chunk's, unconditionally: an entry beyond the end of the list reads
@@ -1776,6 +1802,7 @@ template <int WB, int G = 1, bool FAST = true> SB_HD void ph_store(const StripCt
       }
       e += TR;
     }
+    w_apply(q, acc);
     if (q < nout) g_put_stream<WB>(ostage + (size_t)(ni + q) * (WB * G), WB, acc);
   }
   } else {
@@ -1801,9 +1828,29 @@ template <int WB, int G = 1, bool FAST = true> SB_HD void ph_store(const StripCt
         if (sl[k] != NRQ_NOSLOT) sv_xor<WB>(acc, lds_get<WB, G>(c.slots(), sl[k]));
       e += CH;
     }
+    w_apply(q, acc);
     g_put_stream<WB>(ostage + (size_t)(ni + q) * (WB * G), WB, acc);
   }
   }
+}
+template <int WB, int G = 1, bool FAST = true> SB_HD void ph_store(const StripCtx<WB, G> &c, NRQ_GAS uint8_t *ostage, uint32_t tid, uint32_t nt) {
+  constexpr int STB = 8;
+  const NRQ_GAS uint16_t *colslot = c.template arr<uint16_t>(c.h->off_colslot);
+  const uint32_t L = c.h->L, ni = c.job->inter ? L : 0u;
+  for (uint32_t base = tid; base < ni; base += STB * nt) {
+    uint32_t sl[STB];
+#pragma unroll
+    for (int q = 0; q < STB; q++) {
+      uint32_t col = base + (uint32_t)q * nt;
+      sl[q] = col < L ? colslot[col] : 0u;
+    }
+#pragma unroll
+    for (int q = 0; q < STB; q++) {
+      uint32_t col = base + (uint32_t)q * nt;
+      if (col < L) g_put_stream<WB>(ostage + (size_t)col * (WB * G), WB, lds_get<WB, G>(c.slots(), sl[q]));
+    }
+  }
+  store_gen<WB, G, FAST>(c, ostage, ni, nrq_job_out_view(c.job), tid, nt);
 }
 /* phase 6b for the SPLIT solve of narrow strips (big blocks, nrq_device.hip): instead of back-substitution and results,
  * the strip's slot image after the dense stage (element i < M: slot i, i.e. Y of the pivot rows) and the values of the
