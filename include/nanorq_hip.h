@@ -51,6 +51,9 @@ typedef struct nrq_call_stats {
   uint32_t backsub_strip;    /* bytes per strip of the back-substitution kernel after a narrow-strip solve (32 / 16; 0: no split) */
   uint32_t encplan_device;   /* encode: the plan in use was built by the planner kernel (else by the host planner) */
   uint32_t out_view;         /* decode: jobs of the call launched with the W' image of their lists (nrq_job out_w != 0: no back-substitution) */
+  uint32_t need_view;        /* decode without intermediate symbols: device-planned jobs of the call launched on the needed-pivot view (the
+                              * plan has one and no W' image: the back-substitution takes the pivots the missing symbols' lists name) */
+  uint32_t nneed;            /* the needed pivots of the first such job's plan (a subset of its npiv pivots) */
 } nrq_call_stats;
 
 /* One context per GPU (one process per GPU: no cross-device state).  `stream` is a hipStream_t the

@@ -30,7 +30,8 @@ class CallStats(C.Structure):
                 ("wg_waves_per_simd", C.c_uint32), ("host_planned", C.c_uint32), ("movers_aligned", C.c_uint32),
                 ("plan_ahead", C.c_uint32), ("strip_bytes_b", C.c_uint32), ("blocks_b", C.c_uint32),
                 ("plan_wg_threads", C.c_uint32), ("plan_compact_state", C.c_uint32), ("plan_segmented", C.c_uint32),
-                ("backsub_strip", C.c_uint32), ("encplan_device", C.c_uint32), ("out_view", C.c_uint32)]
+                ("backsub_strip", C.c_uint32), ("encplan_device", C.c_uint32), ("out_view", C.c_uint32),
+                ("need_view", C.c_uint32), ("nneed", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

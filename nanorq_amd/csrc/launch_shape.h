@@ -128,7 +128,10 @@ enum KnobKind { KNOB_FLAG, KNOB_NFLAG, KNOB_NUM, KNOB_BOOLNUM, KNOB_WIDEG, KNOB_
   /* (tests) every plan the context builds on the HOST (decode, encode, the capacity fallback) starts with this many columns                            \
    * more inactive (planner_host.h nrq_host_plan_build_forced): same results, a chosen number of inactive columns u -- and with                         \
    * it the back-substitution form the solve runs (solve_body.h: by wpr = ceil(u / 32)).  0: the plans are what they are */                             \
-  K(uint32_t, plan_force_inact, 0, 0, "plan_force_inact", KNOB_NUM)
+  K(uint32_t, plan_force_inact, 0, 0, "plan_force_inact", KNOB_NUM)                                                                                     \
+  /* (tests) device-planned decodes get no out view (plan.h off_wout; bit 10 of nrq_planjob::mode): their jobs run on the                               \
+   * needed-pivot view, as they do when the image finds no room in the arena (planner_body.h pl_final_b) */                                             \
+  K(bool, plan_no_out_view, false, 0, "plan_no_out_view", KNOB_FLAG)
 
 static inline long long knob_norm(KnobKind kind, long long v) {
   switch (kind) {
@@ -462,7 +465,7 @@ struct PlanShape {
   ShapeErr err = SHAPE_OK;
   /* the instance nrq_plan_kernel<wg_threads, compact> (nrq_call_stats::plan_wg_threads, plan_compact_state, plan_segmented) */
   uint32_t wg_threads = 0, compact = 0, segmented = 0;
-  uint32_t mode = 0;                /* nrq_planjob::mode, bit 8: segmented run, bit 9: entry pass by nrq_wentry_kernel */
+  uint32_t mode = 0;                /* nrq_planjob::mode, bit 8: segmented run, bit 9: entry pass by nrq_wentry_kernel, bit 10: no out view (tests) */
   uint32_t nparts = 0, parts[3] = {0, 0, 0}; /* the kernel's `seg` argument, launch by launch: everything | 3, (entry pass), 4, (W pass, HDPC fold), 2 */
   uint32_t qcap = 0, lowcap = 0, sh_bytes = 0, dyn_bytes = 0; /* capacities and bytes of the workgroup state; dynamic LDS in front of it */
   /* helper kernels of a segmented run, per block: workgroups and LDS bytes */
@@ -524,7 +527,7 @@ static inline PlanShape plan_shape(const Tuning &t, int ncu, const rq_params &p,
   s.nparts = !seg ? 1u : wentry ? 3u : 2u;
   if (seg) { s.parts[0] = wentry ? 3u : 1u; s.parts[1] = wentry ? 4u : 2u; s.parts[2] = 2u; }
   s.segmented = seg ? 1u : 0u;
-  s.mode = seg ? (t.no_wentry ? 0x100u : 0x300u) : 0u;
+  s.mode = (seg ? (t.no_wentry ? 0x100u : 0x300u) : 0u) | (t.plan_no_out_view ? PL_MODE_NO_OUTW : 0u);
   if (seg && (tiny_wg || small_wg || !hbm_state)) s.err = SHAPE_PLAN_SEGMENTED;
   s.wg_threads = tiny_wg ? (uint32_t)PL_NT_TINY : small_wg ? (uint32_t)PL_NT_MIN : (uint32_t)PL_NT;
   /* (the state stays in HBM; plan_wrong_instance names this instance for blocks whose state does not) */

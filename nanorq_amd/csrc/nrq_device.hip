@@ -2138,6 +2138,9 @@ static int decode_device(nrq_ctx *ctx, const DecodeCall &c, std::vector<uint8_t>
       ctx->stats.xor_ops += hd[b].n_xor_ops;
       ctx->stats.plan_bytes += hd[b].total_bytes;
       if (hd[b].off_wout) ctx->stats.out_view++; /* (pl_final_d gave the job the same offset as out_w) */
+      else if (hd[b].off_needslot && !c.inter) { /* (the back-substitution of this job takes the needed-pivot view: solve_body.h) */
+        if (ctx->stats.need_view++ == 0) ctx->stats.nneed = hd[b].nneed;
+      }
     } else if (hd[b].reserved[0] == PL_FAIL_CAPACITY) {
       if (ctx->tune.prof || ctx->tune.diag) fprintf(stderr, "[NRQ_PROF] block %u: device planner capacity exceeded at planner_body.h:%u (npiv %u u %u nlev %u nrows %u M %u nlost %u)\n", b, hd[b].fail_site, hd[b].npiv, hd[b].u, hd[b].nlev, hd[b].nrows, hd[b].M, c.h_nlost[b]);
       (*fallback)[b] = 1;

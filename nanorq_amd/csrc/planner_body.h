@@ -573,7 +573,7 @@ template <int Z> SB_HD void pl_init_a(PlanCtx &c, uint32_t tid, uint32_t nt) {
      * instance expects it goes back to the host planner) */
     if (!st && !PL_PEEL_FORM_OK(Z)) { st = PL_FAIL_CAPACITY; sh->fail_site = __LINE__; } else sh->fail_site = 0;
     sh->status = st;
-    sh->defer_wt = c.job.mode >> 8; /* (bit 8 of the job's mode: set by the host for segmented runs) */
+    sh->defer_wt = (c.job.mode >> 8) & 1u; /* (bit 8 of the job's mode: set by the host for segmented runs) */
     sh->overhead = oh;
     sh->M = p.L + oh;
     sh->npatch = st ? 0 : nr;
@@ -3117,8 +3117,9 @@ SB_HD bool pl_need_wanted(const PlanCtx &c) {
 /* The out view (plan.h off_wout): for the same decodes, whatever the size; its arena offset and stride wait in part()[PL_OUTW],
  * part()[PL_OUTW + 1] ([0, 8): arena offsets, [8, 24): pl_need_a's counts) */
 #define PL_OUTW 24u
+#define PL_MODE_NO_OUTW 0x400u /* bit 10 of the job's mode (tests, the option plan_no_out_view): the plan gets no out view */
 SB_HD bool pl_out_wanted(const PlanCtx &c) {
-  return (c.job.mode & 0xFFu) == 0u && c.job.inter == 0u && c.sh->npiv != 0u && c.sh->wpr != 0u && c.job.nlost != 0u;
+  return (c.job.mode & (0xFFu | PL_MODE_NO_OUTW)) == 0u && c.job.inter == 0u && c.sh->npiv != 0u && c.sh->wpr != 0u && c.job.nlost != 0u;
 }
 SB_HD uint32_t *pl_need_marks(const PlanCtx &c) { uint32_t *q = reinterpret_cast<uint32_t *>(c.claim_l()); PL_ASSUME_LDS(q); return q; }
 template <int Z> SB_HD void pl_final_a(PlanCtx &c, uint32_t tid, uint32_t nt) {

@@ -128,7 +128,10 @@ extern "C" void emu_plan_set_caps(uint32_t qcap, uint32_t lowcap) { g_qcap = qca
 static uint32_t g_split = 0; /* run the phase sequence in its two parts (what big blocks do on the GPU) */
 static uint32_t g_nopk = 0;  /* keep the peeling state in the workspace alone (no compact copy in LDS) when it does not fit the LDS */
 static uint32_t g_went = 0;  /* with g_split: part 1 cut once more, the entry pass by two "workgroups" in between (nrq_wentry_kernel) */
-extern "C" void emu_plan_set_mode(uint32_t mode) { g_mode = mode & 0xFFu; g_split = (mode >> 8) & 1u; g_nopk = (mode >> 9) & 1u; g_went = (mode >> 10) & 1u; }
+static uint32_t g_noutw = 0; /* the plan gets no out view (the option plan_no_out_view: PL_MODE_NO_OUTW in the job's mode) */
+extern "C" void emu_plan_set_mode(uint32_t mode) {
+  g_mode = mode & 0xFFu; g_split = (mode >> 8) & 1u; g_nopk = (mode >> 9) & 1u; g_went = (mode >> 10) & 1u; g_noutw = (mode >> 11) & 1u;
+}
 extern "C" int emu_plan(uint32_t K, uint32_t Kp_hint, const uint8_t *kc, const uint32_t *lost, uint32_t nlost,
                         const uint32_t *rep_esi, uint32_t nrep, uint32_t nrep_avail, uint8_t *arena,
                         uint32_t arena_cap, uint32_t lds_dyn_bytes, nrq_job *job_out) {
@@ -151,7 +154,7 @@ extern "C" int emu_plan(uint32_t K, uint32_t Kp_hint, const uint8_t *kc, const u
   job.work = (uint64_t)(uintptr_t)work.data();
   job.arena = (uint64_t)(uintptr_t)arena;
   job.nlost = nlost; job.nrep = nrep; job.arena_cap = arena_cap; job.nrep_avail = nrep_avail;
-  job.mode = g_mode | (g_split << 8) | ((g_split && g_went) ? 0x200u : 0u);
+  job.mode = g_mode | (g_split << 8) | ((g_split && g_went) ? 0x200u : 0u) | (g_noutw ? PL_MODE_NO_OUTW : 0u);
   PlanCtx c;
   pl_ctx_setup(c, p, kc, job, sh, lds_dyn_bytes ? dyn.data() : nullptr, lds_dyn_bytes, Mcap, npcap, ucap, job_out, g_qcap, g_lowcap, PL_NT);
   if (g_nopk) c.pk_cnt = c.pk_un = c.pk_pa = c.pk_vb = nullptr;

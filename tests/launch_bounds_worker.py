@@ -88,6 +88,21 @@ def decode_cases():
                 n += 1
 
 
+def needview_cases():
+    """decodes without intermediate symbols on device plans that have no out view (the option plan_no_out_view): the needed-pivot view
+    (needslot[nneed], wneed at stride need_pad) ends the arena, and the back-substitution of every strip walks it -- 16-, 12- and
+    8-byte strips and 4-byte ones that do not split, every workgroup size"""
+    n = 0
+    for width in ("w16", "w12", "w8", "w4nosplit"):
+        for cname in ("forced", "default", "few", "full768"):
+            for T in (1, 17, 64, 200):
+                K = KS[n % 3]
+                yield dict(kind="decode", K=K, T=T, nblk=(7, 8, 9, 2)[n % 4], loss=(0.05, 0.1, 0.3)[(n // 3) % 3], overhead=(0, 5)[n % 2],
+                           want_inter=False, site="device", bad_block=(None if n % 4 == 3 else (n * 5) % (7, 8, 9, 2)[n % 4]), no_out_view=True,
+                           opts=dict(WIDTHS[width], **CONTEXTS[cname]), mis=(0, 1, 4, 8)[n % 4], tag="needview/%s/%s" % (width, cname))
+                n += 1
+
+
 def big_cases():
     for K, T in ((1024, 129), (3100, 64)):
         for cname in ("forced", "default", "few768"):
@@ -185,7 +200,7 @@ def forced_must(K):
 
 FORCED_KS = (100, 1000, 3000, 5200, 10000, 15000)
 GROUPS = {w: (lambda orc, w=w: sweep(w)) for w in WIDTHS}
-GROUPS.update(decode=lambda orc: decode_cases(), big=lambda orc: big_cases(), seed0=lambda orc: seed0_cases(), edge=edge_cases)
+GROUPS.update(decode=lambda orc: decode_cases(), needview=lambda orc: needview_cases(), big=lambda orc: big_cases(), seed0=lambda orc: seed0_cases(), edge=edge_cases)
 GROUPS.update({"forced_k%d" % K: (lambda orc, K=K: forced_cases(orc, K)) for K in FORCED_KS})
 
 # the forms a group must have reached (checked at its end): keys of the launch record
@@ -200,6 +215,8 @@ MUST = {
     "wide2": [dict(G=2), dict(G=2, multi=1)],
     "wide4": [dict(G=4)],
     "decode": [dict(split=1), dict(split=0), dict(by_block=1), dict(NT=768), dict(NT=64), dict(G=2), dict(skipped=1), dict(AL=1)],
+    "needview": [dict(NT=768, wb=16, split=0), dict(NT=256, wb=16, split=0), dict(NT=64, wb=16, split=0), dict(wb=12, split=0), dict(wb=8, split=0),
+                 dict(wb=4, split=0), dict(skipped=1), dict(skipped=0)],
     "big": [dict(NT=768, wb=16), dict(NT=256, wb=16)],
     "seed0": [dict(NT=64), dict(NT=256)],
     "edge": [dict(NT=768, wb=16, split=0), dict(NT=768, wb=12), dict(NT=768, wb=4, split=0), dict(multi=1, lsub=3, wb=16, NT=64),

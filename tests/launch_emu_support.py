@@ -209,8 +209,9 @@ def run_encode(orc, K, T, nblk, nrep, opts, want_inter=True, side=0, mis=0, expe
     return d
 
 
-def device_plan(K, lost, rep_esis):
-    """the emulated device planner's arena (cut at total_bytes) and where the job's arrays lie in it (pl_final_b)"""
+def device_plan(K, lost, rep_esis, no_out_view=False):
+    """the emulated device planner's arena (cut at total_bytes) and where the job's arrays lie in it (pl_final_b); no_out_view: the
+    plan of a context with the option plan_no_out_view -- the arena ends behind the needed-pivot view's W rows"""
     P = pemu()
     kc = kconst(K)
     kcb = (C.c_uint8 * len(kc)).from_buffer_copy(kc)
@@ -220,9 +221,13 @@ def device_plan(K, lost, rep_esis):
     arena = np.zeros(cap, np.uint8)
     job = Job()
     P.emu_plan_set_caps(0, 0)
-    P.emu_plan_set_mode(0)
-    rc = P.emu_plan(K, 0, C.addressof(kcb), lost.ctypes.data_as(C.POINTER(C.c_uint32)), len(lost), rep_esis.ctypes.data_as(C.POINTER(C.c_uint32)),
-                    len(rep_esis), len(rep_esis), arena.ctypes.data, cap, 140 * 1024, C.byref(job))
+    P.emu_plan_set_mode(0x800 if no_out_view else 0)
+    try:
+        rc = P.emu_plan(K, 0, C.addressof(kcb), lost.ctypes.data_as(C.POINTER(C.c_uint32)), len(lost),
+                        rep_esis.ctypes.data_as(C.POINTER(C.c_uint32)), len(rep_esis), len(rep_esis), arena.ctypes.data, cap, 140 * 1024,
+                        C.byref(job))
+    finally:
+        P.emu_plan_set_mode(0)
     assert rc == 0
     hdr = nanorq_amd.plan_header(arena.tobytes()[:256])
     base = arena.ctypes.data
@@ -235,12 +240,15 @@ def device_plan(K, lost, rep_esis):
 
 
 def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, mis=0, site="host", bad_block=None, expect=None, seed=2,
-               extra_inact=0, lost_all=None):
+               extra_inact=0, lost_all=None, no_out_view=False):
     """One nrq_decode_blocks call.  site "host": decode_host's arrays (out_slots[] of r16(cols * 2 + NRQ_STORE_SLACK) bytes per block);
     "device": the planner's arena, cut at total_bytes, with rowsrc / out_cptr / out_row / out_slots inside it (pl_final_b).
     bad_block: that block's reception is rank deficient -- the launch must skip it and leave its rows alone.
     extra_inact (site "host"): the plans of a context with the option plan_force_inact; lost_all: every block misses these symbols
-    (the option is the context's: blocks with one reception have one plan, and so one number of inactive columns)."""
+    (the option is the context's: blocks with one reception have one plan, and so one number of inactive columns).
+    no_out_view (site "device", no intermediate symbols): the plans of a context with the option plan_no_out_view -- the arena's last
+    part is the needed-pivot view (needslot[nneed], wneed at stride need_pad with room for every pivot), which the back-substitution
+    then walks."""
     L = lemu()
     p = nanorq_amd.params(K)
     Lsym = p["L"]
@@ -290,11 +298,14 @@ def run_decode(orc, K, T, nblk, loss, overhead, opts, want_inter=False, side=0, 
             _, j.out_slots = A.place("out_slots[%d]" % b, slots, mis=0)
             j.nout = len(lost)
         else:
-            arena, hdr, offs, nout = device_plan(K, lost, esis)
+            arena, hdr, offs, nout = device_plan(K, lost, esis, no_out_view)
             assert (hdr["status"] == 0) == ok, ("verdict", b, hdr["status"], ok)
             if hdr["status"]:
                 continue
             assert nout == len(lost)
+            if no_out_view:  # (the view ends the arena: the page behind it is the fence)
+                assert not want_inter and hdr["off_wout"] == 0 and hdr["off_needslot"] != 0 and 0 < hdr["nneed"] <= hdr["need_pad"], hdr
+                assert len(arena) == hdr["total_bytes"] == r16(hdr["off_wneed"] + 4 * hdr["wpr"] * hdr["npiv_pad"]), hdr  # (room for every pivot)
             _, plan_p = A.place("plan arena[%d] (rowsrc, out lists inside)" % b, arena, mis=0)
             j.rowsrc, j.out_cptr, j.out_row, j.out_slots = (plan_p + offs[k] for k in ("rowsrc", "out_cptr", "out_row", "out_slots"))
             j.nout = nout

@@ -11,7 +11,8 @@ class begins or ends: per boundary b | b + 1 words u = 32 b - 1, 32 b, 32 b + 1 
 
 A case (tests/forced_inact_support.py GPU_CASES: form, u, the n found for the encode plan and for the decode plan, and what the
 launch must be) is three calls of two blocks on the forced context with the host planner: an encode with intermediate symbols, a
-decode without them (the need view: off_needslot / off_wneed) and one with them, at T = 48 (three whole 16-byte strips) and T = 40
+decode without them (host plans have no needed-pivot view: the job carries the W' image of its lists, out_lists.h build_out_w, and
+back-substitutes nothing -- tests/test_gpu_out_view.py asserts that on these plans) and one with them (every pivot), at T = 48 (three whole 16-byte strips) and T = 40
 (a partial last strip) dealt over the three.  Every call is compared with the oracle byte for byte -- repair and intermediate
 symbols; verdict, recovered block, intermediate symbols -- and asserts from the call stats that it ran where the row says:
 strip_bytes, wg_threads, backsub_strip, u, and that every block was planned on the host (stats "planner" == 0, "encplan_device" ==

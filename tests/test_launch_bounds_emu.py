@@ -30,7 +30,7 @@ import sys
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-GROUPS = ("w16", "w12", "w8", "w4", "w2", "w4sb16", "w4nosplit", "wide2", "wide4", "decode", "big", "edge", "seed0",
+GROUPS = ("w16", "w12", "w8", "w4", "w2", "w4sb16", "w4nosplit", "wide2", "wide4", "decode", "needview", "big", "edge", "seed0",
           "forced_k100", "forced_k1000", "forced_k3000", "forced_k5200", "forced_k10000", "forced_k15000")
 
 

@@ -24,7 +24,8 @@ SOLVE_KNOBS = [{}, {"tiny_any": 1}, {"no_tiny": 1}, {"small_waves4": 0}, {"big_w
 LIST_KNOBS = [{}, {"max_wb": 8}, {"max_wb": 12}, {"max_wb": 2}, {"no_wb12": 1}, {"lds_max": 60000}, {"lds_max": 20000}, {"no_lists": 1},
               {"lds_max": 100000, "no_wb12": 1}]
 PLAN_KNOBS = [{}, {"plan_pack": 1}, {"plan_big_wg": 1}, {"plan_split_force": 1}, {"plan_wrong_instance": 1},
-              {"plan_pack": 1, "plan_split_force": 1}, {"plan_pack": 1, "plan_wrong_instance": 1}]
+              {"plan_pack": 1, "plan_split_force": 1}, {"plan_pack": 1, "plan_wrong_instance": 1}, {"plan_no_out_view": 1},
+              {"plan_no_out_view": 1, "plan_split_force": 1}]
 
 
 @pytest.fixture(scope="module")
@@ -80,7 +81,7 @@ def test_knob_names(emu):
     """an option name the table does not hold is refused; fault injection is not a knob"""
     with Tuning(emu, {}) as t:
         for name in (b"no_lists", b"no_wb12", b"max_wb", b"no_split", b"wide_g", b"lds_max", b"plan_ucap", b"tx_dword", b"host_plan_auto",
-                     b"backsub_sb", b"plan_force_inact"):
+                     b"backsub_sb", b"plan_force_inact", b"plan_no_out_view"):
             assert emu.emu_tuning_set(t.p, name, 1) == 0, name
         for name in (b"fail_after", b"faults_injected", b"nonsense", b"NRQ_NO_LISTS", b""):
             assert emu.emu_tuning_set(t.p, name, 1) == -1, name
@@ -200,18 +201,27 @@ def test_plan_shape_holds_for_any_tuning(emu):
                     assert 2 * emu.emu_lds_alloc(s["dyn_bytes"] + s["sh_bytes"]) <= LDS, what
                 if knobs.get("plan_big_wg"):
                     assert s["wg_threads"] == 1024, what
+                # bit 10 of the jobs' mode: no out view (the option plan_no_out_view), and nothing else about the run
+                nov = 0x400 if knobs.get("plan_no_out_view") else 0
+                assert s["mode"] & 0x400 == nov, what
+                if nov:
+                    with Tuning(emu, {k: v for k, v in knobs.items() if k != "plan_no_out_view"}) as t0:
+                        out0 = (U32 * len(PLAN_OUT))()
+                        assert emu.emu_plan_shape(t0.p, ncu, K, nblk, oh, 0, out0) == where, what
+                        s0 = dict(zip(PLAN_OUT, out0))
+                        assert s0 == dict(s, mode=s["mode"] & ~0x400), what
                 if knobs.get("plan_split_force"):
                     assert s["segmented"], what
                 if s["segmented"]:
                     # the full-size compact instance, its state in the workspace; the helper kernels fit the LDS
                     assert (s["wg_threads"], s["compact"], where) == (1024, 1, 0), what
-                    assert s["mode"] in (0x100, 0x300), what
+                    assert s["mode"] & ~0x400 in (0x100, 0x300), what
                     parts = [s["part0"], s["part1"], s["part2"]][:s["nparts"]]
-                    assert parts == ([3, 4, 2] if s["mode"] == 0x300 else [1, 2]), what
+                    assert parts == ([3, 4, 2] if s["mode"] & 0x300 == 0x300 else [1, 2]), what
                     assert s["mh_dyn"] + s["sh_bytes"] <= LDS and s["wpass_lds"] <= LDS, what
                     assert 2 <= s["wentry_wgs"] <= 8 and 1 <= s["mh_wgs"] <= 64 and s["wpass_wgs"] >= 2, what
                 else:
-                    assert (s["nparts"], s["part0"], s["mode"]) == (1, 0, 0), what
+                    assert (s["nparts"], s["part0"], s["mode"]) == (1, 0, nov), what
 
 
 def test_solve_lists_partition(emu):
