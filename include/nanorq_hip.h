@@ -54,6 +54,8 @@ typedef struct nrq_call_stats {
   uint32_t need_view;        /* decode without intermediate symbols: device-planned jobs of the call launched on the needed-pivot view (the
                               * plan has one and no W' image: the back-substitution takes the pivots the missing symbols' lists name) */
   uint32_t nneed;            /* the needed pivots of the first such job's plan (a subset of its npiv pivots) */
+  uint32_t plan_scan_lists;  /* decode: device-planned blocks of the call whose missing symbols' lists the planner laid out in row order by
+                              * its prefix scan (more missing symbols than its frontier queues hold lengths of; nrq_plan_hdr scan_lists) */
 } nrq_call_stats;
 
 /* One context per GPU (one process per GPU: no cross-device state).  `stream` is a hipStream_t the

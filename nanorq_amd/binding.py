@@ -31,7 +31,7 @@ class CallStats(C.Structure):
                 ("plan_ahead", C.c_uint32), ("strip_bytes_b", C.c_uint32), ("blocks_b", C.c_uint32),
                 ("plan_wg_threads", C.c_uint32), ("plan_compact_state", C.c_uint32), ("plan_segmented", C.c_uint32),
                 ("backsub_strip", C.c_uint32), ("encplan_device", C.c_uint32), ("out_view", C.c_uint32),
-                ("need_view", C.c_uint32), ("nneed", C.c_uint32)]
+                ("need_view", C.c_uint32), ("nneed", C.c_uint32), ("plan_scan_lists", C.c_uint32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -203,7 +203,7 @@ PLAN_FIELDS = ("magic status K Kp J S H W L P P1 B M npiv u nlow r2 nfree nlev n
                "npiv_pad n_xor_ops off_ops off_pivslot off_pivcol off_wt off_lowslot off_pivx off_fbits "
                "off_mh off_freex off_hinv off_colslot off_pivof off_uslot total_bytes reserved0 reserved1 fail_site "
                "off_augt lpr aug_stride nneed need_pad off_needslot off_wneed off_wout out_pad out_n off_out_cptr "
-               "off_out_slots").split()
+               "off_out_slots scan_lists").split()
 
 
 def params(K):

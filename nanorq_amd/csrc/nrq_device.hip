@@ -2137,6 +2137,7 @@ static int decode_device(nrq_ctx *ctx, const DecodeCall &c, std::vector<uint8_t>
       }
       ctx->stats.xor_ops += hd[b].n_xor_ops;
       ctx->stats.plan_bytes += hd[b].total_bytes;
+      if (hd[b].scan_lists) ctx->stats.plan_scan_lists++; /* (pl_final_d: the lists in row order, offsets from the scan) */
       if (hd[b].off_wout) ctx->stats.out_view++; /* (pl_final_d gave the job the same offset as out_w) */
       else if (hd[b].off_needslot && !c.inter) { /* (the back-substitution of this job takes the needed-pivot view: solve_body.h) */
         if (ctx->stats.need_view++ == 0) ctx->stats.nneed = hd[b].nneed;

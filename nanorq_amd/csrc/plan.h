@@ -193,6 +193,8 @@ typedef struct nrq_plan_hdr {
   uint32_t out_n;       /* lists the image covers (the job's nout) */
   uint32_t off_out_cptr;  /* device planner: the job's out_cptr[] and out_slots[] inside this arena (0 in host-built plans, whose */
   uint32_t off_out_slots; /* lists travel beside the arena) */
+  uint32_t scan_lists;  /* device planner: 1 = the missing symbols' lists lie in row order, their offsets from the prefix scan (more than
+                         * 2 * qcap of them: planner_body.h pl_final_c2); 0 = sorted by length.  Written by the branch of pl_final_d that ran */
 } nrq_plan_hdr;
 /* (emu_device_plan and plan_header read the header from the first 256 bytes of a plan) */
 #ifdef __cplusplus

@@ -259,6 +259,9 @@ typedef struct pl_shared {
 SB_HD uint32_t pl_shared_bytes(uint32_t qcap, uint32_t lowcap, uint32_t nt) {
   return pl_r16((uint32_t)sizeof(pl_shared)) + pl_r16(qcap * 8u) + pl_r16(nt * 4u) + pl_r16(lowcap * 2u);
 }
+/* the prefix scan over the lists of more than 2 * qcap missing symbols keeps nt + 1 words in the frontier queues: the rule is
+ * stated at pl_final_c2 */
+SB_HD bool pl_scan_fits(uint32_t qcap, uint32_t nt) { return nt + 1u <= qcap; }
 
 SB_HD bool pl_bin_in_stream(uint32_t L) { return L < NRQ_AUG_MATRIX_MIN_L; } /* (plan.h: the GF(2) combinations as ops of the stream) */
 
@@ -336,6 +339,7 @@ struct PlanCtx {
   const uint32_t *lost, *rep_esi;
   pl_shared *sh;
   uint32_t qcap, lowcap, sh_bytes; /* capacities of the arrays behind pl_shared (pl_shared_bytes) */
+  bool scan_ok;      /* more than 2 * qcap missing symbols can be laid out: the scan's words fit this workgroup's queues (pl_scan_fits) */
   uint16_t *qmem;    /* queue[2][qcap], claim_l[qcap], claim_c[qcap] */
   uint32_t *partial; /* [nt] */
   uint8_t *gjmem;    /* gj_flag[lowcap], gj_used[lowcap] */
@@ -409,6 +413,7 @@ SB_HD void pl_ctx_setup(PlanCtx &c, const rq_params &prm, const uint8_t *kc, con
                         nrq_job *jobout, uint32_t qcap = PL_QCAP, uint32_t lowcap = PL_LOWCAP, uint32_t nt = PL_NT) {
   c.qcap = qcap; c.lowcap = lowcap;
   c.sh_bytes = pl_shared_bytes(qcap, lowcap, nt);
+  c.scan_ok = pl_scan_fits(qcap, nt) || job.nlost <= 2u * qcap; /* (else pl_init_a fails the block: PL_FAIL_CAPACITY, the host plans it) */
   {
     uint8_t *t = reinterpret_cast<uint8_t *>(sh) + pl_r16((uint32_t)sizeof(pl_shared));
     c.qmem = reinterpret_cast<uint16_t *>(t); t += pl_r16(qcap * 8u);
@@ -572,6 +577,8 @@ template <int Z> SB_HD void pl_init_a(PlanCtx &c, uint32_t tid, uint32_t nt) {
     /* (the kernel instances carry one form of the peeling phases each, PL_PEEL_DISPATCH3: a block whose state is not where its
      * instance expects it goes back to the host planner) */
     if (!st && !PL_PEEL_FORM_OK(Z)) { st = PL_FAIL_CAPACITY; sh->fail_site = __LINE__; } else sh->fail_site = 0;
+    /* (pl_ctx_setup: the prefix scan of this many lists does not fit the queues of this workgroup -- the rule at pl_final_c2) */
+    if (!st && !c.scan_ok) { st = PL_FAIL_CAPACITY; sh->fail_site = __LINE__; }
     sh->status = st;
     sh->defer_wt = (c.job.mode >> 8) & 1u; /* (bit 8 of the job's mode: set by the host for segmented runs) */
     sh->overhead = oh;
@@ -3234,7 +3241,14 @@ template <int Z> SB_HD void pl_final_c(PlanCtx &c, uint32_t tid, uint32_t nt) {
   if (ops) PL_ATOM_ADD(&sh->tmp1, ops);
 }
 /* many missing symbols (more than the frontier queues hold lengths of): the list offsets by a three-step scan over pivdeg[]
- * instead of a running sum by one thread */
+ * instead of a running sum by one thread.
+ * THE LAYOUT RULE of the scan (pl_scan_fits): its nt + 1 words -- a partial sum per thread and the total -- start at queue(0) and must
+ * end in front of claim_l(), 4 * qcap bytes on (the two frontier queues, two bytes an entry): (nt + 1) * 4 <= 4 * qcap, i.e.
+ * nt + 1 <= qcap.  Behind that line lie the need marks (pl_need_marks = claim_l()), which pl_final_d zeroes while other threads of
+ * its phase still read their partial sums and thread 0 reads the total afterwards, and behind claim_c() lies part(), whose first
+ * words hold the arena offsets pl_final_b left.  plan_shape() pairs 1024 threads with qcap 2048, 256 with 512 / 1024 (2048 with the
+ * full-size state) and 128 with 256 / 512: all inside.  pl_init_a refuses a block with more than 2 * qcap missing symbols in a
+ * workgroup that breaks the rule (PL_FAIL_CAPACITY: the host plans it), tests/test_launch_shape_emu.py checks every PlanShape. */
 template <int Z> SB_HD void pl_final_c2(PlanCtx &c, uint32_t tid, uint32_t nt) {
   pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
   const uint32_t nl = c.job.nlost;
@@ -3261,6 +3275,7 @@ template <int Z> SB_HD void pl_final_c3(PlanCtx &c, uint32_t tid, uint32_t nt) {
 template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
   pl_shared *sh = c.sh; PL_ASSUME_LDS(sh);
   const rq_params &p = c.p;
+  uint32_t scanned = 0u;
   if (!sh->status && c.job.nlost <= 2u * c.qcap) {
     /* the lists of the missing symbols in non-increasing length, equal lengths in the order of c.lost[] (ph_store deals them to
      * its threads in this order: the 64 lists of a wave are then of near-equal length): every thread finds the place of its own
@@ -3288,6 +3303,7 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
       for (uint32_t j = 0; j < PL_BATCH; j++) if (g0 + j < b) { cptr[g0 + j] = run; run += v[j]; }
     }
     if (tid == 0) cptr[nl] = ps[nt];
+    scanned = 1u; /* (the header says which branch laid the lists out: nrq_plan_hdr scan_lists) */
   }
   if (!sh->status && c.part()[7]) /* (the marks of pl_final_e: one bit per slot) */
     for (uint32_t i = tid; i < (sh->M + 31u) / 32u; i += nt) pl_need_marks(c)[i] = 0u;
@@ -3308,6 +3324,7 @@ template <int Z> SB_HD void pl_final_d(PlanCtx &c, uint32_t tid, uint32_t nt) {
   h.off_freex = c.off_freex; h.off_hinv = c.off_hinv; h.off_colslot = c.off_colslot; h.off_pivof = c.off_pivof;
   h.off_uslot = c.off_uslot; h.total_bytes = sh->arena_top;
   h.off_augt = sh->off_augt; h.lpr = pl_bin_in_stream(p.L) ? 0u : sh->lpr; h.aug_stride = sh->aug_stride;
+  h.scan_lists = scanned;
   if (!sh->status && c.part()[PL_OUTW]) { /* (filled by pl_out_w, or by pl_wt_fill after a segmented run) */
     h.off_wout = c.part()[PL_OUTW]; h.out_pad = c.part()[PL_OUTW + 1u]; h.out_n = c.job.nlost;
     h.off_out_cptr = c.part()[2]; h.off_out_slots = c.part()[4];

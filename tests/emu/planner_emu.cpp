@@ -1,8 +1,9 @@
 /*
  * planner_emu.cpp -- CPU emulation of the GPU planner workgroup (TEST SUPPORT ONLY).
  * Runs nanorq_amd/csrc/planner_body.h -- the per-thread phase code of the HIP planner kernel -- with
- * the 256 threads of each phase executed sequentially and barriers as loop boundaries, in the phase
- * order of planner_seq.h.  Not part of the product.
+ * the threads of each phase executed sequentially and barriers as loop boundaries, in the phase
+ * order of planner_seq.h: 1024 of them, or the workgroup size given with the capacities of a run
+ * (emu_plan_set_threads).  Not part of the product.
  */
 #include <cstdint>
 #include <cstdlib>
@@ -125,6 +126,10 @@ static void emu_wpass_strips(PlanCtx &c) {
 static uint32_t g_mode = 0; /* nrq_planjob::mode of the next emu_plan call (1 = encode plan) */
 static uint32_t g_qcap = PL_QCAP, g_lowcap = PL_LOWCAP; /* capacities of the arrays behind pl_shared (small blocks get small ones) */
 extern "C" void emu_plan_set_caps(uint32_t qcap, uint32_t lowcap) { g_qcap = qcap ? qcap : PL_QCAP; g_lowcap = lowcap ? lowcap : PL_LOWCAP; }
+/* threads of the emulated workgroup: what plan_shape() pairs with the capacities -- 1024 with the big ones, 256 with (512, 384) and
+ * (1024, 768), 128 with the smallest blocks' form (0 = 1024).  The arrays behind pl_shared are sized by it, as on the device. */
+static uint32_t g_nt = PL_NT;
+extern "C" void emu_plan_set_threads(uint32_t nt) { g_nt = nt ? nt : PL_NT; }
 static uint32_t g_split = 0; /* run the phase sequence in its two parts (what big blocks do on the GPU) */
 static uint32_t g_nopk = 0;  /* keep the peeling state in the workspace alone (no compact copy in LDS) when it does not fit the LDS */
 static uint32_t g_went = 0;  /* with g_split: part 1 cut once more, the entry pass by two "workgroups" in between (nrq_wentry_kernel) */
@@ -144,7 +149,7 @@ extern "C" int emu_plan(uint32_t K, uint32_t Kp_hint, const uint8_t *kc, const u
   const uint32_t Mcap = kh->L + ohcap + PL_EXTRA_ROWS + 8, npcap = nrep_avail + PL_EXTRA_ROWS + 8, ucap = kh->P + 768u;
   pl_work_layout wl = pl_work_plan(kh->L, Mcap, npcap, ucap, kh->nnz + npcap * PL_PATCH_STRIDE);
   std::vector<uint8_t> work(wl.total + 64, 0xCC), dyn(lds_dyn_bytes + 64, 0xDD);
-  const uint32_t shb = pl_shared_bytes(g_qcap, g_lowcap, PL_NT);
+  const uint32_t shb = pl_shared_bytes(g_qcap, g_lowcap, g_nt);
   std::vector<uint8_t> shmem(shb + 64, 0xEE); /* pl_shared and the arrays behind it */
   pl_shared *sh = reinterpret_cast<pl_shared *>(shmem.data());
   nrq_planjob job;
@@ -156,16 +161,16 @@ extern "C" int emu_plan(uint32_t K, uint32_t Kp_hint, const uint8_t *kc, const u
   job.nlost = nlost; job.nrep = nrep; job.arena_cap = arena_cap; job.nrep_avail = nrep_avail;
   job.mode = g_mode | (g_split << 8) | ((g_split && g_went) ? 0x200u : 0u) | (g_noutw ? PL_MODE_NO_OUTW : 0u);
   PlanCtx c;
-  pl_ctx_setup(c, p, kc, job, sh, lds_dyn_bytes ? dyn.data() : nullptr, lds_dyn_bytes, Mcap, npcap, ucap, job_out, g_qcap, g_lowcap, PL_NT);
+  pl_ctx_setup(c, p, kc, job, sh, lds_dyn_bytes ? dyn.data() : nullptr, lds_dyn_bytes, Mcap, npcap, ucap, job_out, g_qcap, g_lowcap, g_nt);
   if (g_nopk) c.pk_cnt = c.pk_un = c.pk_pa = c.pk_vb = nullptr;
-#define PL_PHASE(fn) do { for (uint32_t t_ = 0; t_ < PL_NT; t_++) fn<1>(c, t_, PL_NT); } while (0)
-#define PL_PHASE1(fn, a) do { for (uint32_t t_ = 0; t_ < PL_NT; t_++) fn<1>(c, (a), t_, PL_NT); } while (0)
+#define PL_PHASE(fn) do { for (uint32_t t_ = 0; t_ < g_nt; t_++) fn<1>(c, t_, g_nt); } while (0)
+#define PL_PHASE1(fn, a) do { for (uint32_t t_ = 0; t_ < g_nt; t_++) fn<1>(c, (a), t_, g_nt); } while (0)
 #define PL_PHASE1_CLAIM(fn, a) PL_PHASE1(fn, a)
 #define PL_WFAST_RUN(wb) emu_wfast_run(c, (wb))
 #define PL_MHREV_RUN(wb) emu_mhrev_run(c, (wb))
 #define PL_SEG g_seg
 #define PL_STEER_SYNC do { } while (0)
-#define PL_NT_ PL_NT
+#define PL_NT_ g_nt
 #define PL_Z 1u
   const uint32_t segs_[3] = {(g_split && g_went) ? 3u : 1u, (g_split && g_went) ? 4u : 2u, 2u};
   for (uint32_t pass_ = 0; pass_ < (!g_split ? 1u : g_went ? 3u : 2u); pass_++) {
@@ -178,7 +183,7 @@ extern "C" int emu_plan(uint32_t K, uint32_t Kp_hint, const uint8_t *kc, const u
         c.nrec_ptr = &c.wentry[0];
         c.own_ptr = &c.wentry[3];
         for (uint32_t part = 0; part < 2u; part++)
-          for (uint32_t t_ = 0; t_ < PL_NT; t_++) pl_w_init_part<1>(c, part, 2u, t_, PL_NT);
+          for (uint32_t t_ = 0; t_ < g_nt; t_++) pl_w_init_part<1>(c, part, 2u, t_, g_nt);
         PL_PHASE(pl_wentry_report);
         c.cls_glob = nullptr;
         c.nrec_ptr = &sh->nrec;

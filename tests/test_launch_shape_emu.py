@@ -181,6 +181,7 @@ def test_solve_shape_holds_for_any_tuning(emu):
 def test_plan_shape_holds_for_any_tuning(emu):
     LDS = emu.emu_lds_max()
     out = (U32 * len(PLAN_OUT))()
+    scan_rule_met = scan_rule_small = 0
     for knobs in PLAN_KNOBS:
         with Tuning(emu, knobs) as t:
             for K, nblk, oh, ncu in itertools.product((10, 100, 256, 500, 1000, 1500, 2500, 4000, 8192, 15000, 27000, 56403),
@@ -201,6 +202,13 @@ def test_plan_shape_holds_for_any_tuning(emu):
                     assert 2 * emu.emu_lds_alloc(s["dyn_bytes"] + s["sh_bytes"]) <= LDS, what
                 if knobs.get("plan_big_wg"):
                     assert s["wg_threads"] == 1024, what
+                # the layout rule of the planner's prefix scan (planner_body.h pl_final_c2): a block may miss all K source symbols, and
+                # with more than 2 * qcap missing the list offsets come from a scan whose wg_threads + 1 words start at the first
+                # frontier queue and must end in front of the claim lists, 4 * qcap bytes on (two queues of qcap two-byte entries)
+                if K > 2 * s["qcap"]:
+                    scan_rule_met += 1
+                    assert (s["wg_threads"] + 1) * 4 <= 4 * s["qcap"], what
+                scan_rule_small += K > 2 * s["qcap"] and s["wg_threads"] < 1024
                 # bit 10 of the jobs' mode: no out view (the option plan_no_out_view), and nothing else about the run
                 nov = 0x400 if knobs.get("plan_no_out_view") else 0
                 assert s["mode"] & 0x400 == nov, what
@@ -222,6 +230,8 @@ def test_plan_shape_holds_for_any_tuning(emu):
                     assert 2 <= s["wentry_wgs"] <= 8 and 1 <= s["mh_wgs"] <= 64 and s["wpass_wgs"] >= 2, what
                 else:
                     assert (s["nparts"], s["part0"], s["mode"]) == (1, 0, nov), what
+    # the sweep holds shapes the rule is about, 256-thread ones among them (K = 2500 in packed workgroups: qcap 1024)
+    assert scan_rule_met > 100 and scan_rule_small > 10
 
 
 def test_solve_lists_partition(emu):

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import nanorq_amd
-from emu_support import ROW_ZERO, decode_setup, emu, emu_device_plan, emu_solve, lt_lists
+from emu_support import ROW_ZERO, decode_setup, emu, emu_device_plan, emu_solve, emu_solve_job, lt_lists
 from util import loss_pattern, payload, received_set
 
 
@@ -223,7 +223,9 @@ def test_device_planner_emulated_matches_oracle(orc, K, T, wb, p, oh, lds):
     the oracle's; `lds` (KiB) small enough forces the peeling state out of LDS into the HBM workspace.  Every case
     also runs SEGMENTED, the way big blocks run on the GPU (planner_seq.h): part 1, the HDPC fold by two "workgroups"
     (nrq_mh_kernel), part 2 with pl_shared restored from the workspace, W transposed afterwards (nrq_wt_kernel) --
-    and must produce the identical plan."""
+    and must produce the identical plan.  Blocks of K <= 1024 also run with a small block's capacities (512, 384) in the 256-thread
+    workgroup the launch pairs with them (never 1024 threads: no launch makes that pairing): the plan of that workgroup, which the
+    capacities must not change and which must decode."""
     prm = orc.params(K)
     src = payload(K * T, seed=15).reshape(K, T)
     kc = nanorq_amd.host_kconst(K)
@@ -248,9 +250,18 @@ def test_device_planner_emulated_matches_oracle(orc, K, T, wb, p, oh, lds):
             # big blocks on the GPU); without the mirror the same plan must come out
             plan4, hdr4 = emu_device_plan(K, kc, lost, rep_esis, lds_bytes=lds * 1024, compact=False)
             assert plan4 == plan, "the compact peeling state built a different plan"
-        if K <= 1024:   # small blocks run with small queues / claim lists / Gauss-Jordan flags behind pl_shared
+        if K <= 1024:   # small blocks run with small queues / claim lists / Gauss-Jordan flags behind pl_shared, in the 256-thread
+            # workgroup the launch gives those capacities to (emu_support.CAPS_THREADS: plan_shape's pairing)
+            # -- a planner workgroup's peel takes its claims in arrival order, so another thread count builds another (valid) plan:
+            # the capacities must not change the plan of THAT workgroup, and its plan must decode
             plan3, hdr3 = emu_device_plan(K, kc, lost, rep_esis, lds_bytes=lds * 1024, caps=(512, 384))
-            assert plan3 == plan
+            assert plan3 == emu_device_plan(K, kc, lost, rep_esis, lds_bytes=lds * 1024, threads=256)[0]
+            assert plan3 == emu_device_plan(K, kc, lost, rep_esis, lds_bytes=lds * 1024, caps=(512, 384), split=True)[0]
+            work3 = src.copy()
+            work3[lost] = 0x33
+            _, rowsrc3 = decode_setup(orc, K, lost, rep_esis)
+            r3, _ = emu_solve(plan3, kc, rowsrc3, work3, rep, T, prm["L"], lt_lists(orc, K, lost, plan3), lost, work3, wb)
+            assert hdr3["status"] == 0 and r3 == 1 and np.array_equal(work3, src)
         _, rowsrc = decode_setup(orc, K, lost, rep_esis)
         work = src.copy()
         work[lost] = 0x77
@@ -268,6 +279,92 @@ def test_device_planner_emulated_matches_oracle(orc, K, T, wb, p, oh, lds):
         assert r5 == 1 and np.array_equal(work5, src)
         done += 1
     assert done >= 1
+
+
+# Receptions that miss most or all of a block's source symbols, at the sizes where a 256-thread planner workgroup lays the lists out
+# by its prefix scan (more than 2 * qcap missing: planner_body.h pl_final_c2 .. pl_final_e).  (K, (qcap, lowcap), loss, overhead);
+# missing symbols: K = 1300 at 0.8 / 0.9 / 1.0 -> 1048 / 1186 / 1300 (> 1024), K = 2300 at 0.9 / 1.0 -> 2092 / 2300 (> 2048).
+HIGH_LOSS = [(1300, (512, 384), p, oh) for p in (0.8, 0.9, 1.0) for oh in (2, 0)] + \
+            [(2300, (1024, 768), p, oh) for p in (0.9, 1.0) for oh in (2, 0)]
+
+
+@pytest.mark.parametrize("K,caps,p,oh", HIGH_LOSS)
+def test_scan_form_of_the_lists_at_the_launched_thread_count(orc, K, caps, p, oh):
+    """The planner with a small block's capacities in the workgroup the device launches with them (256 threads), on receptions whose
+    lists go out in row order with offsets from the scan.  The plan must say so (header word scan_lists), be the plan of the
+    1024-thread workgroup with the big capacities and of the segmented run, and decode to the oracle's bytes -- through the planner's OWN job
+    record (out_cptr / out_row / out_slots and the W' image), with the out view and without it; lt_lists() rebuilt on the host would not
+    read what the scan wrote."""
+    T, wb = 16, 16
+    src = payload(K * T, seed=41).reshape(K, T)
+    kc = nanorq_amd.host_kconst(K)
+    lost = loss_pattern(K, p, 3)
+    assert len(lost) > 2 * caps[0] and (p < 1.0 or len(lost) == K)
+    esis = received_set(K, lost, oh)
+    rep_esis = esis[esis >= K]
+    rep, _, _ = orc.encode_block(src, K, T, rep_esis)
+    ok, ref_out, _ = orc.decode_block(esis, np.concatenate([src[esis[esis < K]], rep]), K, T)
+    plan, hdr, lists, out_w = emu_device_plan(K, kc, lost, rep_esis, caps=caps, want_job=True)
+    assert (hdr["status"] == 0) == ok, hdr
+    plan2, hdr2, lists2, out_w2 = emu_device_plan(K, kc, lost, rep_esis, caps=caps, split=True, want_job=True)
+    assert hdr2["status"] == hdr["status"]
+    if not ok:
+        return
+    assert np.array_equal(ref_out, src)
+    assert hdr["scan_lists"] == 1 and hdr["u"] < hdr["P"] + 768, hdr   # (inside the inactive-column capacity of the device planner)
+    assert plan2 == plan and out_w2 == out_w, "the segmented run built a different plan"
+    assert all(np.array_equal(x, y) for x, y in zip(lists, lists2))
+    # the same workgroup with the big capacities (qcap 2048: below 4096 missing symbols the lists are sorted by length): the same
+    # plan in front of the lists, the same list and the same W' row for every missing symbol, in another order
+    big, big_hdr, big_lists, big_w = emu_device_plan(K, kc, lost, rep_esis, threads=256, want_job=True)
+    assert big_hdr == dict(hdr, scan_lists=0) and big_w == out_w
+    o = hdr["off_out_cptr"]
+    assert 256 < o < hdr["off_out_slots"] < hdr["off_wout"] and plan[256:o] == big[256:o]
+    cptr, cols, rows = lists
+    bc, bs, br = big_lists
+    assert not np.array_equal(br, rows) and sorted(br.tolist()) == rows.tolist()
+    wout = lambda pl, q: np.frombuffer(pl, np.uint32, count=hdr["wpr"] * hdr["out_pad"], offset=out_w).reshape(hdr["wpr"], -1)[:, q]
+    where = {int(e): q for q, e in enumerate(br)}
+    for q, e in enumerate(rows):
+        qb = where[int(e)]
+        assert np.array_equal(cols[cptr[q]:cptr[q + 1]], bs[bc[qb]:bc[qb + 1]]), e
+        assert np.array_equal(wout(plan, q), wout(big, qb)), e
+    nsl = hdr["off_needslot"]
+    assert nsl and plan[nsl:out_w] == big[nsl:out_w]       # (the needed-pivot view: marked through the scan's offsets)
+    # the job's lists: in row order, one per missing symbol, offsets a running sum of the LT list lengths
+    assert np.array_equal(rows, lost) and out_w == hdr["off_wout"] != 0
+    lens = [len(orc.lt_columns(K, int(e))) for e in lost]
+    assert np.array_equal(cptr, np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32))
+    _, rowsrc = decode_setup(orc, K, lost, rep_esis)
+    work = src.copy()
+    work[lost] = 0x6B
+    assert emu_solve_job(plan, kc, rowsrc, work, rep, lists, out_w, T, wb) == 1
+    assert np.array_equal(work, ref_out)
+    # without the out view: the needed-pivot view, marked by pl_final_e through the same offsets
+    plan3, hdr3, lists3, out_w3 = emu_device_plan(K, kc, lost, rep_esis, caps=caps, no_out_view=True, want_job=True)
+    assert hdr3["status"] == 0 and hdr3["scan_lists"] == 1 and out_w3 == 0 and hdr3["off_wout"] == 0 and hdr3["off_needslot"] != 0
+    assert all(np.array_equal(x, y) for x, y in zip(lists, lists3))
+    work = src.copy()
+    work[lost] = 0x6B
+    assert emu_solve_job(plan3, kc, rowsrc, work, rep, lists3, 0, T, wb) == 1
+    assert np.array_equal(work, ref_out)
+
+
+@pytest.mark.parametrize("K,nl", [(1300, 1300), (1300, 1048), (1100, 1100), (1400, 1125)])
+def test_scan_form_refuses_a_workgroup_its_words_do_not_fit(orc, K, nl):
+    """The layout rule of the scan (planner_body.h pl_final_c2): nt + 1 words from the first frontier queue must end in front of the
+    claim lists, nt + 1 <= qcap.  1024 threads with the capacities (512, 384) -- a pairing no launch makes -- break it: 1025 words
+    overrun the queues, the claim lists and the first word of part().  Such a block must come back as a capacity failure raised in
+    pl_init_a (the host planner takes it), not as a plan; at or below 2 * qcap missing symbols the same pairing plans as ever."""
+    kc = nanorq_amd.host_kconst(K)
+    lost = np.sort(np.random.default_rng(K + nl).permutation(K)[:nl]).astype(np.uint32)
+    rep_esis = np.arange(K, K + nl + 2, dtype=np.uint32)
+    _, hdr = emu_device_plan(K, kc, lost, rep_esis, caps=(512, 384), threads=1024)
+    assert (hdr["status"], hdr["reserved0"]) == (1, 2), hdr   # PL_FAIL_CAPACITY
+    assert hdr["npiv"] == 0 and hdr["fail_site"] != 0, hdr    # refused before the peel
+    ref, ref_hdr = emu_device_plan(K, kc, lost[:1024], rep_esis[:1026])   # (1024 threads with their own capacities)
+    edge, edge_hdr = emu_device_plan(K, kc, lost[:1024], rep_esis[:1026], caps=(512, 384), threads=1024)
+    assert ref_hdr["status"] == 0 and ref_hdr["scan_lists"] == 0 and edge == ref
 
 
 def test_device_planner_failure_parity(orc):
