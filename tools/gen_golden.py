@@ -36,7 +36,7 @@ def sha(a):
 
 
 SURVEY = {
-    "provenance": "SURVEY.md section 8(c) PROBE KATs and section 8 tables: reference lib/*.c run at survey time; "
+    "provenance": "SURVEY.md section 8(c) PROBE KATs and section 8 tables: reference lib/*.c run at survey time (the symbols, digests and OTI words are re-derived from the reference by tools/gen_ref_kat.py: tests/golden/ref_kat.json 'survey'); "
                   "payload byte i = ((uint32)i * 2654435761) >> 24 (tests/util.py kat_payload), one block, Al=8",
     "small": {"K": 10, "T": 8, "symbols": {"10": "1bad540de9c8d3c2", "11": "7db6a373c0213e10", "12": "78e7c05eb6bfe9aa"}},
     "sha256_of_repair": [
@@ -137,7 +137,8 @@ def main():
     with open(os.path.join(GOLD, "survey_kat.json"), "w") as f:
         json.dump(SURVEY, f, indent=1)
         f.write("\n")
-    vec = {"provenance": "oracle/rq_oracle.c (C restatement of reference lib/precode.c + lib/nanorq.c), generated by "
+    vec = {"provenance": "oracle/rq_oracle.c (C restatement of reference lib/precode.c + lib/nanorq.c; itself held to the reference's own library by "
+                         "tests/golden/ref_kat.json), generated by "
                          "tools/gen_golden.py; payload(nbytes, seed) and loss_pattern(K, p, seed) are tests/util.py's; "
                          "repair symbols received are ESI K..K+n_lost+overhead-1; order: sorted = surviving source "
                          "symbols ascending then repair ascending, repair_first = repair descending then source, "

@@ -52,8 +52,8 @@ def main():
         assert rep is not None and systematic_sample(Kp, src, inter), "K'=%d: singular or not systematic" % Kp
         out.append({"Kp": Kp, "J": J, "i": int(st["i"]), "u": int(st["u"]), "sha256_repair": hashlib.sha256(rep.tobytes()).hexdigest(),
                     "sha256_intermediate": hashlib.sha256(inter.tobytes()).hexdigest()})
-    doc = {"provenance": "oracle/rq_oracle.c (C restatement of the reference algorithm; the reference is unbuildable here: deps/oblas "
-                         "absent).  One encode per row of RFC 6330 Table 2 (reference include/table2.h:6-211, lib/params.c:21-45, "
+    doc = {"provenance": "oracle/rq_oracle.c (C restatement of the reference algorithm, held to the reference's own library, built over a "
+                         "stand-in for its absent deps/oblas, by tests/golden/ref_kat.json).  One encode per row of RFC 6330 Table 2 (reference include/table2.h:6-211, lib/params.c:21-45, "
                          "lib/tuple.c:21-43): K = K', T = 8, payload = tests/util.py payload(K'*8, seed=477, block=K'); repair ESIs "
                          "K'..K'+3.  Every row was found nonsingular and systematic by tools/gen_kprime_sweep.py.",
            "T": T, "payload_seed": SEED, "repair_per_row": NREP, "rows": out}
