@@ -260,6 +260,8 @@ class Context:
             raise NrqError("nrq_ctx_create failed (%d): no usable HIP device -- the HIP path has no CPU fallback" % rc)
         self._h = h
         self.device = device
+        self._stream = int(stream or 0)
+        self._tstream = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -278,6 +280,23 @@ class Context:
 
     def set_stream(self, stream):
         self._chk(self._L.nrq_ctx_set_stream(self._h, C.c_void_p(stream or 0)))
+        self._stream = int(stream or 0)
+        self._tstream = None
+
+    def torch_stream(self):
+        """The context's stream as a torch stream (0: torch's default stream, which is the null stream)."""
+        if self._tstream is None:
+            import torch
+            self._tstream = (torch.cuda.ExternalStream(self._stream, device=self.device) if self._stream
+                             else torch.cuda.default_stream(self.device))
+        return self._tstream
+
+    def new_tensor(self, shape, dtype, zero=False):
+        """A device tensor of the binding's own, allocated (and zeroed) ON THE CONTEXT'S STREAM whatever torch's current stream
+        is: the library's next write to it on that stream comes after the allocator's last use of the block and after the fill."""
+        import torch
+        with torch.cuda.stream(self.torch_stream()):
+            return (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device="cuda:%d" % self.device)
 
     def set_planner(self, device=True):
         self._chk(self._L.nrq_ctx_set_planner(self._h, int(bool(device))))
@@ -468,7 +487,7 @@ class Receiver(_Handle):
         self._source = None
         if src is None:
             import torch
-            self._source = torch.empty((nblk, K, T), dtype=torch.uint8, device="cuda:%d" % ctx.device)
+            self._source = ctx.new_tensor((nblk, K, T), torch.uint8)
             src, src_stride = self._source, K * T
         self._keep = (src, rep)  # the tensors stay alive as long as the reception
         h = C.c_void_p()
@@ -601,7 +620,7 @@ def _held(rx):
     n = C.c_uint32(0)
     fn = getattr(rx._L, rx._api + "_held")
     rx.ctx._chk(fn(rx._h, None, 0, C.byref(n)))
-    out = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % rx.ctx.device)
+    out = rx.ctx.new_tensor(n.value, torch.int32)
     if n.value:
         rx.ctx._chk(fn(rx._h, C.c_void_p(_dptr(out)), n.value, C.byref(n)))
         rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
@@ -618,7 +637,7 @@ def _want(rx, extra, source, esi_from):
     fn = getattr(rx._L, rx._api + "_want")
     args = (WANT_SOURCE if source else 0, extra, esi_from)
     rx.ctx._chk(fn(rx._h, *args, None, 0, C.byref(n)))
-    out = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % rx.ctx.device)
+    out = rx.ctx.new_tensor(n.value, torch.int32)
     if n.value:
         rx.ctx._chk(fn(rx._h, *args, C.c_void_p(_dptr(out)), n.value, C.byref(n)))
         rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
@@ -633,9 +652,8 @@ def _list_syms(rx, name, args):
         raise NrqError("this build of the library has no listings in packets of several symbols (%s%s)" % (rx._api, name))
     npkt = C.c_uint32(0)
     rx.ctx._chk(fn(rx._h, *args, None, None, 0, C.byref(npkt), None))
-    dev = "cuda:%d" % rx.ctx.device
-    tags = torch.empty(npkt.value, dtype=torch.int32, device=dev)
-    nsym = torch.empty(npkt.value, dtype=torch.uint8, device=dev)
+    tags = rx.ctx.new_tensor(npkt.value, torch.int32)
+    nsym = rx.ctx.new_tensor(npkt.value, torch.uint8)
     if npkt.value:
         rx.ctx._chk(fn(rx._h, *args, C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), npkt.value, C.byref(npkt), None))
         rx.ctx.sync()  # (torch's stream and the library's are not ordered: the list is complete on return)
@@ -663,7 +681,7 @@ class _Emitter(_Handle):
         if out is not None:
             return out, out.stride(0) * out.element_size()
         import torch
-        out = torch.empty((n, self.stride(inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        out = self.ctx.new_tensor((n, self.stride(inline)), torch.uint8)
         return out, out.shape[1]
 
     def encode(self):
@@ -690,7 +708,7 @@ class _Emitter(_Handle):
         if out is not None:
             return out, out.stride(0) * out.element_size()
         import torch
-        out = torch.empty((n, self.stride_syms(G, inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        out = self.ctx.new_tensor((n, self.stride_syms(G, inline)), torch.uint8)
         return out, out.shape[1]
 
     def emit_syms(self, tags, G, nsym=None, out=None, inline=False, results=None, held=False):
@@ -708,10 +726,11 @@ class _Emitter(_Handle):
 
     def _range_syms(self, fn, head, npkt, G, interleave, inline, out):
         import torch
-        dev = "cuda:%d" % self.ctx.device
         out, stride = self._out_syms(npkt, G, inline, out)
-        tags = torch.zeros(npkt, dtype=torch.int32, device=dev)
-        nsym = torch.zeros(npkt, dtype=torch.uint8, device=dev)
+        # (no fill: the call writes the first tag and the count of every one of its npkt packets, and a fill on torch's current
+        # stream would not be ordered against that write on the context's)
+        tags = self.ctx.new_tensor(npkt, torch.int32)
+        nsym = self.ctx.new_tensor(npkt, torch.uint8)
         got = C.c_uint32()
         self.ctx._chk(fn(self._h, *head, G, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride, _tx_flags(inline, False),
                          C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), C.byref(got)))
@@ -948,8 +967,7 @@ class ObjectReceiver(_Handle):
         object's layout; bytes past F and incomplete blocks are left untouched.  Returns (out, blocks still incomplete)."""
         if out is None:
             import torch
-            out = torch.zeros(self.F, dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
-            torch.cuda.synchronize()  # (torch's stream and the library's are not ordered)
+            out = self.ctx.new_tensor(self.F, torch.uint8, zero=True)  # (zeroed on the context's stream, ahead of the write)
         elif out.numel() * out.element_size() < self.F:
             raise ValueError("out is shorter than the object")
         rc = self._L.nrq_orx_write(self._h, C.c_void_p(_dptr(out)))
@@ -1074,8 +1092,8 @@ class ReceiverSet(_Handle):
         n = C.c_uint32(0)
         cnt = np.zeros(len(self.blocks()[0]), np.uint32)
         self.ctx._chk(fn(self._h, *args, None, None, 0, _u32(cnt) if per_block else None, C.byref(n)))
-        keys = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
-        tags = torch.empty(n.value, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        keys = self.ctx.new_tensor(n.value, torch.int32)
+        tags = self.ctx.new_tensor(n.value, torch.int32)
         if n.value:
             self.ctx._chk(fn(self._h, *args, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n.value, None, C.byref(n)))
             self.ctx.sync()  # (torch's stream and the library's are not ordered: the lists are complete on return)
@@ -1099,10 +1117,9 @@ class ReceiverSet(_Handle):
         npkt = C.c_uint32(0)
         cnt = np.zeros(len(self.blocks()[0]), np.uint32)
         self.ctx._chk(fn(self._h, *args, None, None, None, 0, _u32(cnt) if per_block else None, C.byref(npkt), None))
-        dev = "cuda:%d" % self.ctx.device
-        keys = torch.empty(npkt.value, dtype=torch.int32, device=dev)
-        tags = torch.empty(npkt.value, dtype=torch.int32, device=dev)
-        nsym = torch.empty(npkt.value, dtype=torch.uint8, device=dev)
+        keys = self.ctx.new_tensor(npkt.value, torch.int32)
+        tags = self.ctx.new_tensor(npkt.value, torch.int32)
+        nsym = self.ctx.new_tensor(npkt.value, torch.uint8)
         if npkt.value:
             self.ctx._chk(fn(self._h, *args, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), C.c_void_p(_dptr(nsym)), npkt.value, None,
                              C.byref(npkt), None))
@@ -1174,7 +1191,7 @@ class SenderSet(_Handle):
         n = int(tags.shape[0])
         if out is None:
             import torch
-            out = torch.empty((n, self.stride(inline, key_inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            out = self.ctx.new_tensor((n, self.stride(inline, key_inline)), torch.uint8)
             stride = out.shape[1]
         else:
             stride = out.stride(0) * out.element_size()
@@ -1199,7 +1216,7 @@ class SenderSet(_Handle):
         n = int(tags.shape[0])
         if out is None:
             import torch
-            out = torch.empty((n, self.stride_syms(G, inline, key_inline)), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+            out = self.ctx.new_tensor((n, self.stride_syms(G, inline, key_inline)), torch.uint8)
             stride = out.shape[1]
         else:
             stride = out.stride(0) * out.element_size()

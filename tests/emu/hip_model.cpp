@@ -595,6 +595,11 @@ int hm_effect_touch_tail(const void *p, int write) {
   if (!a) return m.cur_s ? effect_touch(m, p, 1, write != 0, "buffer") : 0;
   return effect_touch(m, p, a->base + a->size - (uintptr_t)p, write != 0, "buffer");
 }
+uint64_t hm_effect_base(const void *p) {
+  Model &m = M(); /* (called from an effect: the model is locked) */
+  Alloc *a = m.cur_s ? find(m, (uintptr_t)p) : nullptr;
+  return a ? (uint64_t)a->base : 0;
+}
 void hm_effect_wrote(const void *p, size_t n) {
   Model &m = M();
   if (m.cur_s) note_written(m, find(m, (uintptr_t)p), p, n);

@@ -28,8 +28,12 @@
  *     its bytes at enqueue, so that control arrays are in place when the next launch's footprint is taken.
  *   - Kernels do not run.  Three kernels whose whole effect is a copy have that effect and an exact footprint (hm_set_effect):
  *     nrq_ctl_copy_kernel (control arrays: job records, address lists, whose pointers the footprint of a later launch follows),
- *     nrq_scatter_kernel and nrq_move_rows_kernel (rows by address list).  Every other kernel is a no-op whose footprint is what
- *     its arguments can reach.
+ *     nrq_scatter_kernel and nrq_move_rows_kernel (rows by address list).  The decode planner and the kernels that run a batch of
+ *     job records (solve, back-substitution, collect) have exact footprints too (tests/emu/model_effects.cpp): the records and what
+ *     each record's addresses name, not every word of those allocations one level further.  Every other kernel is a no-op whose
+ *     footprint is what its arguments can reach.
+ *   - A plain hipMemcpy is an operation on stream 0 -- whatever stream the context of the caller is on -- that the host then
+ *     waits for: it is ordered behind what the host has synchronised with and behind stream 0, and behind nothing else.
  *   - No guard pages and no signal handler: a range that is not inside a live allocation is reported and NOT touched.  "Device"
  *     and page-locked memory are carved from two reserved address ranges and addresses are never handed out twice, so a 64-bit
  *     word can be recognised as a device pointer and a stale pointer never names a newer allocation.
@@ -76,6 +80,7 @@ typedef void (*hm_effect_fn)(const hm_arg *args, int nargs);
 void hm_set_effect(const char *name_part, hm_effect_fn fn, int exact);
 int hm_effect_touch(const void *p, size_t n, int write);
 int hm_effect_touch_tail(const void *p, int write); /* from p to the end of its allocation (a buffer whose size the launch does not say) */
+uint64_t hm_effect_base(const void *p);             /* the base of the live allocation that holds p (0: none), to touch an allocation once */
 void hm_effect_wrote(const void *p, size_t n);       /* the effect has put bytes there itself: they may hold addresses a later launch follows */
 void hm_effect_grid(unsigned out[3]);               /* the grid of the launch whose effect is running */
 

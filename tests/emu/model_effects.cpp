@@ -6,7 +6,9 @@
  * run reads its job records, lists and constants and writes its workspace, arenas, headers and the solve's job records; it only
  * FORWARDS the addresses of the symbol buffers.  The symbols themselves are never computed: no kernel runs. */
 #include <cstdint>
+#include <algorithm>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "../../nanorq_amd/csrc/planner_body.h"
@@ -103,8 +105,58 @@ void plan_helper_effect(const hm_arg *a, int n) {
   else if (n >= 1) (void)planjob_footprint((const nrq_planjob *)a[0].p, g[1], nullptr);
 }
 
+/* The kernels that run a batch of job records: nrq_solve_kernel(const nrq_job *jobs, nblk, ...), and the two that finish a split
+ * solve, nrq_backsub_kernel(jobs, T, ybuf, ...) with one block per grid z and nrq_collect_kernel(jobs, T, ybuf, ...) with one per
+ * grid y.  Exact: the job records, what each record's nine addresses name (from the address to the end of its allocation: the
+ * plan and the lists read, the block's rows and its intermediate symbols written) and the launch's other pointer arguments.
+ * The footprint from the arguments alone would go one level further, through every word of the plan's allocation -- and the
+ * buffer of a device-built encode plan also holds the planner's own job record behind the plan, whose words name the
+ * planner's workspace: the solve never reads that record, and the next build of a plan on the planner's stream, which writes
+ * the workspace, needs no order against it. */
+void jobs_footprint(const hm_arg *a, int n, uint32_t nblk) {
+  if (n < 1 || a[0].kind != HM_ARG_CONST_PTR || !a[0].p) return;
+  const nrq_job *jobs = (const nrq_job *)a[0].p;
+  if (!hm_effect_touch(jobs, (size_t)nblk * sizeof(nrq_job), 0)) return;
+  /* one touch per allocation (an operation counts once on the allocations it touches): from the lowest address named, written
+   * if any of them is */
+  std::map<uint64_t, std::pair<uint64_t, int>> al; /* base -> (lowest address, written) */
+  auto name = [&](uint64_t p, int write) {
+    if (!p) return;
+    const uint64_t base = hm_effect_base((const void *)(uintptr_t)p);
+    if (!base) { (void)hm_effect_touch((const void *)(uintptr_t)p, 1, write); return; } /* (H2) */
+    auto it = al.emplace(base, std::make_pair(p, write)).first;
+    it->second.first = std::min(it->second.first, p);
+    it->second.second |= write;
+  };
+  for (uint32_t b = 0; b < nblk; b++) {
+    const nrq_job &j = jobs[b];
+    for (uint64_t r : {j.plan, j.rowsrc, j.rep, j.out_cptr, j.out_slots, j.out_row}) name(r, 0);
+    for (uint64_t w : {j.src, j.inter, j.out}) name(w, 1);
+  }
+  for (int i = 1; i < n; i++)
+    if (a[i].kind == HM_ARG_PTR || a[i].kind == HM_ARG_CONST_PTR) name((uint64_t)(uintptr_t)a[i].p, a[i].kind == HM_ARG_PTR);
+  for (auto &kv : al) (void)hm_effect_touch_tail((const void *)(uintptr_t)kv.second.first, kv.second.second);
+}
+void solve_effect(const hm_arg *a, int n) {
+  uint32_t nblk;
+  if (n >= 2 && u32_arg(a[1], &nblk)) jobs_footprint(a, n, nblk);
+}
+void backsub_effect(const hm_arg *a, int n) {
+  unsigned g[3];
+  hm_effect_grid(g);
+  jobs_footprint(a, n, g[2]);
+}
+void collect_effect(const hm_arg *a, int n) {
+  unsigned g[3];
+  hm_effect_grid(g);
+  jobs_footprint(a, n, g[1]);
+}
+
 struct Register {
   Register() {
+    hm_set_effect("nrq_solve_kernel", solve_effect, 1);
+    hm_set_effect("nrq_backsub_kernel", backsub_effect, 1);
+    hm_set_effect("nrq_collect_kernel", collect_effect, 1);
     hm_set_effect("nrq_plan_kernel", plan_effect, 1);
     for (const char *k : {"nrq_wentry_kernel", "nrq_wpass_kernel", "nrq_mh_kernel", "nrq_wt_kernel"}) hm_set_effect(k, plan_helper_effect, 1);
   }

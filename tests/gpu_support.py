@@ -2,13 +2,16 @@
 
 Two shared contexts: "forced" (ctx(), the options below pin the device planner and every small workgroup form) and
 "default" (default_ctx(), no option set: the launch choices a product caller gets).  gpu_encode / gpu_decode take
-kind= to pick one; bound(kind) gives a module-like view with the same three functions bound to it."""
+kind= to pick one; bound(kind) gives a module-like view with the same three functions bound to it.  A third kind, "side", is a
+default context created on a torch.cuda.Stream() of its own (side_stream() is that stream; new_side() makes further ones): the
+null stream orders caller and library work by accident, a side stream does not (tests/test_gpu_streams.py)."""
 import numpy as np
 
 import nanorq_amd
 
-KINDS = ("forced", "default")
+KINDS = ("forced", "default", "side")
 _CTXS = {}
+_STREAMS = {}   # context -> its torch stream (kept alive as long as the context)
 
 
 def _torch_up():
@@ -25,13 +28,15 @@ def _torch_up():
 
 
 def ctx(kind="forced"):
+    if isinstance(kind, nanorq_amd.Context):   # (a context of the caller's own: gpu_encode / gpu_decode run on it)
+        return kind
     c = _CTXS.get(kind)
     if c is not None:
         return c
     if kind not in KINDS:
         raise ValueError("unknown context kind %r" % kind)
     _torch_up()
-    c = nanorq_amd.Context(0)
+    c = new_side()[0] if kind == "side" else nanorq_amd.Context(0)
     if kind == "forced":
         # the parity tests are about the DEVICE planner at every size and block count; a product context gives calls of one or two small
         # blocks to the host planner (nrq_decode_blocks_lazy "host_small"), which test_small_calls_take_the_host_planner covers
@@ -43,6 +48,73 @@ def ctx(kind="forced"):
         c.set_option("tiny_any", 1)
     _CTXS[kind] = c
     return c
+
+
+_PROBE = []     # the probe's work tensor
+_REJECTED = []  # streams the probe turned down, kept alive so that torch hands out others
+
+
+def shares_a_queue(s, other=None, ms=5.0):
+    """Does work on stream s wait for work on `other` (default: the null stream)?  The runtime multiplexes a process's streams
+    over a few hardware queues (GPU_MAX_HW_QUEUES); two streams on one queue take turns, so a kernel put on the wrong one of them
+    still runs in order -- by accident, exactly what a side-stream test wants to rule out.  The probe: a few ms of passes over a
+    tensor on `other`, one tiny kernel on s, wait for s: did the passes end first?"""
+    import torch
+    other = other or torch.cuda.default_stream()
+    if not _PROBE:
+        _PROBE.append(torch.zeros(16 << 20, dtype=torch.int32, device="cuda"))
+        for _ in range(3):
+            _PROBE[0].add_(1)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(50):
+            _PROBE[0].add_(1)
+        b.record()
+        torch.cuda.synchronize()
+        _PROBE.append(max(1, int(ms / (a.elapsed_time(b) / 50))))
+    torch.cuda.synchronize()
+    with torch.cuda.stream(other):
+        for _ in range(_PROBE[1]):
+            _PROBE[0].add_(1)
+        ev = torch.cuda.Event()
+        ev.record(other)
+    with torch.cuda.stream(s):
+        torch.zeros(1, device="cuda")
+    s.synchronize()
+    shared = ev.query()
+    torch.cuda.synchronize()
+    return shared
+
+
+def new_side(tries=12):
+    """(context, stream): a fresh context with no option set on a fresh torch.cuda.Stream() (non-blocking: the null stream does
+    not wait for it, nor it for the null stream) -- one that does not share its hardware queue with the null stream, if `tries`
+    streams yield one (side_independent(c) says whether)."""
+    import torch
+    _torch_up()
+    for k in range(tries):
+        s = torch.cuda.Stream()
+        shared = shares_a_queue(s)
+        if not shared:
+            break
+        _REJECTED.append(s)
+    c = nanorq_amd.Context(0, s.cuda_stream)
+    _STREAMS[c] = s
+    _INDEPENDENT[c] = not shared
+    return c, s
+
+
+_INDEPENDENT = {}
+
+
+def side_independent(c=None):
+    """the side stream of c (default: of ctx("side")) was seen NOT to wait for work on the null stream"""
+    return _INDEPENDENT[c or ctx("side")]
+
+
+def side_stream(c=None):
+    """the torch stream of a side-stream context (default: of ctx("side"))"""
+    return _STREAMS[c or ctx("side")]
 
 
 def default_ctx():

@@ -625,7 +625,180 @@ def group_refusal():
     return out
 
 
-GROUPS = {"detector": group_detector, "pool": group_pool, "fuzz0": group_fuzz0, "sync": group_sync, "refusal": group_refusal}
+# ------------------------------------------------------------------- g. a context on a stream of the caller's own ----
+def caller_ctx(r, device_planner):
+    """a context on a fresh model stream (every other group's contexts live on stream 0, where an operation the library puts on
+    stream 0 by mistake IS in stream order)"""
+    s = r.stream()
+    c = nanorq_amd.Context(0, s)
+    c.set_planner(device_planner)
+    return c, s
+
+
+def more_scenarios(c, r):
+    """on context c: the device build of an encode plan, nrq_decode_plan_ahead on one block list, a decode whose blocks go out in
+    two lists, and the row movers / the control copy on the stream selectors 0 .. 3 over buffers the context's stream has just
+    written.  Returns what each step saw."""
+    L = r.L
+    out = {}
+    # the encode plan built on the device (the planner kernel on a stream of the context's own, the encode behind it)
+    K, T, nblk = 300, 32, 3
+    L_ = nanorq_amd.params(K)["L"]
+    src = np.stack([payload(K * T, seed=4, block=b).reshape(K, T) for b in range(nblk)])
+    esis = np.arange(K, K + 20, dtype=np.uint32)
+    d_src, d_rep, d_int = c.alloc(nblk * K * T), c.alloc(nblk * 20 * T), c.alloc(nblk * L_ * T)
+    c.upload(d_src, src)
+    c.set_option("encplan_dev_min_l", 1)
+    for rnd in range(3):
+        c.clear_plan_cache()
+        c.memset(d_rep, rnd, nblk * 20 * T)
+        c.precalculate(K)
+        c.encode_blocks(K, T, nblk, d_src, K * T, d_rep, 20 * T, esis, d_int, L_ * T)
+    out["encplan"] = dict(encplan_device=c.stats()["encplan_device"])
+    c.set_option("encplan_dev_min_l", 12000)   # (its default)
+    c.sync()
+    # two lists: receptions that grow heavier over the batch, the LDS bound lowered until some blocks' images no longer fit
+    K, T, nblk = 1000, 32, 8
+    src = np.stack([payload(K * T, seed=6, block=b).reshape(K, T) for b in range(nblk)])
+    lost = [loss_pattern(K, 0.10 + 0.5 * b / nblk, seed=11, block=b) for b in range(nblk)]
+    nrep = max(len(x) for x in lost) + 2
+    la = np.zeros((nblk, max(len(x) for x in lost)), np.uint32)
+    for b in range(nblk):
+        la[b, :len(lost[b])] = lost[b]
+    nl = np.array([len(x) for x in lost], np.uint32)
+    re = np.tile(np.arange(K, K + nrep, dtype=np.uint32), (nblk, 1))
+    e_src, e_rep = c.alloc(nblk * K * T), c.alloc(nblk * nrep * T)
+    c.upload(e_src, src)
+    two = None
+    for kb in range(160, 8, -4):
+        c.set_option("lds_max", kb * 1024)
+        c.memset(e_rep, kb, nblk * nrep * T)
+        try:
+            st = c.decode_blocks(K, T, nblk, e_src, K * T, la, nl, re, nl + 2, e_rep, nrep * T)
+        except nanorq_amd.NrqError:
+            break
+        s_ = c.stats()
+        if 0 < s_["blocks_b"] < nblk:
+            two = dict(lds_max=kb * 1024, blocks_b=s_["blocks_b"], strip_bytes=s_["strip_bytes"], strip_bytes_b=s_["strip_bytes_b"],
+                       status=[int(x) for x in st])
+            # ... and once more with the planner run issued ahead
+            c.decode_plan_ahead(K, T, nblk, e_src, K * T, la, nl, re, nl + 2, None, e_rep, nrep * T)
+            c.memset(e_rep, 1, nblk * nrep * T)
+            c.decode_blocks(K, T, nblk, e_src, K * T, la, nl, re, nl + 2, e_rep, nrep * T)
+            two["plan_ahead"] = c.stats()["plan_ahead"]
+            break
+    c.set_option("lds_max", 0)
+    out["two_lists"] = two
+    c.sync()
+    # rows by address list and the control copy, selectors 0 .. 3: each on buffers the context's stream wrote last, ordered by the
+    # caller's event (nrq_event_record on selector 0, nrq_stream_wait on the selector's stream) -- and back
+    L.nrq_scatter_symbols.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint32, vp]
+    L.nrq_move_rows_dev.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint32]
+    L.nrq_ctl_copy.argtypes = [vp, C.c_int, vp, vp, sz]
+    L.nrq_event_new.argtypes = [vp, C.POINTER(vp)]
+    L.nrq_event_record.argtypes = [vp, vp, C.c_int]
+    L.nrq_stream_wait.argtypes = [vp, C.c_int, vp]
+    L.nrq_event_free.argtypes = [vp]
+    L.nrq_stream_sync.argtypes = [vp, C.c_int]
+    n, T = 64, 48
+    blob, rows, rows2, pairs = c.alloc(n * T), c.alloc(n * T), c.alloc(n * T), c.alloc(n * 16)
+    pin, pv = r.pinned(n * 16)
+    ev = vp()
+    assert L.nrq_event_new(c._h, C.byref(ev)) == 0
+    movers = []
+    for sel in range(4):
+        dst = (rows + np.arange(n, dtype=np.uint64)[::-1] * T).astype(np.uint64)
+        pv.view(np.uint64)[:] = np.stack([rows + np.arange(n, dtype=np.uint64) * T, rows2 + np.arange(n, dtype=np.uint64) * T], 1).reshape(-1)
+        c.memset(blob, 0x20 + sel, n * T)          # the context's stream writes the buffers ...
+        c.memset(rows, 0, n * T)
+        c.memset(rows2, 0, n * T)
+        assert L.nrq_event_record(c._h, ev, 0) == 0 and L.nrq_stream_wait(c._h, sel, ev) == 0
+        rc = [L.nrq_ctl_copy(c._h, sel, vp(pairs), vp(pin), n * 16),            # ... the selector's stream moves them ...
+              L.nrq_scatter_symbols(c._h, sel, vp(blob), n, T, dst.ctypes.data_as(vp)),
+              L.nrq_move_rows_dev(c._h, sel, vp(pairs), n, T)]
+        assert L.nrq_event_record(c._h, ev, sel) == 0 and L.nrq_stream_wait(c._h, 0, ev) == 0
+        got = c.download(rows2, n * T)             # ... and the context's stream reads the result
+        movers.append(dict(sel=sel, rc=rc, moved=bool((got == 0x20 + sel).all())))
+        assert L.nrq_stream_sync(c._h, sel) == 0   # (the pinned list is rewritten in the next round)
+    out["movers"] = movers
+    L.nrq_event_free(ev)
+    for p in (d_src, d_rep, d_int, e_src, e_rep, blob, rows, rows2, pairs):
+        c.free(p)
+    return out
+
+
+def set_stream_scenario(r):
+    """nrq_ctx_set_stream to a second model stream between two calls that touch the same buffers, and back to stream 0"""
+    c, s1 = caller_ctx(r, False)
+    s2 = r.stream()
+    K, T, nblk = 300, 64, 4
+    L_ = nanorq_amd.params(K)["L"]
+    src = np.stack([payload(K * T, seed=3, block=b).reshape(K, T) for b in range(nblk)])
+    esis = np.arange(K, K + 30, dtype=np.uint32)
+    d_src, d_rep, d_int = c.alloc(nblk * K * T), c.alloc(nblk * 30 * T), c.alloc(nblk * L_ * T)
+    c.upload(d_src, src)
+    pend = []
+    for st in (s2, 0, s1):
+        c.encode_blocks(K, T, nblk, d_src, K * T, d_rep, 30 * T, esis, d_int, L_ * T)
+        c.memset(d_src, 1, nblk * K * T)
+        before = model().hm_pending_on(vp(d_rep))
+        c.set_stream(st)
+        pend.append((before, model().hm_pending_on(vp(d_rep))))
+        c.memset(d_rep, 2, nblk * 30 * T)
+        c.encode_blocks(K, T, nblk, d_src, K * T, d_rep, 30 * T, esis, d_int, L_ * T)
+    c.sync()
+    for p in (d_src, d_rep, d_int):
+        c.free(p)
+    c.close()
+    return dict(pending_before_and_after_set_stream=pend)
+
+
+def group_callerstream():
+    r = Rt()
+    hazards()
+    out = {}
+    for name, dev in (("host_planner", False), ("device_planner", True)):
+        c, _ = caller_ctx(r, dev)
+        c.set_option("host_plan_auto", 0)
+        res = sync_scenarios(c, dev)
+        res["more"] = more_scenarios(c, r)
+        c.set_option("host_plan_auto", 1)
+        W = Checked(c)
+        f = random_shapes(W, 0, trials=8)
+        f.update(bad_downloads=W.bad_downloads, pending_after_sync=W.pending_after_sync[:8], syncs=W.calls)
+        res["fuzz"] = f
+        c.close()
+        res["hazards"] = brief(hazards())
+        out[name] = res
+    out["set_stream"] = set_stream_scenario(r)
+    out["set_stream"]["hazards"] = brief(hazards())
+    # the detector on the library's own pattern: a blocking copy goes to stream 0, whatever stream the context is on
+    det = {}
+
+    def done(name):
+        det[name] = dict(kinds=[h["kind"] for h in hazards(clear=False)], text=brief(hazards()))
+
+    s1 = r.stream()
+    d = r.malloc(4096)
+    host = np.zeros(4096, np.uint8)
+    r.launch("k_reads_table", s1, ("cptr", d))
+    r.ok(r.L.hipMemcpy(vp(d), vp(host.ctypes.data), 4096, H2D))
+    done("blocking_copy_beside_a_kernel_on_the_context_stream")
+    r.sync(s1)
+    r.launch("k_reads_table", s1, ("cptr", d))
+    r.sync(s1)
+    r.ok(r.L.hipMemcpy(vp(d), vp(host.ctypes.data), 4096, H2D))
+    done("blocking_copy_behind_a_stream_synchronisation")
+    r.launch("k_reads_table", s1, ("cptr", d))      # (the blocking copy has returned: the host has waited for it)
+    done("kernel_behind_a_blocking_copy")
+    r.sync(s1)
+    out["detector"] = det
+    out["counters"] = counters()
+    out["pending_at_end"] = model().hm_pending_total()
+    return out
+
+
+GROUPS = {"detector": group_detector, "callerstream": group_callerstream, "pool": group_pool, "fuzz0": group_fuzz0, "sync": group_sync, "refusal": group_refusal}
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@ allocation's lifetime; it reports
     H3  a host allocation released under a pending operation,
     H4  a page-locked upload source changed before the host synchronised behind the copy.
 Kernels do not run (hip_model.h lists the assumptions); what the GPU tier cannot see -- an ordering that only holds by luck -- is
-what these tests are about, what only kernels compute is not.  Each group runs once, in a child process (host_model_worker.py)."""
+what these tests are about, what only kernels compute is not.  Each group runs once, in a child process (host_model_worker.py).
+Group g runs the host layer with its context on a stream of the caller's own, where a call the library puts on stream 0 shows."""
 import json
 import os
 import subprocess
@@ -162,6 +163,58 @@ def test_a_split_launch_whose_tables_exceed_the_lds_is_refused_before_any_launch
     assert r["next"]["status"] == [1, 1] and r["next"]["strip_bytes"] == 4 and r["next"]["backsub_strip"] == 32 and r["next"]["u"] < 200, r
     assert r["launches_of_the_next_call"] == 3, r
     assert r["hazards"] == [], r["hazards"][:6]
+
+
+# ------------------------------------------------------------------- g. a context on a stream of the caller's own ----
+# Every group above creates its contexts on stream 0, where an operation the library puts on stream 0 instead of the context's
+# stream IS in stream order.  Here the context lives on a model stream of its own (host_model_worker.py "callerstream").
+@pytest.mark.parametrize("planner", ["host_planner", "device_planner"])
+def test_a_context_on_a_caller_s_stream_raises_no_hazard(planner):
+    """the scenarios of group d, the device build of an encode plan (three times, the plan cache cleared in between), a decode whose
+    blocks go out in two lists (and once more behind nrq_decode_plan_ahead), nrq_ctl_copy / nrq_scatter_symbols / nrq_move_rows_dev on
+    the stream selectors 0 .. 3 ordered by the caller's events, and eight draws of random_shapes[0]: no hazard, nothing pending
+    behind nrq_ctx_sync"""
+    s = run("callerstream")[planner]
+    dev = planner == "device_planner"
+    for step in ("encode", "decode", "plan_ahead"):
+        assert s[step]["after_sync"] == [0, 0, 0], (step, s[step])
+    assert s["encode"]["before_sync"] == [1, 1, 1] and s["decode"]["before_sync"] == [1, 1, 1]   # (there was work in flight)
+    assert s["decode"]["planner"] == int(dev) and s["decode"]["status"] == [1] * 5
+    assert all(r["status"] == [1] * 5 and r["plan_ahead"] == int(dev) for r in s["plan_ahead"]["rounds"]), s["plan_ahead"]
+    assert s["plan_ahead_two_deep"]["after_sync"] == [0, 0, 0] and s["plan_ahead_two_deep"]["status"] == [1] * 10
+    m = s["more"]
+    two = m["two_lists"]
+    assert two and 0 < two["blocks_b"] < 8 and two["status"] == [1] * 8 and two["strip_bytes_b"] < two["strip_bytes"], two
+    assert two["plan_ahead"] == int(dev), two
+    assert [x["sel"] for x in m["movers"]] == [0, 1, 2, 3] and all(x["rc"] == [0, 0, 0] and x["moved"] for x in m["movers"]), m["movers"]
+    f = s["fuzz"]
+    assert f["decodes"] == 8 and f["bad_downloads"] == [] and f["pending_after_sync"] == [] and f["syncs"] == 16, f
+    assert f["host_planned"] == (4 if dev else 8), f    # (a default context gives its calls of one or two blocks to the host planner)
+    assert s["hazards"] == [], s["hazards"][:6]
+
+
+def test_set_stream_between_two_calls_on_the_same_buffers():
+    """nrq_ctx_set_stream to a second stream, to stream 0 and back, each time between an encode and a memset + encode over the same
+    three buffers: the move waits for the stream it leaves, so nothing is pending on them when the new stream takes over"""
+    s = run("callerstream")["set_stream"]
+    assert s["pending_before_and_after_set_stream"] == [[1, 0]] * 3, s
+    assert s["hazards"] == [], s["hazards"][:6]
+
+
+CALLER_DETECTOR = [   # the library's own pattern for its tables: a blocking copy is an operation on stream 0 the host then waits for
+    ("blocking_copy_beside_a_kernel_on_the_context_stream", ["H1"]), ("blocking_copy_behind_a_stream_synchronisation", []),
+    ("kernel_behind_a_blocking_copy", []),
+]
+
+
+@pytest.mark.parametrize("name,kinds", CALLER_DETECTOR, ids=[d[0] for d in CALLER_DETECTOR])
+def test_the_detector_sees_a_blocking_copy_as_an_operation_on_stream_0(name, kinds):
+    d = run("callerstream")
+    assert d["detector"][name]["kinds"] == kinds, d["detector"][name]["text"]
+    if kinds:
+        t = d["detector"][name]["text"][0]
+        assert "hipMemcpy H2D 4096 B [stream 0" in t and "launch k_reads_table [stream" in t, t
+    assert d["pending_at_end"] == 0 and d["counters"]["unnamed_launches"] == 0
 
 
 # ------------------------------------------------------------- e. the object layer under fault injection, f. ----
