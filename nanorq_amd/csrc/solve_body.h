@@ -246,6 +246,17 @@ template <int WB, int G = 1> SB_HD void lds_xor(uint8_t *lds, uint32_t idx, cons
   lds_put<WB, G>(lds, idx, t);
 #endif
 }
+/* a PIECE of an element: PB = 4 or 8 bytes at byte offset `at` of the region (a multiple of PB: elements of 8 and 16 bytes lie on
+ * their own width, the 12-byte ones on 4 bytes and take pieces of 4 only) -- one ds_read_b32 / ds_read_b64, one ds_xor_b32 /
+ * ds_xor_b64.  For phases that deal the bytes of an element over adjacent lanes (ph_hdpc). */
+template <int PB> SB_HD SV<PB> lds_get_piece(const uint8_t *lds, uint32_t at) {
+  static_assert(PB == 4 || PB == 8, "pieces of one or two dwords");
+  return lds_get<PB>(lds + at, 0u);
+}
+template <int PB> SB_HD void lds_xor_piece(uint8_t *lds, uint32_t at, const SV<PB> &v) {
+  static_assert(PB == 4 || PB == 8, "pieces of one or two dwords");
+  lds_xor<PB>(lds + at, 0u, v);
+}
 
 /* ---- global strip access: `valid` bytes (<= WB) at p ---- */
 template <int WB> SB_HD SV<WB> g_get(const NRQ_GAS uint8_t *p, uint32_t valid) {
@@ -1129,19 +1140,54 @@ template <int WB, int G> SB_HD void hdpc_chunk_regs(const StripCtx<WB, G> &c, ui
     if (h < H) lds_xor<WB, G>(c.cf(), mine + h, acc[h]);
   }
 }
-template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt) {
+/* PIECE form of the LDS-atomic path (strips of 8, 12 and 16 bytes): the closing fold costs a chunk 8 x H masked XORs per dword
+ * whatever the chunk holds, so with one chunk per thread over the whole strip width it is paid nt x WB / 4 times.  Byte columns
+ * are independent: GP = WB / PB adjacent lanes share ONE chunk, GP times as long, and each carries its own PB bytes of the
+ * strip through the same recurrence -- nt / GP chunks, the same steps, a GP-th of the folds.  The lanes of a chunk write the
+ * same accumulator entries at their own offsets. */
+#ifndef NRQ_HDPC_PIECE
+#define NRQ_HDPC_PIECE -1 /* piece bytes of every variant that can take them: 4, 8, or 0 = whole-strip chunks (-1: hdpc_piece's own choice) */
+#endif
+/* bytes of the strip a thread of an nt-thread HDPC phase carries (WB: a chunk per thread).  16-byte strips, measured (ms per
+ * step, whole strip / pieces of 4 / of 8): 512 threads of the 768-thread workgroup K=8192 12.79 / 12.70 / 12.67, K=5000 9.12 /
+ * 8.97 / 8.85; 256 threads K=1000 2.716 / 2.617 / 2.693, K=2000 4.094 / 4.060 / 4.117; the single wave K=500 1.824 / 1.776 /
+ * 1.775.  12-byte strips keep the whole-strip chunk (K=10000, decode solve 6.96 -> 7.15 ms with pieces of 4); 8-byte strips were
+ * not measured and keep it too. */
+template <int WB, int G> SB_HD constexpr uint32_t hdpc_piece(uint32_t nt) {
+  if (G != 1 || WB < 8) return (uint32_t)WB;
+  if (NRQ_HDPC_PIECE == 0) return (uint32_t)WB;
+  if (NRQ_HDPC_PIECE == 8) return WB == 16 ? 8u : (uint32_t)WB;
+  if (NRQ_HDPC_PIECE == 4) return 4u;
+  if (WB != 16) return (uint32_t)WB;
+  return nt >= 512u ? 8u : 4u;
+}
+template <int WB, int G, bool REGS, int PB> SB_HD void hdpc_chunks(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt_) {
+  static_assert(PB == WB || (G == 1 && !REGS && WB % PB == 0), "pieces: whole dwords of a plain strip, LDS-atomic form");
+  constexpr uint32_t GP = (uint32_t)(WB / PB);
   const nrq_kconst_hdr *kh = reinterpret_cast<const nrq_kconst_hdr *>(c.kc);
   const NRQ_GAS uint8_t *Gm = gptr<uint8_t>(c.kc + kh->off_g); /* the HDPC block */
   const NRQ_GAS uint8_t *b12 = gptr<uint8_t>(c.kc + kh->off_b12);
   const NRQ_GAS uint16_t *pivof = c.template arr<uint16_t>(c.h->off_pivof);
   const uint32_t n = kh->n, H = c.h->H;
-  const uint32_t mine = (tid & (hdpc_nsets<WB, G>(c) - 1u)) * H; /* this lane's copy of the H accumulators */
-  /* chunks of whole 8-column groups, as equal as possible; the threads that take one group more are the FIRST
+  const uint32_t nt = nt_ / GP, pofs = (tid % GP) * (uint32_t)PB; /* chunks; this lane's bytes of every element */
+  tid /= GP;                                                      /* (from here on: the chunk) */
+  if (GP > 1u && tid >= nt) return;                               /* (12-byte strips: lanes that make no whole triple) */
+  const uint32_t mine = (tid & (hdpc_nsets<WB, G>(c) - 1u)) * H; /* this chunk's copy of the H accumulators */
+  /* element idx of the slots / of the accumulator copies, this lane's piece of it */
+  auto y_get = [&](uint32_t idx) -> SV<PB> {
+    if constexpr (PB == WB) return lds_get<WB, G>(c.slots(), idx);
+    else return lds_get_piece<PB>(c.slots(), idx * (uint32_t)WB + pofs);
+  };
+  auto acc_xor = [&](uint32_t idx, const SV<PB> &v) {
+    if constexpr (PB == WB) lds_xor<WB, G>(c.cf(), idx, v);
+    else lds_xor_piece<PB>(c.cf(), idx * (uint32_t)WB + pofs, v);
+  };
+  /* chunks of whole 8-column groups, as equal as possible; the chunks that take one group more are the FIRST
    * ones, so that a single wave (not one lane of every wave) runs the longer loop */
-  /* (small blocks: groups of 4 or 2 columns while there are fewer groups than threads -- the closing fold below costs a wave the
+  /* (small blocks: groups of 4 or 2 columns while there are fewer groups than chunks -- the closing fold below costs a wave the
    * same instructions whether its lanes close 8 columns or 2, the recurrence costs it per column of its longest lane: K=100 on
    * a single wave is 15 lanes x 8 columns as groups of 8, 59 lanes x 2 as groups of 2) */
-  const uint32_t gsz = (n + 1u) / 2u <= nt ? 2u : (n + 3u) / 4u <= nt ? 4u : 8u; /* (smaller than 8: at most one group per thread) */
+  const uint32_t gsz = (n + 1u) / 2u <= nt ? 2u : (n + 3u) / 4u <= nt ? 4u : 8u; /* (smaller than 8: at most one group per chunk) */
   const uint32_t groups = (n + gsz - 1u) / gsz, base = groups / nt, extra = groups - base * nt;
   const uint32_t a = gsz * (tid * base + (tid < extra ? tid : extra));
   if (a >= n || (base == 0u && tid >= extra)) return;
@@ -1153,8 +1199,8 @@ template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCt
       return;
     }
   }
-  SV<WB> g = sv_zero<WB>();
-  if (gsz < 8u) { /* one group of at most 4 columns per thread (groups < nt): slot numbers and MT rows column by column, in flight together */
+  SV<PB> g = sv_zero<PB>();
+  if (gsz < 8u) { /* one group of at most 4 columns per chunk (groups < nt): slot numbers and MT rows column by column, in flight together */
     uint32_t sl4[4], e4[4];
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++) {
@@ -1166,19 +1212,73 @@ template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCt
     for (uint32_t q = 0; q < 4; q++) {
       const uint32_t col = a + q;
       if (col >= b) break;
-      g = sv_xtime<WB>(g);
+      g = sv_xtime<PB>(g);
       if (sl4[q] != NRQ_NOSLOT) {
-        SV<WB> y = lds_get<WB, G>(c.slots(), sl4[q]);
-        sv_xor<WB>(g, y);
+        SV<PB> y = y_get(sl4[q]);
+        sv_xor<PB>(g, y);
       }
       if (col + 1 < n) {
-        lds_xor<WB, G>(c.cf(), mine + (e4[q] & 15u), g);
-        lds_xor<WB, G>(c.cf(), mine + (e4[q] >> 4), g);
+        acc_xor(mine + (e4[q] & 15u), g);
+        acc_xor(mine + (e4[q] >> 4), g);
       } else { /* last column of MT is alpha^h */
-        SV<WB> v = g;
+        SV<PB> v = g;
         for (uint32_t h = 0; h < H; h++) {
-          lds_xor<WB, G>(c.cf(), mine + h, v);
-          v = sv_xtime<WB>(v);
+          acc_xor(mine + h, v);
+          v = sv_xtime<PB>(v);
+        }
+      }
+    }
+  } else if constexpr (GP > 1u) {
+    /* pieces, 8 columns per step.  A chunk holds GP times as many groups, each behind a trip to L2 of its own: the NEXT group's slot
+     * numbers and MT rows are asked for before this group's columns, as in hdpc_chunk_regs; and a piece is small enough to read
+     * the group's eight of them first, unconditionally (a column without a slot, or beyond the chunk, reads the lane's zero
+     * scratch slot), so that no column waits for its own trip to the LDS.  Whole groups -- all but the block's last -- then run
+     * without a test per column. */
+    const uint32_t zero_at = (tid * GP + pofs / (uint32_t)PB) & (NRQ_SCRATCH - 1u);
+    uint4 sl_n = *reinterpret_cast<const NRQ_GAS uint4 *>(pivof + a);
+    uint2 bb_n = *reinterpret_cast<const NRQ_GAS uint2 *>(b12 + a);
+    for (uint32_t c0 = a; c0 < b; c0 += 8) {
+      const uint4 sl = sl_n;
+      const uint2 bb = bb_n;
+      if (c0 + 8u < b) {
+        sl_n = *reinterpret_cast<const NRQ_GAS uint4 *>(pivof + c0 + 8u);
+        bb_n = *reinterpret_cast<const NRQ_GAS uint2 *>(b12 + c0 + 8u);
+      }
+      const uint32_t slw[4] = {sl.x, sl.y, sl.z, sl.w};
+      const uint32_t bbw[2] = {bb.x, bb.y};
+      SV<PB> y[8];
+#pragma unroll
+      for (uint32_t q = 0; q < 8; q++) {
+        const uint32_t sq = (slw[q >> 1] >> ((q & 1u) * 16u)) & 0xFFFFu;
+        y[q] = lds_get_piece<PB>(c.lds, ((c0 + q < b && sq != NRQ_NOSLOT) ? sq + NRQ_SCRATCH : zero_at) * (uint32_t)WB + pofs);
+      }
+      if (c0 + 8u <= b && c0 + 8u < n) { /* a whole group, MT's last column not in it */
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) {
+          const uint32_t e = (bbw[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu;
+          g = sv_xtime<PB>(g);
+          sv_xor<PB>(g, y[q]);
+          acc_xor(mine + (e & 15u), g);
+          acc_xor(mine + (e >> 4), g);
+        }
+        continue;
+      }
+#pragma unroll
+      for (uint32_t q = 0; q < 8; q++) {
+        const uint32_t col = c0 + q;
+        if (col >= b) break;
+        g = sv_xtime<PB>(g);
+        sv_xor<PB>(g, y[q]);
+        if (col + 1 < n) {
+          const uint32_t e = (bbw[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu;
+          acc_xor(mine + (e & 15u), g);
+          acc_xor(mine + (e >> 4), g);
+        } else { /* last column of MT is alpha^h */
+          SV<PB> v = g;
+          for (uint32_t h = 0; h < H; h++) {
+            acc_xor(mine + h, v);
+            v = sv_xtime<PB>(v);
+          }
         }
       }
     }
@@ -1195,20 +1295,20 @@ template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCt
       const uint32_t col = c0 + q;
       if (col >= b) break;
       const uint32_t s = (slw[q >> 1] >> ((q & 1u) * 16u)) & 0xFFFFu;
-      g = sv_xtime<WB>(g);
+      g = sv_xtime<PB>(g);
       if (s != NRQ_NOSLOT) {
-        SV<WB> y = lds_get<WB, G>(c.slots(), s);
-        sv_xor<WB>(g, y);
+        SV<PB> y = y_get(s);
+        sv_xor<PB>(g, y);
       }
       if (col + 1 < n) {
         const uint32_t e = (bbw[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu;
-        lds_xor<WB, G>(c.cf(), mine + (e & 15u), g);
-        lds_xor<WB, G>(c.cf(), mine + (e >> 4), g);
+        acc_xor(mine + (e & 15u), g);
+        acc_xor(mine + (e >> 4), g);
       } else { /* last column of MT is alpha^h */
-        SV<WB> v = g;
+        SV<PB> v = g;
         for (uint32_t h = 0; h < H; h++) {
-          lds_xor<WB, G>(c.cf(), mine + h, v);
-          v = sv_xtime<WB>(v);
+          acc_xor(mine + h, v);
+          v = sv_xtime<PB>(v);
         }
       }
     }
@@ -1216,11 +1316,11 @@ template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCt
   NRQ_MARK(c, 0);
   if (b < n) {
     /* H products of the same vector: its 8 multiples by alpha^k once, then one masked XOR per set coefficient bit */
-    SV<WB> pw[8];
-    pw[0] = sv_xtime<WB>(g);
+    SV<PB> pw[8];
+    pw[0] = sv_xtime<PB>(g);
 #pragma unroll
-    for (int k = 1; k < 8; k++) pw[k] = sv_xtime<WB>(pw[k - 1]);
-    if (nt >= NRQ_HDPC_COEF_ALL_NT) { /* the H coefficients loaded together: one trip to L2 instead of one per HDPC row (the compiler may not
+    for (int k = 1; k < 8; k++) pw[k] = sv_xtime<PB>(pw[k - 1]);
+    if (nt_ >= NRQ_HDPC_COEF_ALL_NT) { /* the H coefficients loaded together: one trip to L2 instead of one per HDPC row (the compiler may not
                                        * move the next load above the LDS atomic of the term before) */
       uint32_t coef[16]; /* (H <= 16) */
 #pragma unroll
@@ -1228,21 +1328,32 @@ template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCt
 #pragma unroll
       for (uint32_t h = 0; h < 16; h++) {
         if (h >= H) break;
-        SV<WB> t = sv_zero<WB>();
+        SV<PB> t = sv_zero<PB>();
 #pragma unroll
-        for (int k = 0; k < 8; k++) sv_xor_masked<WB>(t, pw[k], 0u - ((coef[h] >> k) & 1u));
-        lds_xor<WB, G>(c.cf(), mine + h, t);
+        for (int k = 0; k < 8; k++) sv_xor_masked<PB>(t, pw[k], 0u - ((coef[h] >> k) & 1u));
+        acc_xor(mine + h, t);
       }
     } else {
       for (uint32_t h = 0; h < H; h++) {
         const uint32_t coef = Gm[(size_t)h * n + b];
-        SV<WB> t = sv_zero<WB>();
+        SV<PB> t = sv_zero<PB>();
 #pragma unroll
-        for (int k = 0; k < 8; k++) sv_xor_masked<WB>(t, pw[k], 0u - ((coef >> k) & 1u));
-        lds_xor<WB, G>(c.cf(), mine + h, t);
+        for (int k = 0; k < 8; k++) sv_xor_masked<PB>(t, pw[k], 0u - ((coef >> k) & 1u));
+        acc_xor(mine + h, t);
       }
     }
   }
+}
+/* nt: the threads of the phase (the kernel passes a constant: the form is chosen at compile time) */
+template <int WB, int G = 1, bool REGS = false> SB_HD void ph_hdpc(const StripCtx<WB, G> &c, uint32_t tid, uint32_t nt) {
+  if constexpr (G == 1 && !REGS && WB >= 8) {
+    const uint32_t pb = hdpc_piece<WB, G>(nt);
+    if constexpr (WB == 16) {
+      if (pb == 8u) { hdpc_chunks<WB, G, REGS, 8>(c, tid, nt); return; }
+    }
+    if (pb == 4u) { hdpc_chunks<WB, G, REGS, 4>(c, tid, nt); return; }
+  }
+  hdpc_chunks<WB, G, REGS, WB>(c, tid, nt);
 }
 
 /* phase 4a: the GF(2) combinations of the dense stage, E_p (slot M+p, zeroed by ph_clear) = XOR of the leftover rows that
