@@ -134,14 +134,14 @@ def _build_emu(target, src, headers, force):
 
 def build_emu(force=False):
     return _build_emu(EMU, os.path.join(ROOT, "tests", "emu", "solve_emu.cpp"),
-                      ("solve_body.h", "split_body.h", "plan.h", "rq_math.h", os.path.join(ROOT, "tests", "emu", "strip_emu.h")), force)
+                      ("solve_body.h", "solve_roles.h", "split_body.h", "plan.h", "rq_math.h", os.path.join(ROOT, "tests", "emu", "strip_emu.h")), force)
 
 
 def build_launch_emu(force=False):
     """tests/emu/liblaunch_emu.so: a whole solve launch on the CPU -- the shape launch_shape.h decides, every workgroup's work slots,
     movers and staging sets as nrq_solve_kernel runs them -- on arrays between pages nobody may touch (tests/emu/launch_emu.cpp)."""
     return _build_emu(NEMU, os.path.join(ROOT, "tests", "emu", "launch_emu.cpp"),
-                      ("launch_shape.h", "planner_body.h", "solve_body.h", "split_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h",
+                      ("launch_shape.h", "planner_body.h", "solve_body.h", "solve_roles.h", "split_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h",
                        os.path.join(ROOT, "tests", "emu", "strip_emu.h"), os.path.join(ROOT, "tests", "emu", "wave_emu.h")), force)
 
 
@@ -244,7 +244,7 @@ def build_obj_emu(force=False):
 def build_shape_emu(force=False):
     """tests/emu/libshape_emu.so: the launch decisions (launch_shape.h) behind a C interface; host code as it is, no emulation."""
     return _build_emu(SEMU, os.path.join(ROOT, "tests", "emu", "shape_emu.cpp"),
-                      ("launch_shape.h", "planner_body.h", "solve_body.h", "plan.h", "rq_math.h", "rfc6330_tables.h"), force)
+                      ("launch_shape.h", "planner_body.h", "solve_body.h", "solve_roles.h", "plan.h", "rq_math.h", "rfc6330_tables.h"), force)
 
 
 def build_model_lib(force=False, out=None, sanitize=False):
@@ -302,7 +302,7 @@ def build_rows_probe(force=False):
     third forms, rev_rows, fwd_rows_wide) and its address helpers in kernels that run them on images of the caller's.  A library
     of its own, so that libnanorq_hip.so holds no kernel it does not ship; cross-compiles without a GPU."""
     src = os.path.join(ROOT, "tests", "gpu", "rows_probe.hip")
-    if force or _newer(ROWS, [src, os.path.join(CSRC, "solve_body.h"), os.path.join(CSRC, "plan.h")]):
+    if force or _newer(ROWS, [src, os.path.join(CSRC, "solve_body.h"), os.path.join(CSRC, "solve_roles.h"), os.path.join(CSRC, "plan.h")]):
         subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + CSRC, "-shared", "-fPIC", src, "-o", ROWS], check=True)
     return ROWS
 

@@ -1,7 +1,8 @@
 /*
  * launch_shape.h -- what a launch will look like, decided before anything is launched.
  *
- *   Tuning / NRQ_KNOBS      every tuning and test knob, one row each
+ *   Tuning / NRQ_KNOBS      every tuning and test knob of the host, one row each
+ *   (solve_roles.h)         what an instance of nrq_solve_kernel decides about itself: its compile-time knobs, wave roles, phase forms
  *   NRQ_SOLVE_INSTANCES     every compiled nrq_solve_kernel instance, once (NRQ_PLAN_INSTANCES: nrq_plan_kernel)
  *   solve_lists()           which blocks of a batch are solved at which strip width (one launch or two)
  *   solve_shape()           one solve launch: instance, workgroups per CU, grid, work slots, staging strides, the split
@@ -22,6 +23,7 @@
 #include "plan.h"
 #include "rq_math.h"
 #include "solve_body.h"
+#include "solve_roles.h"
 #include "planner_body.h"
 
 #define NRQ_LDS_MAX 163840u /* 160 KiB per workgroup on gfx950 */
@@ -195,6 +197,10 @@ struct SolveKey {
 static const SolveKey nrq_solve_keys[] = {NRQ_SOLVE_INSTANCES(NRQ_SOLVE_KEY)};
 #undef NRQ_SOLVE_KEY
 static const int nrq_solve_nkeys = (int)(sizeof(nrq_solve_keys) / sizeof(nrq_solve_keys[0]));
+/* an instance that cannot work (solve_roles.h) fails the host build too, not only the kernels' */
+#define NRQ_SOLVE_CHECK(WB, NT, WV, G, AL) static_assert(solve_roles_valid(WB, NT, WV, G, AL), "nrq_solve_kernel<" #WB ", " #NT ", " #WV ", " #G ", " #AL ">");
+NRQ_SOLVE_INSTANCES(NRQ_SOLVE_CHECK)
+#undef NRQ_SOLVE_CHECK
 /* row of a key in nrq_solve_keys[] (and in the launch table made from the same list); -1: not compiled */
 static inline int solve_key_index(const SolveKey &k) {
   for (int i = 0; i < nrq_solve_nkeys; i++)

@@ -51,7 +51,7 @@
 static_assert(RQ_LT_COLS_MAX_REAL <= NRQ_LT_LIST_MAX, "solve_body.h sizes the slack behind out_slots[] for the longest LT list");
 static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's column list for the longest LT list");
 
-#include "launch_shape.h" /* the knobs, the instance lists, what a launch looks like: host code the tests compile on their own */
+#include "launch_shape.h" /* the knobs, the solve kernel's roles (solve_roles.h), the instance lists, what a launch looks like: host code the tests compile on their own */
 
 #define NRQ_GEN_WG 256
 
@@ -66,25 +66,6 @@ static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's colu
  * load -> forward passes -> HDPC -> dense stage -> back-substitution -> store).  While wave 0 runs the forward
  * passes of a strip, a few of the other waves gather a portion of the NEXT line group into the input staging
  * buffers and scatter a portion of the PREVIOUS group's results from the output staging buffers to their rows. */
-#ifndef NRQ_HDPC_NT
-#define NRQ_HDPC_NT 512 /* threads of the HDPC phase; measured: 256 / 512 / 768 -> 34 k / 28 k / 29 k clocks (the closing fold is per thread) */
-#endif
-#define NRQ_HDPC_NT_ ((uint32_t)NRQ_HDPC_NT)
-#ifndef NRQ_GATHER_WAVES_NARROW
-#define NRQ_GATHER_WAVES_NARROW 2u /* gather waves of the 768-thread workgroup on strips of at most NRQ_GATHER_WAVES_NARROW_WB bytes */
-#endif
-#ifndef NRQ_GATHER_WAVES_NARROW_WB
-#define NRQ_GATHER_WAVES_NARROW_WB 2
-#endif
-#ifndef NRQ_MOVER_WAVES
-#define NRQ_MOVER_WAVES 2u
-#endif
-#ifndef NRQ_RING_5W
-#define NRQ_RING_5W 36u /* five waves per SIMD: 102 registers per thread */
-#endif
-#ifndef NRQ_BIG_RING
-#define NRQ_BIG_RING NRQ_RING_MAX /* op-word ring (rows) of the two forward waves of the 768-thread workgroup */
-#endif
 /* NT threads per workgroup: NRQ_WG when one strip image owns the CU's LDS (big blocks), 256 when several fit (small
  * blocks: more workgroups per CU beat more waves per workgroup, each has its own single-wave forward pass).
  * `lsub`: log2 of the strips per work slot -- a whole line (128/WB strips) unless that leaves CUs without work. */
@@ -103,15 +84,6 @@ static_assert(RQ_LT_COLS_MAX_REAL <= TX_COLS, "emit_body.h sizes a packet's colu
                          * slot to see a scatter at all (the first slot has no results of a slot before it to move): strip 9 is in the second
                          * slot when slots are 8 strips (16- and 12-byte strips), in the first when they are 16 or more (8 bytes and narrower) */
 #endif
-#ifndef NRQ_W12_FW
-#define NRQ_W12_FW 3 /* forward waves of the 12-byte strip: 3 (a dword each) or 2 (two dwords, one dword) */
-#endif
-#ifndef NRQ_W12_GW
-#define NRQ_W12_GW 2 /* gather / scatter waves beside the three forward waves of the 12-byte strip */
-#endif
-#ifndef NRQ_W12_SW
-#define NRQ_W12_SW 2
-#endif
 template <int WB, int NT, int WV, int G = 1, bool AL = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WV)))
 void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
@@ -122,49 +94,13 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
                                                        uint8_t *__restrict__ ybuf, size_t ybuf_stride) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t tid = threadIdx.x;
-  /* NFW waves run the forward passes (two, half the strip width each, when the strip is wide enough and the workgroup
-   * big enough to spare a second SIMD); the waves on the other SIMDs move data meanwhile: NGW gather, NSW scatter */
-  static_assert(G == 1 || WB == 16, "wide strips are made of 16-byte lanes");
-  static_assert(WB != 12 || NT >= 512, "12-byte strips: the 768-thread workgroup only (blocks whose 16-byte image does not fit the LDS)");
-  constexpr uint32_t WBE = (uint32_t)WB * G; /* bytes of a strip */
-  constexpr bool ALX = AL && G == 1 && WB >= 4;
+  static_assert(solve_roles_valid(WB, NT, WV, G, AL), "wide strips are 16-byte lanes, 12-byte strips need the 768-thread workgroup, several waves need two movers");
+  /* who runs the forward passes, who moves data and in which form, the phases' forms: solve_roles.h.  (R is read in constant
+   * expressions only: read at run time it would be an object in the kernel's frame.) */
+  constexpr SolveRoles R = solve_roles(WB, NT, WV, G, AL);
+  constexpr uint32_t WBE(R.WBE), VNT(R.VNT), SPL(nrq_group_strips(WBE)), NFW(R.NFW), NGW(R.NGW), NSW(R.NSW), RU(R.RU), HNT(R.HNT), SLATE(R.SLATE), GLATE(R.GLATE);
+  constexpr bool MPIPE(R.MPIPE), ALX(R.ALX), LATE(R.LATE);
   const uint32_t vt = tid / G, subl = tid % G; /* virtual thread, lane inside it */
-  constexpr uint32_t VNT = NT / G;
-  constexpr uint32_t SPL = nrq_group_strips(WBE), NFW = (G == 1 && WB == 12 && NT >= 512) ? (uint32_t)NRQ_W12_FW : (G == 1 && WB >= 8 && NT >= 512) ? 2u : 1u,
-                     NMV = (NT / 64u) / 4u * (4u - NFW) + ((NT / 64u) % 4u > NFW ? (NT / 64u) % 4u - NFW : 0u),
-                     /* two gather and two scatter waves in the big workgroup, not three: every mover wave that keeps loads in
-                      * flight slows the forward waves' op words down (measured, headline encode: 3+3 -> row pipeline 89 k clocks,
-                      * gather done at 70 k; 2+2 -> 79 k / 83 k; 1+1 -> 72 k / 125 k) */
-                     /* (2-byte strips: the GATHER, not the forward wave, ends the window -- with work slots of 8 strips a row piece is
-                      * 16 bytes of a 128-byte line and the two gather waves are bound by their requests in flight; round 6, NRQ_PROF
-                      * marks at K'=56403: forward wave done 77 k clocks before the window's end, gather at its end) */
-                     /* (12-byte strips: three forward waves leave one SIMD free of them, three waves -- two gathering and one scattering
-                      * ended the forward window at 1.5 x (encode) and 2.7 x (decode) the forward waves' own time at K=10000; so the
-                      * movers are NRQ_W12_GW + NRQ_W12_SW of ALL nine other waves, the free SIMD's first) */
-                     NGW = NFW == 3u ? (uint32_t)NRQ_W12_GW : NMV >= 6u ? (WB <= NRQ_GATHER_WAVES_NARROW_WB ? NRQ_GATHER_WAVES_NARROW : NRQ_MOVER_WAVES) : NMV >= 3u ? 2u : 1u,
-                     NSW = NFW == 3u ? (uint32_t)NRQ_W12_SW : NMV >= 6u ? NRQ_MOVER_WAVES : NMV - NGW;
-  static_assert(NMV >= 2u || NT == 64, "workgroup too small for the data movers");
-  /* op-word ring of the forward wave(s), in rows: what the variant's register budget holds without spilling */
-#ifndef NRQ_PIPE_SMALL
-#define NRQ_PIPE_SMALL 0 /* (round 3: with the movers' aligned-only form the software-pipelined loops of the 256-thread variant keep so many
-                          * requests in flight that its forward wave waits for its op words: K=1000 9.7 / 8.6 ms with them, 8.2 / 7.7 without;
-                          * K=500 14.6 / 13.4 vs 12.4 / 11.8; K=2000 8.5 / 7.3 vs 7.2 / 6.5) */
-#endif
-  /* software-pipelined data movers in the 768-thread workgroup (168 registers per thread); the 256-thread variant had them in
-   * round 2 (K=1000 977 -> 1031 Gbit/s with the loops as they were then), see NRQ_PIPE_SMALL */
-#ifndef NRQ_PIPE_BIG
-#define NRQ_PIPE_BIG 1
-#endif
-  constexpr bool MPIPE = (NRQ_PIPE_BIG && NT >= 512) || (NRQ_PIPE_SMALL && NT == 256 && WV == 4);
-#ifndef NRQ_RING_4W
-#define NRQ_RING_4W NRQ_RING
-#endif
-#ifndef NRQ_RING_TINY
-#define NRQ_RING_TINY 24u /* the single-wave variant: a dozen workgroups per CU hide each other's op-word latency, and a short ring is less code for
-                           * them to share the instruction cache with (K=100 T=1024 / K=256, ring 60 / 36 / 24 / 12 rows: 460 / 468 / 471 / 473 and
-                           * 815 / 833 / 835 / 836 Gbit/s; the 256-thread variant loses with a shorter ring: K=1000 1156 / 1093 / 1087 / 1057) */
-#endif
-  constexpr uint32_t RU = NT >= 512 ? NRQ_BIG_RING : NT == 64 ? NRQ_RING_TINY : WV >= 5 ? NRQ_RING_5W : NRQ_RING_4W;
   /* NT == 64: ONE wave solves the strip on its own (no mover waves: it gathers and scatters its portions itself after
    * the forward passes; barriers are free).  For images of a few KB -- K up to ~400 -- where a strip is a chain of
    * short phases with little parallel work: 19-20 such workgroups share a CU instead of five 256-thread ones, i.e.
@@ -177,40 +113,13 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
   (void)SPL;
   NRQ_GAS uint8_t *stage0 = gptr_w<uint8_t>((uint64_t)(uintptr_t)(stage_all + (size_t)blockIdx.x * wg_bytes));
   NRQ_GAS uint8_t *ostage0 = stage0 + 2u * SPL * (size_t)stage_stride;
-  auto group_src = [&](uint32_t q, GroupSrc<WB> &g, uint32_t *blk_out) {
-    uint32_t blk, grp;
-    nrq_map_group(q, nblk, gpb, by_block != 0u, &blk, &grp);
-    const nrq_job *j = jobs + blk;
-    g.rowsrc = nrq_uniform_ptr(gptr<uint32_t>(j->rowsrc)); g.src = nrq_uniform_ptr(gptr<uint8_t>(j->src)); g.rep = nrq_uniform_ptr(gptr<uint8_t>(j->rep));
-    g.M = nrq_uniform(reinterpret_cast<const nrq_plan_hdr *>(j->plan)->M);
-    g.T = nrq_uniform(T); g.strip0 = nrq_uniform(grp * sub); g.nstrips = nrq_uniform(nstrips); g.lsub = nrq_uniform(lsub);
-    *blk_out = nrq_uniform(blk);
-  };
-  auto group_dst = [&](uint32_t q, GroupDst<WB> &g) -> uint32_t { /* returns the staged elements per strip */
-    uint32_t blk, grp;
-    nrq_map_group(q, nblk, gpb, by_block != 0u, &blk, &grp);
-    const nrq_job *j = jobs + blk;
-    g.inter = gptr_w<uint8_t>(j->inter); g.out = gptr_w<uint8_t>(j->out); g.orow = gptr<uint32_t>(j->out_row);
-    g.ni = j->inter ? reinterpret_cast<const nrq_plan_hdr *>(j->plan)->L : 0u;
-    g.nout = j->nout; g.T = nrq_uniform(T); g.strip0 = nrq_uniform(grp * sub); g.nstrips = nrq_uniform(nstrips); g.lsub = nrq_uniform(lsub);
-    g.orow = nrq_uniform_ptr(g.orow);
-    if (ybuf) { /* split solve: the slot image and C_u go to rows [0, M + u) of the block's work buffer */
-      const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(j->plan);
-      g.inter = gptr_w<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride));
-      g.ni = h->M + h->u;
-      g.nout = 0u;
-    }
-    g.inter = nrq_uniform_ptr(g.inter); g.out = nrq_uniform_ptr(g.out);
-    g.ni = nrq_uniform(g.ni); g.nout = nrq_uniform(g.nout);
-    return g.ni + g.nout;
-  };
   uint32_t q = nrq_next_group(blockIdx.x, gridDim.x, nslots, jobs, nblk, gpb, by_block != 0u);
   if (q >= nslots) return;
   uint32_t buf = 0, done = 0, qp = nslots; /* qp: the group whose results wait in the other output set */
   {
     GroupSrc<WB> g0;
     uint32_t b0;
-    group_src(q, g0, &b0);
+    nrq_group_src<WB>(q, jobs, nblk, gpb, by_block, sub, T, nstrips, lsub, g0, &b0);
     pf_gather_impl<WB, G, MPIPE, ALX>(g0, stage0, stage_stride, 0u, g0.M << lsub, (tid) / G, (NT) / G, subl); /* the first group: nothing to overlap it with */
     __syncthreads();
   }
@@ -219,46 +128,22 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
     GroupSrc<WB> gn;
     GroupDst<WB> gp;
     uint32_t blk, blkn = 0, units_n = 0, units_p = 0;
-    if (qn < nslots) { group_src(qn, gn, &blkn); units_n = gn.M << lsub; }
-    if (qp < nslots) units_p = group_dst(qp, gp) << lsub;
+    if (qn < nslots) { nrq_group_src<WB>(qn, jobs, nblk, gpb, by_block, sub, T, nstrips, lsub, gn, &blkn); units_n = gn.M << lsub; }
+    if (qp < nslots) units_p = nrq_group_dst<WB>(qp, jobs, nblk, gpb, by_block, sub, T, nstrips, lsub, ybuf, ybuf_stride, gp) << lsub;
     {
       GroupSrc<WB> gc;
-      group_src(q, gc, &blk);
+      nrq_group_src<WB>(q, jobs, nblk, gpb, by_block, sub, T, nstrips, lsub, gc, &blk);
     }
     NRQ_GAS uint8_t *stage_cur = stage0 + (size_t)buf * SPL * stage_stride, *stage_nxt = stage0 + (size_t)(buf ^ 1u) * SPL * stage_stride;
     NRQ_GAS uint8_t *ostage_cur = ostage0 + (size_t)buf * SPL * ostage_stride, *ostage_prv = ostage0 + (size_t)(buf ^ 1u) * SPL * ostage_stride;
     const uint32_t strip0 = ((by_block ? (q >> 3) : q) % gpb) * sub;
     for (uint32_t sidx = 0; sidx < sub; sidx++) {
-      const uint32_t u0 = (uint32_t)(((uint64_t)units_n * sidx) >> lsub), u1 = (uint32_t)(((uint64_t)units_n * (sidx + 1u)) >> lsub);
-      const uint32_t s0 = (uint32_t)(((uint64_t)units_p * sidx) >> lsub), s1 = (uint32_t)(((uint64_t)units_p * (sidx + 1u)) >> lsub);
-      /* part of the scatter portion is left to the waves that the HDPC phase does not use (when there are any) */
-#ifndef NRQ_SCATTER_LATE_PCT
-#define NRQ_SCATTER_LATE_PCT 20u
-#endif
-      /* ... and part of the gather portion: the gather of an encode strip is bound by its bytes in flight against the memory
-       * latency and ends with the forward waves (more of it in flight there would delay their op words); in the HDPC window
-       * nobody waits for op words.  K=8192 T=1280, encode / decode solve kernel in ms at gather % / scatter %: 0/35 7.09 / 6.28,
-       * 40/20 6.61 / 6.30, 35/35 6.79 / 6.25, 50/25 6.82 / 6.37, 60/35 7.02 / 6.34 (beyond 40 % the HDPC window grows by more
-       * than the forward window shrinks) */
-#ifndef NRQ_GATHER_LATE_PCT
-#define NRQ_GATHER_LATE_PCT 40u
-#endif
-#ifndef NRQ_SCATTER_LATE_PCT_NARROW
-#define NRQ_SCATTER_LATE_PCT_NARROW 10u
-#endif
-#ifndef NRQ_GATHER_LATE_PCT_NARROW
-#define NRQ_GATHER_LATE_PCT_NARROW 15u
-#endif
-#ifndef NRQ_W12_SLATE
-#define NRQ_W12_SLATE NRQ_SCATTER_LATE_PCT
-#endif
-#ifndef NRQ_W12_GLATE
-#define NRQ_W12_GLATE NRQ_GATHER_LATE_PCT
-#endif
-      constexpr uint32_t SLATE = WB == 12 ? NRQ_W12_SLATE : WB >= 8 ? NRQ_SCATTER_LATE_PCT : NRQ_SCATTER_LATE_PCT_NARROW,
-                         GLATE = WB == 12 ? NRQ_W12_GLATE : WB >= 8 ? NRQ_GATHER_LATE_PCT : NRQ_GATHER_LATE_PCT_NARROW;
-      const uint32_t sm = NT > NRQ_HDPC_NT_ ? s1 - (uint32_t)((uint64_t)(s1 - s0) * SLATE / 100u) : s1;
-      const uint32_t um = NT > NRQ_HDPC_NT_ ? u1 - (uint32_t)((uint64_t)(u1 - u0) * GLATE / 100u) : u1;
+      /* this strip index's portions of the next group's gather and of the previous group's scatter; [um, u1) and [sm, s1) of them
+       * are left to the waves that the HDPC phase does not use (when there are any) */
+      const uint32_t u0 = NRQ_PORTION_AT(units_n, sidx, lsub), u1 = NRQ_PORTION_AT(units_n, sidx + 1u, lsub);
+      const uint32_t s0 = NRQ_PORTION_AT(units_p, sidx, lsub), s1 = NRQ_PORTION_AT(units_p, sidx + 1u, lsub);
+      const uint32_t sm = NRQ_PORTION_LATE_AT(s0, s1, SLATE, LATE);
+      const uint32_t um = NRQ_PORTION_LATE_AT(u0, u1, GLATE, LATE);
       const uint32_t strip = strip0 + sidx;
       if (strip >= nstrips) { /* no such strip: everybody moves this portion */
         if (u1 > u0) pf_gather_impl<WB, G, MPIPE, ALX>(gn, stage_nxt, stage_stride, u0, u1, (tid) / G, (NT) / G, subl);
@@ -294,7 +179,7 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
       c.dbg_t0 = tid == 0;
       done++;
       NRQ_STAMP(0);
-      pf_commit<WB, G, (NT == 64 ? 4 : 8)>(c, stage_cur + (size_t)sidx * stage_stride + subl * WB, 0u, vt, VNT);
+      pf_commit<WB, G, R.commit_pb>(c, stage_cur + (size_t)sidx * stage_stride + subl * WB, 0u, vt, VNT);
       ph_clear<WB, G>(c, vt, VNT);
       __syncthreads();
       NRQ_STAMP(1);
@@ -330,9 +215,8 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
         }
         __builtin_amdgcn_s_setprio(0);
         NRQ_MARK(c, 1);
-      } else if ((wv & 3u) >= NFW || NFW == 3u) { /* the waves that do not share a SIMD with the forward waves; index among them: */
-        const uint32_t mv = NFW == 3u ? ((wv & 3u) == 3u ? (wv >> 2) : (wv >> 2) * 3u + (wv & 3u)) /* (SIMD 3's: 0-2; waves 4-6, 8-10: 3-8) */
-                                      : (wv >> 2) * (4u - NFW) + (wv & 3u) - NFW;
+      } else if (NRQ_WAVE_MOVES(NFW, wv)) { /* the waves that do not share a SIMD with the forward waves; index among them: */
+        const uint32_t mv = NRQ_MOVER_INDEX(NFW, wv);
         if (mv < NGW) {
 #if !defined(NRQ_EXPERIMENT_NO_MOVERS) && !defined(NRQ_EXPERIMENT_NO_GATHER) /* (measurement only: what the forward window costs with no mover traffic beside it; results are garbage) */
           if (um > u0) pf_gather_impl<WB, G, MPIPE, ALX>(gn, stage_nxt, stage_stride, u0, um, (mv * 64u + (tid & 63u)) / G, (NGW * 64u) / G, subl);
@@ -349,26 +233,10 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
       NRQ_STAMP(2);
       NRQ_STOP(1)
 
-      {
-        /* (the 256-thread variant: NRQ_HDPC_NT_SMALL threads -- every thread of the phase ends in a closing fold of 8 x H masked XORs,
-         * ~800 instructions whatever its chunk holds, and four such workgroups share a CU's issue slots) */
-#ifndef NRQ_HDPC_NT_SMALL
-#define NRQ_HDPC_NT_SMALL 256
-#endif
-        constexpr uint32_t HNT = NT == 256 ? (uint32_t)NRQ_HDPC_NT_SMALL : NT < NRQ_HDPC_NT_ ? NT : NRQ_HDPC_NT_;
-        /* (narrow strips: the H sums in registers -- on 16-byte strips that form is slower, 24 k against 17.5 k clocks for the
-         * recurrence: 4 x H operations per column instead of four LDS atomics) */
-#ifndef NRQ_HDPC_REGS_MAX_WB
-#define NRQ_HDPC_REGS_MAX_WB 4
-#endif
-#ifndef NRQ_HDPC_REGS_12
-#define NRQ_HDPC_REGS_12 0
-#endif
-        if (tid < HNT) { ph_hdpc<WB, G, (NT >= 512 && G == 1 && (WB <= NRQ_HDPC_REGS_MAX_WB || (WB == 12 && NRQ_HDPC_REGS_12)))>(c, tid / G, HNT / G); }
-        else { /* the waves HDPC leaves idle */
-          if (u1 > um) pf_gather_impl<WB, G, MPIPE, ALX>(gn, stage_nxt, stage_stride, um, u1, (tid - HNT) / G, (NT - HNT) / G, subl);
-          if (s1 > sm) pf_scatter_impl<WB, G, MPIPE, ALX>(gp, ostage_prv, ostage_stride, sm, s1, (tid - HNT) / G, (NT - HNT) / G, subl);
-        }
+      if (tid < HNT) { ph_hdpc<WB, G, R.hdpc_regs>(c, tid / G, HNT / G); }
+      else { /* the waves HDPC leaves idle */
+        if (u1 > um) pf_gather_impl<WB, G, MPIPE, ALX>(gn, stage_nxt, stage_stride, um, u1, (tid - HNT) / G, (NT - HNT) / G, subl);
+        if (s1 > sm) pf_scatter_impl<WB, G, MPIPE, ALX>(gp, ostage_prv, ostage_stride, sm, s1, (tid - HNT) / G, (NT - HNT) / G, subl);
       }
       __syncthreads();
       ph_hdpc_reduce<WB, G>(c, vt, VNT);
@@ -391,10 +259,7 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
       }
       NRQ_STAMP(4);
       NRQ_STOP(3)
-#ifndef NRQ_FOLD_PRE256
-#define NRQ_FOLD_PRE256 0 /* coefficients the 256-thread variant's dense fold asks for at once (0: one per term, a trip to L2 each) */
-#endif
-      ph_dense_fold<WB, G, (NT == 64 ? 8 : NT == 256 ? NRQ_FOLD_PRE256 : 0)>(c, vt, VNT);
+      ph_dense_fold<WB, G, R.fold_batch>(c, vt, VNT);
       __syncthreads();
       NRQ_MARK(c, 4);
       if (dense_fold_shared(VNT) || G > 1) { /* (then the fold leaves its products in the accumulator copies) */
@@ -402,10 +267,10 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
         __syncthreads();
       }
       NRQ_MARK(c, 5);
-      ph_dense_free<WB, G, (NT == 64)>(c, vt, VNT);
+      ph_dense_free<WB, G, R.batch>(c, vt, VNT);
       __syncthreads();
       NRQ_MARK(c, 6);
-      ph_dense_cu<WB, G, (NT == 64)>(c, vt, VNT);
+      ph_dense_cu<WB, G, R.batch>(c, vt, VNT);
       __syncthreads();
       NRQ_STAMP(5);
       NRQ_STOP(4)
@@ -418,12 +283,12 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
         __syncthreads();
         NRQ_STAMP(6);
         NRQ_STOP(5)
-        ph_backsub<WB, G, (NT >= 512)>(c, vt, VNT);
+        ph_backsub<WB, G, R.fast>(c, vt, VNT);
         ph_park<WB, G>(c, vt, VNT);
         __syncthreads();
         NRQ_STAMP(7);
         NRQ_STOP(6)
-        ph_store<WB, G, (NT >= 512)>(c, ostage_cur + (size_t)sidx * ostage_stride + subl * WB, vt, VNT);
+        ph_store<WB, G, R.fast>(c, ostage_cur + (size_t)sidx * ostage_stride + subl * WB, vt, VNT);
       }
       __syncthreads();
       NRQ_STAMP(8);
@@ -438,7 +303,7 @@ void nrq_solve_kernel(const nrq_job *__restrict__ jobs, uint32_t nblk,
   /* the results of the last group */
   if (qp < nslots) {
     GroupDst<WB> gp;
-    const uint32_t units_p = group_dst(qp, gp) << lsub;
+    const uint32_t units_p = nrq_group_dst<WB>(qp, jobs, nblk, gpb, by_block, sub, T, nstrips, lsub, ybuf, ybuf_stride, gp) << lsub;
     pf_scatter_impl<WB, G, MPIPE, ALX>(gp, ostage0 + (size_t)(buf ^ 1u) * SPL * ostage_stride, ostage_stride, 0u, units_p, (tid) / G, (NT) / G, subl);
   }
 }

@@ -2121,4 +2121,42 @@ SB_HD uint32_t nrq_next_group(uint32_t q, uint32_t grid, uint32_t nslots, const 
   return nslots;
 }
 
+/* The line group of work slot q as the movers see it (gpb: slots per block, sub = 1 << lsub strips each): where its rows come
+ * from ...  Shared by nrq_solve_kernel and the launch emulation.  The launch's values come by reference, as the kernel's own
+ * lambdas captured them (JP, YP: its pointers are __restrict__ ones): taken by value, the kernels came out of the compiler with
+ * the loads of a group's descriptor in another order. */
+template <int WB, class JP>
+SB_HD void nrq_group_src(uint32_t q, const JP &jobs, const uint32_t &nblk, const uint32_t &gpb, const uint32_t &by_block, const uint32_t &sub, const uint32_t &T,
+                         const uint32_t &nstrips, const uint32_t &lsub, GroupSrc<WB> &g, uint32_t *blk_out) {
+  uint32_t blk, grp;
+  nrq_map_group(q, nblk, gpb, by_block != 0u, &blk, &grp);
+  const nrq_job *j = jobs + blk;
+  g.rowsrc = nrq_uniform_ptr(gptr<uint32_t>(j->rowsrc)); g.src = nrq_uniform_ptr(gptr<uint8_t>(j->src)); g.rep = nrq_uniform_ptr(gptr<uint8_t>(j->rep));
+  g.M = nrq_uniform(reinterpret_cast<const nrq_plan_hdr *>(j->plan)->M);
+  g.T = nrq_uniform(T); g.strip0 = nrq_uniform(grp * sub); g.nstrips = nrq_uniform(nstrips); g.lsub = nrq_uniform(lsub);
+  *blk_out = nrq_uniform(blk);
+}
+/* ... and where its results go; returns the staged elements per strip.  ybuf: the work buffers of a split solve, ybuf_stride
+ * bytes per block (nullptr: the results go to the job's own rows). */
+template <int WB, class JP, class YP>
+SB_HD uint32_t nrq_group_dst(uint32_t q, const JP &jobs, const uint32_t &nblk, const uint32_t &gpb, const uint32_t &by_block, const uint32_t &sub, const uint32_t &T,
+                             const uint32_t &nstrips, const uint32_t &lsub, const YP &ybuf, const size_t &ybuf_stride, GroupDst<WB> &g) {
+  uint32_t blk, grp;
+  nrq_map_group(q, nblk, gpb, by_block != 0u, &blk, &grp);
+  const nrq_job *j = jobs + blk;
+  g.inter = gptr_w<uint8_t>(j->inter); g.out = gptr_w<uint8_t>(j->out); g.orow = gptr<uint32_t>(j->out_row);
+  g.ni = j->inter ? reinterpret_cast<const nrq_plan_hdr *>(j->plan)->L : 0u;
+  g.nout = j->nout; g.T = nrq_uniform(T); g.strip0 = nrq_uniform(grp * sub); g.nstrips = nrq_uniform(nstrips); g.lsub = nrq_uniform(lsub);
+  g.orow = nrq_uniform_ptr(g.orow);
+  if (ybuf) { /* split solve: the slot image and C_u go to rows [0, M + u) of the block's work buffer */
+    const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(j->plan);
+    g.inter = gptr_w<uint8_t>((uint64_t)(uintptr_t)(ybuf + (size_t)blk * ybuf_stride));
+    g.ni = h->M + h->u;
+    g.nout = 0u;
+  }
+  g.inter = nrq_uniform_ptr(g.inter); g.out = nrq_uniform_ptr(g.out);
+  g.ni = nrq_uniform(g.ni); g.nout = nrq_uniform(g.nout);
+  return g.ni + g.nout;
+}
+
 #endif /* NRQ_SOLVE_BODY_H */

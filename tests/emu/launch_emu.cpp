@@ -166,15 +166,6 @@ uint32_t lemu_store_slack(void) { return NRQ_STORE_SLACK; }
  * ========================================================================================== */
 namespace {
 
-/* The defaults of the macros of nrq_device.hip that shape the kernel's roles, as run_launch assumes them: NRQ_<name> = value */
-#define LEMU_KERNEL_DEFAULTS(X)                                                                                                        \
-  X(W12_FW, 3) X(W12_GW, 2) X(W12_SW, 2) X(MOVER_WAVES, 2) X(GATHER_WAVES_NARROW, 2) X(GATHER_WAVES_NARROW_WB, 2) X(PIPE_BIG, 1)       \
-  X(PIPE_SMALL, 0) X(HDPC_NT, 512) X(HDPC_NT_SMALL, 256) X(SCATTER_LATE_PCT, 20) X(GATHER_LATE_PCT, 40) X(SCATTER_LATE_PCT_NARROW, 10) \
-  X(GATHER_LATE_PCT_NARROW, 15) X(HDPC_REGS_MAX_WB, 4) X(HDPC_REGS_12, 0) X(FOLD_PRE256, 0)
-#define LEMU_K(name, value) constexpr uint32_t K_##name = value;
-LEMU_KERNEL_DEFAULTS(LEMU_K)
-#undef LEMU_K
-
 /* the movers in the form the instance is compiled with: MPIPE (software-pipelined, the big workgroup) and ALX (aligned only) */
 template <int WB, int G>
 void gather(bool pipe, bool alx, const GroupSrc<WB> &g, uint8_t *stage, size_t stride, uint32_t u0, uint32_t u1, uint32_t p, uint32_t np, uint32_t sub) {
@@ -207,30 +198,9 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
   const uint32_t NT = r.NT, nstrips = r.nstrips, nslots = r.nslots, lsub = r.lsub, grid = r.grid;
   const uint32_t stage_stride = r.stage_stride, ostage_stride = r.ostage_stride;
   const bool by_block = r.by_block != 0;
-  constexpr uint32_t WBE = (uint32_t)WB * G;
-  const bool ALX = r.AL && G == 1 && WB >= 4;
-  constexpr uint32_t SPL = nrq_group_strips(WBE);
-  /* The kernel's roles, restated with the DEFAULTS of the macros nrq_device.hip defines for them (K_* below, one per macro:
-   * tests/test_launch_bounds_emu.py reads the #defines and fails when one moves away from what is assumed here).
-   * kernel: `constexpr uint32_t SPL = ..., NFW = ..., NMV = ..., NGW = ..., NSW = ...`, `MPIPE`, `HNT`, `SLATE` / `GLATE` */
-  const uint32_t NFW = (G == 1 && WB == 12 && NT >= 512) ? K_W12_FW : (G == 1 && WB >= 8 && NT >= 512) ? 2u : 1u;
-  const uint32_t NMV = (NT / 64u) / 4u * (4u - NFW) + ((NT / 64u) % 4u > NFW ? (NT / 64u) % 4u - NFW : 0u);
-  const uint32_t NGW = NFW == 3u ? K_W12_GW : NMV >= 6u ? ((uint32_t)WB <= K_GATHER_WAVES_NARROW_WB ? K_GATHER_WAVES_NARROW : K_MOVER_WAVES) : NMV >= 3u ? 2u : 1u;
-  const uint32_t NSW = NFW == 3u ? K_W12_SW : NMV >= 6u ? K_MOVER_WAVES : NMV - NGW;
-  if (NT != 64 && NMV < 2u) return -3;
-  const bool MPIPE = (K_PIPE_BIG && NT >= 512) || (K_PIPE_SMALL && NT == 256 && r.WV == 4);
-  const uint32_t NRQ_HDPC_NT_ = K_HDPC_NT;
-  const uint32_t HNT = NT == 256 ? K_HDPC_NT_SMALL : NT < NRQ_HDPC_NT_ ? NT : NRQ_HDPC_NT_;
-  const uint32_t SLATE = WB == 12 ? K_SCATTER_LATE_PCT : WB >= 8 ? K_SCATTER_LATE_PCT : K_SCATTER_LATE_PCT_NARROW; /* (NRQ_W12_SLATE / _GLATE are the wide ones) */
-  const uint32_t GLATE = WB == 12 ? K_GATHER_LATE_PCT : WB >= 8 ? K_GATHER_LATE_PCT : K_GATHER_LATE_PCT_NARROW;
-  StripForm form;
-  form.hnt = HNT;
-  form.hdpc_regs = NT >= 512 && G == 1 && ((uint32_t)WB <= K_HDPC_REGS_MAX_WB || (WB == 12 && K_HDPC_REGS_12));
-  form.fold_batch = NT == 64 ? 8 : NT == 256 ? (int)K_FOLD_PRE256 : 0;
-  form.batch = NT == 64;
-  form.fast = NT >= 512;
-  form.commit8 = NT != 64;
-
+  const SolveRoles R = solve_roles(WB, (int)NT, (int)r.WV, G, r.AL != 0); /* the kernel's own roles and phase forms (solve_roles.h) */
+  constexpr uint32_t WBE = (uint32_t)WB * G, SPL = nrq_group_strips(WBE);
+  if (!solve_roles_valid(WB, (int)NT, (int)r.WV, G, r.AL != 0)) return -3;
   const uint32_t sub = 1u << lsub;                 /* strips per slot */
   const uint32_t gpb = (nstrips + sub - 1u) / sub; /* slots per block */
   const size_t wg_bytes = 2u * SPL * ((size_t)stage_stride + ostage_stride);
@@ -241,36 +211,12 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
     memset(smem, 0xA5, r.lds_bytes); /* what the workgroup before left in the LDS */
     uint8_t *stage0 = stage_all + (size_t)bid * wg_bytes;
     uint8_t *ostage0 = stage0 + 2u * SPL * (size_t)stage_stride;
-    auto group_src = [&](uint32_t q, GroupSrc<WB> &g, uint32_t *blk_out) {
-      uint32_t blk, grp;
-      nrq_map_group(q, nblk, gpb, by_block, &blk, &grp);
-      const nrq_job *j = jobs + blk;
-      g.rowsrc = gptr<uint32_t>(j->rowsrc); g.src = gptr<uint8_t>(j->src); g.rep = gptr<uint8_t>(j->rep);
-      g.M = reinterpret_cast<const nrq_plan_hdr *>(j->plan)->M;
-      g.T = T; g.strip0 = grp * sub; g.nstrips = nstrips; g.lsub = lsub;
-      *blk_out = blk;
-    };
-    auto group_dst = [&](uint32_t q, GroupDst<WB> &g) -> uint32_t {
-      uint32_t blk, grp;
-      nrq_map_group(q, nblk, gpb, by_block, &blk, &grp);
-      const nrq_job *j = jobs + blk;
-      g.inter = gptr_w<uint8_t>(j->inter); g.out = gptr_w<uint8_t>(j->out); g.orow = gptr<uint32_t>(j->out_row);
-      g.ni = j->inter ? reinterpret_cast<const nrq_plan_hdr *>(j->plan)->L : 0u;
-      g.nout = j->nout; g.T = T; g.strip0 = grp * sub; g.nstrips = nstrips; g.lsub = lsub;
-      if (ybuf) {
-        const nrq_plan_hdr *h = reinterpret_cast<const nrq_plan_hdr *>(j->plan);
-        g.inter = ybuf + (size_t)blk * r.ybuf_stride;
-        g.ni = h->M + h->u;
-        g.nout = 0u;
-      }
-      return g.ni + g.nout;
-    };
     /* all NT threads of the workgroup move [a, b): thread tid as (tid / G) of NT / G, lane tid % G */
     auto all_gather = [&](const GroupSrc<WB> &g, uint8_t *st, uint32_t a, uint32_t b, uint32_t first, uint32_t n) {
-      for (uint32_t k = 0; k < n; k++) gather<WB, G>(MPIPE, ALX, g, st, stage_stride, a, b, k / G, n / G, (first + k) % G);
+      for (uint32_t k = 0; k < n; k++) gather<WB, G>(R.MPIPE, R.ALX, g, st, stage_stride, a, b, k / G, n / G, (first + k) % G);
     };
     auto all_scatter = [&](const GroupDst<WB> &g, const uint8_t *st, uint32_t a, uint32_t b, uint32_t first, uint32_t n) {
-      for (uint32_t k = 0; k < n; k++) scatter<WB, G>(MPIPE, ALX, g, st, ostage_stride, a, b, k / G, n / G, (first + k) % G);
+      for (uint32_t k = 0; k < n; k++) scatter<WB, G>(R.MPIPE, R.ALX, g, st, ostage_stride, a, b, k / G, n / G, (first + k) % G);
     };
     uint32_t q = nrq_next_group(bid, grid, nslots, jobs, nblk, gpb, by_block);
     if (q >= nslots) continue;
@@ -278,7 +224,7 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
     {
       GroupSrc<WB> g0;
       uint32_t b0;
-      group_src(q, g0, &b0);
+      nrq_group_src<WB>(q, jobs, nblk, gpb, r.by_block, sub, T, nstrips, lsub, g0, &b0);
       g_where = {"first gather", bid, q, 0};
       all_gather(g0, stage0, 0u, g0.M << lsub, 0u, NT); /* (kernel: the first group, nothing to overlap it with) */
     }
@@ -287,20 +233,19 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
       GroupSrc<WB> gn;
       GroupDst<WB> gp;
       uint32_t blk, blkn = 0, units_n = 0, units_p = 0;
-      if (qn < nslots) { group_src(qn, gn, &blkn); units_n = gn.M << lsub; }
-      if (qp < nslots) units_p = group_dst(qp, gp) << lsub;
+      if (qn < nslots) { nrq_group_src<WB>(qn, jobs, nblk, gpb, r.by_block, sub, T, nstrips, lsub, gn, &blkn); units_n = gn.M << lsub; }
+      if (qp < nslots) units_p = nrq_group_dst<WB>(qp, jobs, nblk, gpb, r.by_block, sub, T, nstrips, lsub, ybuf, (size_t)r.ybuf_stride, gp) << lsub;
       {
         GroupSrc<WB> gc;
-        group_src(q, gc, &blk);
+        nrq_group_src<WB>(q, jobs, nblk, gpb, r.by_block, sub, T, nstrips, lsub, gc, &blk);
       }
       uint8_t *stage_cur = stage0 + (size_t)buf * SPL * stage_stride, *stage_nxt = stage0 + (size_t)(buf ^ 1u) * SPL * stage_stride;
       uint8_t *ostage_cur = ostage0 + (size_t)buf * SPL * ostage_stride, *ostage_prv = ostage0 + (size_t)(buf ^ 1u) * SPL * ostage_stride;
       const uint32_t strip0 = ((by_block ? (q >> 3) : q) % gpb) * sub;
       for (uint32_t sidx = 0; sidx < sub; sidx++) {
-        const uint32_t u0 = (uint32_t)(((uint64_t)units_n * sidx) >> lsub), u1 = (uint32_t)(((uint64_t)units_n * (sidx + 1u)) >> lsub);
-        const uint32_t s0 = (uint32_t)(((uint64_t)units_p * sidx) >> lsub), s1 = (uint32_t)(((uint64_t)units_p * (sidx + 1u)) >> lsub);
-        const uint32_t sm = NT > NRQ_HDPC_NT_ ? s1 - (uint32_t)((uint64_t)(s1 - s0) * SLATE / 100u) : s1;
-        const uint32_t um = NT > NRQ_HDPC_NT_ ? u1 - (uint32_t)((uint64_t)(u1 - u0) * GLATE / 100u) : u1;
+        const uint32_t u0 = NRQ_PORTION_AT(units_n, sidx, lsub), u1 = NRQ_PORTION_AT(units_n, sidx + 1u, lsub);
+        const uint32_t s0 = NRQ_PORTION_AT(units_p, sidx, lsub), s1 = NRQ_PORTION_AT(units_p, sidx + 1u, lsub);
+        const uint32_t sm = NRQ_PORTION_LATE_AT(s0, s1, R.SLATE, R.LATE), um = NRQ_PORTION_LATE_AT(u0, u1, R.GLATE, R.LATE);
         const uint32_t strip = strip0 + sidx;
         if (strip >= nstrips) { /* no such strip: everybody moves this portion */
           g_where = {"strip-less gather", bid, q, sidx};
@@ -309,7 +254,7 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
           if (s1 > s0) all_scatter(gp, ostage_prv, s0, s1, 0u, NT);
           continue;
         }
-        /* ---- the forward window: who moves what (kernel: `if constexpr (NT == 64)` ... `else if ((wv & 3u) >= NFW || NFW == 3u)`) ---- */
+        /* ---- the forward window: who moves what (kernel: `if constexpr (NT == 64)` ... `else if (wv < NFW)` ... `else if (NRQ_WAVE_MOVES(NFW, wv))`) ---- */
         if (NT == 64) { /* the single wave moves its own portions behind its forward passes */
           g_where = {"gather (single wave)", bid, q, sidx};
           if (u1 > u0) all_gather(gn, stage_nxt, u0, u1, 0u, 64u);
@@ -318,24 +263,23 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
         } else {
           for (uint32_t tid = 0; tid < NT; tid++) {
             const uint32_t wv = tid >> 6;
-            if (wv < NFW) continue; /* the forward waves */
-            if (!((wv & 3u) >= NFW || NFW == 3u)) continue; /* (a wave that shares a SIMD with a forward wave idles) */
-            const uint32_t mv = NFW == 3u ? ((wv & 3u) == 3u ? (wv >> 2) : (wv >> 2) * 3u + (wv & 3u)) : (wv >> 2) * (4u - NFW) + (wv & 3u) - NFW;
-            if (mv < NGW) {
+            if (wv < R.NFW || !NRQ_WAVE_MOVES(R.NFW, wv)) continue; /* the forward waves; the waves that share a SIMD with one idle */
+            const uint32_t mv = NRQ_MOVER_INDEX(R.NFW, wv);
+            if (mv < R.NGW) {
               g_where = {"gather waves", bid, q, sidx};
-              if (um > u0) gather<WB, G>(MPIPE, ALX, gn, stage_nxt, stage_stride, u0, um, (mv * 64u + (tid & 63u)) / G, (NGW * 64u) / G, tid % G);
-            } else if (mv < NGW + NSW) {
+              if (um > u0) gather<WB, G>(R.MPIPE, R.ALX, gn, stage_nxt, stage_stride, u0, um, (mv * 64u + (tid & 63u)) / G, (R.NGW * 64u) / G, tid % G);
+            } else if (mv < R.NGW + R.NSW) {
               g_where = {"scatter waves", bid, q, sidx};
-              if (sm > s0) scatter<WB, G>(MPIPE, ALX, gp, ostage_prv, ostage_stride, s0, sm, ((mv - NGW) * 64u + (tid & 63u)) / G, (NSW * 64u) / G, tid % G);
+              if (sm > s0) scatter<WB, G>(R.MPIPE, R.ALX, gp, ostage_prv, ostage_stride, s0, sm, ((mv - R.NGW) * 64u + (tid & 63u)) / G, (R.NSW * 64u) / G, tid % G);
             }
           }
         }
         /* ---- the HDPC window: the waves the phase leaves idle (kernel: `if (tid < HNT) ... else`) ---- */
-        if (NT > HNT) {
+        if (NT > R.HNT) {
           g_where = {"late gather (waves HDPC leaves idle)", bid, q, sidx};
-          if (u1 > um) all_gather(gn, stage_nxt, um, u1, HNT, NT - HNT);
+          if (u1 > um) all_gather(gn, stage_nxt, um, u1, R.HNT, NT - R.HNT);
           g_where.role = "late scatter (waves HDPC leaves idle)";
-          if (s1 > sm) all_scatter(gp, ostage_prv, sm, s1, HNT, NT - HNT);
+          if (s1 > sm) all_scatter(gp, ostage_prv, sm, s1, R.HNT, NT - R.HNT);
         }
         /* ---- the strip itself (the movers above touch the other staging sets and the symbol rows, the phases the LDS image and
          * this strip's two staging buffers: the order between them does not matter) ---- */
@@ -357,7 +301,7 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
         if (c[0].lay.total > r.lds_bytes) return -5; /* the launch's dynamic LDS does not hold this block's image */
         const uint8_t *st_in = stage_cur + (size_t)sidx * stage_stride;
         uint8_t *st_out = ostage_cur + (size_t)sidx * ostage_stride;
-        const int rc = strip_phases<WB, G>(c, NT, form, st_in, st_out, ybuf != nullptr);
+        const int rc = strip_phases<WB, G>(c, NT, R, st_in, st_out, ybuf != nullptr);
         if (rc != 1) return rc;
       }
       qp = q;
@@ -367,7 +311,7 @@ int run_launch(const LaunchRec &r, const nrq_job *jobs, uint32_t nblk, uint32_t 
     /* the results of the last group */
     if (qp < nslots) {
       GroupDst<WB> gp;
-      const uint32_t units_p = group_dst(qp, gp) << lsub;
+      const uint32_t units_p = nrq_group_dst<WB>(qp, jobs, nblk, gpb, r.by_block, sub, T, nstrips, lsub, ybuf, (size_t)r.ybuf_stride, gp) << lsub;
       g_where = {"last scatter", bid, qp, 0};
       all_scatter(gp, ostage0 + (size_t)(buf ^ 1u) * SPL * ostage_stride, 0u, units_p, 0u, NT);
     }
@@ -421,13 +365,30 @@ extern "C" int lemu_run(const LaunchRec *r, const nrq_job *jobs, uint32_t nblk, 
 #undef LEMU_RUN
 }
 
-/* "NRQ_W12_FW=3 NRQ_W12_GW=2 ...": what run_launch assumes of nrq_device.hip's macros */
-extern "C" const char *lemu_kernel_defaults(void) {
+/* What the test pins against numbers of its own: "NRQ_W12_FW=3 ...", the role knobs as compiled here (the macros themselves), */
+extern "C" const char *lemu_role_knobs(void) {
+#define LEMU_K(name) " NRQ_" #name "=%u"
+#define LEMU_V(name) , (unsigned)(NRQ_##name)
+#define LEMU_KNOBS(X)                                                                                                                \
+  X(W12_FW) X(W12_GW) X(W12_SW) X(MOVER_WAVES) X(GATHER_WAVES_NARROW) X(GATHER_WAVES_NARROW_WB) X(PIPE_BIG) X(PIPE_SMALL) X(HDPC_NT) \
+  X(HDPC_NT_SMALL) X(SCATTER_LATE_PCT) X(GATHER_LATE_PCT) X(SCATTER_LATE_PCT_NARROW) X(GATHER_LATE_PCT_NARROW) X(HDPC_REGS_MAX_WB)   \
+  X(HDPC_REGS_12) X(FOLD_PRE256)
   static char buf[1024];
-  buf[0] = 0;
-#define LEMU_K(name, value) snprintf(buf + strlen(buf), sizeof(buf) - strlen(buf), "NRQ_" #name "=%u ", (unsigned)(value));
-  LEMU_KERNEL_DEFAULTS(LEMU_K)
+  snprintf(buf, sizeof(buf), LEMU_KNOBS(LEMU_K) LEMU_KNOBS(LEMU_V));
+#undef LEMU_KNOBS
+#undef LEMU_V
 #undef LEMU_K
+  return buf;
+}
+/* ... and what solve_roles() makes of them for instance i of NRQ_SOLVE_INSTANCES: "WB NT WV G AL: NFW NGW NSW MPIPE ALX RU HNT
+ * SLATE GLATE hdpc_regs fold_batch batch fast commit_pb" (nullptr behind the last) */
+extern "C" const char *lemu_instance_roles(int i) {
+  static char buf[256];
+  if (i < 0 || i >= nrq_solve_nkeys) return nullptr;
+  const SolveKey k = nrq_solve_keys[i];
+  const SolveRoles R = solve_roles(k.WB, k.NT, k.WV, k.G, k.AL);
+  snprintf(buf, sizeof(buf), "%d %d %d %d %d: %u %u %u %d %d %u %u %u %u %d %d %d %d %d", k.WB, k.NT, k.WV, k.G, (int)k.AL, R.NFW, R.NGW, R.NSW,
+           (int)R.MPIPE, (int)R.ALX, R.RU, R.HNT, R.SLATE, R.GLATE, (int)R.hdpc_regs, R.fold_batch, (int)R.batch, (int)R.fast, R.commit_pb);
   return buf;
 }
 

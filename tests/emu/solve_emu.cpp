@@ -59,8 +59,8 @@ template <int WB> static int run_strip(const nrq_job &job, uint32_t T, uint32_t 
   const uint32_t nstrips = (T + WB - 1) / WB, ne = ybuf ? c.h->M + c.h->u : out_elems<WB>(c.job, c.h);
   const size_t ostride = ((size_t)ne * WB + 255u) & ~(size_t)255u;
   if (strip % SPL == 0) ostage.assign(ostride * SPL + 64, 0x3C);
-  StripForm f; /* (the forms this emulation has always run: the dense fold of the 256-thread workgroup, the batched dense phases) */
-  f.hnt = NT; f.hdpc_regs = g_hdpc_regs != 0;
+  SolveRoles f = solve_roles(WB, NT, 4, 1, false); /* (overridden: the forms this emulation has always run, whatever the kernel's 256 threads run) */
+  f.HNT = NT; f.hdpc_regs = g_hdpc_regs != 0; f.fold_batch = 8; f.batch = true; f.fast = true; f.commit_pb = 4;
   const int r = strip_phases<WB, 1>(&c, NT, f, stage.data() + (size_t)(strip % SPL) * stride, ostage.data() + (size_t)(strip % SPL) * ostride, ybuf != nullptr);
   if (r != 1) return r;
   if (ybuf) { /* the split solve: slot image and C_u, staged per strip, scattered to full-width rows of the work buffer */

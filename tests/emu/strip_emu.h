@@ -14,15 +14,7 @@
 
 #include <vector>
 
-/* which compiled form of a phase the workgroup runs (nrq_solve_kernel chooses them by NT, WB and G) */
-struct StripForm {
-  uint32_t hnt = 256;     /* threads of the HDPC phase */
-  bool hdpc_regs = false; /* ph_hdpc<.., REGS> */
-  int fold_batch = 8;     /* ph_dense_fold<.., BATCH>: 8 or 0 */
-  bool batch = true;      /* ph_dense_free / ph_dense_cu <.., BATCH> */
-  bool fast = true;       /* ph_backsub / ph_store <.., FAST> */
-  bool commit8 = false;   /* pf_commit<.., PB = 8> (else 4) */
-};
+#include "../../nanorq_amd/csrc/solve_roles.h" /* SolveRoles: which compiled form of a phase the workgroup runs */
 
 /* The forward passes in the order the kernel's wave 0 issues them (plan.h): step q applies row q-NRQ_PIPE,
  * then reads the sources of row q -- so a plan that puts dependent rows closer than NRQ_PIPE rows apart
@@ -48,26 +40,26 @@ template <int WB, int G> static bool emu_forward(const StripCtx<WB, G> *c) {
 }
 
 /* One strip: the image from `stage` (this strip's input staging buffer), every phase, the results into `ostage` (this strip's
- * output staging buffer).  c[0 .. G): the context of every lane; NT threads; raw: the split solve, which stops after the dense
+ * output staging buffer).  c[0 .. G): the context of every lane; NT threads; f: the phases' forms (HNT and the five below it); raw: the split solve, which stops after the dense
  * stage (ph_store_raw).  1, or -7 for a plan of another pipeline depth. */
 template <int WB, int G>
-static int strip_phases(const StripCtx<WB, G> *c, uint32_t NT, const StripForm &f, const uint8_t *stage, uint8_t *ostage, bool raw) {
+static int strip_phases(const StripCtx<WB, G> *c, uint32_t NT, const SolveRoles &f, const uint8_t *stage, uint8_t *ostage, bool raw) {
   const uint32_t VNT = NT / G;
   auto each = [&](uint32_t n, auto fn) {
     for (uint32_t t = 0; t < n; t++) fn(c[t % G], t / G, (uint32_t)(t % G));
   };
   typedef const StripCtx<WB, G> &CX;
   each(NT, [&](CX x, uint32_t vt, uint32_t sub) {
-    if (f.commit8) pf_commit<WB, G, 8>(x, stage + sub * WB, 0u, vt, VNT);
+    if (f.commit_pb == 8) pf_commit<WB, G, 8>(x, stage + sub * WB, 0u, vt, VNT);
     else pf_commit<WB, G, 4>(x, stage + sub * WB, 0u, vt, VNT);
   });
   each(NT, [&](CX x, uint32_t vt, uint32_t) { ph_clear<WB, G>(x, vt, VNT); });
   if (!emu_forward<WB, G>(c)) return -7;
-  each(f.hnt, [&](CX x, uint32_t vt, uint32_t) {
+  each(f.HNT, [&](CX x, uint32_t vt, uint32_t) {
     if constexpr (G == 1) {
-      if (f.hdpc_regs) { ph_hdpc<WB, G, true>(x, vt, f.hnt / G); return; }
+      if (f.hdpc_regs) { ph_hdpc<WB, G, true>(x, vt, f.HNT / G); return; }
     }
-    ph_hdpc<WB, G, false>(x, vt, f.hnt / G);
+    ph_hdpc<WB, G, false>(x, vt, f.HNT / G);
   });
   each(NT, [&](CX x, uint32_t vt, uint32_t) { ph_hdpc_reduce<WB, G>(x, vt, VNT); });
   const uint32_t lpr = c[0].h->lpr;

@@ -17,10 +17,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "solve_body.h"
+#include "solve_roles.h"
 
 #define PROBE_NT 256u
 #define PROBE_LDS_MAX 163840u
@@ -34,9 +36,8 @@ struct DevCase {
 };
 
 /* ---- the forms, called as their call sites call them ---- */
-/* nrq_solve_kernel, one forward wave: `if (tid < NRQ_ROW) fwd_rows<WB, RU>(ops, nrows, tid)`; U = NRQ_RING_TINY (64 threads),
- * NRQ_RING_5W / NRQ_RING_4W (256 threads, 5 / 4 workgroups per CU), NRQ_BIG_RING (768 threads, WB < 8).  Also PL_WFAST_RUN of
- * the planner kernels (fwd_rows<16 / 8 / 4>, U = NRQ_RING) and nrq_wpass_kernel (fwd_rows<2>, U = NRQ_RING). */
+/* nrq_solve_kernel, one forward wave: `if (tid < NRQ_ROW) fwd_rows<WB, RU>(ops, nrows, tid)`, U = the instance's ring (solve_roles.h
+ * RU).  Also PL_WFAST_RUN of the planner kernels (fwd_rows<16 / 8 / 4>) and nrq_wpass_kernel (fwd_rows<2>), both U = NRQ_RING. */
 template <int WB, uint32_t U> struct FormFwd {
   static __device__ __forceinline__ void run(const NRQ_GAS uint32_t *ops, uint32_t nrows, uint32_t tid) {
     if (tid < NRQ_ROW) fwd_rows<WB, U>(ops, nrows, tid);
@@ -128,34 +129,34 @@ __global__ __launch_bounds__(PROBE_NT) void rows_t4_kernel(const uint32_t *__res
 /* ---- the instance table: what the kernels instantiate (nrq_device.hip) ---- */
 typedef void (*probe_fn)(const DevCase *, uint32_t);
 struct Instance {
-  const char *name;
+  const char *form; /* the name, with %u for `ring` where the form has one */
+  uint32_t ring;
   probe_fn fn;
   uint32_t slot_bytes; /* LDS bytes per image index */
 };
-#define FWD(WB, U) {"fwd_rows<" #WB "," #U ">", rows_probe_kernel<FormFwd<WB, U>>, WB}
+/* the op-word ring of the solve workgroup of NT threads built for WV waves per SIMD (solve_roles.h) */
+#define RING(WB, NT, WV) solve_roles(WB, NT, WV, 1, false).RU
+#define FWD(WB, U) {"fwd_rows<" #WB ",%u>", U, rows_probe_kernel<FormFwd<WB, U>>, WB}
+/* the 64-thread solve; the 256-thread solve, five / four workgroups per CU (NRQ_RING: also PL_WFAST_RUN and nrq_wpass_kernel) */
+#define FWD_SMALL(WB) FWD(WB, RING(WB, 64, 1)), FWD(WB, RING(WB, 256, 5)), FWD(WB, RING(WB, 256, 4))
 static const Instance g_inst[] = {
-    /* U = 24: the 64-thread solve (NRQ_RING_TINY); 36 / 60: the 256-thread solve, five / four workgroups per CU (NRQ_RING_5W /
-     * NRQ_RING_4W); 60 also: PL_WFAST_RUN (WB 16, 8, 4) and nrq_wpass_kernel (WB 2) */
-    FWD(16, 24), FWD(16, 36), FWD(16, 60),
-    FWD(8, 24), FWD(8, 36), FWD(8, 60),
-    FWD(4, 24), FWD(4, 36), FWD(4, 60),
-    FWD(2, 24), FWD(2, 36), FWD(2, 60),
-    /* the 768-thread solve (NRQ_BIG_RING) on strips too narrow for two forward waves */
-    FWD(4, 120), FWD(2, 120),
+    FWD_SMALL(16), FWD_SMALL(8), FWD_SMALL(4), FWD_SMALL(2),
+    /* the 768-thread solve on strips too narrow for two forward waves */
+    FWD(4, RING(4, 768, 1)), FWD(2, RING(2, 768, 1)),
     /* the 768-thread solve: two waves on halves, three on the dwords of the 12-byte strip */
-    {"fwd_rows_half<16,120>", rows_probe_kernel<FormHalf<16, 120>>, 16},
-    {"fwd_rows_half<8,120>", rows_probe_kernel<FormHalf<8, 120>>, 8},
-    {"fwd_rows_third<120>", rows_probe_kernel<FormThird<120>>, 12},
+    {"fwd_rows_half<16,%u>", RING(16, 768, 1), rows_probe_kernel<FormHalf<16, RING(16, 768, 1)>>, 16},
+    {"fwd_rows_half<8,%u>", RING(8, 768, 1), rows_probe_kernel<FormHalf<8, RING(8, 768, 1)>>, 8},
+    {"fwd_rows_third<%u>", RING(12, 768, 1), rows_probe_kernel<FormThird<RING(12, 768, 1)>>, 12},
     /* a build with NRQ_W12_FW = 2 only */
-    {"fwd_rows_two_thirds<120>", rows_probe_kernel<FormTwoThirds<120>>, 12},
+    {"fwd_rows_two_thirds<%u>", RING(12, 768, 1), rows_probe_kernel<FormTwoThirds<RING(12, 768, 1)>>, 12},
     /* PL_MHREV_RUN */
-    {"rev_rows<16>", rows_probe_kernel<FormRev<16>>, 16},
-    {"rev_rows<8>", rows_probe_kernel<FormRev<8>>, 8},
-    {"rev_rows<4>", rows_probe_kernel<FormRev<4>>, 4},
+    {"rev_rows<16>", 0, rows_probe_kernel<FormRev<16>>, 16},
+    {"rev_rows<8>", 0, rows_probe_kernel<FormRev<8>>, 8},
+    {"rev_rows<4>", 0, rows_probe_kernel<FormRev<4>>, 4},
     /* wide strips */
-    {"fwd_rows_wide<2>", rows_probe_kernel<FormWide<2>>, 32},
-    {"fwd_rows_wide<4>", rows_probe_kernel<FormWide<4>>, 64},
-    {"fwd_rows_wide<8>", rows_probe_kernel<FormWide<8>>, 128},
+    {"fwd_rows_wide<2>", 0, rows_probe_kernel<FormWide<2>>, 32},
+    {"fwd_rows_wide<4>", 0, rows_probe_kernel<FormWide<4>>, 64},
+    {"fwd_rows_wide<8>", 0, rows_probe_kernel<FormWide<8>>, 128},
 };
 static const uint32_t g_ninst = sizeof(g_inst) / sizeof(g_inst[0]);
 
@@ -180,7 +181,11 @@ struct DevBuf { /* freed on every path */
 extern "C" {
 
 uint32_t rows_probe_ninstances(void) { return g_ninst; }
-const char *rows_probe_name(uint32_t i) { return i < g_ninst ? g_inst[i].name : nullptr; }
+const char *rows_probe_name(uint32_t i) { /* "fwd_rows<16,24>": the form with its ring filled in */
+  static char names[sizeof(g_inst) / sizeof(g_inst[0])][40];
+  if (i < g_ninst) snprintf(names[i], sizeof(names[i]), g_inst[i].form, g_inst[i].ring);
+  return i < g_ninst ? names[i] : nullptr;
+}
 uint32_t rows_probe_slot_bytes(uint32_t i) { return i < g_ninst ? g_inst[i].slot_bytes : 0u; }
 
 /* All cases of one instance in one launch.  Returns the HIP status (0 = hipSuccess), or -1 for arguments that make no sense,

@@ -120,19 +120,70 @@ def test_a_wave_s_lanes_run_in_step():
     assert S.lemu().lemu_wave_selftest() == 5000
 
 
-def test_the_kernel_s_role_macros_are_what_the_emulation_assumes():
-    """run_launch restates the kernel's mover roles with the defaults of macros that nrq_device.hip defines: each #define read from the
-    source must have the value the emulation was built with"""
+# What solve_roles() (nanorq_amd/csrc/solve_roles.h) must say of every instance of NRQ_SOLVE_INSTANCES, in that list's order:
+# (WB, NT, WV, G, AL): (NFW, NGW, NSW, MPIPE, ALX, RU, HNT, SLATE, GLATE, ph_hdpc REGS, ph_dense_fold BATCH, ph_dense_free / _cu BATCH,
+# ph_backsub / ph_store FAST, pf_commit PB).  Numbers, worked out once from the expressions the kernel and the emulation each held
+# before there was one statement.  (NSW of the single wave: NMV - NGW = 0 - 1 in unsigned arithmetic; it has no mover waves and
+# nobody reads it.)
+ROLES = {
+    (16, 768, 1, 1, 0): (2, 2, 2, 1, 0, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (16, 768, 1, 1, 1): (2, 2, 2, 1, 1, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (16, 256, 4, 1, 0): (1, 2, 1, 0, 0, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 256, 4, 1, 1): (1, 2, 1, 0, 1, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 256, 5, 1, 0): (1, 2, 1, 0, 0, 36, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 256, 5, 1, 1): (1, 2, 1, 0, 1, 36, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 64, 3, 1, 0): (1, 1, 4294967295, 0, 0, 24, 64, 20, 40, 0, 8, 1, 0, 4),
+    (16, 64, 3, 1, 1): (1, 1, 4294967295, 0, 1, 24, 64, 20, 40, 0, 8, 1, 0, 4),
+    (16, 256, 4, 2, 0): (1, 2, 1, 0, 0, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 256, 4, 4, 0): (1, 2, 1, 0, 0, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (16, 256, 4, 8, 0): (1, 2, 1, 0, 0, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (12, 768, 1, 1, 0): (3, 2, 2, 1, 0, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (12, 768, 1, 1, 1): (3, 2, 2, 1, 1, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (8, 768, 1, 1, 0): (2, 2, 2, 1, 0, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (8, 768, 1, 1, 1): (2, 2, 2, 1, 1, 120, 512, 20, 40, 0, 0, 0, 1, 8),
+    (8, 256, 4, 1, 0): (1, 2, 1, 0, 0, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (8, 256, 4, 1, 1): (1, 2, 1, 0, 1, 60, 256, 20, 40, 0, 0, 0, 0, 8),
+    (8, 256, 5, 1, 0): (1, 2, 1, 0, 0, 36, 256, 20, 40, 0, 0, 0, 0, 8),
+    (8, 256, 5, 1, 1): (1, 2, 1, 0, 1, 36, 256, 20, 40, 0, 0, 0, 0, 8),
+    (8, 64, 3, 1, 0): (1, 1, 4294967295, 0, 0, 24, 64, 20, 40, 0, 8, 1, 0, 4),
+    (8, 64, 3, 1, 1): (1, 1, 4294967295, 0, 1, 24, 64, 20, 40, 0, 8, 1, 0, 4),
+    (4, 768, 1, 1, 0): (1, 2, 2, 1, 0, 120, 512, 10, 15, 1, 0, 0, 1, 8),
+    (4, 768, 1, 1, 1): (1, 2, 2, 1, 1, 120, 512, 10, 15, 1, 0, 0, 1, 8),
+    (4, 256, 4, 1, 0): (1, 2, 1, 0, 0, 60, 256, 10, 15, 0, 0, 0, 0, 8),
+    (4, 256, 4, 1, 1): (1, 2, 1, 0, 1, 60, 256, 10, 15, 0, 0, 0, 0, 8),
+    (4, 256, 5, 1, 0): (1, 2, 1, 0, 0, 36, 256, 10, 15, 0, 0, 0, 0, 8),
+    (4, 256, 5, 1, 1): (1, 2, 1, 0, 1, 36, 256, 10, 15, 0, 0, 0, 0, 8),
+    (4, 64, 3, 1, 0): (1, 1, 4294967295, 0, 0, 24, 64, 10, 15, 0, 8, 1, 0, 4),
+    (4, 64, 3, 1, 1): (1, 1, 4294967295, 0, 1, 24, 64, 10, 15, 0, 8, 1, 0, 4),
+    (2, 768, 1, 1, 0): (1, 2, 2, 1, 0, 120, 512, 10, 15, 1, 0, 0, 1, 8),
+    (2, 768, 1, 1, 1): (1, 2, 2, 1, 0, 120, 512, 10, 15, 1, 0, 0, 1, 8),
+    (2, 256, 4, 1, 0): (1, 2, 1, 0, 0, 60, 256, 10, 15, 0, 0, 0, 0, 8),
+    (2, 256, 4, 1, 1): (1, 2, 1, 0, 0, 60, 256, 10, 15, 0, 0, 0, 0, 8),
+    (2, 256, 5, 1, 0): (1, 2, 1, 0, 0, 36, 256, 10, 15, 0, 0, 0, 0, 8),
+    (2, 256, 5, 1, 1): (1, 2, 1, 0, 0, 36, 256, 10, 15, 0, 0, 0, 0, 8),
+    (2, 64, 3, 1, 0): (1, 1, 4294967295, 0, 0, 24, 64, 10, 15, 0, 8, 1, 0, 4),
+    (2, 64, 3, 1, 1): (1, 1, 4294967295, 0, 0, 24, 64, 10, 15, 0, 8, 1, 0, 4),
+}
+KNOBS = {"NRQ_W12_FW": 3, "NRQ_W12_GW": 2, "NRQ_W12_SW": 2, "NRQ_MOVER_WAVES": 2, "NRQ_GATHER_WAVES_NARROW": 2, "NRQ_GATHER_WAVES_NARROW_WB": 2,
+         "NRQ_PIPE_BIG": 1, "NRQ_PIPE_SMALL": 0, "NRQ_HDPC_NT": 512, "NRQ_HDPC_NT_SMALL": 256, "NRQ_SCATTER_LATE_PCT": 20, "NRQ_GATHER_LATE_PCT": 40,
+         "NRQ_SCATTER_LATE_PCT_NARROW": 10, "NRQ_GATHER_LATE_PCT_NARROW": 15, "NRQ_HDPC_REGS_MAX_WB": 4, "NRQ_HDPC_REGS_12": 0, "NRQ_FOLD_PRE256": 0}
+
+
+def test_the_kernel_s_roles_are_pinned():
+    """the kernel and the emulation take their wave roles and phase forms from one statement (solve_roles.h); what it says is pinned
+    here against numbers: the 17 role knobs as the emulation library was compiled with them (the macros themselves), and for every
+    compiled instance the fields of solve_roles() that steer the kernel"""
     import ctypes as C
-    import re
     import launch_emu_support as S
     L = S.lemu()
-    L.lemu_kernel_defaults.restype = C.c_char_p
-    assumed = dict(kv.split("=") for kv in L.lemu_kernel_defaults().decode().split())
-    assert len(assumed) == 17
-    text = open(os.path.join(os.path.dirname(HERE), "nanorq_amd", "csrc", "nrq_device.hip")).read()
-    for name, value in assumed.items():
-        found = re.findall(r"^#define %s ([0-9]+)u?\b" % name, text, re.M)
-        assert found == [value], (name, value, found)
-    # the 12-byte strip's late percentages are defined as the wide strips'
-    assert re.search(r"^#define NRQ_W12_SLATE NRQ_SCATTER_LATE_PCT$", text, re.M) and re.search(r"^#define NRQ_W12_GLATE NRQ_GATHER_LATE_PCT$", text, re.M)
+    L.lemu_role_knobs.restype = C.c_char_p
+    L.lemu_instance_roles.restype = C.c_char_p
+    L.lemu_instance_roles.argtypes = [C.c_int]
+    knobs = {k: int(v) for k, v in (kv.split("=") for kv in L.lemu_role_knobs().decode().split())}
+    assert len(KNOBS) == 17 and knobs == KNOBS
+    got, i = [], 0
+    while L.lemu_instance_roles(i) is not None:
+        key, fields = L.lemu_instance_roles(i).decode().split(":")
+        got.append((tuple(int(x) for x in key.split()), tuple(int(x) for x in fields.split())))
+        i += 1
+    assert len(ROLES) == 37 and got == list(ROLES.items())

@@ -112,9 +112,10 @@ def test_case_table_is_legal_and_complete(name):
 
 
 def test_pinned_macros():
-    """the probe's instance table (tests/gpu/rows_probe.hip) restates which rings and which forward waves the kernels instantiate:
-    the #defines it rests on, read from the sources"""
+    """the probe's instance table (tests/gpu/rows_probe.hip) takes its rings from solve_roles.h and rows_support restates them:
+    the #defines they rest on, read from the sources"""
     dev = open(os.path.join(ROOT, "nanorq_amd", "csrc", "nrq_device.hip")).read()
+    roles = open(os.path.join(ROOT, "nanorq_amd", "csrc", "solve_roles.h")).read()
     plan = open(os.path.join(ROOT, "nanorq_amd", "csrc", "plan.h")).read()
 
     def define(text, name):
@@ -122,11 +123,11 @@ def test_pinned_macros():
         assert len(found) == 1, (name, found)
         return found[0]
 
-    assert define(dev, "NRQ_RING_TINY") == "24u"
-    assert define(dev, "NRQ_RING_5W") == "36u"
-    assert define(dev, "NRQ_RING_4W") == "NRQ_RING"
-    assert define(dev, "NRQ_BIG_RING") == "NRQ_RING_MAX"
-    assert define(dev, "NRQ_W12_FW") == "3"
+    assert define(roles, "NRQ_RING_TINY") == "24u"
+    assert define(roles, "NRQ_RING_5W") == "36u"
+    assert define(roles, "NRQ_RING_4W") == "NRQ_RING"
+    assert define(roles, "NRQ_BIG_RING") == "NRQ_RING_MAX"
+    assert define(roles, "NRQ_W12_FW") == "3"
     assert define(plan, "NRQ_PIPE") == "2u"
     assert define(plan, "NRQ_RING_MULT") == "5u"
     assert (R.PIPE, R.RING, R.RING_MAX, R.PAD_ROWS) == (2, 60, 120, 246)
