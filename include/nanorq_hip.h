@@ -723,6 +723,51 @@ int nrq_rxset_add_syms(nrq_rxset *set, const void *d_pkts, size_t pkt_stride, co
 int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, uint32_t G, const uint8_t *d_nsym,
                         void *d_pkts, size_t pkt_stride, uint32_t flags, int32_t *d_results);
 
+/* ---- sender sets: the range mode -- every member's symbols in one call, no list from the host ----
+ * The carousel of a node that serves many objects or flows: the next symbols of every block of every member, fresh repair symbols
+ * included, where nrq_txset_emit needs (d_keys[k], d_tags[k]) for every packet.  The set forms of nrq_tx_emit_range /
+ * nrq_otx_emit_all and their _syms forms.
+ *
+ * The map.  The set's blocks are numbered g = 0 .. nb-1 in the set's block order (nrq_txset_blocks: members sorted by (key, first
+ * SBN), a member's blocks in SBN order); block g has the K of its member (an object: of its block class).  A call names
+ *   source (0 or 1): whether the block's K source symbols are sent;
+ *   rep0, nrep:      the repair ESIs K + rep0 .. K + rep0 + nrep - 1 of every block, each block with its own K;
+ *   G:               symbols per packet (1 in nrq_txset_emit_all).
+ * Block g's packet list is the source run [0, K) cut into packets of G from its start, the last one short (only with source), then
+ * the repair run [K + rep0, K + rep0 + nrep) cut the same way: len_g = (source ? ceil(K / G) : 0) + ceil(nrep / G) packets.  With
+ * source = 1 and rep0 = 0 this is exactly the list of nrq_otx_emit_all_syms / nrq_tx_emit_range_syms(0, K + nrep), and
+ * len_g = nrq_pkt_count(K, 0, K + nrep, G).  Packet j of block g has first tag (SBN_g << 24) | e, count c and key key_g.
+ *   order 0 (block-major): packet (g, j) has index sum_{g' < g} len_g' + j.
+ *   order 1 (interleaved): round j holds packet j of every block with len_g > j, in block order -- the rule nrq_otx_emit_all_syms
+ *     states for order 1, over the set's block order; a block with fewer packets drops out of the later rounds.  The index of
+ *     (g, j) is sum_{g'} min(len_g', j) + #{g' < g : len_g' > j}.
+ *
+ * nrq_txset_count_all: the packets of such a call, *h_npkt (nullable), and per block in block order h_cnt (nullable, room for
+ * the set's blocks).  Host state only: no wait, no launch.  It refuses G, source and the totals as the emits do, and the ESI bound
+ * with rep0 = 0.
+ *
+ * nrq_txset_emit_all_syms: packet k of the map at d_pkts + k*pkt_stride, byte for byte what nrq_txset_emit_syms writes for
+ * (key_k, first tag_k, count_k) under the same flags -- one device pass computes the lists, then the list emit's own payload
+ * kernels write the packets.  flags: NRQ_TX_TAG_INLINE, and with it NRQ_TX_KEY_INLINE; the header is 0, 4 or 8 bytes as in
+ * nrq_txset_emit_syms, pkt_stride >= hdr + G * T, and the bytes behind hdr + c * T of a packet are untouched.  d_keys_out,
+ * d_tags_out (n words each) and d_nsym_out (n bytes) receive the lists; each is nullable on its own (the lists then live in the
+ * set's scratch).  *h_npkt (nullable) is the number of packets, final on return.  Enqueue only, on the context's stream, no host
+ * wait; the members' ready state is taken as it is at the call.  nrq_txset_emit_all is nrq_txset_emit_all_syms with G = 1 and no
+ * counts, through the one-symbol payload kernels of nrq_txset_emit.
+ * An empty set, and source == 0 with nrep == 0: 0 with *h_npkt = 0 and no launch.
+ * Refused (-1 and a text, nothing enqueued, nothing written): what nrq_txset_emit refuses -- a member that is not encoded, a relay
+ * whose reception was destroyed, an unknown flag, NRQ_TX_KEY_INLINE without NRQ_TX_TAG_INLINE, NULL packets, a stride below
+ * hdr + G * T; NRQ_TX_HELD (as nrq_tx_emit_range and nrq_otx_emit_all: every block is in the map); a relay member with a block that
+ * is not ready (the text names the key and the first such SBN, as nrq_tx_emit_range on a relay); order or source outside {0, 1};
+ * G outside 1..NRQ_PKT_SYMS_MAX; nrep > 0 with Kmax + rep0 + nrep - 1 > 0xFFFFFF (Kmax: the largest K in the set); more than
+ * 0x7FFFFFFF packets, or packets * G above that -- found from the counts, before any allocation. */
+int nrq_txset_count_all(nrq_txset *set, uint32_t source, uint32_t nrep, uint32_t G, uint32_t *h_cnt, uint32_t *h_npkt);
+int nrq_txset_emit_all(nrq_txset *set, uint32_t source, uint32_t rep0, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride,
+                       uint32_t flags, uint32_t *d_keys_out, uint32_t *d_tags_out, uint32_t *h_npkt);
+int nrq_txset_emit_all_syms(nrq_txset *set, uint32_t source, uint32_t rep0, uint32_t nrep, uint32_t G, int order, void *d_pkts,
+                            size_t pkt_stride, uint32_t flags, uint32_t *d_keys_out, uint32_t *d_tags_out, uint8_t *d_nsym_out,
+                            uint32_t *h_npkt);
+
 /* Per-launch duration of the solve kernel, measured with HIP events recorded on the launch stream
  * immediately around each launch (bench.py's roofline leg).  enable(1) starts collecting; read()
  * synchronises, returns the durations of the launches since the last read/enable in launch order. */

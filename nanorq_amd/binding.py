@@ -178,6 +178,11 @@ def lib():
         u32 = C.c_uint32
         L.nrq_rxset_add_syms.argtypes = [vp, vp, sz, vp, vp, u32, u32, vp, u32, vp]
         L.nrq_txset_emit_syms.argtypes = [vp, vp, vp, u32, u32, vp, vp, sz, u32, vp]
+    if hasattr(L, "nrq_txset_emit_all"):  # (likewise a build from before the sets' range mode: count_all / emit_all then raise)
+        u32 = C.c_uint32
+        L.nrq_txset_count_all.argtypes = [vp, u32, u32, u32, u32p, u32p]
+        L.nrq_txset_emit_all.argtypes = [vp, u32, u32, u32, C.c_int, vp, sz, u32, vp, vp, u32p]
+        L.nrq_txset_emit_all_syms.argtypes = [vp, u32, u32, u32, u32, C.c_int, vp, sz, u32, vp, vp, vp, u32p]
     if hasattr(L, "nrq_rx_want_syms"):  # (likewise a build from before the listings as runs: want_syms / held_syms then raise)
         u32 = C.c_uint32
         L.nrq_rx_want_syms.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, u32p, u32p]
@@ -1224,6 +1229,53 @@ class SenderSet(_Handle):
         self.ctx._chk(self._L.nrq_txset_emit_syms(self._h, C.c_void_p(_dptr(keys)), C.c_void_p(_dptr(tags)), n, G, C.c_void_p(_dptr(nsym)),
                                                   C.c_void_p(_dptr(out)), stride, flags, C.c_void_p(_dptr(results))))
         return out
+
+    def _range_fn(self, name):
+        fn = getattr(self._L, name, None)
+        if fn is None:
+            raise NrqError("this library build has no range mode of a sender set (%s)" % name)
+        return fn
+
+    def count_all(self, nrep, G=1, source=True, per_block=False):
+        """packets of emit_all(nrep, source=source) / emit_all_syms(nrep, G, source=source) (nrq_txset_count_all); per_block: (total,
+        uint32 array of the packets of every block in the set's block order).  Host state only."""
+        n = C.c_uint32(0)
+        cnt = np.zeros(len(self.blocks()[0]), np.uint32) if per_block else None
+        self.ctx._chk(self._range_fn("nrq_txset_count_all")(self._h, 1 if source else 0, nrep, G, None if cnt is None else _u32(cnt), C.byref(n)))
+        return (n.value, cnt) if per_block else n.value
+
+    def _range(self, syms, nrep, G, interleave, inline, key_inline, out, rep0, source, keys_out, tags_out, nsym_out, held):
+        npkt = self.count_all(nrep, G, source)
+        if out is None:
+            import torch
+            out = self.ctx.new_tensor((npkt, self.stride_syms(G, inline, key_inline)), torch.uint8)
+            stride = out.shape[1]
+        else:
+            stride = out.stride(0) * out.element_size()
+        flags = _tx_flags(inline, held) | (TX_KEY_INLINE if key_inline else 0)
+        head = (self._h, 1 if source else 0, rep0, nrep) + ((G,) if syms else ())
+        tail = (C.c_void_p(_dptr(keys_out)), C.c_void_p(_dptr(tags_out))) + ((C.c_void_p(_dptr(nsym_out)),) if syms else ())
+        got = C.c_uint32()
+        fn = self._range_fn("nrq_txset_emit_all_syms" if syms else "nrq_txset_emit_all")
+        self.ctx._chk(fn(*head, 1 if interleave else 0, C.c_void_p(_dptr(out)), stride, flags, *tail, C.byref(got)))
+        assert got.value == npkt, (got.value, npkt)
+        return out
+
+    def emit_all(self, nrep, interleave=True, inline=False, key_inline=False, out=None, rep0=0, source=True, keys_out=None, tags_out=None,
+                 held=False):
+        """The range mode (nrq_txset_emit_all): of every block of every member the K source symbols (source) and the repair ESIs
+        K + rep0 .. K + rep0 + nrep - 1, each block with its own K -- count_all(nrep, source=source) packets, block-major in the
+        set's block order or interleaved (round j: packet j of every block that has one, in block order), with no list from the
+        host.  inline / key_inline as in emit(); keys_out / tags_out: optional [packets] int32 device tensors for each packet's
+        key and tag; held: refused, as Sender.emit_range.  out None: a new [packets, stride] tensor.  Enqueue only.  Returns out."""
+        return self._range(False, nrep, 1, interleave, inline, key_inline, out, rep0, source, keys_out, tags_out, None, held)
+
+    def emit_all_syms(self, nrep, G, interleave=True, inline=False, key_inline=False, out=None, rep0=0, source=True, keys_out=None,
+                      tags_out=None, nsym_out=None, held=False):
+        """emit_all in packets of G symbols (nrq_txset_emit_all_syms): per block the source run, then the repair run, each cut into
+        packets of G from its start, the last one short -- count_all(nrep, G, source) packets; nsym_out: optional [packets] uint8
+        device tensor for each packet's count.  Returns out."""
+        return self._range(True, nrep, G, interleave, inline, key_inline, out, rep0, source, keys_out, tags_out, nsym_out, held)
 
 
 def plan_ops(plan, header=None):

@@ -29,6 +29,7 @@ REMU = os.path.join(ROOT, "tests", "emu", "librxset_emu.so")
 LEMU = os.path.join(ROOT, "tests", "emu", "librxset_lists_emu.so")
 QEMU = os.path.join(ROOT, "tests", "emu", "librxset_want_emu.so")
 TEMU = os.path.join(ROOT, "tests", "emu", "libtxset_emu.so")
+KEMU = os.path.join(ROOT, "tests", "emu", "libtxset_range_emu.so")
 YEMU = os.path.join(ROOT, "tests", "emu", "libsyms_emu.so")
 ZEMU = os.path.join(ROOT, "tests", "emu", "libsyms_set_emu.so")
 GEMU = os.path.join(ROOT, "tests", "emu", "libruns_emu.so")
@@ -207,6 +208,12 @@ def build_txset_emu(force=False):
     return _build_emu(TEMU, os.path.join(CSRC, "txset_emu.cpp"), ("emit_set_body.h", "emit_body.h", "rq_math.h"), force)
 
 
+def build_txset_range_emu(force=False):
+    """tests/emu/libtxset_range_emu.so: CPU emulation of the map pass of a sender set's range mode (csrc/txset_range_emu.cpp over
+    emit_set_range_body.h)."""
+    return _build_emu(KEMU, os.path.join(CSRC, "txset_range_emu.cpp"), ("emit_set_range_body.h", "emit_set_body.h", "emit_body.h", "rq_math.h"), force)
+
+
 def build_syms_emu(force=False):
     """tests/emu/libsyms_emu.so: CPU emulation of the emit and ingest of packets of several symbols (csrc/syms_emu.cpp over
     syms_body.h), with the count rule, the range packetisation and the path rules behind C entry points."""
@@ -337,6 +344,7 @@ if __name__ == "__main__":
     build_rxset_lists_emu(force="-f" in sys.argv)
     build_rxset_want_emu(force="-f" in sys.argv)
     build_txset_emu(force="-f" in sys.argv)
+    build_txset_range_emu(force="-f" in sys.argv)
     build_syms_emu(force="-f" in sys.argv)
     build_syms_set_emu(force="-f" in sys.argv)
     build_runs_emu(force="-f" in sys.argv)

@@ -43,6 +43,7 @@
 #include "want_set_body.h"
 #include "emit_body.h"
 #include "emit_set_body.h"
+#include "emit_set_range_body.h"
 #include "syms_body.h"
 #include "syms_set_body.h"
 #include "runs_body.h"
@@ -5804,19 +5805,17 @@ static int txset_attach(nrq_txset *set, const char *who, uint32_t key, tx_sender
   return txset_commit(set, mem);
 }
 
-/* What the set's emits share once their arguments are checked: the members' state, the ready bits of the global blocks, the payload
- * path (*mode: TX_V16 .. TX_BYTE or TXS_V16_KEY), the call over n packets with its arrays carved out of the set's scratch, and the
- * three bucketing passes over the tags, enqueued.  The emit kernel is the caller's. */
-static int txset_call_of(nrq_txset *set, const char *who, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts,
-                         size_t pkt_stride, uint32_t hdr, bool held, int32_t *d_results, txs_ready *rdyp, txs_call *cp, int *mode) {
+/* What every emit of the set does first once its own arguments are checked -- the list route (txset_call_of) and the range route
+ * (txset_range): the members' state, the set's scratch grown to `need` bytes, the ready bits of the global blocks, the payload path
+ * (*mode: TX_V16 .. TX_BYTE or TXS_V16_KEY).  Nothing is enqueued here. */
+static int txset_prepare(nrq_txset *set, const char *who, size_t need, void *d_pkts, size_t pkt_stride, uint32_t hdr, bool held, txs_ready *rdyp,
+                         int *mode) {
   nrq_ctx *ctx = set->ctx;
   for (const txset_member &m : set->mem) {
     if (m.tx->detached) return fail(ctx, -1, "%s: the reception of the relay under key %u was destroyed", who, m.key);
     if (!m.tx->encoded) return fail(ctx, -1, "%s: the member under key %u is not encoded (%s)", who, m.key, m.tx->unencoded);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const uint32_t nb = set->nblk, nbins = nb + 1u;
-  const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
   const int rc = set->scratch.ensure(ctx, need);
   if (rc) return rc;
   /* the ready bits of the global blocks as the members have them NOW, by value into this call's kernel arguments: a relay's mask
@@ -5838,6 +5837,18 @@ static int txset_call_of(nrq_txset *set, const char *who, const uint32_t *d_keys
   }
   *mode = sys_emit_path(al, hdr, ctx->tune.tx_dword ? 1u : 0u);
   *rdyp = rdy;
+  return 0;
+}
+
+/* The list route once its arguments are checked: txset_prepare, the call over n packets with its arrays carved out of the set's
+ * scratch, and the three bucketing passes over the tags, enqueued.  The emit kernel is the caller's. */
+static int txset_call_of(nrq_txset *set, const char *who, const uint32_t *d_keys, const uint32_t *d_tags, uint32_t n, void *d_pkts,
+                         size_t pkt_stride, uint32_t hdr, bool held, int32_t *d_results, txs_ready *rdyp, txs_call *cp, int *mode) {
+  nrq_ctx *ctx = set->ctx;
+  const uint32_t nb = set->nblk, nbins = nb + 1u;
+  const size_t o_seg = rx_al((size_t)nbins * 4u), o_order = o_seg + rx_al((size_t)n * 4u), need = o_order + rx_al((size_t)n * 4u);
+  const int rc = txset_prepare(set, who, need, d_pkts, pkt_stride, hdr, held, rdyp, mode);
+  if (rc) return rc;
   uint8_t *p = (uint8_t *)set->scratch.p;
   uint32_t *cnt = (uint32_t *)p;
   txs_call c{};
@@ -6241,6 +6252,165 @@ int nrq_txset_emit_syms(nrq_txset *set, const uint32_t *d_keys, const uint32_t *
                      c, y);
   HIPCHK(ctx, hipGetLastError());
   return 0;
+}
+
+} /* extern "C" */
+
+/* ================================================ sender sets: the range mode (nrq_txset_emit_all*, emit_set_range_body.h) ==== */
+/* The packets of "the next symbols of every block of every member" with no list from the host: ONE pass computes the packet map
+ * (emit_set_range_body.h states it) into the (keys, tags, nsym) lists, the packets' segments and the work order, in the set's
+ * scratch or in the caller's out arrays; behind it run the list route's payload kernels (nrq_emit_set_kernel,
+ * nrq_emit_set_syms_kernel) on those arrays, by the list route's path rule.  One thread per work item in block-major order; the
+ * per-segment words are staged in LDS (at most 64 entries: every lane of a block's run reads the same one, as in
+ * nrq_txs_hist_kernel), each thread walks them once for its segment and once for its packet index. */
+__global__ __launch_bounds__(256) void nrq_txs_range_kernel(const txs_tab *__restrict__ t, txr_call c) {
+  __shared__ txr_stage_t s;
+  const uint32_t nseg = min(t->nseg, TXS_MAX_SEGS), i = threadIdx.x;
+  if (i < nseg) txr_stage(t, &c, i, &s);
+  __syncthreads();
+  if (i <= nseg) txr_stage_prefix(nseg, i, &s);
+  __syncthreads();
+  const uint32_t w = blockIdx.x * 256u + i;
+  if (w < c.n && w < s.pre[nseg]) txr_map(&s, nseg, &c, w);
+}
+
+/* the packets of a range call from the host's copy of the table: *total, and per block in block order h_cnt (nullable).  The
+ * checks nrq_txset_count_all and the emits share: G, source, the ESI bound, the totals. */
+static int txset_range_count(nrq_txset *set, const char *who, uint32_t source, uint32_t rep0, uint32_t nrep, uint32_t G, uint32_t *h_cnt,
+                             uint32_t *total) {
+  nrq_ctx *ctx = set->ctx;
+  if (G == 0 || G > NRQ_PKT_SYMS_MAX) return fail(ctx, -1, "%s: G=%u outside 1..%u", who, G, NRQ_PKT_SYMS_MAX);
+  if (source > 1u) return fail(ctx, -1, "%s: source %u is neither 0 nor 1", who, source);
+  uint32_t kmax = 0;
+  for (const txset_seg &r : set->segs) kmax = std::max(kmax, r.tx->s.seg[r.g].K);
+  if (nrep && (uint64_t)kmax + rep0 + nrep - 1u > 0xFFFFFFu)
+    return fail(ctx, -1, "%s: repair ESIs up to %llu reach past 2^24 - 1", who, (unsigned long long)((uint64_t)kmax + rep0 + nrep - 1u));
+  uint64_t n = 0;
+  for (const txset_seg &r : set->segs) {
+    const tx_blk &t = r.tx->s.seg[r.g];
+    n += (uint64_t)t.nblk * txr_len(t.K, source, nrep, G);
+  }
+  if (n > 0x7FFFFFFFu || n * G > 0x7FFFFFFFu)
+    return fail(ctx, -1, "%s: %llu packets of %u symbols are more than one call takes", who, (unsigned long long)n, G);
+  *total = (uint32_t)n;
+  if (h_cnt) {
+    uint32_t g = 0;
+    for (const txset_seg &r : set->segs) {
+      const tx_blk &t = r.tx->s.seg[r.g];
+      for (uint32_t b = 0; b < t.nblk; b++) h_cnt[g++] = txr_len(t.K, source, nrep, G);
+    }
+  }
+  return 0;
+}
+
+/* The one function behind nrq_txset_emit_all and nrq_txset_emit_all_syms (syms: the several-symbol payload kernels and the
+ * counts; else G = 1 and the one-symbol kernels).  Checks first; then txset_prepare as the list route; the map pass; the emit. */
+static int txset_range(nrq_txset *set, const char *who, bool syms, uint32_t source, uint32_t rep0, uint32_t nrep, uint32_t G, int order,
+                       void *d_pkts, size_t pkt_stride, uint32_t flags, uint32_t *d_keys_out, uint32_t *d_tags_out, uint8_t *d_nsym_out,
+                       uint32_t *h_npkt) {
+  using set_fn = void (*)(const txs_tab *, txs_ready, txs_call);
+  using syms_fn = void (*)(const txs_tab *, txs_ready, txs_call, sy_tx);
+  static const set_fn kern[5] = {nrq_emit_set_kernel<TX_V16, false>, nrq_emit_set_kernel<TX_V16_SHIFT, false>, nrq_emit_set_kernel<TX_DWORD, false>,
+                                 nrq_emit_set_kernel<TX_BYTE, false>, nrq_emit_set_kernel<TXS_V16_KEY, false>}; /* [mode] */
+  static const syms_fn skern[5] = {nrq_emit_set_syms_kernel<TX_V16>, nrq_emit_set_syms_kernel<TX_V16_SHIFT>, nrq_emit_set_syms_kernel<TX_DWORD>,
+                                   nrq_emit_set_syms_kernel<TX_BYTE>, nrq_emit_set_syms_kernel<TXS_V16_KEY>}; /* [mode] */
+  if (!set) return -1;
+  nrq_ctx *ctx = set->ctx;
+  const bool inl = (flags & NRQ_TX_TAG_INLINE) != 0, kinl = (flags & NRQ_TX_KEY_INLINE) != 0;
+  if (flags & ~(uint32_t)(NRQ_TX_TAG_INLINE | NRQ_TX_HELD | NRQ_TX_KEY_INLINE)) return fail(ctx, -1, "%s: unknown flags 0x%x", who, flags);
+  if (flags & NRQ_TX_HELD) return fail(ctx, -1, "%s: NRQ_TX_HELD goes with a tag list (the range forms map packets to every block)", who);
+  if (kinl && !inl) return fail(ctx, -1, "%s: NRQ_TX_KEY_INLINE needs NRQ_TX_TAG_INLINE", who);
+  if (order != 0 && order != 1) return fail(ctx, -1, "%s: order %d is neither 0 (block-major) nor 1 (interleaved)", who, order);
+  uint32_t n = 0;
+  int rc = txset_range_count(set, who, source, rep0, nrep, G, nullptr, &n);
+  if (rc) return rc;
+  if (n == 0) { /* an empty set; neither source nor repair symbols */
+    if (h_npkt) *h_npkt = 0;
+    return 0;
+  }
+  if (!d_pkts) return fail(ctx, -1, "%s: d_pkts is NULL", who);
+  const uint32_t hdr = kinl ? 8u : inl ? 4u : 0u;
+  if ((uint64_t)G * set->T > 0xFFFFFFFFu || pkt_stride < (size_t)G * set->T + hdr)
+    return fail(ctx, -1, "%s: pkt_stride %zu shorter than a packet of %u symbols", who, pkt_stride, G);
+  /* every block is in the map, so every block must be ready (as nrq_tx_emit_range on a relay) */
+  for (const txset_seg &r : set->segs) {
+    const tx_sender *tx = r.tx;
+    if (!tx->relay || tx->detached) continue; /* (a detached relay: txset_prepare says so) */
+    const tx_blk &t = tx->s.seg[r.g];
+    for (uint32_t b = 0; b < t.nblk; b++)
+      if (!tx_is_ready(tx, t.sbn0 + b - tx->s.sbn0))
+        return fail(ctx, -1, "%s: a block of the relay under key %u is not ready: SBN %u", who, txset_key_of(set, tx), t.sbn0 + b);
+  }
+  /* the per-packet arrays: segments and work order always in the scratch, the lists there unless the caller takes them */
+  const size_t words = rx_al((size_t)n * 4u);
+  size_t need = 2u * words;
+  const size_t o_keys = need;
+  if (!d_keys_out) need += words;
+  const size_t o_tags = need;
+  if (!d_tags_out) need += words;
+  const size_t o_nsym = need;
+  if (syms && !d_nsym_out) need += rx_al((size_t)n);
+  txs_ready rdy;
+  int mode;
+  if ((rc = txset_prepare(set, who, need, d_pkts, pkt_stride, hdr, false, &rdy, &mode))) return rc;
+  uint8_t *p = (uint8_t *)set->scratch.p;
+  txr_call r{};
+  r.source = source; r.rep0 = rep0; r.nrep = nrep; r.G = G;
+  r.order = (uint32_t)order;
+  r.n = n;
+  r.seg = (uint32_t *)p;
+  r.worder = (uint32_t *)(p + words);
+  r.keys = d_keys_out ? d_keys_out : (uint32_t *)(p + o_keys);
+  r.tags = d_tags_out ? d_tags_out : (uint32_t *)(p + o_tags);
+  r.nsym = !syms ? nullptr : d_nsym_out ? d_nsym_out : p + o_nsym;
+  txs_call c{};
+  c.pkts = (uint8_t *)d_pkts;
+  c.pkt_stride = pkt_stride;
+  c.n = n;
+  c.hdr = hdr;
+  c.T = set->T;
+  c.keys = r.keys;
+  c.tags = r.tags;
+  c.seg = r.seg;
+  c.order = r.worder;
+  const txs_tab *t = (const txs_tab *)set->tab;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(nrq_txs_range_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, t, r);
+  HIPCHK(ctx, hipGetLastError());
+  if (syms) {
+    sy_tx y{};
+    y.G = G; y.nsym = r.nsym;
+    const uint32_t per = 64u / G, waves = (n + per - 1u) / per;
+    hipLaunchKernelGGL(skern[mode], dim3((waves + TX_WAVES - 1u) / TX_WAVES), dim3(64u * TX_WAVES), 0, st, t, rdy, c, y);
+  } else {
+    hipLaunchKernelGGL(kern[mode], dim3((n + TX_WAVES * TX_WAVE_PKTS - 1u) / (TX_WAVES * TX_WAVE_PKTS)), dim3(64u * TX_WAVES), 0, st, t, rdy, c);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (h_npkt) *h_npkt = n;
+  return 0;
+}
+
+extern "C" {
+
+int nrq_txset_count_all(nrq_txset *set, uint32_t source, uint32_t nrep, uint32_t G, uint32_t *h_cnt, uint32_t *h_npkt) {
+  if (!set) return -1;
+  uint32_t n = 0;
+  const int rc = txset_range_count(set, "nrq_txset_count_all", source, 0, nrep, G, h_cnt, &n);
+  if (rc) return rc;
+  if (h_npkt) *h_npkt = n;
+  return 0;
+}
+
+int nrq_txset_emit_all(nrq_txset *set, uint32_t source, uint32_t rep0, uint32_t nrep, int order, void *d_pkts, size_t pkt_stride, uint32_t flags,
+                       uint32_t *d_keys_out, uint32_t *d_tags_out, uint32_t *h_npkt) {
+  return txset_range(set, "nrq_txset_emit_all", false, source, rep0, nrep, 1u, order, d_pkts, pkt_stride, flags, d_keys_out, d_tags_out, nullptr,
+                     h_npkt);
+}
+
+int nrq_txset_emit_all_syms(nrq_txset *set, uint32_t source, uint32_t rep0, uint32_t nrep, uint32_t G, int order, void *d_pkts, size_t pkt_stride,
+                            uint32_t flags, uint32_t *d_keys_out, uint32_t *d_tags_out, uint8_t *d_nsym_out, uint32_t *h_npkt) {
+  return txset_range(set, "nrq_txset_emit_all_syms", true, source, rep0, nrep, G, order, d_pkts, pkt_stride, flags, d_keys_out, d_tags_out,
+                     d_nsym_out, h_npkt);
 }
 
 } /* extern "C" */
